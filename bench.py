@@ -12,7 +12,16 @@ of the sequence inside the timed region.
 each rank streaming its block from page-locked host memory through orbfe_stream_submit in batches of <= --pairs, and ONE gather of
 the per-frame records (left keypoints + descriptors + right_u + depth, 152 KB per frame) to rank 0 over RCCL, inside the timed region.
 
-Extra objects in the JSON line:
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the outputs of the last step when
+`--dump-outputs DIR` is given, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step and the step loop's
+configuration).  It leaves GPU_MAX_HW_QUEUES as the caller set it; `--full` and `--sequence` raise it to 16 for the streaming legs.  Everything else -- the checks of the last batch against the committed digests, the per-stage profile and the
+rooflines, the extra legs and the CPU baseline -- runs with `--full` only.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of orbfe_stereo_batch_device receives it, to DIR/<name>.npy
+(float32 / float64; rank 0's shard): the keypoint counts and match counts of every pair, and keypoints, descriptors, right_u and depth of
+a fixed, seeded sample of pairs (at most 64 MB in all).  The inputs depend on the arguments only, so two builds can be compared file by file.
+
+Extra objects in the JSON line (`--full`):
   host_io       the same step fed from page-locked HOST memory and delivering its results to host memory (orbfe_stream_submit:
                 upload of batch k+1 and download of batch k-1 under the compute of batch k) -- the PCIe-inclusive rate; `value`
                 itself is device-resident
@@ -31,11 +40,6 @@ import time
 
 import numpy as np
 
-if "--only-leg" not in sys.argv:
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # before the first HIP call: one hardware queue per stream of the streaming legs
-                                                        # (= orbfe_recommended_hw_queues(); the library only warns, it cannot set it).  The
-                                                        # one-frame latency leg runs in a child WITHOUT it (--only-leg): what a drop-in user has
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -45,6 +49,37 @@ from benchlib.host_io import host_io_leg  # noqa: E402
 from benchlib.legs import ba_leg, cfg3_leg, latency_leg  # noqa: E402
 from benchlib.sequence_leg import run_sequence_mode, sequence_batch, sequence_job  # noqa: E402
 from benchlib.sweep import content_sweep  # noqa: E402
+
+
+DUMP_SEED, DUMP_SAMPLE_PAIRS = 20251015, 32
+
+
+def dump_outputs(ctx, counts, n_matches, out_dir):
+    """The last step's results as a caller of orbfe_stereo_batch_device receives them (slots 2p / 2p + 1 = left / right image of pair p),
+    as DIR/<name>.npy in float32 / float64: the keypoint counts [pairs][2] and match counts of every pair; keypoints [x y size angle
+    response octave class_id], descriptors (one value per byte), right_u and depth of a fixed, seeded sample of pairs (entries past a
+    slot's count are zero).  About 21 MB at 2000 features."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_pairs = len(n_matches)
+    pairs = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pairs, min(n_pairs, DUMP_SAMPLE_PAIRS), replace=False))
+    nf = ctx.n_features
+    kps = np.zeros((len(pairs), 2, nf, 7), np.float32)
+    desc = np.zeros((len(pairs), 2, nf, 32), np.float32)
+    ru = np.zeros((len(pairs), nf), np.float64)
+    dp = np.zeros((len(pairs), nf), np.float64)
+    for i, p in enumerate(pairs):
+        k, d, c = ctx.fetch_batch(2 * int(p), 2)
+        for e in range(2):
+            n = int(c[e])
+            kps[i, e, :n] = np.stack([k[e, :n][f].astype(np.float32) for f in k.dtype.names], axis=-1)
+            desc[i, e, :n] = d[e, :n]
+        r, z, _ = ctx.fetch_stereo_batch(int(p), 1)
+        ru[i, :int(c[0])] = r[0, :int(c[0])]
+        dp[i, :int(c[0])] = z[0, :int(c[0])]
+    out = {"counts": np.asarray(counts, np.float64).reshape(n_pairs, 2), "n_matches": np.asarray(n_matches, np.float64),
+           "sample_pairs": pairs.astype(np.float64), "keypoints": kps, "descriptors": desc, "right_u": ru, "depth": dp}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -75,7 +110,7 @@ def main():
                          "the records are gathered on rank 0 over the collective and drained over rank 0's link")
     ap.add_argument("--sequence-window", type=int, default=1, help="batches per gather window of the sequence job (sharding.WindowGather)")
     ap.add_argument("--only-leg", default="", help="(internal) run ONE extra leg (cfg3 | ba | latency) in this process and print its JSON object: "
-                    "the default line runs the latency leg this way, in a child started WITHOUT GPU_MAX_HW_QUEUES -- the streaming legs of the "
+                    "--full runs the latency leg this way, in a child started WITHOUT GPU_MAX_HW_QUEUES -- the streaming legs of the "
                     "parent want 16 hardware queues, a caller that processes one frame at a time has the runtime's default, ~50 us per frame "
                     "faster (ADVICE r4)")
     ap.add_argument("--content-steps", type=int, default=40,
@@ -84,7 +119,18 @@ def main():
     ap.add_argument("--legs", default="cfg3,ba,latency", help="comma-separated extra legs of the default line (north_star beyond the stereo step): "
                     "cfg3 (2000x2000 Hamming), ba (config-5 edge evaluation / normal equations / local BA / pose-only), latency (one pair, host "
                     "to host, in the reference's call shape); '' skips them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the checks of the last batch against the golden digests, the "
+                         "per-stage profile and rooflines, host_io, the sequence job, the content sweep, the CPU baseline and the --legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (rank 0's shard) to DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if (args.full or args.sequence > 0) and not args.only_leg:
+        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # before the first HIP call: one hardware queue per stream of the streaming legs
+                                                            # (= orbfe_recommended_hw_queues(); the library only warns, it cannot set it).  The
+                                                            # one-frame latency leg runs in a child WITHOUT it (--only-leg): what a drop-in user has
+    if args.dump_outputs and args.sequence > 0:
+        raise SystemExit("bench.py: --dump-outputs writes the step loop's outputs; it is not available with --sequence")
 
     if args.only_leg:
         dev_id = int(os.environ.get("LOCAL_RANK", "0"))
@@ -106,16 +152,16 @@ def main():
     U_seq = max(1, min(args.sequence_unique, 4541))
     t_gen = time.perf_counter()
     step_frames = list(range(rank_env * n_unique, (rank_env + 1) * n_unique)) if args.sequence <= 0 else []
-    seq_frames = list(range(U_seq)) if (args.sequence > 0 or args.sequence_leg > 0) else []
+    seq_frames = list(range(U_seq)) if (args.sequence > 0 or (args.full and args.sequence_leg > 0)) else []
     wanted = sorted(set(step_frames) | set(seq_frames))
-    frame_cache = generate_pairs_child(wanted)   # (a child process forks the workers: this one may already carry a profiler's preload)
+    frame_cache = generate_pairs_child(wanted)   # (a child process forks the workers: this one may already carry a profiler's library)
     t_gen = time.perf_counter() - t_gen
 
     # The one-frame latency leg runs NOW, in a child process, while nothing else holds a context on the GPU (the r5
     # record's p99 of 0.8 - 1.0 ms were this leg's C++ harness running beside the idle contexts of this process and of the leg's own
     # Python half).  The child is started WITHOUT GPU_MAX_HW_QUEUES: the setting a one-frame-at-a-time caller has (recorded in the leg).
     latency_result = None
-    if args.sequence <= 0 and args.gpus == 1 and rank_env == 0 and "latency" in [x for x in args.legs.split(",") if x]:
+    if args.full and args.sequence <= 0 and args.gpus == 1 and rank_env == 0 and "latency" in [x for x in args.legs.split(",") if x]:
         import subprocess
         env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
         env["LOCAL_RANK"] = os.environ.get("LOCAL_RANK", "0")
@@ -252,23 +298,24 @@ def main():
         step()
     ctx.sync()
 
-    n_cand_img = sum(len(ctx.debug_candidates(0, l)) for l in range(NLEVELS))  # FAST candidates of one image (slot 0)
-    per_image_bytes, match_bytes, pair_bytes = algorithmic_bytes(ctx, n_cand_img)
+    if args.full:
+        n_cand_img = sum(len(ctx.debug_candidates(0, l)) for l in range(NLEVELS))  # FAST candidates of one image (slot 0)
+        per_image_bytes, match_bytes, pair_bytes = algorithmic_bytes(ctx, n_cand_img)
 
-    # per-stage device time (HIP events on the library stream), every kernel timed ALONE, in an untimed pass: this picks the
-    # dominant stage and fills `all_stages`
-    ctx.profile_enable(1)
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-    ctx.sync()
-    prof = ctx.profile_read()
-    ctx.profile_enable(0)
-    stages = {k: (ms / n if n else 0.0) for k, (ms, n) in prof.items() if n}
-    images_per_launch = 2 * B
-    stage_bytes = {k: per_image_bytes[k] * images_per_launch for k in per_image_bytes}
-    stage_bytes["stereo"] = match_bytes * B
-    dom = max((k for k in stages if k in stage_bytes), key=lambda k: stages[k])
-    stage_id = {"resize": 0, "blur": 1, "fast": 2, "quadtree": 3, "orient_brief": 4, "stereo": 5}[dom]
+        # per-stage device time (HIP events on the library stream), every kernel timed ALONE, in an untimed pass: this picks the
+        # dominant stage and fills `all_stages`
+        ctx.profile_enable(1)
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+        ctx.sync()
+        prof = ctx.profile_read()
+        ctx.profile_enable(0)
+        stages = {k: (ms / n if n else 0.0) for k, (ms, n) in prof.items() if n}
+        images_per_launch = 2 * B
+        stage_bytes = {k: per_image_bytes[k] * images_per_launch for k in per_image_bytes}
+        stage_bytes["stereo"] = match_bytes * B
+        dom = max((k for k in stages if k in stage_bytes), key=lambda k: stages[k])
+        stage_id = {"resize": 0, "blur": 1, "fast": 2, "quadtree": 3, "orient_brief": 4, "stereo": 5}[dom]
 
     # warm-up of the exchange: the first torch indexing / RCCL call initialises lazily (tens of ms).  BEFORE the sustained load below, not
     # between it and the clock: the chip's clocks sag within milliseconds of idling, and a 20-step run (0.1 s) is over before they are back
@@ -285,9 +332,10 @@ def main():
         step()
     sync_all()
     # the timed region runs the production schedule (blur under the quadtree, stereo match of a batch under the front of the next);
-    # the dominant stage alone carries HIP events on the stream it is launched on, so its duration is measured LIVE in this region --
-    # the figure the rocprofv3 kernel trace of this command shows for the same kernels
-    ctx.profile_enable(2 + stage_id)
+    # with --full the dominant stage alone carries HIP events on the stream it is launched on, so its duration is measured LIVE in this
+    # region -- the figure the rocprofv3 kernel trace of this command shows for the same kernels
+    if args.full:
+        ctx.profile_enable(2 + stage_id)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -296,12 +344,53 @@ def main():
     gathered = gather_results()
     sync_all()
     dt = time.perf_counter() - t0
-    live = ctx.profile_read()
-    ctx.profile_enable(0)
+    if args.full:
+        live = ctx.profile_read()
+        ctx.profile_enable(0)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=xdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, d_counts.cpu().numpy(), d_nmatch.cpu().numpy(), args.dump_outputs)
+
+    total_pairs = args.steps * B * world
+    fps = total_pairs / dt
+    line = {
+        "metric": "stereo frames/sec (extract+match) KITTI-00 1241x376; HBM GB/s vs roofline",
+        "value": fps,
+        "unit": "stereo pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+    }
+    if not args.full:
+        line["config"] = {
+            "workload": f"Single 1241x376 KITTI-shaped stereo pair, 8-level pyramid, 2000 FAST+rBRIEF keypoints per image, searchByStereo; "
+                        f"batched ({B} pairs per step, {n_unique} of them distinct synthetic frames).  `value` is DEVICE-RESIDENT; the checks, "
+                        "rooflines, host_io, sequence job, content sweep, CPU baseline and extra legs run with --full",
+            "io": "device-resident",
+            "pairs_per_step_per_gpu": B,
+            "distinct_pairs_per_step": n_unique,
+            "steps_only_ms_per_step": t_steps / args.steps * 1e3, "exchange_and_barrier_ms": (dt - t_steps) * 1e3,
+            "n_features": NFEAT,
+            "levels": NLEVELS,
+            "frame_generation_seconds": round(t_gen, 2),
+        }
+        line["rccl"] = rccl_note
+        ctx.close()
+        if rank == 0:
+            emit(line)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
 
     # sanity: the last batch produced features and matches, and the gathered summaries agree with the fetched results
     nm, ru, dp, _, _ = ctx.fetch_stereo(0)
@@ -373,21 +462,7 @@ def main():
     dom_ms = stages[dom]
     achieved = stage_bytes[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
 
-    total_pairs = args.steps * B * world
-    fps = total_pairs / dt
-    line = {
-        "metric": "stereo frames/sec (extract+match) KITTI-00 1241x376; HBM GB/s vs roofline",
-        "value": fps,
-        "unit": "stereo pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
+    line.update({
         "verified_pairs": verified,   # pairs of the last timed batch (all ranks) whose results equal the committed golden digests
         "host_io": host_io,
         "sequence": seq_leg,
@@ -440,7 +515,7 @@ def main():
             "all_stages": {k: {"ms": round(stages_inline[k], 4), "GBps": round(stage_bytes[k] / (stages_inline[k] * 1e-3) / 1e9, 1)}
                            for k in stages_inline if k in stage_bytes and stages_inline[k] > 0},
         },
-    }
+    })
 
     # The dominant kernel and the whole step against the VALU ISSUE ceiling (committed rocprofv3 SQ_* pass), and the dominant kernel's
     # memory-side traffic (committed FETCH_SIZE / WRITE_SIZE passes): benchlib/profile_reader.py

@@ -164,7 +164,7 @@ def generate_pairs(frames, workers=None):
 
 
 def generate_pairs_child(frames):
-    """{frame: (left, right)} through tools/gen_frames.py run as a CHILD process with a clean environment (no profiler preload): the child
+    """{frame: (left, right)} through tools/gen_frames.py run as a CHILD process (numpy only, it never touches the GPU): the child
     forks the worker pool, this process never forks -- safe whatever this process has already loaded (bench.py under rocprofv3 has the
     profiler's library, which initialises the GPU before Python starts; a GPU test session holds a context)."""
     import subprocess
@@ -178,12 +178,11 @@ def generate_pairs_child(frames):
         if i == len(frames) or frames[i] != frames[i - 1] + 1:
             runs.append((frames[a], i - a))
             a = i
-    env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD" and not k.startswith(("ROCP", "ROCPROF", "HSA_TOOLS"))}
     shm = "/dev/shm" if os.path.isdir("/dev/shm") else None
     for first, count in runs:
         with tempfile.TemporaryDirectory(prefix="orbfe_frames_", dir=shm) as td:
             npy = os.path.join(td, "f.npy")
-            subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_frames.py"), str(first), str(count), npy], check=True, env=env, timeout=1800)
+            subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_frames.py"), str(first), str(count), npy], check=True, timeout=1800)
             arr = np.load(npy)
         for k in range(count):
             out[first + k] = (arr[k, 0], arr[k, 1])

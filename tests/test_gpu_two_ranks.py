@@ -18,7 +18,7 @@ def test_bench_with_two_gloo_ranks_on_one_gpu():
     env = dict(os.environ, ORBFE_BENCH_ONE_DEVICE="1", ORBFE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--pairs", "32", "--steps", "4", "--warmup", "1", "--prewarm-seconds", "0.1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--pairs", "32", "--steps", "4", "--warmup", "1", "--prewarm-seconds", "0.1",
            "--cpu-seconds", "0", "--host-io-steps", "3", "--sequence-leg", "301", "--sequence-unique", "24", "--content-steps", "0", "--legs", ""]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -7,7 +7,7 @@ for round in $(seq 1 ${2:-3}); do
   for v in $1; do
     if [ "$v" = cur ]; then cp /tmp/keep.so orb_slam2_ros2_amd/liborbfe_hip.so; else cp tools/exp/libs/liborbfe_$v.so orb_slam2_ros2_amd/liborbfe_hip.so; fi
     echo -n "$v : "
-    timeout -k 10 400 python3 bench.py --steps 300 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' --content-steps 0 2>/dev/null | python3 -c "
+    timeout -k 10 400 python3 bench.py --full --steps 300 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' --content-steps 0 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); c=d['config']; print(round(d['value']), round(d['ms_per_step'],3), d['verified_pairs'], {k[6:-3]: c[k] for k in c if k.startswith('stage_')})"
   done
 done

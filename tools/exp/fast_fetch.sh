@@ -6,7 +6,7 @@ cp orb_slam2_ros2_amd/liborbfe_hip.so /tmp/keep.so
 for v in "$@"; do
   cp tools/exp/libs/liborbfe_$v.so orb_slam2_ros2_amd/liborbfe_hip.so
   rm -rf /tmp/prof_f
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/prof_f -- python3 bench.py --steps 4 --warmup 1 --prewarm-seconds 0.2 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' > /dev/null 2> /tmp/prof_f.err || tail -3 /tmp/prof_f.err
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/prof_f -- python3 bench.py --full --steps 4 --warmup 1 --prewarm-seconds 0.2 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' > /dev/null 2> /tmp/prof_f.err || { tail -3 /tmp/prof_f.err; break; }
   F=$(find /tmp/prof_f -name '*counter_collection.csv' | head -1)
   python3 - "$F" "$v" <<'PY'
 import csv, sys, collections

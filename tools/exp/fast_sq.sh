@@ -7,7 +7,7 @@ for v in "$@"; do
   cp tools/exp/libs/liborbfe_$v.so orb_slam2_ros2_amd/liborbfe_hip.so
   for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS"; do
     rm -rf /tmp/prof_sq
-    rocprofv3 --pmc $set --output-format csv -d /tmp/prof_sq -- python3 bench.py --steps 4 --warmup 1 --prewarm-seconds 0.2 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' > /dev/null 2> /tmp/prof_sq.err || tail -3 /tmp/prof_sq.err
+    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d /tmp/prof_sq -- python3 bench.py --full --steps 4 --warmup 1 --prewarm-seconds 0.2 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' > /dev/null 2> /tmp/prof_sq.err || { tail -3 /tmp/prof_sq.err; break 2; }
     F=$(find /tmp/prof_sq -name '*counter_collection.csv' | head -1)
     python3 - "$F" "$v" <<'PY'
 import csv, sys, collections

@@ -1,11 +1,12 @@
 #!/bin/bash
 # Runs on the GPU box: durations of every k_pose_only_reg launch of bench.py's latency leg, in launch order (kernel trace)
 R=${GRAFT_REPO_ROOT:-.}
-OUT=$R/gpurun_out
+OUT=${OUT:-$R/prof_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R
 rm -rf $OUT/prof_pd
-rocprofv3 --kernel-trace -d $OUT/prof_pd -- python3 bench.py --steps 2 --warmup 1 --prewarm-seconds 0.1 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs latency > /dev/null 2> $OUT/prof_pd.err
+timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/prof_pd -- python3 bench.py --full --steps 2 --warmup 1 --prewarm-seconds 0.1 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs latency > /dev/null 2> $OUT/prof_pd.err || exit 1
 DB=$(find $OUT/prof_pd -name "*.db" | head -1)
 python3 - "$DB" <<'PY'
 import sqlite3, sys

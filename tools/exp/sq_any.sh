@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
 rm -rf /tmp/prof_any
-timeout -k 10 300 rocprofv3 --pmc SQ_WAVES $1 --output-format csv -d /tmp/prof_any -- python3 bench.py --steps 4 --warmup 1 --prewarm-seconds 0.2 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' --content-steps 0 > /dev/null 2> /tmp/prof_any.err || tail -5 /tmp/prof_any.err
+timeout -k 10 300 rocprofv3 --pmc SQ_WAVES $1 --output-format csv -d /tmp/prof_any -- python3 bench.py --full --steps 4 --warmup 1 --prewarm-seconds 0.2 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs '' --content-steps 0 > /dev/null 2> /tmp/prof_any.err || tail -5 /tmp/prof_any.err
 F=$(find /tmp/prof_any -name '*counter_collection.csv' | head -1)
 python3 - "$F" "${2:-k_}" <<'PY'
 import csv, sys, collections

@@ -1,14 +1,14 @@
 #!/bin/bash
-# Runs on the GPU box: kernel + copy trace of bench.py's latency leg -> gpurun_out/<tag>_track_chain_timeline.txt (one orbfe_track_local_map call)
+# Runs on the GPU box: kernel + copy trace of bench.py's latency leg -> $OUT (default prof_out/)/<tag>_track_chain_timeline.txt (one orbfe_track_local_map call)
 set -e
 TAG=${1:-rX}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
-OUT=$R/gpurun_out
+OUT=${OUT:-$R/prof_out}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R
 rm -rf $OUT/prof_trk
-rocprofv3 --kernel-trace --memory-copy-trace -d $OUT/prof_trk -- python3 bench.py --steps 2 --warmup 1 --prewarm-seconds 0.1 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs latency > $OUT/${TAG}_track_bench.json 2> $OUT/prof_trk.err
+timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -d $OUT/prof_trk -- python3 bench.py --full --steps 2 --warmup 1 --prewarm-seconds 0.1 --cpu-seconds 0 --host-io-steps 0 --sequence-leg 0 --legs latency > $OUT/${TAG}_track_bench.json 2> $OUT/prof_trk.err || exit 1
 DB=$(find $OUT/prof_trk -name "*.db" | head -1)
 python3 - "$DB" > $OUT/${TAG}_track_chain_timeline.txt <<'PY'
 import sqlite3, sys
