@@ -104,7 +104,7 @@ typedef struct orbfe_level_info {
 int orbfe_abi_version(void);
 orbfe_status orbfe_create(const orbfe_config* cfg, orbfe_ctx** out);
 void orbfe_destroy(orbfe_ctx* ctx);
-const char* orbfe_last_error(const orbfe_ctx* ctx); /* ctx may be NULL: error of the last failed orbfe_create */
+const char* orbfe_last_error(const orbfe_ctx* ctx); /* ctx may be NULL: error of the last failed orbfe_create / orbfe_vocab_* call */
 
 orbfe_status orbfe_get_level_info(const orbfe_ctx* ctx, int32_t level, orbfe_level_info* out);
 orbfe_status orbfe_get_scale_factors(const orbfe_ctx* ctx, float* out, int32_t n);
@@ -553,6 +553,64 @@ typedef struct orbfe_map_ba_report {
 orbfe_status orbfe_map_local_ba(orbfe_ctx* ctx, const uint8_t* pb, size_t len, uint64_t kf_id, const orbfe_camera* cam,
                                 const volatile uint8_t* stop_flag, uint8_t* out, size_t cap, size_t* out_len,
                                 orbfe_map_ba_report* report);
+
+/* ---- bag of words: DBoW3's Vocabulary::transform on the device -----------------------------------
+ * VirtualFrame::computeBow (include/ORB_SLAM2/Frame.h:224-231) runs mpVoc->transform(mvLeftDescriptor, mBowVec, mFeatVec, 4) for
+ * searchByBow, every new keyframe and every relocalisation / loop query.  orbfe_vocab holds a vocabulary tree in the ORB-SLAM2 text
+ * format (`Path.Vocabulary: ORBvoc.txt`); it is host data plus ONE device copy per HIP device, uploaded on the first transform on that
+ * device and shared by every context there (a failed upload leaves nothing behind: the next call on that device tries again).
+ * orbfe_vocab_destroy frees every device copy; no call that uses the vocabulary may still be running or queued.  It restores the
+ * calling thread's current HIP device.
+ *
+ * Text format: line 1 `k L scoring weighting`; every further non-blank line is one node `parent_id is_leaf b0 .. b31 weight` (bytes in
+ * decimal, weight a decimal number -- [+-]digits[.digits][e[+-]digits], read independently of the locale; no nan / inf / hex).
+ * The root is the implicit node 0, node i is the i-th node line; a node's children keep file order; leaves get
+ * word ids 0, 1, .. in file order.  ORBFE_EBADARG (text in orbfe_last_error(NULL)) for: a malformed header; k outside 2..20 or L outside
+ * 1..10; scoring / weighting other than 0 0 (L1 norm, TF-IDF); is_leaf other than 0 / 1; parent_id >= own id or a leaf parent; more than
+ * k children under a node; an inner node (the root included) without children; depth > L; a byte outside 0..255; a truncated line or
+ * extra tokens.  Blank lines are skipped (DBoW2's `while (!f.eof())` loop makes a garbage node of a trailing empty line).             */
+typedef struct orbfe_vocab orbfe_vocab;
+typedef struct orbfe_vocab_info {
+  int32_t k, L;
+  int32_t n_nodes; /* root included */
+  int32_t n_words;
+} orbfe_vocab_info;
+orbfe_status orbfe_vocab_load_txt(const char* path, orbfe_vocab** out);
+orbfe_status orbfe_vocab_info_get(const orbfe_vocab* v, orbfe_vocab_info* out);
+/* The parsed arrays in node-id order, n_nodes entries each (any pointer may be NULL): parent (-1 for the root), is_leaf, desc
+ * [n_nodes][32] (zeros for the root), weight, word_id (-1 for inner nodes).                                                          */
+orbfe_status orbfe_vocab_export(const orbfe_vocab* v, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight, int32_t* word_id);
+void orbfe_vocab_destroy(orbfe_vocab* v);
+
+/* DBoW2 / DBoW3 TemplatedVocabulary::transform(features, v, fv, levelsup) for binary features under L1 / TF-IDF, bit-exact:
+ *   descent   from the root; at each node the Hamming-256 distance to every child in file order, the FIRST minimum (strict <); stop at a leaf
+ *   node      the node the path passes at level L - levelsup (the root if that is <= 0; the leaf itself if the leaf comes first -- DBoW
+ *             leaves it unset there, a documented decision)
+ *   skip      a feature whose leaf weight is not > 0 adds nothing (neither BowVector nor FeatureVector)
+ *   BowVector words ascending; a word hit c times holds w + w + .. + w (c terms in sequence, BowVector::addWeight); then L1: norm = the
+ *             sequential sum of |value| in ascending word order, value = value / norm when norm > 0
+ *   FeatureVector  nodes ascending, each node's feature indices ascending
+ * Outputs (host CSR, the capacity is the call's feature count / the context's n_features per slot): words / values [n_words]; nodes
+ * [n_nodes], node_offsets [n_nodes + 1] into features [number of features kept].  Any array pointer may be NULL.                   */
+typedef struct orbfe_bow_out {
+  uint32_t* words;        /* [cap]     */
+  double* values;         /* [cap]     */
+  int32_t* n_words;       /* [1]       */
+  uint32_t* nodes;        /* [cap]     */
+  int32_t* node_offsets;  /* [cap + 1] */
+  uint32_t* features;     /* [cap]     */
+  int32_t* n_nodes;       /* [1]       */
+} orbfe_bow_out;
+#define ORBFE_BOW_MAX_FEATURES 65535
+/* n host descriptors (n * 32 bytes), 0 <= n <= ORBFE_BOW_MAX_FEATURES (more: ORBFE_ECAPACITY), any levelsup >= 0; cap = n.           */
+orbfe_status orbfe_bow_transform(orbfe_ctx* ctx, const orbfe_vocab* v, const uint8_t* desc, int32_t n, int32_t levelsup,
+                                 const orbfe_bow_out* out);
+/* The descriptors the last extraction left in slots slot0, slot0 + slot_step, .. (n_slots of them), read on the device (no upload).
+ * slot_step 2 takes the left images of a batch of stereo pairs (pair p in slots 2p / 2p + 1) without the right ones.  Every out array is
+ * [n_slots][cap] with cap = orbfe_get_capacity(ctx) (node_offsets [n_slots][cap + 1]); n_words / n_nodes are [n_slots].  Slot rules as
+ * orbfe_fetch_batch.                                                                                                                 */
+orbfe_status orbfe_bow_slots(orbfe_ctx* ctx, const orbfe_vocab* v, int32_t slot0, int32_t n_slots, int32_t slot_step, int32_t levelsup,
+                             const orbfe_bow_out* out);
 
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated

@@ -111,6 +111,14 @@ class BatchResults(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("kps", "desc", "counts", "right_u", "depth", "n_matches")]
 
 
+class VocabInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("n_nodes", C.c_int32), ("n_words", C.c_int32)]
+
+
+class BowOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("words", "values", "n_words", "nodes", "node_offsets", "features", "n_nodes")]
+
+
 class BaEdgeOut(C.Structure):
     _fields_ = [("error", C.c_void_p), ("chi2", C.c_void_p), ("rho", C.c_void_p), ("j_point", C.c_void_p),
                 ("j_pose", C.c_void_p), ("depth_positive", C.c_void_p)]
@@ -123,8 +131,10 @@ EXPORTS = [
     "orbfe_host_alloc", "orbfe_host_alloc_on", "orbfe_host_free", "orbfe_recommended_hw_queues", "orbfe_stream_submit", "orbfe_stream_wait", "orbfe_stream_device_results", "orbfe_record_bytes", "orbfe_stream_pack_records",
     "orbfe_fetch_features", "orbfe_fetch_stereo", "orbfe_device_results", "orbfe_match_bruteforce", "orbfe_ba_eval_edges", "orbfe_ba_build_system", "orbfe_ba_local_optimize", "orbfe_pose_only_optimize", "orbfe_search_in_area", "orbfe_search_in_area_features", "orbfe_search_in_area_features_ex", "orbfe_extract_color", "orbfe_frame_rgbd", "orbfe_project_map_points", "orbfe_track_local_map",
     "orbfe_map_pb_summary", "orbfe_map_pb_reencode", "orbfe_map_pb_to_txt", "orbfe_map_txt_to_pb", "orbfe_map_local_graph", "orbfe_map_local_ba",
+    "orbfe_vocab_load_txt", "orbfe_vocab_info_get", "orbfe_vocab_export", "orbfe_vocab_destroy", "orbfe_bow_transform", "orbfe_bow_slots",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates",
 ]
+BOW_MAX_FEATURES = 65535
 
 _lib = None
 
@@ -207,6 +217,13 @@ def load() -> C.CDLL:
     L.orbfe_map_local_graph.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.POINTER(i32 * 4), C.POINTER(MapGraph)]
     L.orbfe_map_local_ba.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_uint64, C.POINTER(Camera), vp, vp, C.c_size_t,
                                      C.POINTER(C.c_size_t), C.POINTER(MapBaReport)]
+    L.orbfe_vocab_load_txt.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.orbfe_vocab_info_get.argtypes = [vp, C.POINTER(VocabInfo)]
+    L.orbfe_vocab_export.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.orbfe_vocab_destroy.argtypes = [vp]
+    L.orbfe_vocab_destroy.restype = None
+    L.orbfe_bow_transform.argtypes = [vp, vp, vp, i32, i32, C.POINTER(BowOut)]
+    L.orbfe_bow_slots.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(BowOut)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -300,6 +317,59 @@ def map_local_graph(pb: bytes, kf_id: int) -> dict:
     _status(L.orbfe_map_local_graph(pb, len(pb), kf_id, C.byref(sizes), C.byref(mg)), "map_local_graph")
     g["n_group"] = n_group
     return g
+
+
+class Vocabulary:
+    """A DBoW vocabulary tree in the ORB-SLAM2 text format (orbfe_vocab: host data + one device copy per HIP device, made on first use)."""
+
+    def __init__(self, handle):
+        self.lib = load()
+        self.h = handle
+
+    @classmethod
+    def load_txt(cls, path):
+        L, h = load(), C.c_void_p(None)
+        st = L.orbfe_vocab_load_txt(os.fsencode(path), C.byref(h))
+        if st != ORBFE_OK:
+            raise OrbfeError(st, L.orbfe_last_error(None).decode())
+        return cls(h)
+
+    def info(self) -> dict:
+        vi = VocabInfo()
+        _status(self.lib.orbfe_vocab_info_get(self.h, C.byref(vi)), "vocab_info")
+        return {k: getattr(vi, k) for k, _ in VocabInfo._fields_}
+
+    def export(self) -> dict:
+        """the parsed arrays in node-id order: parent (-1 root), is_leaf, desc [n][32], weight, word_id (-1 inner nodes)"""
+        n = self.info()["n_nodes"]
+        a = dict(parent=np.zeros(n, np.int32), is_leaf=np.zeros(n, np.uint8), desc=np.zeros((n, 32), np.uint8), weight=np.zeros(n),
+                 word_id=np.zeros(n, np.int32))
+        _status(self.lib.orbfe_vocab_export(self.h, *[ptr(a[k]) for k in ("parent", "is_leaf", "desc", "weight", "word_id")]), "vocab_export")
+        return a
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbfe_vocab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bow_arrays(n_img, cap):
+    c = max(cap, 1)
+    return dict(words=np.zeros((n_img, c), np.uint32), values=np.zeros((n_img, c)), n_words=np.zeros(n_img, np.int32),
+                nodes=np.zeros((n_img, c), np.uint32), node_offsets=np.zeros((n_img, cap + 1), np.int32),
+                features=np.zeros((n_img, c), np.uint32), n_nodes=np.zeros(n_img, np.int32))
+
+
+def _bow_split(a, i):
+    nw, nn = int(a["n_words"][i]), int(a["n_nodes"][i])
+    off = a["node_offsets"][i, :nn + 1].copy()
+    return (a["words"][i, :nw].copy(), a["values"][i, :nw].copy(), a["nodes"][i, :nn].copy(), off, a["features"][i, :off[-1]].copy())
 
 
 class Context:
@@ -855,6 +925,25 @@ class Context:
         self._check(self.lib.orbfe_frame_rgbd_image(self.h, slot, img.ctypes.data, img.strides[0], color_order, C.byref(cm), ptr(depth), dtype,
                                                     stride, depth_scale, ptr(kps), ptr(desc), C.byref(n), ptr(d), ptr(ru)))
         return kps[:n.value].copy(), desc[:n.value].copy(), d, ru
+
+    # ---- bag of words (DBoW3 Vocabulary::transform) ------------------------------------------------------
+    def bow_transform(self, vocab: Vocabulary, desc, levelsup=4):
+        """(words, values, nodes, offsets, features) of n host descriptors [n][32]: BowVector words / values, FeatureVector nodes and
+        their feature lists features[offsets[i]:offsets[i + 1]]"""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(d)
+        a = _bow_arrays(1, n)
+        o = BowOut(*[ptr(a[k]).value for k, _ in BowOut._fields_])
+        self._check(self.lib.orbfe_bow_transform(self.h, vocab.h, ptr(d), n, int(levelsup), C.byref(o)))
+        return _bow_split(a, 0)
+
+    def bow_slots(self, vocab: Vocabulary, slot0, n, levelsup=4, step=1):
+        """bow_transform of the descriptors the last extraction left in slots slot0, slot0 + step, .. (n slots), read on the device: a list
+        of n tuples (step 2: the left images of a batch of stereo pairs)"""
+        a = _bow_arrays(n, self.n_features)
+        o = BowOut(*[ptr(a[k]).value for k, _ in BowOut._fields_])
+        self._check(self.lib.orbfe_bow_slots(self.h, vocab.h, slot0, n, step, int(levelsup), C.byref(o)))
+        return [_bow_split(a, i) for i in range(n)]
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -211,3 +211,19 @@ struct LmLaunch {
   const volatile uint8_t* abort_flag;  // device address of a host-mapped byte the caller's stop flag is mirrored into
   BaParamsDev prm;
 };
+
+// ---- bag of words (k_bow.hip, orbfe_bow.hip) --------------------------------------------------------------------------------------
+// Device layout of a vocabulary: every node but the root has a POSITION; the children of a node occupy consecutive positions in file order,
+// so one node's children are one contiguous block of 32-byte descriptors (desc[2 p], desc[2 p + 1]) and of records.
+struct BowChild {
+  int32_t first;  // position of the node's first child (-1: leaf)
+  int32_t nc;     // its number of children (0: leaf)
+  uint32_t word;  // word id (leaves; 0xFFFFFFFF for inner nodes)
+  uint32_t node;  // node id (line order of the text file, root = 0)
+};
+struct BowVocabDev {
+  const BowChild* rec;
+  const uint4* desc;
+  const double* weight;  // per position: the node's weight
+  int32_t root_first, root_nc, L;
+};

@@ -552,7 +552,7 @@ class ORBMatcher {
   }
 
   // ORBMatcher::searchByBow (src/ORBMatcher.cc:170-253) given the two DBoW feature vectors (node id -> feature ids, ordered maps
-  // like DBoW3::FeatureVector); the BoW transform stays with DBoW3.  good* = map point non-null and not bad, inMap* = isInMap().
+  // like DBoW3::FeatureVector); the BoW transform is the caller's (host/compat/DBoW3/DBoW3.h runs it on the device).  good* = map point non-null and not bad, inMap* = isInMap().
   std::vector<DMatch> searchByBow(orbfe_ctx* ctx, const std::vector<Descriptor>& descF, const std::vector<Descriptor>& descKF,
                                   const std::map<unsigned, std::vector<unsigned>>& featVecF,
                                   const std::map<unsigned, std::vector<unsigned>>& featVecKF, const std::vector<uint8_t>& goodF,
