@@ -612,6 +612,51 @@ orbfe_status orbfe_bow_transform(orbfe_ctx* ctx, const orbfe_vocab* v, const uin
 orbfe_status orbfe_bow_slots(orbfe_ctx* ctx, const orbfe_vocab* v, int32_t slot0, int32_t n_slots, int32_t slot_step, int32_t levelsup,
                              const orbfe_bow_out* out);
 
+/* ---- keyframe database: KeyFrameDB's place-recognition query on the device ------------------------------------------------------
+ * KeyFrameDB (src/KeyFrameDB.cc) answers Tracking::trackReLocalize (findRelocKfs, src/Tracking.cc:418) and LoopClosing::detectLoop
+ * (findLoopCloseKfs, src/LoopClosing.cc:224).  orbfe_kfdb holds keyframes keyed by a uint64 id -- each one's BowVector (words strictly
+ * ascending and < n_words, 0 .. ORBFE_BOW_MAX_FEATURES of them) -- on ONE device; any context on that device may query it (a context on
+ * another device: ORBFE_EBADARG).  One lock per database serialises add, erase, set_bad and query (the reference's mMutex).
+ *   add      keyframes as one CSR: keyframe i has words[offsets[i] .. offsets[i + 1]); an id already present is left as it is (OK: the
+ *            reference's std::set); capacity grows as needed.  An invalid keyframe (unsorted / repeated / out-of-vocabulary words, a
+ *            size beyond the limit, an id repeated inside the call) rejects the whole call with ORBFE_EBADARG and adds nothing.
+ *   set_bad  KeyFrame::isBad() as the database sees it (flags[i] != 0: bad); bad keyframes stay listed and every query skips them.
+ *            Unknown ids: ORBFE_EBADARG, nothing changed.
+ *   erase    removes the ids (unknown ids are ignored, as std::set::erase does).
+ *   query    the shared-word count of every listed keyframe that is not bad and not in `ignore`, then minWordFilter -- dropped when
+ *            (float)count < (float)((double)(float)max_count * 0.8) -- and, when min_score is not NULL (loop mode), minScoreFilter --
+ *            dropped when score < *min_score.  Survivors in ascending id order: id, count, score = DBoW's L1 score of (query, keyframe),
+ *            bit-equal to DBoW3::Vocabulary::l1Score(query, keyframe) (sequential sum in ascending word order).  *n_out is the number
+ *            of survivors even when it exceeds cap (ORBFE_ECAPACITY, and then nothing is written).  One upload and one download on
+ *            the context's stream.  Ignored ids that are not in the database are skipped.
+ *   score    the L1 score of the query against each chosen keyframe (bad or not); an id not in the database: ORBFE_EBADARG.
+ * The group filter (groupFilter, src/KeyFrameDB.cc:125-174) is host code over the survivors and each one's ordered covisible list (the
+ * caller's KeyFrame::getOrderedConnectedKfs(10) without null / bad entries): a group starts at survivor i with acc = 0 + score[i] and
+ * best = i; each covisible id that is a survivor (others are skipped) adds its score, a strictly greater score makes it the best;
+ * th2 = (max over groups of acc, floor 0) * 0.75; out = the best ids of the groups with acc > th2, ascending and unique
+ * (out has room for n).  No device, no context.                                                                                      */
+typedef struct orbfe_kfdb orbfe_kfdb;
+typedef struct orbfe_kfdb_query_in {
+  const uint32_t* words;      /* [n_words] strictly ascending                        */
+  const double* values;       /* [n_words]                                           */
+  int32_t n_words;            /* 0 .. ORBFE_BOW_MAX_FEATURES                         */
+  const uint64_t* ignore;     /* [n_ignore] ids left out of the count (any order)    */
+  int32_t n_ignore;
+  const double* min_score;    /* NULL: relocalisation; else loop mode with this floor */
+} orbfe_kfdb_query_in;
+orbfe_status orbfe_kfdb_create(int32_t device_id, int32_t n_words, orbfe_kfdb** out);
+void orbfe_kfdb_destroy(orbfe_kfdb* db);  /* no call on the database may still run */
+orbfe_status orbfe_kfdb_add(orbfe_kfdb* db, int32_t n_kf, const uint64_t* ids, const int64_t* offsets, const uint32_t* words,
+                            const double* values);
+orbfe_status orbfe_kfdb_set_bad(orbfe_kfdb* db, int32_t n, const uint64_t* ids, const uint8_t* flags);
+orbfe_status orbfe_kfdb_erase(orbfe_kfdb* db, int32_t n, const uint64_t* ids);
+orbfe_status orbfe_kfdb_size(orbfe_kfdb* db, int64_t* out);
+orbfe_status orbfe_kfdb_query(orbfe_ctx* ctx, orbfe_kfdb* db, const orbfe_kfdb_query_in* q, uint64_t* out_ids, int32_t* out_counts,
+                              double* out_scores, int64_t cap, int64_t* n_out);
+orbfe_status orbfe_kfdb_score(orbfe_ctx* ctx, orbfe_kfdb* db, const orbfe_kfdb_query_in* q, const uint64_t* ids, int32_t n, double* scores);
+orbfe_status orbfe_kfdb_group_filter(int64_t n, const uint64_t* ids, const double* scores, const int64_t* conn_offsets, const uint64_t* conn_ids,
+                                     uint64_t* out, int64_t* n_out);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

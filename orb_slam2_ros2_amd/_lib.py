@@ -119,6 +119,11 @@ class BowOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("words", "values", "n_words", "nodes", "node_offsets", "features", "n_nodes")]
 
 
+class KfdbQueryIn(C.Structure):
+    _fields_ = [("words", C.c_void_p), ("values", C.c_void_p), ("n_words", C.c_int32), ("ignore", C.c_void_p), ("n_ignore", C.c_int32),
+                ("min_score", C.c_void_p)]
+
+
 class BaEdgeOut(C.Structure):
     _fields_ = [("error", C.c_void_p), ("chi2", C.c_void_p), ("rho", C.c_void_p), ("j_point", C.c_void_p),
                 ("j_pose", C.c_void_p), ("depth_positive", C.c_void_p)]
@@ -132,6 +137,8 @@ EXPORTS = [
     "orbfe_fetch_features", "orbfe_fetch_stereo", "orbfe_device_results", "orbfe_match_bruteforce", "orbfe_ba_eval_edges", "orbfe_ba_build_system", "orbfe_ba_local_optimize", "orbfe_pose_only_optimize", "orbfe_search_in_area", "orbfe_search_in_area_features", "orbfe_search_in_area_features_ex", "orbfe_extract_color", "orbfe_frame_rgbd", "orbfe_project_map_points", "orbfe_track_local_map",
     "orbfe_map_pb_summary", "orbfe_map_pb_reencode", "orbfe_map_pb_to_txt", "orbfe_map_txt_to_pb", "orbfe_map_local_graph", "orbfe_map_local_ba",
     "orbfe_vocab_load_txt", "orbfe_vocab_info_get", "orbfe_vocab_export", "orbfe_vocab_destroy", "orbfe_bow_transform", "orbfe_bow_slots",
+    "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_set_bad", "orbfe_kfdb_erase", "orbfe_kfdb_size", "orbfe_kfdb_query",
+    "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates",
 ]
 BOW_MAX_FEATURES = 65535
@@ -224,6 +231,16 @@ def load() -> C.CDLL:
     L.orbfe_vocab_destroy.restype = None
     L.orbfe_bow_transform.argtypes = [vp, vp, vp, i32, i32, C.POINTER(BowOut)]
     L.orbfe_bow_slots.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(BowOut)]
+    L.orbfe_kfdb_create.argtypes = [i32, i32, C.POINTER(vp)]
+    L.orbfe_kfdb_destroy.argtypes = [vp]
+    L.orbfe_kfdb_destroy.restype = None
+    L.orbfe_kfdb_add.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.orbfe_kfdb_set_bad.argtypes = [vp, i32, vp, vp]
+    L.orbfe_kfdb_erase.argtypes = [vp, i32, vp]
+    L.orbfe_kfdb_size.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.orbfe_kfdb_query.argtypes = [vp, vp, C.POINTER(KfdbQueryIn), vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.orbfe_kfdb_score.argtypes = [vp, vp, C.POINTER(KfdbQueryIn), vp, i32, vp]
+    L.orbfe_kfdb_group_filter.argtypes = [C.c_int64, vp, vp, vp, vp, vp, C.POINTER(C.c_int64)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -357,6 +374,111 @@ class Vocabulary:
             self.close()
         except Exception:
             pass
+
+
+class KeyFrameDB:
+    """KeyFrameDB's place-recognition index on one device (orbfe_kfdb, include/orbfe.h): keyframes keyed by uint64 id, each one's BowVector
+    (the words / values that Context.bow_transform / bow_slots return).  Any Context on the same device queries it."""
+
+    def __init__(self, n_words, device_id=0):
+        self.lib = load()
+        h = C.c_void_p(None)
+        st = self.lib.orbfe_kfdb_create(int(device_id), int(n_words), C.byref(h))
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+        self.h = h
+        self.n_words = int(n_words)
+
+    def _check(self, st):
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbfe_kfdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, ids, words, values, offsets=None):
+        """one keyframe (ids an int, words / values its BowVector) or many as a CSR: keyframe i has words[offsets[i]:offsets[i + 1]]"""
+        if offsets is None:
+            ids = [int(ids)]
+            offsets = [0, len(words)]
+        i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        o = np.ascontiguousarray(offsets, np.int64)
+        w = np.ascontiguousarray(words, np.uint32)
+        v = np.ascontiguousarray(values, np.float64)
+        if len(o) != len(i) + 1 or len(w) != len(v) or (len(o) and o[-1] != len(w)):
+            raise ValueError("add: offsets must have len(ids) + 1 entries ending at len(words) == len(values)")
+        self._check(self.lib.orbfe_kfdb_add(self.h, len(i), ptr(i), ptr(o), ptr(w), ptr(v)))
+
+    def set_bad(self, ids, flags=True):
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(flags, np.uint8), i.shape), np.uint8)
+        self._check(self.lib.orbfe_kfdb_set_bad(self.h, len(i), ptr(i), ptr(f)))
+
+    def erase(self, ids):
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        self._check(self.lib.orbfe_kfdb_erase(self.h, len(i), ptr(i)))
+
+    def __len__(self):
+        n = C.c_int64(0)
+        self._check(self.lib.orbfe_kfdb_size(self.h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def _query_in(words, values, ignore, min_score):
+        w = np.ascontiguousarray(words, np.uint32)
+        v = np.ascontiguousarray(values, np.float64)
+        if len(w) != len(v):
+            raise ValueError("words and values differ in length")
+        ig = np.ascontiguousarray(np.asarray(list(ignore) if not isinstance(ignore, np.ndarray) else ignore, np.uint64).reshape(-1))
+        ms = None if min_score is None else np.array([float(min_score)], np.float64)
+        q = KfdbQueryIn(ptr(w).value if len(w) else None, ptr(v).value if len(v) else None, len(w), ptr(ig).value if len(ig) else None,
+                        len(ig), None if ms is None else ptr(ms).value)
+        return q, (w, v, ig, ms)   # the arrays stay alive with the structure
+
+    def query(self, ctx, words, values, ignore=(), min_score=None):
+        """(ids, counts, scores) of the survivors, ids ascending: relocalisation with min_score None, else loop mode"""
+        q, keep = self._query_in(words, values, ignore, min_score)
+        cap = max(len(self), 1)
+        ids, counts, scores = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap)
+        n = C.c_int64(0)
+        ctx._check(self.lib.orbfe_kfdb_query(ctx.h, self.h, C.byref(q), ptr(ids), ptr(counts), ptr(scores), cap, C.byref(n)))
+        k = n.value
+        return ids[:k].copy(), counts[:k].copy(), scores[:k].copy()
+
+    def score(self, ctx, words, values, ids):
+        """DBoW's L1 score of the query against each of the keyframes `ids`"""
+        q, keep = self._query_in(words, values, (), None)
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        out = np.zeros(len(i))
+        ctx._check(self.lib.orbfe_kfdb_score(ctx.h, self.h, C.byref(q), ptr(i), len(i), ptr(out)))
+        return out
+
+
+def group_filter(ids, scores, connected):
+    """KeyFrameDB::groupFilter on the host: ids / scores of the survivors, connected[i] the ordered covisible ids of survivor i.
+    Returns the candidate ids, ascending."""
+    i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+    s = np.ascontiguousarray(scores, np.float64).reshape(-1)
+    if len(connected) != len(i) or len(s) != len(i):
+        raise ValueError("group_filter: ids, scores and connected differ in length")
+    off = np.zeros(len(i) + 1, np.int64)
+    off[1:] = np.cumsum([len(c) for c in connected])
+    conn = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint64).reshape(-1) for c in connected]) if len(connected) else np.zeros(0), np.uint64)
+    out = np.zeros(max(len(i), 1), np.uint64)
+    n = C.c_int64(0)
+    L = load()
+    st = L.orbfe_kfdb_group_filter(len(i), ptr(i), ptr(s), ptr(off), ptr(conn) if len(conn) else None, ptr(out), C.byref(n))
+    if st != ORBFE_OK:
+        raise OrbfeError(st, L.orbfe_last_error(None).decode())
+    return out[:n.value].copy()
 
 
 def _bow_arrays(n_img, cap):

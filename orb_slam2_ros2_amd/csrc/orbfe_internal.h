@@ -227,3 +227,25 @@ struct BowVocabDev {
   const double* weight;  // per position: the node's weight
   int32_t root_first, root_nc, L;
 };
+
+// ---- keyframe database (k_kfdb.hip, orbfe_kfdb.hip) ------------------------------------------------------------------------------
+// One slot per keyframe; its sorted words and their values sit at [off, off + len) of the database's word / value pools.
+struct KfSlot {
+  uint64_t off;
+  uint32_t len;
+  uint32_t flags;  // KFDB_LIVE | KFDB_BAD; a free slot has neither
+};
+#define KFDB_LIVE 1u
+#define KFDB_BAD 2u
+// The query's device header: the grid-wide maximum of the shared-word counts (k_kfdb_count's atomicMax, read by the NEXT launch) and the
+// number of survivors k_kfdb_score has claimed.  Zeroed by the query's upload.
+struct KfdbHdr {
+  uint32_t max_count;
+  uint32_t n_out;
+};
+// one survivor: its slot (the host maps slots to ids), shared-word count and score
+struct KfdbRec {
+  uint32_t slot;
+  int32_t count;
+  double score;
+};
