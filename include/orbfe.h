@@ -657,6 +657,41 @@ orbfe_status orbfe_kfdb_score(orbfe_ctx* ctx, orbfe_kfdb* db, const orbfe_kfdb_q
 orbfe_status orbfe_kfdb_group_filter(int64_t n, const uint64_t* ids, const double* scores, const int64_t* conn_offsets, const uint64_t* conn_ids,
                                      uint64_t* out, int64_t* n_out);
 
+/* ---- EPnP RANSAC (PnPSolver + Ransac<PnPRet>, src/PnPSolver.cc, include/ORB_SLAM2/Ransac.hpp) --------------------------------------
+ * One orbfe_pnp set holds the PnP problems of a relocalisation -- one per candidate keyframe, in the order Tracking creates its
+ * solvers -- on ONE device: problem i has the points [offsets[i], offsets[i + 1]) of xyz (map points, world frame), uv (keypoints)
+ * and octave (0 .. n_levels - 1, the threshold (float)(5.991 * level_sigma2[octave])), 0 .. ORBFE_PNP_MAX_POINTS of them.  params
+ * NULL: setRansacParams() (min set 4, at most 100 iterations, ratio 0.4, probability 0.99); min_set must be 4.  One upload.
+ *   iterate  Ransac::iterate(n_iterations, modelRet, bNoMore, vnInlierIndices) of one problem, exactly: pose
+ *            (Rcw row-major, then tcw) and has_pose (0: the empty cv::Mats) are in / out, as are inliers[0 .. *n_inliers) (problem-local
+ *            indices, the list is appended to, duplicates included); *no_more is only ever set to 1; *ret the return value.  cap: room in
+ *            inliers; a longer result is ORBFE_ECAPACITY with *n_inliers the size needed and nothing changed.  An iterate call that is
+ *            not the predicted one (another problem or n, a non-empty entry pose or list, an engine moved since) starts a new
+ *            speculation: the schedule Tracking runs -- round-robin over the live problems, ascending, n_iterations each, no refine
+ *            success -- in one upload, two launches and one download, replayed call by call from then on.  Speculation only changes
+ *            the speed, never a result.
+ *   engine   the process-wide sampling engine (Ransac<PnPRet>'s static std::default_random_engine, default seed: state 1): get and / or
+ *            set its state (1 .. 2^31 - 2).  One lock serialises the engine and every set's iterate.
+ *   stats    launch sequences and hypotheses evaluated on the device so far.
+ * Errors: ORBFE_EBADARG (NULL pointers, problem out of range, octave out of range, min_set != 4, inlier index out of range, engine
+ * state out of range), ORBFE_EDEVICE (no device, HIP failure), ORBFE_ENOMEM, ORBFE_ECAPACITY (inliers too small).                     */
+#define ORBFE_PNP_MAX_POINTS 65536
+typedef struct orbfe_pnp orbfe_pnp;
+typedef struct orbfe_pnp_params {
+  int32_t min_set;        /* mnMinSet (4)          */
+  int32_t max_iterations; /* nMaxIterations (100)  */
+  float ratio;            /* fRatio (0.4)          */
+  float prob;             /* fProb (0.99)          */
+} orbfe_pnp_params;
+orbfe_status orbfe_pnp_create(int32_t device_id, int32_t n_problems, const int64_t* offsets /*[n_problems + 1]*/, const float* xyz /*[N][3]*/,
+                              const float* uv /*[N][2]*/, const int32_t* octave /*[N]*/, const float* level_sigma2, int32_t n_levels,
+                              const orbfe_camera* cam /* fx fy cx cy */, const orbfe_pnp_params* params, orbfe_pnp** out);
+void orbfe_pnp_destroy(orbfe_pnp* set);  /* no call on the set may still run */
+orbfe_status orbfe_pnp_iterate(orbfe_pnp* set, int32_t problem, int32_t n_iterations, float* pose /*[12] in/out*/, int32_t* has_pose,
+                               int32_t* inliers, int64_t* n_inliers, int64_t cap, int32_t* ret, int32_t* no_more);
+orbfe_status orbfe_pnp_engine(uint32_t* get, const uint32_t* set);
+orbfe_status orbfe_pnp_stats(orbfe_pnp* set, int64_t* launches, int64_t* hypotheses);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

@@ -139,6 +139,7 @@ EXPORTS = [
     "orbfe_vocab_load_txt", "orbfe_vocab_info_get", "orbfe_vocab_export", "orbfe_vocab_destroy", "orbfe_bow_transform", "orbfe_bow_slots",
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_set_bad", "orbfe_kfdb_erase", "orbfe_kfdb_size", "orbfe_kfdb_query",
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
+    "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates",
 ]
 BOW_MAX_FEATURES = 65535
@@ -241,6 +242,12 @@ def load() -> C.CDLL:
     L.orbfe_kfdb_query.argtypes = [vp, vp, C.POINTER(KfdbQueryIn), vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.orbfe_kfdb_score.argtypes = [vp, vp, C.POINTER(KfdbQueryIn), vp, i32, vp]
     L.orbfe_kfdb_group_filter.argtypes = [C.c_int64, vp, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.orbfe_pnp_create.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, C.POINTER(Camera), C.POINTER(PnpParams), C.POINTER(vp)]
+    L.orbfe_pnp_destroy.argtypes = [vp]
+    L.orbfe_pnp_destroy.restype = None
+    L.orbfe_pnp_iterate.argtypes = [vp, i32, i32, vp, C.POINTER(i32), vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(i32), C.POINTER(i32)]
+    L.orbfe_pnp_engine.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.orbfe_pnp_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -374,6 +381,87 @@ class Vocabulary:
             self.close()
         except Exception:
             pass
+
+
+class PnpParams(C.Structure):
+    _fields_ = [("min_set", C.c_int32), ("max_iterations", C.c_int32), ("ratio", C.c_float), ("prob", C.c_float)]
+
+
+class PnPSet:
+    """The PnPSolvers of one relocalisation on one device (orbfe_pnp, include/orbfe.h): problem i has the points
+    [offsets[i], offsets[i + 1]) of xyz (world) / uv (keypoints) / octave.  cam = (fx, fy, cx, cy); params = (min_set, max_iterations,
+    ratio, prob) or None for setRansacParams()'s defaults."""
+
+    def __init__(self, offsets, xyz, uv, octave, level_sigma2, cam, params=None, device_id=0):
+        self.lib = load()
+        o = np.ascontiguousarray(offsets, np.int64)
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        oc = np.ascontiguousarray(octave, np.int32).reshape(-1)
+        s2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(o) < 1 or o[-1] != len(x) or len(u) != len(x) or len(oc) != len(x):
+            raise ValueError("PnPSet: offsets must end at len(xyz) == len(uv) == len(octave)")
+        self.sizes = np.diff(o)
+        cm = Camera(*(float(v) for v in cam), 0, 0, 0, 0, 0, 0)
+        pp = None if params is None else C.byref(PnpParams(*params))
+        h = C.c_void_p(None)
+        st = self.lib.orbfe_pnp_create(int(device_id), len(o) - 1, ptr(o), ptr(x), ptr(u), ptr(oc), ptr(s2), len(s2), C.byref(cm), pp,
+                                       C.byref(h))
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+        self.h = h
+
+    def _check(self, st):
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbfe_pnp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def iterate(self, problem, n, pose=None, inliers=None):
+        """Ransac::iterate(n, modelRet, bNoMore, vnInlierIndices) of one problem: (ret, no_more, Rcw (3, 3) float32 or None,
+        tcw (3,) float32 or None, inliers int32).  pose: None (empty Mats) or (Rcw, tcw); inliers: the entry list (appended to)."""
+        ent = np.zeros(0, np.int32) if inliers is None else np.ascontiguousarray(inliers, np.int32).reshape(-1)
+        cap = len(ent) + (int(n) + 2) * int(self.sizes[problem]) + 1
+        buf = np.zeros(cap, np.int32)
+        buf[:len(ent)] = ent
+        pz = np.zeros(12, np.float32)
+        has = C.c_int32(0)
+        if pose is not None:
+            pz[:9] = np.asarray(pose[0], np.float32).reshape(9)
+            pz[9:] = np.asarray(pose[1], np.float32).reshape(3)
+            has.value = 1
+        k = C.c_int64(len(ent))
+        ret, nm = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.orbfe_pnp_iterate(self.h, int(problem), int(n), ptr(pz), C.byref(has), ptr(buf), C.byref(k), cap, C.byref(ret),
+                                               C.byref(nm)))
+        R, t = (pz[:9].reshape(3, 3).copy(), pz[9:].copy()) if has.value else (None, None)
+        return bool(ret.value), bool(nm.value), R, t, buf[:k.value].copy()
+
+    def stats(self):
+        """(launch sequences, hypotheses evaluated on the device)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.orbfe_pnp_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def pnp_engine(state=None):
+    """the process-wide PnP sampling engine's state (minstd_rand0's x); with `state`, set it first and return the old one"""
+    L = load()
+    g = C.c_uint32(0)
+    s = None if state is None else C.c_uint32(int(state))
+    st = L.orbfe_pnp_engine(C.byref(g), None if s is None else C.byref(s))
+    if st != ORBFE_OK:
+        raise OrbfeError(st, L.orbfe_last_error(None).decode())
+    return g.value
 
 
 class KeyFrameDB:

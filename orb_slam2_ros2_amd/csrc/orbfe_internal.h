@@ -249,3 +249,31 @@ struct KfdbRec {
   int32_t count;
   double score;
 };
+
+// ---- EPnP RANSAC (k_pnp.hip, orbfe_pnp.hip) ---------------------------------------------------------------------------------------
+// One problem (PnPSolver) of a set: its points at [off, off + n) of the set's xyz / uv / threshold arrays, an inlier mask of `words`
+// uint64 words, mnMinInlier.
+struct PnpProb {
+  int32_t off, n, words, min_inlier;
+};
+// One hypothesis of a speculated schedule: four problem-local sample indices or, with given = 1, a pose to count (the entry pose of the
+// first call).  Its inlier mask sits at mask_off (in words) of the hypothesis masks, its refine mask at the same place of the refine masks.
+struct PnpHyp {
+  int32_t prob, given, mask_off, pad;
+  int32_t idx[4];
+  float pose[12];  // R row-major, then t
+};
+// One speculated iterate call: hypotheses [h0, h0 + nh), the entry pose's record (-1: none), the entry list at [entry_off, + entry_len)
+// of the uploaded indices, the list scratch [list_off, + list_cap) of the call.
+struct PnpCall {
+  int32_t prob, h0, nh, entry_hyp;
+  int32_t entry_off, entry_len;
+  int64_t list_off, list_cap;
+};
+// What the device found for one hypothesis: Phase A's pose / count / degenerate flag, Phase B's refine (refined = 1 when it ran).
+struct PnpOut {
+  float pose[12];
+  int32_t count, degen, refined, ref_degen;
+  int32_t ref_count, err, pad0, pad1;
+  float ref_pose[12];
+};

@@ -1,0 +1,478 @@
+// orbfe_pnp.hip -- host side of the EPnP RANSAC sets (include/orbfe.h): setRansacParams, the process-wide sampling engine, the speculated
+// schedule (one upload, two launches, one download) and the exact replay of every Ransac<PnPRet>::iterate call from its records.
+// The kernels: k_pnp.hip.
+#include <emmintrin.h>
+
+#include "orbfe_ctx.h"
+
+void launch_pnp(hipStream_t st, const PnpHyp* hyps, int n_hyp, const PnpCall* calls, int n_calls, const PnpProb* probs, const float* xyz,
+                const float* uv, const float* thr, const float cam[4], const int* entry, PnpOut* out, uint64_t* masks, uint64_t* ref_masks,
+                int* lists);
+
+namespace {
+
+// Ransac<PnPRet>'s function-local static std::default_random_engine (P6): one per process, shared by every set, behind one lock that
+// also serialises every set's iterate.
+std::mutex g_pnp_mu;
+uint32_t g_engine = 1;
+
+// minstd_rand0 and libstdc++'s uniform_int_distribution<size_t>(0, n - 1) (the scaling path: minstd's range is not 2^32 - 1)
+inline uint32_t minstd(uint32_t& x) {
+  x = (uint32_t)((uint64_t)x * 16807u % 2147483647u);
+  return x;
+}
+inline uint32_t uniform_int(uint32_t& x, uint32_t n) {
+  const uint64_t urngrange = 2147483645u, uerange = n;
+  const uint64_t scaling = urngrange / uerange, past = uerange * scaling;
+  uint64_t r;
+  do r = (uint64_t)minstd(x) - 1u;
+  while (r >= past);
+  return (uint32_t)(r / scaling);
+}
+void random_sample(uint32_t& x, uint32_t n, int32_t out[4]) {
+  int k = 0;
+  while (k != 4) {
+    const int32_t r = (int32_t)uniform_int(x, n);
+    bool seen = false;
+    for (int i = 0; i < k; ++i) seen |= out[i] == r;
+    if (!seen) out[k++] = r;
+  }
+}
+
+// setRansacParams(): its float / double mix, cvRound as cvtsd2si
+void ransac_params(int32_t N, const orbfe_pnp_params& p, int32_t* min_inlier, int32_t* max_it) {
+  *min_inlier = (int32_t)std::max((float)p.min_set, (float)N * p.ratio);
+  const float r = (float)*min_inlier / (float)N;
+  if (r >= 1) {
+    *max_it = 0;
+    return;
+  }
+  const double q = std::log(1 - p.prob) / std::log(1 - std::pow(r, p.min_set));
+  *max_it = std::min(p.max_iterations, _mm_cvtsd_si32(_mm_set_sd(q)));
+}
+
+struct Prob {
+  int32_t off = 0, n = 0, words = 0, min_inlier = 0, max_it = 0;
+  int32_t cur = 0, best = 0;
+  bool called = false;
+  float best_pose[12] = {};
+  std::vector<int32_t> best_list;
+};
+
+// what one speculated call found: its hypotheses [h0, h0 + nh) of the download, the engine before it and after each hypothesis
+struct CallRec {
+  int32_t prob, n, h0, nh, entry_hyp;
+  uint32_t engine_start;
+  std::vector<uint32_t> after;
+};
+
+}  // namespace
+
+struct orbfe_pnp {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  float cam[4] = {};
+  std::vector<Prob> probs;
+  // device: the problems' points, thresholds and records
+  float *d_xyz = nullptr, *d_uv = nullptr, *d_thr = nullptr;
+  PnpProb* d_probs = nullptr;
+  uint8_t* d_io = nullptr;  // a speculation's upload, results and list scratch
+  size_t io_bytes = 0;
+  uint8_t* h_io = nullptr;  // its page-locked staging
+  size_t h_bytes = 0;
+  // the speculation being replayed
+  std::vector<CallRec> recs;
+  size_t next = 0;
+  std::vector<PnpHyp> hyps;
+  std::vector<PnpOut> out;
+  std::vector<uint64_t> masks, ref_masks;
+  int64_t launches = 0, hypotheses = 0;
+};
+
+namespace {
+
+orbfe_status io_reserve(orbfe_pnp* s, size_t dev_bytes, size_t host_bytes) {
+  if (s->io_bytes < dev_bytes) {
+    if (s->d_io) (void)hipFree(s->d_io);
+    s->d_io = nullptr;
+    s->io_bytes = 0;
+    const size_t b = std::max<size_t>(dev_bytes + dev_bytes / 2, 1 << 20);
+    HIP_TRY(nullptr, hipMalloc((void**)&s->d_io, b));
+    s->io_bytes = b;
+  }
+  if (s->h_bytes < host_bytes) {
+    if (s->h_io) (void)hipHostFree(s->h_io);
+    s->h_io = nullptr;
+    s->h_bytes = 0;
+    const size_t b = std::max<size_t>(host_bytes + host_bytes / 2, 1 << 20);
+    HIP_TRY(nullptr, hipHostMalloc((void**)&s->h_io, b, hipHostMallocDefault));
+    s->h_bytes = b;
+  }
+  return ORBFE_OK;
+}
+
+bool alive(const Prob& p, int32_t cur, bool called) { return p.n >= 4 ? (cur < p.max_it || !called) : !called; }
+
+constexpr size_t kMaxHyps = 1 << 17;  // one speculation covers at most this many hypotheses (the rest: a later one)
+
+// Speculate from the call (p, n, entry state): the schedule Tracking will most likely run -- round-robin over the live problems,
+// ascending, n each, no refine success -- its samples drawn from a copy of the engine, then one upload, Phase A + B, one download.
+orbfe_status speculate(orbfe_pnp* s, int32_t p, int32_t n, const float* pose, bool has_pose, const int32_t* entry, int64_t entry_len) {
+  s->recs.clear();
+  s->next = 0;
+  s->hyps.clear();
+  const int P = (int)s->probs.size();
+  std::vector<int32_t> cur(P);
+  std::vector<char> called(P);
+  for (int q = 0; q < P; ++q) {
+    cur[q] = s->probs[q].cur;
+    called[q] = s->probs[q].called;
+  }
+  uint32_t eng = g_engine;
+  std::vector<PnpCall> calls;
+  int64_t list_total = 0;
+  auto add_call = [&](int32_t q, bool first) {
+    const Prob& pr = s->probs[q];
+    CallRec r{q, n, 0, 0, -1, eng, {}};
+    PnpCall c{q, 0, 0, -1, 0, 0, 0, 0};
+    if (first && has_pose && pr.n >= 4) {
+      PnpHyp h{};
+      h.prob = q;
+      h.given = 1;
+      std::memcpy(h.pose, pose, sizeof h.pose);
+      r.entry_hyp = c.entry_hyp = (int32_t)s->hyps.size();
+      s->hyps.push_back(h);
+    }
+    r.h0 = c.h0 = (int32_t)s->hyps.size();
+    const int32_t k = pr.n >= 4 ? std::max(0, std::min(n, pr.max_it - cur[q])) : 0;
+    for (int32_t i = 0; i < k; ++i) {
+      PnpHyp h{};
+      h.prob = q;
+      random_sample(eng, (uint32_t)pr.n, h.idx);
+      r.after.push_back(eng);
+      s->hyps.push_back(h);
+    }
+    r.nh = c.nh = k;
+    c.entry_off = 0;
+    c.entry_len = first ? (int32_t)entry_len : 0;
+    c.list_off = list_total;
+    c.list_cap = c.entry_len + (int64_t)(k + 1) * pr.n;
+    list_total += c.list_cap;
+    cur[q] += k;
+    called[q] = 1;
+    s->recs.push_back(std::move(r));
+    calls.push_back(c);
+  };
+  add_call(p, true);
+  // the rest of this round, then whole rounds, while a problem is live
+  for (int q = p + 1; q < P && s->hyps.size() < kMaxHyps; ++q)
+    if (alive(s->probs[q], cur[q], called[q])) add_call(q, false);
+  for (bool any = true; any && s->hyps.size() < kMaxHyps;) {
+    any = false;
+    for (int q = 0; q < P && s->hyps.size() < kMaxHyps; ++q)
+      if (alive(s->probs[q], cur[q], called[q])) {
+        add_call(q, false);
+        any = true;
+      }
+  }
+  // mask offsets
+  int64_t words = 0;
+  for (PnpHyp& h : s->hyps) {
+    h.mask_off = (int32_t)words;
+    words += s->probs[h.prob].words;
+  }
+  if (words > 0x7FFFFFFF) return fail(nullptr, ORBFE_ECAPACITY, "pnp_iterate: speculation too large");
+  const size_t nh = s->hyps.size(), nc = calls.size();
+  // upload: hyps | calls | entry list;  download: out | masks | refine masks;  device only: list scratch
+  const size_t o_h = 0, o_c = align_up(nh * sizeof(PnpHyp), 256), o_e = o_c + align_up(nc * sizeof(PnpCall), 256);
+  const size_t up = o_e + align_up((size_t)std::max<int64_t>(entry_len, 1) * 4, 256);
+  const size_t o_out = up, o_m = o_out + align_up(nh * sizeof(PnpOut), 256), o_rm = o_m + align_up((size_t)words * 8, 256);
+  const size_t o_l = o_rm + align_up((size_t)words * 8, 256), total = o_l + (size_t)std::max<int64_t>(list_total, 1) * 4;
+  TRY(io_reserve(s, total, o_l));
+  uint8_t* h = s->h_io;
+  uint8_t* d = s->d_io;
+  if (nh) std::memcpy(h + o_h, s->hyps.data(), nh * sizeof(PnpHyp));
+  std::memcpy(h + o_c, calls.data(), nc * sizeof(PnpCall));
+  if (entry_len) std::memcpy(h + o_e, entry, (size_t)entry_len * 4);
+  HIP_TRY(nullptr, hipSetDevice(s->device));
+  HIP_TRY(nullptr, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s->stream));
+  launch_pnp(s->stream, (const PnpHyp*)(d + o_h), (int)nh, (const PnpCall*)(d + o_c), (int)nc, s->d_probs, s->d_xyz, s->d_uv, s->d_thr, s->cam,
+             (const int*)(d + o_e), (PnpOut*)(d + o_out), (uint64_t*)(d + o_m), (uint64_t*)(d + o_rm), (int*)(d + o_l));
+  HIP_TRY(nullptr, hipGetLastError());
+  HIP_TRY(nullptr, hipMemcpyAsync(h + o_out, d + o_out, o_l - o_out, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(nullptr, hipStreamSynchronize(s->stream));
+  s->out.resize(nh);
+  s->masks.resize((size_t)words);
+  s->ref_masks.resize((size_t)words);
+  if (nh) std::memcpy(s->out.data(), h + o_out, nh * sizeof(PnpOut));
+  if (words) {
+    std::memcpy(s->masks.data(), h + o_m, (size_t)words * 8);
+    std::memcpy(s->ref_masks.data(), h + o_rm, (size_t)words * 8);
+  }
+  s->launches += 1;
+  s->hypotheses += (int64_t)nh;
+  return ORBFE_OK;
+}
+
+void append_bits(const uint64_t* m, int32_t words, std::vector<int32_t>& list) {
+  for (int32_t w = 0; w < words; ++w)
+    for (uint64_t b = m[w]; b; b &= b - 1) list.push_back(w * 64 + __builtin_ctzll(b));
+}
+
+}  // namespace
+
+extern "C" {
+
+orbfe_status orbfe_pnp_create(int32_t device_id, int32_t n_problems, const int64_t* offsets, const float* xyz, const float* uv,
+                              const int32_t* octave, const float* level_sigma2, int32_t n_levels, const orbfe_camera* cam,
+                              const orbfe_pnp_params* params, orbfe_pnp** out) {
+  if (!out || n_problems < 0 || !offsets || !cam || (n_levels > 0 && !level_sigma2) || n_levels < 0)
+    return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: bad arguments");
+  *out = nullptr;
+  const orbfe_pnp_params prm = params ? *params : orbfe_pnp_params{4, 100, 0.4f, 0.99f};
+  if (prm.min_set != 4) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: min_set %d (EPnP samples 4 points)", prm.min_set);
+  if (offsets[0] != 0) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: offsets[0] must be 0");
+  for (int32_t i = 0; i < n_problems; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > ORBFE_PNP_MAX_POINTS)
+      return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: problem %d has %lld points (0 .. %d)", i, (long long)(offsets[i + 1] - offsets[i]),
+                  ORBFE_PNP_MAX_POINTS);
+  const int64_t total = offsets[n_problems];
+  if (total > 0x3FFFFFFF) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: %lld points in all", (long long)total);
+  if (total > 0 && (!xyz || !uv || !octave)) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: NULL points");
+  for (int64_t i = 0; i < total; ++i)
+    if (octave[i] < 0 || octave[i] >= n_levels)
+      return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: point %lld has octave %d of %d levels", (long long)i, octave[i], n_levels);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, ORBFE_EDEVICE, "orbfe_pnp_create: no HIP device (this library has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_create: device %d of %d", device_id, ndev);
+  std::unique_ptr<orbfe_pnp> s(new (std::nothrow) orbfe_pnp());
+  if (!s) return fail(nullptr, ORBFE_ENOMEM, "orbfe_pnp_create: out of memory");
+  s->device = device_id;
+  s->cam[0] = cam->fx;
+  s->cam[1] = cam->fy;
+  s->cam[2] = cam->cx;
+  s->cam[3] = cam->cy;
+  s->probs.resize((size_t)n_problems);
+  std::vector<PnpProb> dp((size_t)n_problems);
+  for (int32_t i = 0; i < n_problems; ++i) {
+    Prob& p = s->probs[(size_t)i];
+    p.off = (int32_t)offsets[i];
+    p.n = (int32_t)(offsets[i + 1] - offsets[i]);
+    p.words = (p.n + 63) / 64;
+    ransac_params(p.n, prm, &p.min_inlier, &p.max_it);
+    dp[(size_t)i] = PnpProb{p.off, p.n, p.words, p.min_inlier};
+  }
+  // mvfErrors: (float)(5.991 * Frame::getScaledFactor2(octave))
+  std::vector<float> thr((size_t)total);
+  for (int64_t i = 0; i < total; ++i) thr[(size_t)i] = (float)(5.991 * (double)level_sigma2[octave[i]]);
+  int cur = -1;
+  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+  orbfe_status st = ORBFE_OK;
+  const size_t nb = (size_t)std::max<int64_t>(total, 1);
+  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
+    st = fail(nullptr, ORBFE_EDEVICE, "orbfe_pnp_create: cannot create a stream on device %d", device_id);
+  else if (hipMalloc((void**)&s->d_xyz, nb * 12) != hipSuccess || hipMalloc((void**)&s->d_uv, nb * 8) != hipSuccess ||
+           hipMalloc((void**)&s->d_thr, nb * 4) != hipSuccess ||
+           hipMalloc((void**)&s->d_probs, std::max<size_t>(dp.size(), 1) * sizeof(PnpProb)) != hipSuccess)
+    st = fail(nullptr, ORBFE_ENOMEM, "orbfe_pnp_create: cannot allocate %lld points on device %d", (long long)total, device_id);
+  else if ((total && (hipMemcpy(s->d_xyz, xyz, (size_t)total * 12, hipMemcpyHostToDevice) != hipSuccess ||
+                      hipMemcpy(s->d_uv, uv, (size_t)total * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                      hipMemcpy(s->d_thr, thr.data(), (size_t)total * 4, hipMemcpyHostToDevice) != hipSuccess)) ||
+           (!dp.empty() && hipMemcpy(s->d_probs, dp.data(), dp.size() * sizeof(PnpProb), hipMemcpyHostToDevice) != hipSuccess))
+    st = fail(nullptr, ORBFE_EDEVICE, "orbfe_pnp_create: upload failed");
+  if (have_cur) (void)hipSetDevice(cur);
+  if (st != ORBFE_OK) {
+    orbfe_pnp_destroy(s.release());
+    return st;
+  }
+  *out = s.release();
+  return ORBFE_OK;
+}
+
+void orbfe_pnp_destroy(orbfe_pnp* s) {
+  if (!s) return;
+  int cur = -1;
+  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+  (void)hipSetDevice(s->device);
+  for (void* p : {(void*)s->d_xyz, (void*)s->d_uv, (void*)s->d_thr, (void*)s->d_probs, (void*)s->d_io})
+    if (p) (void)hipFree(p);
+  if (s->h_io) (void)hipHostFree(s->h_io);
+  if (s->stream) (void)hipStreamDestroy(s->stream);
+  if (have_cur) (void)hipSetDevice(cur);
+  delete s;
+}
+
+orbfe_status orbfe_pnp_iterate(orbfe_pnp* s, int32_t problem, int32_t n_iterations, float* pose, int32_t* has_pose, int32_t* inliers,
+                               int64_t* n_inliers, int64_t cap, int32_t* ret, int32_t* no_more) {
+  if (!s || !pose || !has_pose || !n_inliers || !ret || !no_more || cap < 0 || *n_inliers < 0 || *n_inliers > cap || (cap > 0 && !inliers))
+    return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_iterate: bad arguments");
+  if (problem < 0 || problem >= (int32_t)s->probs.size())
+    return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_iterate: problem %d of %zu", problem, s->probs.size());
+  std::lock_guard<std::mutex> lk(g_pnp_mu);
+  Prob& pr = s->probs[(size_t)problem];
+  for (int64_t i = 0; i < *n_inliers; ++i)
+    if (inliers[i] < 0 || inliers[i] >= pr.n) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_iterate: inlier %d of %d points", inliers[i], pr.n);
+  *ret = 0;
+  const bool entry_empty = !*has_pose && *n_inliers == 0;
+  const int32_t k = pr.n >= 4 ? std::max(0, std::min(n_iterations, pr.max_it - pr.cur)) : 0;
+  // the next record serves this call if the call is the predicted one: same problem and n, empty entry state, engine untouched
+  bool hit = s->next > 0 && s->next < s->recs.size() && entry_empty;
+  if (hit) {
+    const CallRec& r = s->recs[s->next];
+    hit = r.prob == problem && r.n == n_iterations && r.engine_start == g_engine && r.nh == k;
+  }
+  if (pr.n < 4) {  // P5
+    if (hit) {
+      s->next += 1;
+    } else {
+      s->recs.clear();
+      s->next = 0;
+    }
+    pr.called = true;
+    *no_more = 1;
+    return ORBFE_OK;
+  }
+  CallRec r;
+  if (hit) {
+    r = s->recs[s->next];
+    s->next += 1;
+  } else if (k == 0) {  // the budget is spent: nothing for the device
+    s->recs.clear();
+    s->next = 0;
+    r = CallRec{problem, n_iterations, 0, 0, -1, g_engine, {}};
+  } else {
+    int cur = -1;
+    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+    const orbfe_status st = speculate(s, problem, n_iterations, pose, *has_pose != 0, inliers, *n_inliers);
+    if (have_cur) (void)hipSetDevice(cur);
+    if (st != ORBFE_OK) {
+      s->recs.clear();
+      s->next = 0;
+      return st;
+    }
+    r = s->recs[0];
+    s->next = 1;
+  }
+  if (r.nh != k || r.prob != problem) {
+    s->recs.clear();
+    s->next = 0;
+    return fail(nullptr, ORBFE_EDEVICE, "orbfe_pnp_iterate: inconsistent speculation");
+  }
+  // replay Ransac::iterate from the records on copies, committed when the result fits
+  std::vector<int32_t> list(inliers, inliers + *n_inliers);
+  float cur_pose[12];
+  std::memcpy(cur_pose, pose, sizeof cur_pose);
+  bool has = *has_pose != 0;
+  int32_t cur = pr.cur, best = pr.best;
+  bool best_changed = false;
+  float best_pose[12];
+  std::vector<int32_t> best_list;
+  const uint64_t* st_mask = nullptr;
+  int32_t st_cnt = 0;
+  if (r.entry_hyp >= 0) {
+    st_mask = s->masks.data() + s->hyps[(size_t)r.entry_hyp].mask_off;
+    st_cnt = s->out[(size_t)r.entry_hyp].count;
+  }
+  bool success = false;
+  uint32_t eng = g_engine;
+  for (int32_t i = 0; i < r.nh && !success; ++i) {
+    const size_t h = (size_t)(r.h0 + i);
+    const PnpOut& o = s->out[h];
+    if (!o.degen) {
+      std::memcpy(cur_pose, o.pose, sizeof cur_pose);
+      has = true;
+      st_mask = s->masks.data() + s->hyps[h].mask_off;
+      st_cnt = o.count;
+    }
+    eng = r.after[(size_t)i];
+    if (has) {
+      if (!st_mask) return fail(nullptr, ORBFE_EDEVICE, "orbfe_pnp_iterate: no record of the entry pose");
+      append_bits(st_mask, pr.words, list);
+      if (st_cnt > pr.min_inlier) {
+        if (st_cnt > best) {
+          best = st_cnt;
+          best_changed = true;
+          std::memcpy(best_pose, cur_pose, sizeof best_pose);
+          best_list = list;
+        }
+        if (!o.refined || o.err) {
+          s->recs.clear();
+          return fail(nullptr, ORBFE_EDEVICE, "orbfe_pnp_iterate: refine record missing");
+        }
+        std::memcpy(cur_pose, o.ref_pose, sizeof cur_pose);
+        st_mask = s->ref_masks.data() + s->hyps[h].mask_off;
+        st_cnt = o.ref_count;
+        list.clear();
+        append_bits(st_mask, pr.words, list);
+        if (st_cnt > pr.min_inlier) {
+          success = true;  // P3: the budget is not spent
+          break;
+        }
+      }
+    }
+    ++cur;
+  }
+  bool set_no_more = false;
+  const std::vector<int32_t>* res = &list;
+  const float* res_pose = cur_pose;
+  bool res_has = has;
+  if (success) {
+    *ret = 1;
+  } else {
+    set_no_more = cur >= pr.max_it;
+    const int32_t b = best_changed ? best : pr.best;
+    if (b > 0) {
+      *ret = 1;
+      res = best_changed ? &best_list : &pr.best_list;
+      res_pose = best_changed ? best_pose : pr.best_pose;
+      res_has = true;
+    }
+  }
+  if ((int64_t)res->size() > cap) {
+    *n_inliers = (int64_t)res->size();
+    *ret = 0;
+    s->recs.clear();
+    s->next = 0;
+    return fail(nullptr, ORBFE_ECAPACITY, "orbfe_pnp_iterate: %zu inliers, room for %lld", res->size(), (long long)cap);
+  }
+  // commit
+  std::copy(res->begin(), res->end(), inliers);
+  *n_inliers = (int64_t)res->size();
+  std::memcpy(pose, res_pose, 12 * sizeof(float));
+  *has_pose = res_has ? 1 : 0;
+  if (set_no_more) *no_more = 1;
+  pr.cur = cur;
+  pr.called = true;
+  if (best_changed) {
+    pr.best = best;
+    std::memcpy(pr.best_pose, best_pose, sizeof best_pose);
+    pr.best_list = std::move(best_list);
+  }
+  g_engine = eng;
+  if (success) {
+    s->recs.clear();
+    s->next = 0;
+  }
+  return ORBFE_OK;
+}
+
+orbfe_status orbfe_pnp_engine(uint32_t* get, const uint32_t* set) {
+  std::lock_guard<std::mutex> lk(g_pnp_mu);
+  if (get) *get = g_engine;
+  if (set) {
+    if (*set == 0 || *set >= 2147483647u) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_engine: state %u outside 1 .. 2^31 - 2", *set);
+    g_engine = *set;
+  }
+  return ORBFE_OK;
+}
+
+orbfe_status orbfe_pnp_stats(orbfe_pnp* s, int64_t* launches, int64_t* hypotheses) {
+  if (!s) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_stats: NULL set");
+  std::lock_guard<std::mutex> lk(g_pnp_mu);
+  if (launches) *launches = s->launches;
+  if (hypotheses) *hypotheses = s->hypotheses;
+  return ORBFE_OK;
+}
+
+}  // extern "C"
