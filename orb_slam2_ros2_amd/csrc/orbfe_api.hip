@@ -1011,9 +1011,14 @@ orbfe_status orbfe_debug_candidates(orbfe_ctx* c, int32_t slot, int32_t level, f
     HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->d_n_cand_sh + ((size_t)slot * c->cfg.n_levels + level) * ns, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < ns; ++s) {
-      const int32_t k = std::min<int32_t>(std::max(cnt[(size_t)s], 0), (int32_t)L.shard_cap);
+      cnt[(size_t)s] = std::min<int32_t>(std::max(cnt[(size_t)s], 0), (int32_t)L.shard_cap);
+      n += cnt[(size_t)s];
+    }
+    rec.resize((size_t)n);  // sized once: the copies below write into it asynchronously
+    n = 0;
+    for (int s = 0; s < ns; ++s) {
+      const int32_t k = cnt[(size_t)s];
       if (!k) continue;
-      rec.resize((size_t)n + k);
       HIP_TRY(c, hipMemcpyAsync(rec.data() + n, c->d_scr_a + (size_t)slot * c->scratch_pitch + L.cand_base + (size_t)s * L.shard_cap, sizeof(uint32_t) * k,
                                 hipMemcpyDeviceToHost, c->stream));
       n += k;

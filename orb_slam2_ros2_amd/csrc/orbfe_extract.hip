@@ -10,8 +10,19 @@ void grid_invalidate(orbfe_ctx* c, int slot) {
   while (!a.compare_exchange_weak(v, ((v >> 32) + 1) << 32)) {
   }
 }
+// An extraction of n_img images keeps FAST's candidate lists in shards (k_fast.hip, SH) -- where FAST is ONE launch of one-cell waves and
+// the quadtree the several-waves-per-tree launch that reads shards (the same conditions as launch_fast / launch_quadtree in run_extract)
+// (contexts of <= 16 slots never group levels: one tree per level, several waves each, when the launch has at most one tree per CU)
+static bool fast_lists_sharded(const orbfe_ctx* c, int n_img) {
+  const int nl = c->cfg.n_levels;
+  return c->fast_shards > 1 && c->d_n_cand_sh && fast_single_launch(c->lv.data(), c->lvl_max_pw, c->lvl_max_ph, nl, n_img) &&
+         (long long)nl * n_img <= c->n_cu;
+}
+// (n: the image count of the extraction; also the layout of the slots' candidate lists that orbfe_debug_candidates reads)
 void note_slots_written(orbfe_ctx* c, int s0, int n, bool small) {
   for (int s = s0; s < s0 + n && s < c->cfg.max_images; ++s) grid_invalidate(c, s);
+  const bool sharded = fast_lists_sharded(c, n);
+  for (int s = s0; s < s0 + n && s < c->cfg.max_images; ++s) c->slot_sharded[(size_t)s] = sharded ? 1 : 0;
   if (!c->slot_table_ok) return;
   for (int s = s0; s < s0 + n && s < c->cfg.max_images; ++s) {
     c->slot_table_ok[(size_t)s] = small ? 1 : 0;
@@ -44,13 +55,10 @@ orbfe_status run_extract(orbfe_ctx* c, hipStream_t st, int img0, int n_img, hipE
   // FAST's candidate counters are zeroed by the resize kernel (block 0): a memset between the blur and FAST is one more launch in the
   // chain -- 4.6 us of a 0.2 ms frame
   const bool zeroed_by_resize = !c->rs_regions.empty();  // (empty: the geometry rules the region-driven resize out -- the per-class tile launches)
-  // A frame or two: FAST's candidate lists in shards (k_fast.hip, SH) -- where FAST is ONE launch of one-cell waves and the quadtree the
-  // several-waves-per-tree launch that reads shards (the same conditions as launch_fast / launch_quadtree below)
-  // (contexts of <= 16 slots never group levels: one tree per level, several waves each, when the launch has at most one tree per CU)
-  const bool sharded = c->fast_shards > 1 && c->d_n_cand_sh && fast_single_launch(c->lv.data(), c->lvl_max_pw, c->lvl_max_ph, nl, n_img) &&
-                       (long long)nl * n_img <= c->n_cu;
+  // A frame or two: FAST's candidate lists in shards (slot_sharded is set by note_slots_written above, and by extract_lane where a captured
+  // graph is replayed: this function does not run then)
+  const bool sharded = fast_lists_sharded(c, n_img);
   int32_t* const n_cand_sh = sharded ? c->d_n_cand_sh + i0 * nl * c->fast_shards : nullptr;
-  for (int i = 0; i < n_img; ++i) c->slot_sharded[(size_t)(i0 + i)] = sharded ? 1 : 0;
   {
     StageTimer t(c, ORBFE_STAGE_RESIZE, st, timing);
     if (zeroed_by_resize)

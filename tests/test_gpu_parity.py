@@ -70,6 +70,29 @@ def test_a_pair_with_and_without_sharded_candidate_lists(orc, lib, monkeypatch, 
     finally:
         ctx.close()
 
+
+def test_candidate_lists_of_a_replayed_slot_graph_after_an_unsharded_batch(orc, lib):
+    """a one-image slot call captures a graph whose FAST keeps sharded lists; a batch of 16 on the same 16-slot context
+    runs unsharded over slot 0; the next slot-0 call REPLAYS the graph (same lane, staging buffer and pyramid buffer) and writes shards
+    again.  orbfe_debug_candidates must read them as shards, not the unsharded counter the resize zeroed."""
+    ctx = lib.Context(1241, 376, max_images=16)
+    try:
+        A = synth.stereo_pair(3)[0]
+        batch = [im for f in range(4, 12) for im in synth.stereo_pair(f)]
+        B = synth.stereo_pair(12)[1]
+        ka, da = ctx.extract_slot(0, A)                     # captures slot 0's graph (sharded lists)
+        assert_image_parity(ctx, 0, orc.extractor(A), ka, da, 8, check_planes=False)
+        res = ctx.extract_batch(batch)                      # 16 images: one list per level
+        assert_image_parity(ctx, 0, orc.extractor(batch[0]), *res[0], 8, check_planes=False)
+        assert_image_parity(ctx, 15, orc.extractor(batch[15]), *res[15], 8, check_planes=False)
+        ex = orc.extractor(B)
+        for _ in range(2):                                  # the second call replays whatever the first one captured
+            kb, db = ctx.extract_slot(0, B)
+            assert_image_parity(ctx, 0, ex, kb, db, 8)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("f", [0, 1, 7])
 def test_kitti_stereo_frame_bit_exact_and_golden(orc, kitti_ctx, f):
     L, R = synth.stereo_pair(f)

@@ -3,15 +3,19 @@ over gloo (ORBFE_BENCH_ONE_DEVICE / ORBFE_BENCH_BACKEND: the bench's own test ho
 cannot host: rank launcher (children started before anything touches the GPU), per-rank frame blocks, weak-scaling step loop with its
 summary gather, and the sequence job through BOTH exchanges, whose record stores must be byte-identical.  No scaling number comes out of
 this (two ranks share one GPU); a real 2 / 4 / 8-GPU curve is the driver's to measure."""
+import hashlib
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FX, BF = 718.856, 718.856 * 0.537166
+W, H = 1241, 376
 
 
 def test_bench_with_two_gloo_ranks_on_one_gpu():
@@ -19,7 +23,7 @@ def test_bench_with_two_gloo_ranks_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--pairs", "32", "--steps", "4", "--warmup", "1", "--prewarm-seconds", "0.1",
-           "--cpu-seconds", "0", "--host-io-steps", "3", "--sequence-leg", "301", "--sequence-unique", "24", "--content-steps", "0", "--legs", ""]
+           "--cpu-seconds", "0", "--host-io-steps", "3", "--sequence-leg", "301", "--sequence-unique", "301", "--content-steps", "0", "--legs", ""]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.strip().split("\n") if l.startswith("{")]
@@ -36,3 +40,35 @@ def test_bench_with_two_gloo_ranks_on_one_gpu():
     assert a["records_sha256"] == b["records_sha256"] and len(a["records_sha256"]) == 64   # both exchanges delivered the same 301 records
     assert a["host_bytes"] == b["host_bytes"] == 301 * seq["result_bytes"] // 301
     assert d["host_io"]["verified_pairs"] > 0
+    # every frame of the two blocks distinct (--sequence-unique = --sequence-leg): no record is checked only against a repeat of itself ...
+    assert seq["records_checked_for_repeat_consistency"] == 0
+    # ... and the record store both exchanges delivered equals the one rank's run of the sequence driver over frames 0 .. 300 in this
+    # process (the child has exited; the frames come from a child process too)
+    a_sha = _single_rank_records_sha256(301, 32, 900)
+    assert a["records_sha256"] == a_sha and b["records_sha256"] == a_sha, "the two-rank record store differs from the single-rank one"
+
+
+def _single_rank_records_sha256(n_frames, batch, timeout):
+    import tempfile
+
+    import torch
+
+    from orb_slam2_ros2_amd._lib import Context
+    from orb_slam2_ros2_amd.sequence import DeviceSequenceProcessor, run_sequence
+    with tempfile.TemporaryDirectory(prefix="orbfe_two_ranks_") as td:
+        npy = os.path.join(td, "frames.npy")
+        subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_frames.py"), "0", str(n_frames), npy], check=True, timeout=timeout)
+        fr = np.load(npy)
+    assert fr.shape == (n_frames, 2, H, W)
+    ctx = Context(W, H, max_images=2 * batch)
+    proc = DeviceSequenceProcessor(ctx, lambda f: (fr[f, 0], fr[f, 1]), batch, FX, BF, torch.device("cuda", 0))
+    try:
+        proc.prepare(range(n_frames))
+        rec, n_local = run_sequence(n_frames, 0, 1, batch, proc.submit, proc.collect)
+        assert n_local == n_frames
+        return hashlib.sha256(np.ascontiguousarray(rec.cpu().numpy()).data).hexdigest()
+    finally:
+        for l, r in proc.pinned.values():
+            l.free()
+            r.free()
+        ctx.close()
