@@ -692,6 +692,54 @@ orbfe_status orbfe_pnp_iterate(orbfe_pnp* set, int32_t problem, int32_t n_iterat
 orbfe_status orbfe_pnp_engine(uint32_t* get, const uint32_t* set);
 orbfe_status orbfe_pnp_stats(orbfe_pnp* set, int64_t* launches, int64_t* hypotheses);
 
+/* ---- new map points of a keyframe (LocalMapping::createNewMapPoints, src/LocalMapping.cc:165-285) ---------------------------------
+ * One call runs loop 1 and loop 2 of createNewMapPoints for the current keyframe `cur` against the neighbours nbs[0 .. n_nb) IN THE
+ * GIVEN ORDER (the reference's std::map order, T2): searchForTriangulation (searchByBow with bAddMPs, ratio 0.6, threshold 50, no
+ * verifyAngle; the mutual epipolar test), the parallax cosines, the three-way branch, triangulate, unProject and checkMapPoint, then
+ * the first-wins resolution and the tail list (quirks T1-T9 and the SVD decision: DESIGN 4.17).  A neighbour closer than `bl` to the
+ * current keyframe ((float)|Ow_cur - Ow_nb| < bl) is skipped (T7).  One upload, a fixed launch sequence, one download.
+ * Outputs: records[0 .. *n_records) in processing order -- the one accepted candidate of each current feature that got a point --
+ * and tail[0 .. *n_tail): the current features, ascending, whose unprocessed point was not consumed and whose slot (flag GOOD of cur)
+ * is empty after loop 2.  Both counts are set even when they exceed their capacity (ORBFE_ECAPACITY, nothing written).
+ * consumed (NULL: not wanted) [cur->n]: 1 where an own-stereo candidate took the feature's unprocessed point, accepted or not (T5) --
+ * the entries loop 2 erases from mmUnprocessMps.
+ * Errors: ORBFE_EBADARG (NULL pointers, n_nb outside 0 .. ORBFE_TRI_MAX_NB, n outside 0 .. ORBFE_BOW_MAX_FEATURES, FeatureVector nodes
+ * not strictly ascending, offsets not starting at 0 / decreasing / past the feature count, feature indices out of range, an octave
+ * outside 0 .. n_levels - 1), ORBFE_EDEVICE, ORBFE_ENOMEM, ORBFE_ECAPACITY.                                                            */
+#define ORBFE_TRI_MAX_NB 64
+#define ORBFE_TRI_GOOD 1  /* flags: the feature's map point is non-null and not bad */
+#define ORBFE_TRI_INMAP 2 /*        ... and isInMap()                              */
+#define ORBFE_TRI_TRIANGULATED 1 /* record kinds: triangulate (LocalMapping.cc:224-230)                                 */
+#define ORBFE_TRI_OWN_STEREO 2   /* the current feature's unprocessed point (:232-239)                                   */
+#define ORBFE_TRI_NB_STEREO 3    /* the neighbour's unprojection (:240-247)                                             */
+typedef struct orbfe_tri_kf {
+  int32_t n;                     /* features                                                                   */
+  const orbfe_keypoint* kps;     /* [n] mvFeatsLeft                                                            */
+  const uint8_t* desc;           /* [n][32]                                                                    */
+  int32_t n_nodes;               /* FeatureVector in orbfe_bow_out's layout                                    */
+  const uint32_t* nodes;         /* [n_nodes] strictly ascending                                               */
+  const int32_t* node_offsets;   /* [n_nodes + 1]                                                              */
+  const uint32_t* features;      /* [node_offsets[n_nodes]]                                                    */
+  const uint8_t* flags;          /* [n] ORBFE_TRI_GOOD | ORBFE_TRI_INMAP                                       */
+  const double* depth;           /* [n] mvDepths (> 0: stereo)                                                 */
+  const double* right_u;         /* [n] mvRightU                                                               */
+  float Tcw[16];                 /* the pose as the keyframe stores it, row-major                              */
+  float Twc[16];                 /* its stored inverse (not recomputed)                                        */
+  float Ow[3];                   /* getFrameCenter()                                                           */
+  const uint8_t* unproc;         /* cur only: [n] the feature has an entry in mmUnprocessMps (else NULL)       */
+  const float* unproc_pos;       /* cur only: [n][3] that point's world position                               */
+} orbfe_tri_kf;
+typedef struct orbfe_tri_record {
+  int32_t nb;                    /* neighbour index                                                            */
+  int32_t query, train;          /* feature of cur, feature of the neighbour                                   */
+  int32_t kind;                  /* ORBFE_TRI_*                                                                */
+  float xyz[3];                  /* world position of the point                                                */
+} orbfe_tri_record;
+orbfe_status orbfe_create_new_map_points(orbfe_ctx* ctx, const orbfe_tri_kf* cur, int32_t n_nb, const orbfe_tri_kf* nbs,
+                                         const orbfe_camera* cam /* fx fy cx cy */, const float* k_inv /*[9] Camera::mKInv*/, float bl,
+                                         const float* scale_factors, int32_t n_levels, orbfe_tri_record* records, int64_t cap,
+                                         int64_t* n_records, int32_t* tail, int64_t tail_cap, int64_t* n_tail, uint8_t* consumed);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

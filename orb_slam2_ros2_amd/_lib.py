@@ -124,6 +124,16 @@ class KfdbQueryIn(C.Structure):
                 ("min_score", C.c_void_p)]
 
 
+class TriKf(C.Structure):
+    _fields_ = [("n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("n_nodes", C.c_int32), ("nodes", C.c_void_p),
+                ("node_offsets", C.c_void_p), ("features", C.c_void_p), ("flags", C.c_void_p), ("depth", C.c_void_p), ("right_u", C.c_void_p),
+                ("Tcw", C.c_float * 16), ("Twc", C.c_float * 16), ("Ow", C.c_float * 3), ("unproc", C.c_void_p), ("unproc_pos", C.c_void_p)]
+
+
+TRI_REC_DTYPE = np.dtype([("nb", "<i4"), ("q", "<i4"), ("t", "<i4"), ("kind", "<i4"), ("xyz", "<f4", (3,))])
+TRI_MAX_NB = 64
+
+
 class BaEdgeOut(C.Structure):
     _fields_ = [("error", C.c_void_p), ("chi2", C.c_void_p), ("rho", C.c_void_p), ("j_point", C.c_void_p),
                 ("j_pose", C.c_void_p), ("depth_positive", C.c_void_p)]
@@ -140,6 +150,7 @@ EXPORTS = [
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_set_bad", "orbfe_kfdb_erase", "orbfe_kfdb_size", "orbfe_kfdb_query",
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
+    "orbfe_create_new_map_points",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates",
 ]
 BOW_MAX_FEATURES = 65535
@@ -248,6 +259,8 @@ def load() -> C.CDLL:
     L.orbfe_pnp_iterate.argtypes = [vp, i32, i32, vp, C.POINTER(i32), vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(i32), C.POINTER(i32)]
     L.orbfe_pnp_engine.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.orbfe_pnp_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.orbfe_create_new_map_points.argtypes = [vp, C.POINTER(TriKf), i32, vp, C.POINTER(Camera), vp, f32, vp, i32, vp, C.c_int64,
+                                              C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64), vp]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -1154,6 +1167,65 @@ class Context:
         o = BowOut(*[ptr(a[k]).value for k, _ in BowOut._fields_])
         self._check(self.lib.orbfe_bow_slots(self.h, vocab.h, slot0, n, step, int(levelsup), C.byref(o)))
         return [_bow_split(a, i) for i in range(n)]
+
+    # ---- new map points of a keyframe ------------------------------------------------------------------------------------------
+    def create_new_map_points(self, cur, nbs, cam, k_inv, bl, scale_factors, cap=None, tail_cap=None):
+        """LocalMapping::createNewMapPoints' loops 1 and 2 (orbfe_create_new_map_points, include/orbfe.h) for the current keyframe `cur`
+        against the neighbours `nbs` in the given order.  A keyframe is a dict: kps [n] KP_DTYPE, desc [n, 32] uint8, fv = (nodes,
+        offsets, features) -- bow_transform's last three outputs --, flags [n] uint8 (1: map point good, 2: in map), depth [n], right_u
+        [n] (float64), Tcw, Twc (4x4 float32), Ow [3]; cur also unproc [n] (bool) and unproc_pos [n, 3] (float32).  cam = (fx, fy, cx,
+        cy).  Returns (records TRI_REC_DTYPE in processing order, tail int32, consumed [n] bool: the features whose unprocessed point
+        an own-stereo candidate took, which loop 2 erases from mmUnprocessMps)."""
+        keep = []
+
+        def arr(a, dt, shape=None):
+            a = np.ascontiguousarray(a, dt)
+            if shape is not None:
+                a = a.reshape(shape)
+            keep.append(a)
+            return a
+
+        def kf(d, with_unproc):
+            n = len(d["kps"])
+            nodes, offs, feats = d["fv"]
+            k = TriKf()
+            k.n = n
+            k.kps = ptr(arr(d["kps"], KP_DTYPE)).value
+            k.desc = ptr(arr(d["desc"], np.uint8, (-1, 32))).value
+            nodes = arr(nodes, np.uint32)
+            k.n_nodes = len(nodes)
+            k.nodes = ptr(nodes).value
+            k.node_offsets = ptr(arr(offs, np.int32)).value
+            k.features = ptr(arr(feats, np.uint32)).value
+            k.flags = ptr(arr(d["flags"], np.uint8)).value
+            k.depth = ptr(arr(d["depth"], np.float64)).value
+            k.right_u = ptr(arr(d["right_u"], np.float64)).value
+            k.Tcw[:] = [float(v) for v in np.asarray(d["Tcw"], np.float32).reshape(16)]
+            k.Twc[:] = [float(v) for v in np.asarray(d["Twc"], np.float32).reshape(16)]
+            k.Ow[:] = [float(v) for v in np.asarray(d["Ow"], np.float32).reshape(3)]
+            if with_unproc:
+                k.unproc = ptr(arr(np.asarray(d["unproc"]).astype(bool), np.uint8)).value
+                k.unproc_pos = ptr(arr(d["unproc_pos"], np.float32, (-1, 3))).value
+            return k
+
+        c = kf(cur, True)
+        nb = (TriKf * max(len(nbs), 1))(*[kf(d, False) for d in nbs])
+        n = len(cur["kps"])
+        cap = n if cap is None else int(cap)
+        tail_cap = n if tail_cap is None else int(tail_cap)
+        recs = np.zeros(max(cap, 1), TRI_REC_DTYPE)
+        tail = np.zeros(max(tail_cap, 1), np.int32)
+        consumed = np.zeros(max(n, 1), np.uint8)
+        cm = Camera(*[float(v) for v in cam[:4]])
+        ki = arr(k_inv, np.float32, (9,))
+        sf = arr(scale_factors, np.float32)
+        nr, nt = C.c_int64(0), C.c_int64(0)
+        st = self.lib.orbfe_create_new_map_points(self.h, C.byref(c), len(nbs), C.cast(nb, C.c_void_p), C.byref(cm), ptr(ki), float(bl),
+                                                  ptr(sf), len(sf), ptr(recs), cap, C.byref(nr), ptr(tail), tail_cap, C.byref(nt),
+                                                  ptr(consumed))
+        self.last_counts = (nr.value, nt.value)
+        self._check(st)
+        return recs[:nr.value].copy(), tail[:nt.value].copy(), consumed[:n].astype(bool)
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

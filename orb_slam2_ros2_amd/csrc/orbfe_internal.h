@@ -277,3 +277,28 @@ struct PnpOut {
   int32_t ref_count, err, pad0, pad1;
   float ref_pose[12];
 };
+
+// ---- new map points (k_tri.hip, orbfe_tri.hip) -----------------------------------------------------------------------------------
+// One keyframe of the call inside the upload: byte offsets of its arrays, its sizes and poses.  kf[0] is the current keyframe,
+// kf[1 + i] neighbour i; a neighbour's FeatureVector entry j is match slot slot0 + j.
+struct TriKf {
+  uint32_t o_kps, o_desc, o_nodes, o_offs, o_feat, o_flags, o_depth, o_ru;
+  int32_t n, n_nodes, n_feat, slot0, skip, pad;
+  float Tcw[16], Twc[16];
+};
+struct TriParams {
+  float fx, fy, cx, cy;
+  float kinv[9];
+  int32_t n_nb, n_levels, n_cur, n_slots;
+  uint32_t o_unproc, o_upos, o_sf;
+  int32_t rec_cap, tail_cap;
+};
+// a match slot after k_tri_match: the current feature (-1: no match), the branch's kind (0: no point), checkMapPoint's verdict, the point
+struct TriSlot {
+  int32_t q, t, nb, kind, ok;
+  float xyz[3];
+};
+struct TriRec {
+  int32_t nb, q, t, kind;
+  float xyz[3];
+};

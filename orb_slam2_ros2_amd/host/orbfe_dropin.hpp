@@ -190,6 +190,12 @@ inline cv::Mat poseToMat(const double p[7]) {  // Converter::ConvertSE32Tcw (:64
 // tests/cpp/test_dropin.cpp keeps the stand-in classes' members protected with exactly that line.  The free functions of the same names
 // after the struct forward to it.
 struct Bodies {
+// the FeatureVector of a frame (VirtualFrame::mFeatVec) for the new-map-points drop-in (orbfe_mapping_dropin.hpp)
+template <class FramePtr>
+static const auto& featVec(const FramePtr& f) {
+  return f->mFeatVec;
+}
+
 // int ORBMatcher::searchByStereo(Frame::SharedPtr pFrame)  (src/ORBMatcher.cc:18-81).  Uses pFrame->mvFeatsLeft, mvDepths, mvFeatsRightU,
 // mpExtractorLeft / mpExtractorRight (ORBMatcher is a friend of Frame, Frame.h:302-303) and Camera::mfFx / mfBf.
 template <class CameraT, class FramePtr>
