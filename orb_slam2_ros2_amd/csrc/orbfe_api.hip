@@ -877,19 +877,20 @@ orbfe_status orbfe_fetch_features(orbfe_ctx* c, int32_t slot, orbfe_keypoint* kp
   const size_t NF = (size_t)c->cfg.n_features;
   // count, keypoints and descriptors of the whole slot into the page-locked staging buffer behind ONE synchronisation (the count first and
   // then exactly n entries into pageable memory were two round trips)
-  const size_t h_k = 256, h_d = h_k + align_up(NF * sizeof(orbfe_keypoint), 256), h_total = h_d + align_up(NF * 32, 256);
-  TRY(ensure_stage(c, h_total));
-  uint8_t* hs = c->main.h_stage;
-  HIP_TRY(c, hipMemcpyAsync(hs, c->d_n_kp + slot, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (kps && NF) HIP_TRY(c, hipMemcpyAsync(hs + h_k, c->d_kps + (size_t)slot * NF, sizeof(orbfe_keypoint) * NF, hipMemcpyDeviceToHost, c->stream));
-  if (desc && NF) HIP_TRY(c, hipMemcpyAsync(hs + h_d, c->d_desc + (size_t)slot * NF * 32, (size_t)32 * NF, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ScratchLayout L;  // (of the staging buffer alone: the sources are the slot's own arrays)
+  const size_t h_n = L.take<int32_t>(1), h_k = L.take<orbfe_keypoint>(NF), h_d = L.take(NF * 32);
+  StagedIo io;
+  TRY(io.reserve(c, 0, L.end()));
+  HIP_TRY(c, hipMemcpyAsync(io.h + h_n, c->d_n_kp + slot, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (kps && NF) HIP_TRY(c, hipMemcpyAsync(io.h + h_k, c->d_kps + (size_t)slot * NF, sizeof(orbfe_keypoint) * NF, hipMemcpyDeviceToHost, c->stream));
+  if (desc && NF) HIP_TRY(c, hipMemcpyAsync(io.h + h_d, c->d_desc + (size_t)slot * NF * 32, (size_t)32 * NF, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, io.wait());
   drain_timers(c);
   int32_t n = 0;
-  std::memcpy(&n, hs, 4);
+  io.get(&n, h_n, 4);
   if (n < 0 || (size_t)n > NF) return fail(c, ORBFE_EDEVICE, "fetch_features: corrupt count %d", n);
-  if (kps && n) std::memcpy(kps, hs + h_k, sizeof(orbfe_keypoint) * (size_t)n);
-  if (desc && n) std::memcpy(desc, hs + h_d, (size_t)32 * n);
+  io.get(kps, h_k, sizeof(orbfe_keypoint) * (size_t)n);
+  io.get(desc, h_d, (size_t)32 * n);
   if (n_out) *n_out = n;
   return ORBFE_OK;
 }
@@ -902,22 +903,22 @@ orbfe_status orbfe_fetch_stereo(orbfe_ctx* c, int32_t pair, double* right_u, dou
   TRY(join_stereo(c));
   const size_t NF = (size_t)c->cfg.n_features;
   const size_t o = (size_t)pair * NF;
-  const size_t o_ru = 0, o_dp = align_up(NF * 8, 256), o_br = o_dp + align_up(NF * 8, 256), o_bd = o_br + align_up(NF * 4, 256),
-               o_nm = o_bd + align_up(NF * 4, 256), total = o_nm + 256;
-  TRY(ensure_stage(c, total));
-  uint8_t* h = c->main.h_stage;
-  if (right_u && NF) HIP_TRY(c, hipMemcpyAsync(h + o_ru, c->d_right_u + o, sizeof(double) * NF, hipMemcpyDeviceToHost, c->stream));
-  if (depth && NF) HIP_TRY(c, hipMemcpyAsync(h + o_dp, c->d_depth + o, sizeof(double) * NF, hipMemcpyDeviceToHost, c->stream));
-  if (best_right && NF) HIP_TRY(c, hipMemcpyAsync(h + o_br, c->d_best_right + o, sizeof(int32_t) * NF, hipMemcpyDeviceToHost, c->stream));
-  if (best_dist && NF) HIP_TRY(c, hipMemcpyAsync(h + o_bd, c->d_best_dist + o, sizeof(int32_t) * NF, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h + o_nm, c->d_n_match + pair, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ScratchLayout L;  // (of the staging buffer alone: the sources are the pair's own arrays)
+  const size_t o_ru = L.take<double>(NF), o_dp = L.take<double>(NF), o_br = L.take<int32_t>(NF), o_bd = L.take<int32_t>(NF), o_nm = L.take<int32_t>(1);
+  StagedIo io;
+  TRY(io.reserve(c, 0, L.end()));
+  if (right_u && NF) HIP_TRY(c, hipMemcpyAsync(io.h + o_ru, c->d_right_u + o, sizeof(double) * NF, hipMemcpyDeviceToHost, c->stream));
+  if (depth && NF) HIP_TRY(c, hipMemcpyAsync(io.h + o_dp, c->d_depth + o, sizeof(double) * NF, hipMemcpyDeviceToHost, c->stream));
+  if (best_right && NF) HIP_TRY(c, hipMemcpyAsync(io.h + o_br, c->d_best_right + o, sizeof(int32_t) * NF, hipMemcpyDeviceToHost, c->stream));
+  if (best_dist && NF) HIP_TRY(c, hipMemcpyAsync(io.h + o_bd, c->d_best_dist + o, sizeof(int32_t) * NF, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(io.h + o_nm, c->d_n_match + pair, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, io.wait());
   drain_timers(c);
-  if (right_u && NF) std::memcpy(right_u, h + o_ru, sizeof(double) * NF);
-  if (depth && NF) std::memcpy(depth, h + o_dp, sizeof(double) * NF);
-  if (best_right && NF) std::memcpy(best_right, h + o_br, sizeof(int32_t) * NF);
-  if (best_dist && NF) std::memcpy(best_dist, h + o_bd, sizeof(int32_t) * NF);
-  if (n_matches) std::memcpy(n_matches, h + o_nm, sizeof(int32_t));
+  io.get(right_u, o_ru, sizeof(double) * NF);
+  io.get(depth, o_dp, sizeof(double) * NF);
+  io.get(best_right, o_br, sizeof(int32_t) * NF);
+  io.get(best_dist, o_bd, sizeof(int32_t) * NF);
+  io.get(n_matches, o_nm, sizeof(int32_t));
   return ORBFE_OK;
 }
 

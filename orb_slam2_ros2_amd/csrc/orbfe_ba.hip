@@ -1,485 +1,314 @@
 // orbfe_ba.hip -- the optimiser entry points: g2o edge evaluation and normal equations (diagnostic), the local BA
 // (Optimizer::OptimizeLocalMap, Optimizer.cc:336-391) and Optimizer::OptimizePoseOnly (:33-178).  (Split from orbfe_api.hip in r5.)
 #include "orbfe_ctx.h"
-extern "C" {
+namespace {
 
-orbfe_status orbfe_ba_eval_edges(orbfe_ctx* c, const orbfe_ba_problem* p, const orbfe_ba_edge_out* o) {
-  ApiLock api_lk(c);
-  if (!c || !p || !o) return fail(c, ORBFE_EBADARG, "ba_eval_edges: NULL argument");
-  const int E = p->n_edges;
-  if (E < 0 || p->n_poses < 0 || p->n_points < 0) return fail(c, ORBFE_EBADARG, "ba_eval_edges: negative size");
-  if (E == 0) return ORBFE_OK;
-  if (!p->poses || !p->points || !p->edge_pose || !p->edge_point || !p->meas || !p->is_stereo || !p->info || !p->huber_delta || !o->error ||
-      !o->chi2 || !o->rho)
-    return fail(c, ORBFE_EBADARG, "ba_eval_edges: NULL array");
-  for (int e = 0; e < E; ++e)
+// every edge of the problem names an existing pose and point
+orbfe_status ba_check_problem(orbfe_ctx* c, const char* who, const orbfe_ba_problem* p) {
+  for (int e = 0; e < p->n_edges; ++e)
     if (p->edge_pose[e] < 0 || p->edge_pose[e] >= p->n_poses || p->edge_point[e] < 0 || p->edge_point[e] >= p->n_points)
-      return fail(c, ORBFE_EBADARG, "ba_eval_edges: edge %d references vertex out of range", e);
-  HIP_TRY(c, hipSetDevice(c->device));
-  TRY(join_stereo(c));
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
-  const size_t o_pose = take((size_t)p->n_poses * 56), o_pt = take((size_t)p->n_points * 24), o_ep = take((size_t)E * 4),
-               o_et = take((size_t)E * 4), o_meas = take((size_t)E * 24), o_st = take((size_t)E), o_info = take((size_t)E * 8),
-               o_delta = take((size_t)E * 8), o_up_end = take(8), o_err = take((size_t)E * 24), o_chi = take((size_t)E * 8),
-               o_rho = take((size_t)E * 16), o_dp = take((size_t)E), o_jpt = take((size_t)E * 72), o_jps = take((size_t)E * 144), o_out_end = take(8);
-  TRY(ensure_tmp(c, off));
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  // up to 16 MB in all: inputs as ONE upload through the page-locked staging buffer and the results as one download (eight copies from
-  // and six to pageable memory otherwise -- each staged by the runtime on its own)
-  const size_t out_last = o->j_pose ? o_out_end : (o->j_point ? o_jps : o_jpt);
-  const bool staged = o_up_end + (out_last - o_err) <= ((size_t)16 << 20);
-  uint8_t* hs = nullptr;
-  if (staged) {
-    TRY(ensure_stage(c, std::max(o_up_end, out_last - o_err)));
-    hs = c->main.h_stage;
-  }
-  auto up = [&](size_t o2, const void* src, size_t bytes) -> hipError_t {
-    if (!bytes) return hipSuccess;
-    if (staged) {
-      std::memcpy(hs + o2, src, bytes);
-      return hipSuccess;
-    }
-    return hipMemcpyAsync(b + o2, src, bytes, hipMemcpyHostToDevice, c->stream);
-  };
-  HIP_TRY(c, up(o_pose, p->poses, (size_t)p->n_poses * 56));
-  HIP_TRY(c, up(o_pt, p->points, (size_t)p->n_points * 24));
-  HIP_TRY(c, up(o_ep, p->edge_pose, (size_t)E * 4));
-  HIP_TRY(c, up(o_et, p->edge_point, (size_t)E * 4));
-  HIP_TRY(c, up(o_meas, p->meas, (size_t)E * 24));
-  HIP_TRY(c, up(o_st, p->is_stereo, (size_t)E));
-  HIP_TRY(c, up(o_info, p->info, (size_t)E * 8));
-  HIP_TRY(c, up(o_delta, p->huber_delta, (size_t)E * 8));
-  if (staged) HIP_TRY(c, hipMemcpyAsync(b, hs, o_up_end, hipMemcpyHostToDevice, c->stream));
-  BaParamsDev prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
-  {
-    StageTimer tm(c, ORBFE_STAGE_BA, c->stream);
-    launch_ba_edges(c->stream, E, (const double*)(b + o_pose), (const double*)(b + o_pt), (const int32_t*)(b + o_ep),
-                    (const int32_t*)(b + o_et), (const double*)(b + o_meas), b + o_st, (const double*)(b + o_info),
-                    (const double*)(b + o_delta), prm, (double*)(b + o_err), (double*)(b + o_chi), (double*)(b + o_rho),
-                    o->j_point ? (double*)(b + o_jpt) : nullptr, o->j_pose ? (double*)(b + o_jps) : nullptr,
-                    o->depth_positive ? b + o_dp : nullptr);
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (staged) {
-    HIP_TRY(c, hipMemcpyAsync(hs, b + o_err, out_last - o_err, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    drain_timers(c);
-    std::memcpy(o->error, hs, (size_t)E * 24);
-    std::memcpy(o->chi2, hs + (o_chi - o_err), (size_t)E * 8);
-    std::memcpy(o->rho, hs + (o_rho - o_err), (size_t)E * 16);
-    if (o->depth_positive) std::memcpy(o->depth_positive, hs + (o_dp - o_err), (size_t)E);
-    if (o->j_point) std::memcpy(o->j_point, hs + (o_jpt - o_err), (size_t)E * 72);
-    if (o->j_pose) std::memcpy(o->j_pose, hs + (o_jps - o_err), (size_t)E * 144);
-    return ORBFE_OK;
-  }
-  HIP_TRY(c, hipMemcpyAsync(o->error, b + o_err, (size_t)E * 24, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(o->chi2, b + o_chi, (size_t)E * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(o->rho, b + o_rho, (size_t)E * 16, hipMemcpyDeviceToHost, c->stream));
-  if (o->j_point) HIP_TRY(c, hipMemcpyAsync(o->j_point, b + o_jpt, (size_t)E * 72, hipMemcpyDeviceToHost, c->stream));
-  if (o->j_pose) HIP_TRY(c, hipMemcpyAsync(o->j_pose, b + o_jps, (size_t)E * 144, hipMemcpyDeviceToHost, c->stream));
-  if (o->depth_positive) HIP_TRY(c, hipMemcpyAsync(o->depth_positive, b + o_dp, (size_t)E, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  drain_timers(c);
+      return fail(c, ORBFE_EBADARG, "%s: edge %d references vertex out of range", who, e);
   return ORBFE_OK;
 }
 
-orbfe_status orbfe_ba_build_system(orbfe_ctx* c, const orbfe_ba_problem* p, const uint8_t* pose_fixed, const orbfe_ba_system_out* o) {
-  ApiLock api_lk(c);
-  if (!c || !p || !o) return fail(c, ORBFE_EBADARG, "ba_build_system: NULL argument");
+// vertex -> edges lists, edges in ascending index (counting sort): the summation order of the segmented reductions
+struct BaVertexLists {
+  std::vector<int32_t> pt_off, pt_edges, ps_off, ps_edges;
+};
+void ba_vertex_lists(const orbfe_ba_problem* p, BaVertexLists* v) {
   const int E = p->n_edges, NK = p->n_poses, NP = p->n_points;
-  if (E < 0 || NK < 0 || NP < 0) return fail(c, ORBFE_EBADARG, "ba_build_system: negative size");
-  if (!o->Hpp || !o->bp || !o->Hll || !o->bl) return fail(c, ORBFE_EBADARG, "ba_build_system: NULL output");
-  if (E && (!p->poses || !p->points || !p->edge_pose || !p->edge_point || !p->meas || !p->is_stereo || !p->info || !p->huber_delta))
-    return fail(c, ORBFE_EBADARG, "ba_build_system: NULL array");
-  for (int e = 0; e < E; ++e)
-    if (p->edge_pose[e] < 0 || p->edge_pose[e] >= NK || p->edge_point[e] < 0 || p->edge_point[e] >= NP)
-      return fail(c, ORBFE_EBADARG, "ba_build_system: edge %d references vertex out of range", e);
-  HIP_TRY(c, hipSetDevice(c->device));
-  TRY(join_stereo(c));
-  // vertex -> edges lists, edges in ascending index (counting sort): the summation order of the segmented reductions
-  std::vector<int32_t> pt_off(NP + 1, 0), ps_off(NK + 1, 0), pt_edges(std::max(E, 1)), ps_edges(std::max(E, 1));
+  v->pt_off.assign(NP + 1, 0), v->ps_off.assign(NK + 1, 0), v->pt_edges.resize(E), v->ps_edges.resize(E);
   for (int e = 0; e < E; ++e) {
-    ++pt_off[p->edge_point[e] + 1];
-    ++ps_off[p->edge_pose[e] + 1];
+    ++v->pt_off[p->edge_point[e] + 1];
+    ++v->ps_off[p->edge_pose[e] + 1];
   }
-  for (int i = 0; i < NP; ++i) pt_off[i + 1] += pt_off[i];
-  for (int i = 0; i < NK; ++i) ps_off[i + 1] += ps_off[i];
-  {
-    std::vector<int32_t> pc(pt_off.begin(), pt_off.end() - 1), kc(ps_off.begin(), ps_off.end() - 1);
-    for (int e = 0; e < E; ++e) {
-      pt_edges[pc[p->edge_point[e]]++] = e;
-      ps_edges[kc[p->edge_pose[e]]++] = e;
-    }
+  for (int i = 0; i < NP; ++i) v->pt_off[i + 1] += v->pt_off[i];
+  for (int i = 0; i < NK; ++i) v->ps_off[i + 1] += v->ps_off[i];
+  std::vector<int32_t> pc(v->pt_off.begin(), v->pt_off.end() - 1), kc(v->ps_off.begin(), v->ps_off.end() - 1);
+  for (int e = 0; e < E; ++e) {
+    v->pt_edges[pc[p->edge_point[e]]++] = e;
+    v->ps_edges[kc[p->edge_pose[e]]++] = e;
   }
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
-  // r3: the system is built by the kernels of the device-side Levenberg-Marquardt path (k_lm.hip: every edge linearised once, eight lanes
-  // per point, a workgroup per pose -- 22 us where round 1's three kernels, each recomputing every edge's Jacobians, took 171); inputs
-  // and lists go up as ONE block through the page-locked staging buffer, the blocks come back as one
-  const size_t o_pose = take((size_t)NK * 56), o_pt = take((size_t)NP * 24), o_ep = take((size_t)E * 4), o_et = take((size_t)E * 4),
-               o_meas = take((size_t)E * 24), o_st = take((size_t)E), o_info = take((size_t)E * 8), o_delta = take((size_t)E * 8),
-               o_fix = take((size_t)NK), o_pto = take((size_t)(NP + 1) * 4), o_pte = take((size_t)E * 4), o_pso = take((size_t)(NK + 1) * 4),
-               o_pse = take((size_t)E * 4), o_state = take(sizeof(LmState)), o_level = take((size_t)E), o_up_end = take(8),
-               o_hpp = take((size_t)NK * 288), o_bp = take((size_t)NK * 48), o_hll = take((size_t)NP * 72),
-               o_bl = take((size_t)NP * 24), o_hpl = take((size_t)E * 144), o_out_end = take(8), o_terms = take((size_t)E * 256),
-               o_chi = take((size_t)((NP + 31) / 32) * 8);
-  TRY(ensure_tmp(c, off));
-  TRY(ensure_stage(c, std::max(o_up_end, o_out_end - o_hpp)));
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* hs = c->main.h_stage;
-  auto up = [&](size_t o2, const void* src, size_t bytes) {
-    if (bytes) std::memcpy(hs + o2, src, bytes);
-  };
-  up(o_pose, p->poses, (size_t)NK * 56);
-  up(o_pt, p->points, (size_t)NP * 24);
-  up(o_ep, p->edge_pose, (size_t)E * 4);
-  up(o_et, p->edge_point, (size_t)E * 4);
-  up(o_meas, p->meas, (size_t)E * 24);
-  up(o_st, p->is_stereo, (size_t)E);
-  up(o_info, p->info, (size_t)E * 8);
-  up(o_delta, p->huber_delta, (size_t)E * 8);
-  if (pose_fixed)
-    up(o_fix, pose_fixed, (size_t)NK);
-  else
-    std::memset(hs + o_fix, 0, (size_t)std::max(NK, 1));
-  up(o_pto, pt_off.data(), (size_t)(NP + 1) * 4);
-  up(o_pte, pt_edges.data(), (size_t)E * 4);
-  up(o_pso, ps_off.data(), (size_t)(NK + 1) * 4);
-  up(o_pse, ps_edges.data(), (size_t)E * 4);
-  std::memset(hs + o_state, 0, o_up_end - o_state);  // control state (buffer 0 current) and the edge levels (all active)
-  HIP_TRY(c, hipMemcpyAsync(b, hs, o_up_end, hipMemcpyHostToDevice, c->stream));
-  BaParamsDev prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
-  {
-    LmLaunch L{};
-    L.NK = NK, L.NP = NP, L.E = E, L.nf = 0;
-    L.poses[0] = L.poses[1] = (double*)(b + o_pose), L.points[0] = L.points[1] = (double*)(b + o_pt);
-    L.terms[0] = L.terms[1] = (double*)(b + o_terms), L.Hpl[0] = L.Hpl[1] = (double*)(b + o_hpl);
-    L.Hpp[0] = L.Hpp[1] = (double*)(b + o_hpp), L.bp[0] = L.bp[1] = (double*)(b + o_bp);
-    L.Hll[0] = L.Hll[1] = (double*)(b + o_hll), L.bl[0] = L.bl[1] = (double*)(b + o_bl);
-    L.chi_part[0] = L.chi_part[1] = (double*)(b + o_chi);
-    L.state = (LmState*)(b + o_state);
-    L.edge_pose = (const int32_t*)(b + o_ep), L.edge_point = (const int32_t*)(b + o_et);
-    L.pt_off = (const int32_t*)(b + o_pto), L.pt_edges = (const int32_t*)(b + o_pte);
-    L.ps_off = (const int32_t*)(b + o_pso), L.ps_edges = (const int32_t*)(b + o_pse);
-    L.meas = (const double*)(b + o_meas), L.info = (const double*)(b + o_info), L.is_stereo = b + o_st, L.fixed = b + o_fix;
-    L.info_eff = (double*)(b + o_info), L.delta_eff = (double*)(b + o_delta), L.chi2_last = nullptr, L.level = b + o_level;
-    L.prm = prm;
-    StageTimer tm(c, ORBFE_STAGE_BA, c->stream);
-    launch_lm_build(c->stream, L, 0, 0, 0, true);
-  }
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs, b + o_hpp, (o->Hpl ? o_out_end : o_hpl) - o_hpp, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  drain_timers(c);
-  std::memcpy(o->Hpp, hs, (size_t)NK * 288);
-  std::memcpy(o->bp, hs + (o_bp - o_hpp), (size_t)NK * 48);
-  std::memcpy(o->Hll, hs + (o_hll - o_hpp), (size_t)NP * 72);
-  std::memcpy(o->bl, hs + (o_bl - o_hpp), (size_t)NP * 24);
-  if (o->Hpl) std::memcpy(o->Hpl, hs + (o_hpl - o_hpp), (size_t)E * 144);
-  return ORBFE_OK;
 }
 
-// Optimizer::OptimizeLocalMap's two optimize() calls (Optimizer.cc:336-362) with g2o's Levenberg-Marquardt control on the host
-// (a handful of scalars per trial) and every vertex / edge / block operation on the device.
-orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, const uint8_t* pose_fixed, int32_t iters_first,
-                                     int32_t iters_second, const volatile uint8_t* stop_flag, const orbfe_ba_optimize_out* o) {
-  ApiLock api_lk(c);
-  static const bool trace_host = getenv("ORBFE_LBA_TRACE") != nullptr;  // diagnostic: host phases of this call on stderr
-  auto t_prev = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!trace_host) return;
+// The problem's arrays in the scratch (every entry point uploads them) and, behind them, the fixed flags and the vertex lists: one table
+// of (source, bytes) that is laid out by ba_take and staged by ba_put.
+enum { BA_POSE, BA_PT, BA_EP, BA_ET, BA_MEAS, BA_ST, BA_INFO, BA_DELTA, BA_FIX, BA_PTO, BA_PTE, BA_PSO, BA_PSE, BA_FIELDS };
+struct BaInputs {
+  struct Field {
+    const void* src;
+    size_t bytes, off;
+  } f[BA_FIELDS];
+  int n;
+  size_t operator[](int k) const { return f[k].off; }
+};
+// v == nullptr: the problem alone (no fixed flags, no lists)
+void ba_take(ScratchLayout& L, const orbfe_ba_problem* p, const uint8_t* pose_fixed, const BaVertexLists* v, BaInputs* in) {
+  const size_t E = (size_t)p->n_edges, NK = (size_t)p->n_poses, NP = (size_t)p->n_points;
+  const BaInputs::Field f[BA_FIELDS] = {
+      {p->poses, NK * 56, 0}, {p->points, NP * 24, 0}, {p->edge_pose, E * 4, 0}, {p->edge_point, E * 4, 0}, {p->meas, E * 24, 0},
+      {p->is_stereo, E, 0}, {p->info, E * 8, 0}, {p->huber_delta, E * 8, 0}, {pose_fixed, NK, 0},
+      // (k_lm_linpoints / k_lm_pose_block, k_lba_solve and k_ba_system read pt_off[point + 1] and ps_off[pose + 1] of the last vertex)
+      {v ? v->pt_off.data() : nullptr, (NP + 1) * 4, 0}, {v ? v->pt_edges.data() : nullptr, E * 4, 0},
+      {v ? v->ps_off.data() : nullptr, (NK + 1) * 4, 0}, {v ? v->ps_edges.data() : nullptr, E * 4, 0}};
+  in->n = v ? BA_FIELDS : BA_FIX;
+  for (int k = 0; k < in->n; ++k) in->f[k] = {f[k].src, f[k].bytes, L.take(f[k].bytes)};
+}
+void ba_put(StagedIo& io, const BaInputs& in) {
+  for (int k = 0; k < in.n; ++k)
+    if (in.f[k].src) io.put(in.f[k].off, in.f[k].src, in.f[k].bytes);
+    else std::memset(io.host<uint8_t>(in.f[k].off), 0, in.f[k].bytes);  // (no pose_fixed array: every pose is free)
+}
+// what the system build and the device-side optimiser tell the k_lm kernels in the same way: sizes, inputs, lists, camera
+void lm_fill_inputs(LmLaunch& L, const StagedIo& io, const BaInputs& in, const orbfe_ba_problem* p) {
+  L.NK = p->n_poses, L.NP = p->n_points, L.E = p->n_edges;
+  L.poses[0] = io.dev<double>(in[BA_POSE]), L.points[0] = io.dev<double>(in[BA_PT]);
+  L.edge_pose = io.dev<int32_t>(in[BA_EP]), L.edge_point = io.dev<int32_t>(in[BA_ET]);
+  L.pt_off = io.dev<int32_t>(in[BA_PTO]), L.pt_edges = io.dev<int32_t>(in[BA_PTE]);
+  L.ps_off = io.dev<int32_t>(in[BA_PSO]), L.ps_edges = io.dev<int32_t>(in[BA_PSE]);
+  L.meas = io.dev<double>(in[BA_MEAS]), L.info = io.dev<double>(in[BA_INFO]), L.is_stereo = io.dev<uint8_t>(in[BA_ST]);
+  L.fixed = io.dev<uint8_t>(in[BA_FIX]), L.delta_eff = io.dev<double>(in[BA_DELTA]);
+  L.prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
+}
+
+// one orbfe_ba_local_optimize call: the arguments, what the entry point derived from them, and its ORBFE_LBA_TRACE marks
+struct LbaCall {
+  orbfe_ctx* c;
+  const orbfe_ba_problem* p;
+  const uint8_t* pose_fixed;
+  int32_t iters_first, iters_second;
+  const volatile uint8_t* stop_flag;
+  const orbfe_ba_optimize_out* o;
+  bool trace;  // ORBFE_LBA_TRACE (diagnostic): host phases of this call on stderr
+  BaVertexLists v;
+  std::vector<int32_t> slot, free_pose;  // pose -> index among the free poses (-1: fixed) and back
+  int nf = 0, pair_cap = 1;              // free poses | the most edges any free pose has
+  std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+  orbfe_status device_lm(), host_lm();
+  void mark(const char* what) {
+    if (!trace) return;
     const auto now = std::chrono::steady_clock::now();
     fprintf(stderr, "[orbfe lba] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - t_prev).count());
     t_prev = now;
-  };
-  if (!c || !p || !o) return fail(c, ORBFE_EBADARG, "ba_local_optimize: NULL argument");
+  }
+};
+
+// ---- Levenberg-Marquardt control on the device (k_lm.hip): enqueue the whole optimisation, synchronise once --------------------------
+orbfe_status LbaCall::device_lm() {
+  const size_t E = (size_t)p->n_edges, NK = (size_t)p->n_poses, NP = (size_t)p->n_points, n = (size_t)6 * nf, NF = (size_t)nf;
+  const bool big_solver = nf > LM_CHOL_MAX_NB;  // the blocked multi-workgroup Cholesky of k_lmbig.hip
+  mark("pair lists");  // (built on the device: k_lm_pairs)
+  HIP_TRY(c, hipSetDevice(c->device));
+  TRY(join_stereo(c));
+  // ONE upload: the inputs and the lists are laid out in page-locked staging memory exactly as in the device scratch and go up as a
+  // single asynchronous copy -- eighteen copies from pageable memory were staged by the runtime one by one, ~0.3 ms of a 4 ms call
+  ScratchLayout L;
+  ScratchRegion up, zero, big_zero, out;
+  BaInputs in;
+  ba_take(L.open(up), p, pose_fixed, &v, &in);
+  const size_t o_info_eff = L.take<double>(E), o_free = L.take<int32_t>(NF), o_slot = L.take<int32_t>(NK),
+               o_lmstate = L.take(sizeof(LmState)),  // (the initial control state rides in the one upload)
+               // the second estimate, both system buffers, per-edge terms, the blocked reduced system
+               o_pose1 = L.close(up).take<double>(NK * 7), o_pt1 = L.take<double>(NP * 3);
+  const size_t chi_blocks = (NP + 31) / 32, scale_blocks = (NP + 31) / 32 + (NK + 255) / 256;  // (k_lm_linpoints: a partial sum per block of 32 points)
+  size_t o_terms[2], o_hpl[2], o_hpp[2], o_bp[2], o_hll[2], o_bl[2], o_chi[2];
+  for (int k = 0; k < 2; ++k)
+    o_terms[k] = L.take<double>(E * 32), o_hpl[k] = L.take<double>(E * 18), o_hpp[k] = L.take<double>(NK * 36), o_bp[k] = L.take<double>(NK * 6),
+    o_hll[k] = L.take<double>(NP * 9), o_bl[k] = L.take<double>(NP * 3), o_chi[k] = L.take<double>(chi_blocks);
+  const size_t KT = big_solver ? (size_t)lm_big_ld(nf) / 48 : 0;
+  const size_t o_w = L.take<double>(E * 18), o_rhs = L.take<double>(n),
+               o_x = L.take<double>(big_solver ? KT * 48 : n),  // k_lmb_back_mw writes and reads the ld entries of the padded system
+               o_ptable = L.take<int32_t>(NF * NP), o_pairs = L.take<int2>(NF * (NF + 1) / 2 * pair_cap), o_paircnt = L.take<int32_t>(NF * (NF + 1) / 2),
+               o_sblk = L.take(big_solver ? 8 : NF * (NF + 1) / 2 * 288), o_scale = L.take<double>(scale_blocks),
+               o_big = L.open(big_zero).take(big_solver ? lm_big_bytes(nf) : 8),  // big_zero: the matrix and the flags behind it
+               o_bigflags = L.take<int32_t>(2 * KT + 1),  // k_lmb_step / k_lmb_back_mw: [KT] bad pivot, [KT + 1, 2 KT + 1) column flags
+               o_biginv = L.close(big_zero).take(big_solver ? lm_big_inv_bytes(nf) : 8),
+               // zero: one block that starts as zeros (ONE fill): edge levels | chi2 of the last linearisation | point inverses
+               o_level = L.open(zero).take(E), o_last = L.take<double>(E), o_dinv = L.take<double>(NP * 9),
+               // out: the results as ONE block (one download): poses | points | chi2 | level | bad | the control state as the last control step left it
+               o_pose_out = L.close(zero).open(out).take<double>(NK * 7), o_pt_out = L.take<double>(NP * 3), o_chi2_out = L.take<double>(E),
+               o_level_out = L.take(E), o_bad_out = L.take(E), o_state_out = L.take(sizeof(LmState));
+  L.close(out);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, out.bytes())));  // (the staging buffer is also the target of the one result download)
+  hipStream_t st = c->stream;
+  ba_put(io, in);
+  io.put(o_info_eff, p->info, E * 8);
+  io.put(o_free, free_pose.data(), NF * 4);
+  io.put(o_slot, slot.data(), NK * 4);
+  LmState init{};
+  init.iters[0] = iters_first, init.iters[1] = iters_second, init.need_chi = 1, init.ok = 1;
+  io.put(o_lmstate, &init, sizeof init);
+  mark("stage inputs");
+  HIP_TRY(c, io.upload(up));
+  HIP_TRY(c, hipMemsetAsync(io.dev<uint8_t>(zero.begin), 0, zero.bytes(), st));  // (every memset is a launch of 4.6 us: six of them preceded the first kernel)
+  if (!c->h_abort) HIP_TRY(c, hipHostMalloc((void**)&c->h_abort, 64, hipHostMallocMapped));
+  void* d_abort = nullptr;
+  HIP_TRY(c, hipHostGetDevicePointer(&d_abort, (void*)c->h_abort, 0));
+  *c->h_abort = (stop_flag && *stop_flag) ? 1 : 0;
+  LmLaunch K{};
+  lm_fill_inputs(K, io, in, p);
+  K.nf = nf;
+  K.poses[1] = io.dev<double>(o_pose1), K.points[1] = io.dev<double>(o_pt1);
+  for (int k = 0; k < 2; ++k)
+    K.terms[k] = io.dev<double>(o_terms[k]), K.Hpl[k] = io.dev<double>(o_hpl[k]), K.Hpp[k] = io.dev<double>(o_hpp[k]), K.bp[k] = io.dev<double>(o_bp[k]),
+    K.Hll[k] = io.dev<double>(o_hll[k]), K.bl[k] = io.dev<double>(o_bl[k]), K.chi_part[k] = io.dev<double>(o_chi[k]);
+  K.state = io.dev<LmState>(o_lmstate);
+  K.free_pose = io.dev<int32_t>(o_free), K.pose_slot = io.dev<int32_t>(o_slot);
+  K.pairs = io.dev<int2>(o_pairs), K.pair_cnt = io.dev<int32_t>(o_paircnt), K.pair_table = io.dev<int32_t>(o_ptable), K.pair_cap = pair_cap;
+  K.info_eff = io.dev<double>(o_info_eff), K.chi2_last = io.dev<double>(o_last), K.level = io.dev<uint8_t>(o_level);
+  K.Dinv = io.dev<double>(o_dinv), K.W = io.dev<double>(o_w), K.Sblk = io.dev<double>(o_sblk), K.rhs = io.dev<double>(o_rhs), K.x = io.dev<double>(o_x);
+  K.scale_part = io.dev<double>(o_scale), K.chi2_out = io.dev<double>(o_chi2_out), K.poses_out = io.dev<double>(o_pose_out);
+  K.points_out = io.dev<double>(o_pt_out), K.bad = io.dev<uint8_t>(o_bad_out), K.level_out = io.dev<uint8_t>(o_level_out);
+  K.abort_flag = (const volatile uint8_t*)d_abort;
+  // (the initial state went up with the inputs; the ticket and the point inverses -- read by a trial whose point block was singular --
+  //  are part of the one zero fill)
+  K.state_out = io.dev<LmState>(o_state_out);
+  K.M = big_solver ? io.dev<double>(o_big) : nullptr, K.ld = big_solver ? lm_big_ld(nf) : 0, K.lmb_flags = io.dev<int32_t>(o_bigflags),
+  K.lmb_inv = io.dev<double>(o_biginv);
+  StageTimer tm(c, ORBFE_STAGE_BA, st);
+  if (big_solver) {
+    HIP_TRY(c, hipMemsetAsync(io.dev<uint8_t>(big_zero.begin), 0, big_zero.bytes(), st));
+    launch_lm_big_init(st, K);
+  }
+  HIP_TRY(c, hipMemsetAsync(K.pair_table, 0xFF, NF * NP * 4, st));
+  launch_lm_pairs(st, K);
+  launch_lm_build(st, K, 0, 0, iters_first > 0 ? 1 : 0, true);  // computeActiveErrors + buildSystem at the initial estimate
+  launch_lm_maxdiag(st, K, 0);
+  // trials provisioned per pass: every iteration needs at least one, a rejected trial costs one more; what is left over runs as no-ops
+  // (a few microseconds each), what is missing is enqueued in the next pass, after the one synchronisation of this one
+  // (measured: a provisioned trial that turns out not to be needed is six empty launches of 4.6 us; one spare
+  // -- in round 0, where coming up one short would leave the ten trials of round 1 as no-ops in this pass; round 1 gets none: if a trial
+  // of it is rejected, the second pass enqueues what is missing)
+  int steps_a = std::min(iters_first + 1, 24), steps_b = std::min(iters_second, 24);
+  LmState fin{};
+  for (int pass = 0;; ++pass) {
+    launch_lm_steps(st, K, steps_a);
+    launch_lm_switch(st, K);
+    launch_lm_steps(st, K, steps_b);
+    launch_lm_final(st, K);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, io.download(out));  // the upload from the staging buffer finished long ago (stream order)
+    if (stop_flag) {
+      // the device polls the mapped byte between the trials; the caller's flag (LocalMapping::mbAbortBA, written by the Tracking
+      // thread) is mirrored into it while this thread waits
+      hipEvent_t ev = nullptr;
+      HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      hipError_t er = hipEventRecord(ev, st);
+      while (er == hipSuccess) {
+        if (*stop_flag) *c->h_abort = 1;
+        er = hipEventQuery(ev);
+        if (er == hipErrorNotReady) {
+          (void)hipGetLastError();
+          er = hipSuccess;
+          sched_yield();
+          continue;
+        }
+        break;
+      }
+      (void)hipEventDestroy(ev);
+      HIP_TRY(c, er);
+    }
+    mark("enqueue");
+    HIP_TRY(c, io.wait());
+    mark("device (wait)");
+    io.get(&fin, o_state_out, sizeof fin);
+    if (fin.finalized) {
+      io.get(o->poses, o_pose_out, NK * 56);
+      io.get(o->points, o_pt_out, NP * 24);
+      io.get(o->chi2, o_chi2_out, E * 8);
+      io.get(o->level, o_level_out, E);
+      io.get(o->bad, o_bad_out, E);
+      break;
+    }
+    if (pass >= 4096) return fail(c, ORBFE_EDEVICE, "ba_local_optimize: the device-side Levenberg-Marquardt loop did not finish (round %d, phase %d)", fin.round, fin.phase);
+    // more trials were needed than provisioned: continue where the state stands
+    steps_a = fin.switched || fin.round == 2 ? 0 : std::min(std::max(iters_first - fin.it, 0) + 2, 24);
+    steps_b = std::min((fin.switched ? std::max(iters_second - fin.it, 0) : iters_second) + 2, 24);
+  }
+  if (o->iterations) {
+    o->iterations[0] = fin.done[0];
+    o->iterations[1] = fin.done[1];
+  }
+  drain_timers(c);
+  mark("results out");
+  return ORBFE_OK;
+}
+
+// ---- g2o's Levenberg-Marquardt control on the host (a handful of scalars per trial), every vertex / edge / block operation on the device:
+// ORBFE_LBA_HOST_LM=1, more than LM_BIG_MAX_NB free keyframes, or a pose that observes a point twice ------------------------------------
+orbfe_status LbaCall::host_lm() {
   const int E = p->n_edges, NK = p->n_poses, NP = p->n_points;
-  if (E < 0 || NK < 0 || NP < 0 || iters_first < 0 || iters_second < 0) return fail(c, ORBFE_EBADARG, "ba_local_optimize: negative size");
-  if (!o->poses || !o->points) return fail(c, ORBFE_EBADARG, "ba_local_optimize: NULL output");
-  if ((NK && !p->poses) || (NP && !p->points) ||
-      (E && (!p->edge_pose || !p->edge_point || !p->meas || !p->is_stereo || !p->info || !p->huber_delta)))
-    return fail(c, ORBFE_EBADARG, "ba_local_optimize: NULL array");
-  for (int e = 0; e < E; ++e)
-    if (p->edge_pose[e] < 0 || p->edge_pose[e] >= NK || p->edge_point[e] < 0 || p->edge_point[e] >= NP)
-      return fail(c, ORBFE_EBADARG, "ba_local_optimize: edge %d references vertex out of range", e);
-  // free poses, vertex -> edges lists (ascending edge index), pose-pair lists of the Schur complement
-  std::vector<int32_t> slot(std::max(NK, 1), -1), free_pose;
-  for (int k = 0; k < NK; ++k)
-    if (!(pose_fixed && pose_fixed[k])) {
-      slot[k] = (int32_t)free_pose.size();
-      free_pose.push_back(k);
-    }
-  const int nf = (int)free_pose.size();
-  // (no bound on nf: up to LBA_MAX_FREE free keyframes the reduced system is factorised by one workgroup out of LDS, beyond that by the
-  //  multi-workgroup path of k_lba.hip with its panel in global memory)
-  std::vector<int32_t> pt_off(NP + 1, 0), ps_off(NK + 1, 0), pt_edges(std::max(E, 1)), ps_edges(std::max(E, 1));
-  for (int e = 0; e < E; ++e) {
-    ++pt_off[p->edge_point[e] + 1];
-    ++ps_off[p->edge_pose[e] + 1];
-  }
-  for (int i = 0; i < NP; ++i) pt_off[i + 1] += pt_off[i];
-  for (int i = 0; i < NK; ++i) ps_off[i + 1] += ps_off[i];
-  {
-    std::vector<int32_t> pc(pt_off.begin(), pt_off.end() - 1), kc(ps_off.begin(), ps_off.end() - 1);
-    for (int e = 0; e < E; ++e) {
-      pt_edges[pc[p->edge_point[e]]++] = e;
-      ps_edges[kc[p->edge_pose[e]]++] = e;
-    }
-  }
-  // The device-side Levenberg-Marquardt path (k_lm.hip) builds the pair lists of the reduced system itself, from a (pose, point) -> edge
-  // table: that needs a pose to observe a point at most once (as every map of the reference does); anything else takes the host-driven path.
-  bool single_obs = true;
-  int pair_cap = 1;
-  {
-    std::vector<int32_t> seen(std::max(NK, 1), -1);
-    for (int pt = 0; pt < NP && single_obs; ++pt)
-      for (int a = pt_off[pt]; a < pt_off[pt + 1]; ++a) {
-        const int k = p->edge_pose[pt_edges[a]];
-        if (seen[k] == pt) {
-          single_obs = false;
-          break;
-        }
-        seen[k] = pt;
-      }
-    for (int k = 0; k < NK; ++k)
-      if (slot[k] >= 0) pair_cap = std::max(pair_cap, ps_off[k + 1] - ps_off[k]);
-  }
-  mark("validate + vertex lists");
-  std::vector<int32_t> pair_off(1, 0);
-  std::vector<int2> pairs;
-  const bool lower_only = c && c->lm_on_device && E > 0 && nf <= LM_BIG_MAX_NB && single_obs;  // (= dev_lm below)
-  const bool big_solver = lower_only && nf > LM_CHOL_MAX_NB;  // the blocked multi-workgroup Cholesky of k_lmbig.hip
-  if (!lower_only) {
-    pair_off.assign((size_t)nf * nf + 1, 0);
+  // pose-pair lists of the Schur complement: for every pair (i, j) of free poses, the edge pairs (e1, e2) through a common point
+  auto each_pair = [&](auto&& f) {
     for (int pt = 0; pt < NP; ++pt)
-      for (int a = pt_off[pt]; a < pt_off[pt + 1]; ++a) {
-        const int i = slot[p->edge_pose[pt_edges[a]]];
+      for (int q1 = v.pt_off[pt]; q1 < v.pt_off[pt + 1]; ++q1) {
+        const int e1 = v.pt_edges[q1], i = slot[p->edge_pose[e1]];
         if (i < 0) continue;
-        for (int b2 = pt_off[pt]; b2 < pt_off[pt + 1]; ++b2) {
-          const int j = slot[p->edge_pose[pt_edges[b2]]];
-          if (j >= 0) ++pair_off[(size_t)i * nf + j + 1];
+        for (int q2 = v.pt_off[pt]; q2 < v.pt_off[pt + 1]; ++q2) {
+          const int e2 = v.pt_edges[q2], j = slot[p->edge_pose[e2]];
+          if (j >= 0) f((size_t)i * nf + j, e1, e2);
         }
       }
-    for (size_t q = 0; q < (size_t)nf * nf; ++q) pair_off[q + 1] += pair_off[q];
-    pairs.resize(std::max<size_t>(pair_off.back(), 1));
-    std::vector<int32_t> cur(pair_off.begin(), pair_off.end() - 1);
-    for (int pt = 0; pt < NP; ++pt)
-      for (int a = pt_off[pt]; a < pt_off[pt + 1]; ++a) {
-        const int e1 = pt_edges[a], i = slot[p->edge_pose[e1]];
-        if (i < 0) continue;
-        for (int b2 = pt_off[pt]; b2 < pt_off[pt + 1]; ++b2) {
-          const int e2 = pt_edges[b2], j = slot[p->edge_pose[e2]];
-          if (j >= 0) pairs[cur[(size_t)i * nf + j]++] = make_int2(e1, e2);
-        }
-      }
-  }
+  };
+  std::vector<int32_t> pair_off((size_t)nf * nf + 1, 0);
+  each_pair([&](size_t q, int, int) { ++pair_off[q + 1]; });
+  for (size_t q = 0; q < (size_t)nf * nf; ++q) pair_off[q + 1] += pair_off[q];
+  std::vector<int2> pairs(pair_off.back());
+  std::vector<int32_t> cur(pair_off.begin(), pair_off.end() - 1);
+  each_pair([&](size_t q, int e1, int e2) { pairs[cur[q]++] = make_int2(e1, e2); });
   mark("pair lists");
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
-  const size_t n = (size_t)6 * nf;
-  const size_t o_pose = take((size_t)NK * 56), o_pt = take((size_t)NP * 24), o_pose_bk = take((size_t)NK * 56), o_pt_bk = take((size_t)NP * 24),
-               o_ep = take((size_t)E * 4), o_et = take((size_t)E * 4), o_meas = take((size_t)E * 24), o_st = take((size_t)E),
-               o_info = take((size_t)E * 8), o_info_eff = take((size_t)E * 8), o_delta = take((size_t)E * 8), o_fix = take((size_t)NK),
-               o_pto = take((size_t)(NP + 1) * 4), o_pte = take((size_t)E * 4), o_pso = take((size_t)(NK + 1) * 4), o_pse = take((size_t)E * 4),
-               o_free = take((size_t)nf * 4), o_slot = take((size_t)NK * 4), o_pairoff = take(pair_off.size() * 4),
-               o_pairs = take(pairs.size() * 8), o_lmstate = take(sizeof(LmState)),  // (the initial control state rides in the one upload)
-               o_hpp = take((size_t)NK * 288), o_bp = take((size_t)NK * 48), o_hll = take((size_t)NP * 72),
-               o_bl = take((size_t)NP * 24), o_hpl = take((size_t)E * 144), o_w = take((size_t)E * 144),
-               o_s = take(n * n * 8), o_rhs = take(n * 8), o_x = take((n + 48) * 8), o_dxp = take((size_t)NK * 48), o_dxl = take((size_t)NP * 24),
-               o_err = take((size_t)E * 24), o_chi2 = take((size_t)E * 8), o_rho = take((size_t)E * 16),
-               // one block that starts as zeros (ONE fill): edge levels | chi2 of the last linearisation | point inverses
-               o_level = take((size_t)E), o_last = take((size_t)E * 8), o_dinv = take((size_t)NP * 72), o_zero_end = take(8),
-               o_depth = take((size_t)E), o_bad = take((size_t)E), o_sc = take(64),
-               o_big = take(nf > LBA_MAX_FREE ? ((n + 1) * 6 + (size_t)nf * 36 + n) * 8 : 8);
-  // the device-side Levenberg-Marquardt path (k_lm.hip): second estimate / system buffers, per-edge terms, blocked reduced system
-  const bool dev_lm = lower_only;
-  const int chi_blocks = (NP + 31) / 32, scale_blocks = (NP + 31) / 32 + (NK + 255) / 256;  // (k_lm_linpoints: a partial sum per block of 32 points)
-  size_t l_ptable = 0, l_pairs = 0, l_paircnt = 0, l_pose1 = 0, l_pt1 = 0, l_terms[2] = {0, 0}, l_hpl1 = 0, l_hpp1 = 0, l_bp1 = 0, l_hll1 = 0, l_bl1 = 0, l_chi[2] = {0, 0}, l_sblk = 0,
-         l_scale = 0, l_big = 0, l_bigflags = 0, l_biginv = 0, l_pose_out = 0, l_pt_out = 0, l_chi2_out = 0, l_level_out = 0, l_bad_out = 0, l_state_out = 0, l_out_end = 0;
-  if (dev_lm) {
-    l_pose1 = take((size_t)NK * 56), l_pt1 = take((size_t)NP * 24);
-    l_ptable = take((size_t)nf * NP * 4), l_pairs = take((size_t)nf * (nf + 1) / 2 * pair_cap * 8), l_paircnt = take((size_t)nf * (nf + 1) / 2 * 4);
-    l_terms[0] = take((size_t)E * 256), l_terms[1] = take((size_t)E * 256);
-    l_hpl1 = take((size_t)E * 144), l_hpp1 = take((size_t)NK * 288), l_bp1 = take((size_t)NK * 48), l_hll1 = take((size_t)NP * 72),
-    l_bl1 = take((size_t)NP * 24);
-    l_chi[0] = take((size_t)chi_blocks * 8), l_chi[1] = take((size_t)chi_blocks * 8);
-    l_sblk = take(big_solver ? 8 : (size_t)nf * (nf + 1) / 2 * 288), l_scale = take((size_t)scale_blocks * 8);
-    l_big = take(big_solver ? lm_big_bytes(nf) : 8), l_bigflags = take(big_solver ? (2 * ((size_t)lm_big_ld(nf) / 48) + 4) * 4 : 8),
-    l_biginv = take(big_solver ? lm_big_inv_bytes(nf) : 8);
-    // the results as ONE block (one download): poses | points | chi2 | level | bad
-    l_pose_out = take((size_t)NK * 56), l_pt_out = take((size_t)NP * 24), l_chi2_out = take((size_t)E * 8), l_level_out = take((size_t)E),
-    l_bad_out = take((size_t)E), l_state_out = take(sizeof(LmState)), l_out_end = take(8);  // (+ the control state as the last control step left it)
-  }
-  TRY(ensure_tmp(c, off));
-  uint8_t* b = (uint8_t*)c->d_tmp;
+  const size_t n = (size_t)6 * nf, NE = (size_t)E, NKs = (size_t)NK, NPs = (size_t)NP;
+  ScratchLayout L;
+  ScratchRegion up, zero;
+  BaInputs in;
+  ba_take(L.open(up), p, pose_fixed, &v, &in);
+  const size_t o_info_eff = L.take<double>(NE), o_free = L.take<int32_t>((size_t)nf), o_slot = L.take<int32_t>(NKs),
+               o_pairoff = L.take<int32_t>(pair_off.size()), o_pairs = L.take<int2>(pairs.size()), o_pose_bk = L.close(up).take<double>(NKs * 7),
+               o_pt_bk = L.take<double>(NPs * 3), o_hpp = L.take<double>(NKs * 36), o_bp = L.take<double>(NKs * 6), o_hll = L.take<double>(NPs * 9),
+               o_bl = L.take<double>(NPs * 3), o_hpl = L.take<double>(NE * 18), o_w = L.take<double>(NE * 18), o_s = L.take<double>(n * n),
+               o_rhs = L.take<double>(n), o_x = L.take<double>(n), o_dxp = L.take<double>(NKs * 6), o_dxl = L.take<double>(NPs * 3),
+               o_err = L.take<double>(NE * 3), o_chi2 = L.take<double>(NE), o_rho = L.take<double>(NE * 2),
+               // zero: one block that starts as zeros (ONE fill): edge levels | chi2 of the last linearisation | point inverses
+               o_level = L.open(zero).take(NE), o_last = L.take<double>(NE), o_dinv = L.take<double>(NPs * 9), o_depth = L.close(zero).take(NE),
+               o_bad = L.take(NE), o_sc = L.take<double>(5),
+               o_big = L.take(nf > LBA_MAX_FREE ? ((n + 1) * 6 + (size_t)nf * 36 + n) * 8 : 8);  // launch_lba_solve's panel in global memory
+  const size_t o_pose = in[BA_POSE], o_pt = in[BA_PT], o_meas = in[BA_MEAS], o_st = in[BA_ST], o_info = in[BA_INFO], o_delta = in[BA_DELTA],
+               o_fix = in[BA_FIX], o_pto = in[BA_PTO], o_pte = in[BA_PTE], o_pso = in[BA_PSO], o_pse = in[BA_PSE];
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), up.end));
+  uint8_t* b = io.d;
   hipStream_t st = c->stream;
-  // ONE upload: the inputs and the lists built above are laid out in page-locked staging memory exactly as in the device scratch
-  // (they are its first o_hpp bytes) and go up as a single asynchronous copy -- eighteen copies from pageable memory were staged by the
-  // runtime one by one, ~0.3 ms of a 4 ms call
-  const size_t up_bytes = o_hpp;
-  TRY(ensure_stage(c, std::max(up_bytes, dev_lm ? l_out_end - l_pose_out : (size_t)0)));  // (also the target of the one result download)
-  uint8_t* hs = c->main.h_stage;
-  auto up = [&](size_t o2, const void* src, size_t bytes) -> hipError_t {
-    if (bytes) std::memcpy(hs + o2, src, bytes);
-    return hipSuccess;
-  };
-  std::vector<uint8_t> fixed_h(std::max(NK, 1), 0);
-  if (pose_fixed) std::memcpy(fixed_h.data(), pose_fixed, NK);
-  HIP_TRY(c, up(o_pose, p->poses, (size_t)NK * 56));
-  HIP_TRY(c, up(o_pt, p->points, (size_t)NP * 24));
-  HIP_TRY(c, up(o_ep, p->edge_pose, (size_t)E * 4));
-  HIP_TRY(c, up(o_et, p->edge_point, (size_t)E * 4));
-  HIP_TRY(c, up(o_meas, p->meas, (size_t)E * 24));
-  HIP_TRY(c, up(o_st, p->is_stereo, (size_t)E));
-  HIP_TRY(c, up(o_info, p->info, (size_t)E * 8));
-  HIP_TRY(c, up(o_info_eff, p->info, (size_t)E * 8));
-  HIP_TRY(c, up(o_delta, p->huber_delta, (size_t)E * 8));
-  HIP_TRY(c, up(o_fix, fixed_h.data(), (size_t)NK));
-  HIP_TRY(c, up(o_pto, pt_off.data(), (size_t)(NP + 1) * 4));
-  HIP_TRY(c, up(o_pte, pt_edges.data(), (size_t)E * 4));
-  HIP_TRY(c, up(o_pso, ps_off.data(), (size_t)(NK + 1) * 4));
-  HIP_TRY(c, up(o_pse, ps_edges.data(), (size_t)E * 4));
-  HIP_TRY(c, up(o_free, free_pose.data(), (size_t)nf * 4));
-  HIP_TRY(c, up(o_slot, slot.data(), (size_t)NK * 4));
-  HIP_TRY(c, up(o_pairoff, pair_off.data(), pair_off.size() * 4));
-  HIP_TRY(c, up(o_pairs, pairs.data(), pairs.size() * 8));
-  {
-    LmState init{};
-    init.iters[0] = iters_first, init.iters[1] = iters_second, init.need_chi = 1, init.ok = 1;
-    HIP_TRY(c, up(o_lmstate, &init, sizeof init));
-  }
+  ba_put(io, in);
+  io.put(o_info_eff, p->info, NE * 8);
+  io.put(o_free, free_pose.data(), (size_t)nf * 4);
+  io.put(o_slot, slot.data(), NKs * 4);
+  io.put(o_pairoff, pair_off.data(), pair_off.size() * 4);
+  io.put(o_pairs, pairs.data(), pairs.size() * 8);
   mark("stage inputs");
-  HIP_TRY(c, hipMemcpyAsync(b, hs, up_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemsetAsync(b + o_level, 0, o_zero_end - o_level, st));  // (every memset is a launch of 4.6 us: six of them preceded the first kernel)
+  HIP_TRY(c, io.upload(up));
+  HIP_TRY(c, hipMemsetAsync(b + zero.begin, 0, zero.bytes(), st));  // (every memset is a launch of 4.6 us: six of them preceded the first kernel)
 
   const BaParamsDev prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
   double* d_poses = (double*)(b + o_pose);
   double* d_points = (double*)(b + o_pt);
-  const int32_t* d_ek = (const int32_t*)(b + o_ep);
-  const int32_t* d_ep = (const int32_t*)(b + o_et);
+  const int32_t* d_ek = (const int32_t*)(b + in[BA_EP]);
+  const int32_t* d_ep = (const int32_t*)(b + in[BA_ET]);
   double* d_sc = (double*)(b + o_sc);  // [0] robust chi2, [1] max diagonal, [2] lambda, [3] ok (int), [4] scale
-  if (dev_lm) {
-    // ---- Levenberg-Marquardt control on the device: enqueue the whole optimisation, synchronise once ------------------------------
-    if (!c->h_abort) {
-      HIP_TRY(c, hipHostMalloc((void**)&c->h_abort, 64, hipHostMallocMapped));
-    }
-    void* d_abort = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer(&d_abort, (void*)c->h_abort, 0));
-    *c->h_abort = (stop_flag && *stop_flag) ? 1 : 0;
-    LmLaunch L{};
-    L.NK = NK, L.NP = NP, L.E = E, L.nf = nf;
-    L.poses[0] = d_poses, L.poses[1] = (double*)(b + l_pose1), L.points[0] = d_points, L.points[1] = (double*)(b + l_pt1);
-    L.terms[0] = (double*)(b + l_terms[0]), L.terms[1] = (double*)(b + l_terms[1]);
-    L.Hpl[0] = (double*)(b + o_hpl), L.Hpl[1] = (double*)(b + l_hpl1), L.Hpp[0] = (double*)(b + o_hpp), L.Hpp[1] = (double*)(b + l_hpp1);
-    L.bp[0] = (double*)(b + o_bp), L.bp[1] = (double*)(b + l_bp1), L.Hll[0] = (double*)(b + o_hll), L.Hll[1] = (double*)(b + l_hll1);
-    L.bl[0] = (double*)(b + o_bl), L.bl[1] = (double*)(b + l_bl1), L.chi_part[0] = (double*)(b + l_chi[0]), L.chi_part[1] = (double*)(b + l_chi[1]);
-    L.state = (LmState*)(b + o_lmstate);
-    L.edge_pose = d_ek, L.edge_point = d_ep, L.pt_off = (const int32_t*)(b + o_pto), L.pt_edges = (const int32_t*)(b + o_pte);
-    L.ps_off = (const int32_t*)(b + o_pso), L.ps_edges = (const int32_t*)(b + o_pse), L.free_pose = (const int32_t*)(b + o_free);
-    L.pose_slot = (const int32_t*)(b + o_slot), L.pairs = (int2*)(b + l_pairs), L.pair_cnt = (int32_t*)(b + l_paircnt);
-    L.pair_table = (int32_t*)(b + l_ptable), L.pair_cap = pair_cap;
-    L.meas = (const double*)(b + o_meas), L.info = (const double*)(b + o_info), L.is_stereo = b + o_st, L.fixed = b + o_fix;
-    L.info_eff = (double*)(b + o_info_eff), L.delta_eff = (double*)(b + o_delta), L.chi2_last = (double*)(b + o_last), L.level = b + o_level;
-    L.Dinv = (double*)(b + o_dinv), L.W = (double*)(b + o_w), L.Sblk = (double*)(b + l_sblk), L.rhs = (double*)(b + o_rhs), L.x = (double*)(b + o_x);
-    L.scale_part = (double*)(b + l_scale), L.chi2_out = (double*)(b + l_chi2_out), L.poses_out = (double*)(b + l_pose_out);
-    L.points_out = (double*)(b + l_pt_out), L.bad = b + l_bad_out, L.level_out = b + l_level_out;
-    L.abort_flag = (const volatile uint8_t*)d_abort, L.prm = prm;
-    // (the initial state went up with the inputs; the ticket and the point inverses -- read by a trial whose point block was singular --
-    //  are part of the one zero fill)
-    L.state_out = (LmState*)(b + l_state_out);
-    L.M = big_solver ? (double*)(b + l_big) : nullptr, L.ld = big_solver ? lm_big_ld(nf) : 0, L.lmb_flags = (int32_t*)(b + l_bigflags), L.lmb_inv = (double*)(b + l_biginv);
-    StageTimer tm(c, ORBFE_STAGE_BA, st);
-    if (big_solver) {
-      HIP_TRY(c, hipMemsetAsync(b + l_big, 0, (l_bigflags - l_big) + (2 * ((size_t)L.ld / 48) + 4) * 4, st));  // the matrix and the flags behind it
-      launch_lm_big_init(st, L);
-    }
-    HIP_TRY(c, hipMemsetAsync(L.pair_table, 0xFF, (size_t)nf * NP * 4, st));
-    launch_lm_pairs(st, L);
-    launch_lm_build(st, L, 0, 0, iters_first > 0 ? 1 : 0, true);  // computeActiveErrors + buildSystem at the initial estimate
-    launch_lm_maxdiag(st, L, 0);
-    // trials provisioned per pass: every iteration needs at least one, a rejected trial costs one more; what is left over runs as no-ops
-    // (a few microseconds each), what is missing is enqueued in the next pass, after the one synchronisation of this one
-    // (measured: a provisioned trial that turns out not to be needed is six empty launches of 4.6 us; one spare
-    // -- in round 0, where coming up one short would leave the ten trials of round 1 as no-ops in this pass; round 1 gets none: if a trial
-    // of it is rejected, the second pass enqueues what is missing)
-    int steps_a = std::min(iters_first + 1, 24), steps_b = std::min(iters_second, 24);
-    LmState fin{};
-    for (int pass = 0;; ++pass) {
-      launch_lm_steps(st, L, steps_a);
-      launch_lm_switch(st, L);
-      launch_lm_steps(st, L, steps_b);
-      launch_lm_final(st, L);
-      HIP_TRY(c, hipGetLastError());
-      const size_t out_bytes = l_out_end - l_pose_out;
-      HIP_TRY(c, hipMemcpyAsync(hs, b + l_pose_out, out_bytes, hipMemcpyDeviceToHost, st));  // the upload from hs finished long ago (stream order)
-      if (stop_flag) {
-        // the device polls the mapped byte between the trials; the caller's flag (LocalMapping::mbAbortBA, written by the Tracking
-        // thread) is mirrored into it while this thread waits
-        hipEvent_t ev = nullptr;
-        HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t er = hipEventRecord(ev, st);
-        while (er == hipSuccess) {
-          if (*stop_flag) *c->h_abort = 1;
-          er = hipEventQuery(ev);
-          if (er == hipErrorNotReady) {
-            (void)hipGetLastError();
-            er = hipSuccess;
-            sched_yield();
-            continue;
-          }
-          break;
-        }
-        (void)hipEventDestroy(ev);
-        HIP_TRY(c, er);
-      }
-      mark("enqueue");
-      HIP_TRY(c, hipStreamSynchronize(st));
-      mark("device (wait)");
-      std::memcpy(&fin, hs + (l_state_out - l_pose_out), sizeof fin);
-      if (fin.finalized) {
-        std::memcpy(o->poses, hs, (size_t)NK * 56);
-        std::memcpy(o->points, hs + (l_pt_out - l_pose_out), (size_t)NP * 24);
-        if (o->chi2) std::memcpy(o->chi2, hs + (l_chi2_out - l_pose_out), (size_t)E * 8);
-        if (o->level) std::memcpy(o->level, hs + (l_level_out - l_pose_out), (size_t)E);
-        if (o->bad) std::memcpy(o->bad, hs + (l_bad_out - l_pose_out), (size_t)E);
-        break;
-      }
-      if (pass >= 4096) return fail(c, ORBFE_EDEVICE, "ba_local_optimize: the device-side Levenberg-Marquardt loop did not finish (round %d, phase %d)", fin.round, fin.phase);
-      // more trials were needed than provisioned: continue where the state stands
-      steps_a = fin.switched || fin.round == 2 ? 0 : std::min(std::max(iters_first - fin.it, 0) + 2, 24);
-      steps_b = std::min((fin.switched ? std::max(iters_second - fin.it, 0) : iters_second) + 2, 24);
-    }
-    if (o->iterations) {
-      o->iterations[0] = fin.done[0];
-      o->iterations[1] = fin.done[1];
-    }
-    drain_timers(c);
-    mark("results out");
-    return ORBFE_OK;
-  }
   struct HostScalars {
     double chi, maxdiag, lambda;
     int32_t ok, pad;
     double scale;
   };
-  auto evaluate = [&](const double* d_info) {  // computeActiveErrors + activeRobustChi2
-    launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, d_info, (const double*)(b + o_delta), prm,
-                    (double*)(b + o_err), (double*)(b + o_chi2), (double*)(b + o_rho), nullptr, nullptr, b + o_depth);
+  auto edges = [&](size_t o_inf) {  // computeError() on every edge, with the given information values
+    launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, (const double*)(b + o_inf),
+                    (const double*)(b + o_delta), prm, (double*)(b + o_err), (double*)(b + o_chi2), (double*)(b + o_rho), nullptr, nullptr,
+                    b + o_depth);
+  };
+  auto evaluate = [&]() {  // computeActiveErrors + activeRobustChi2
+    edges(o_info_eff);
     launch_lba_chi2_sum(st, E, (const double*)(b + o_chi2), (const double*)(b + o_rho), b + o_level, (double*)(b + o_last), d_sc);
   };
   auto read_scalars = [&](HostScalars& h) -> hipError_t {
@@ -495,7 +324,7 @@ orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, co
     for (int it = 0; it < iterations; ++it) {
       if (stopped()) break;
       ++done;
-      evaluate((const double*)(b + o_info_eff));
+      evaluate();
       launch_ba_system(st, NK, NP, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, (const double*)(b + o_info_eff),
                        (const double*)(b + o_delta), prm, b + o_fix, (const int32_t*)(b + o_pto), (const int32_t*)(b + o_pte),
                        (const int32_t*)(b + o_pso), (const int32_t*)(b + o_pse), (double*)(b + o_hpp), (double*)(b + o_bp),
@@ -524,7 +353,7 @@ orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, co
                          (const double*)(b + o_hll), (const double*)(b + o_bl), (const double*)(b + o_hpl), d_sc + 2, (double*)(b + o_dinv),
                          (double*)(b + o_w), (double*)(b + o_s), (double*)(b + o_rhs), (double*)(b + o_x), (int*)(d_sc + 3), d_poses, d_points,
                          (double*)(b + o_dxp), (double*)(b + o_dxl), d_sc + 4, (double*)(b + o_big));
-        evaluate((const double*)(b + o_info_eff));
+        evaluate();
         HIP_TRY(c, read_scalars(h));
         const bool ok2 = h.ok != 0;
         const double temp_chi = ok2 ? h.chi : std::numeric_limits<double>::max();
@@ -553,28 +382,22 @@ orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, co
   TRY(optimize(iters_first, it1));
   if (!stopped()) {
     // edge->chi2() is the chi2 of the last evaluated trial; isDepthPositive() reads the current estimates (Optimizer.cc:338-359)
-    launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, (const double*)(b + o_info),
-                    (const double*)(b + o_delta), prm, (double*)(b + o_err), (double*)(b + o_chi2), (double*)(b + o_rho), nullptr, nullptr,
-                    b + o_depth);
+    edges(o_info);
     launch_lba_classify(st, E, (const double*)(b + o_last), b + o_depth, b + o_st, b + o_level, (double*)(b + o_info_eff),
                         (double*)(b + o_delta));
     TRY(optimize(iters_second, it2));
   }
   // final computeError() on every edge with the final estimates (Optimizer.cc:364-391)
-  launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, (const double*)(b + o_info),
-                  (const double*)(b + o_delta), prm, (double*)(b + o_err), (double*)(b + o_chi2), (double*)(b + o_rho), nullptr, nullptr,
-                  b + o_depth);
+  edges(o_info);
   launch_lba_final(st, E, (const double*)(b + o_chi2), b + o_depth, b + o_st, b + o_bad);
   HIP_TRY(c, hipGetLastError());
-  auto down = [&](void* dst, size_t o2, size_t bytes) -> hipError_t {
-    return (bytes && dst) ? hipMemcpyAsync(dst, b + o2, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  HIP_TRY(c, down(o->poses, o_pose, (size_t)NK * 56));
-  HIP_TRY(c, down(o->points, o_pt, (size_t)NP * 24));
-  HIP_TRY(c, down(o->level, o_level, (size_t)E));
-  HIP_TRY(c, down(o->chi2, o_chi2, (size_t)E * 8));
-  HIP_TRY(c, down(o->bad, o_bad, (size_t)E));
-  HIP_TRY(c, hipStreamSynchronize(st));
+  io.staged = false;  // the results go straight from the scratch to the caller's arrays
+  io.get(o->poses, o_pose, NKs * 56);
+  io.get(o->points, o_pt, NPs * 24);
+  io.get(o->level, o_level, NE);
+  io.get(o->chi2, o_chi2, NE * 8);
+  io.get(o->bad, o_bad, NE);
+  HIP_TRY(c, io.wait());
   if (o->iterations) {
     o->iterations[0] = it1;
     o->iterations[1] = it2;
@@ -582,6 +405,159 @@ orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, co
   return ORBFE_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+orbfe_status orbfe_ba_eval_edges(orbfe_ctx* c, const orbfe_ba_problem* p, const orbfe_ba_edge_out* o) {
+  ApiLock api_lk(c);
+  if (!c || !p || !o) return fail(c, ORBFE_EBADARG, "ba_eval_edges: NULL argument");
+  const int E = p->n_edges;
+  if (E < 0 || p->n_poses < 0 || p->n_points < 0) return fail(c, ORBFE_EBADARG, "ba_eval_edges: negative size");
+  if (E == 0) return ORBFE_OK;
+  if (!p->poses || !p->points || !p->edge_pose || !p->edge_point || !p->meas || !p->is_stereo || !p->info || !p->huber_delta || !o->error ||
+      !o->chi2 || !o->rho)
+    return fail(c, ORBFE_EBADARG, "ba_eval_edges: NULL array");
+  TRY(ba_check_problem(c, "ba_eval_edges", p));
+  HIP_TRY(c, hipSetDevice(c->device));
+  TRY(join_stereo(c));
+  const size_t NE = (size_t)E;
+  ScratchLayout L;
+  ScratchRegion up, out;
+  BaInputs in;
+  ba_take(L.open(up), p, nullptr, nullptr, &in);
+  const size_t o_err = L.close(up).open(out).take<double>(NE * 3), o_chi = L.take<double>(NE), o_rho = L.take<double>(NE * 2), o_dp = L.take(NE),
+               o_jpt = L.take<double>(NE * 9), o_jps = L.take<double>(NE * 18);
+  L.close(out);
+  // up to 16 MB in all: inputs as ONE upload through the page-locked staging buffer and the results as one download (eight copies from
+  // and six to pageable memory otherwise -- each staged by the runtime on its own)
+  const ScratchRegion down = o->j_pose ? out : out.upto(o->j_point ? o_jps : o_jpt);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes()), up.end + down.bytes() <= ((size_t)16 << 20)));
+  ba_put(io, in);
+  HIP_TRY(c, io.upload(up));
+  BaParamsDev prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
+  {
+    StageTimer tm(c, ORBFE_STAGE_BA, c->stream);
+    launch_ba_edges(c->stream, E, io.dev<double>(in[BA_POSE]), io.dev<double>(in[BA_PT]), io.dev<int32_t>(in[BA_EP]), io.dev<int32_t>(in[BA_ET]),
+                    io.dev<double>(in[BA_MEAS]), io.dev<uint8_t>(in[BA_ST]), io.dev<double>(in[BA_INFO]), io.dev<double>(in[BA_DELTA]), prm,
+                    io.dev<double>(o_err), io.dev<double>(o_chi), io.dev<double>(o_rho), o->j_point ? io.dev<double>(o_jpt) : nullptr,
+                    o->j_pose ? io.dev<double>(o_jps) : nullptr, o->depth_positive ? io.dev<uint8_t>(o_dp) : nullptr);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, io.download(down));
+  if (io.staged) HIP_TRY(c, io.wait());  // (staged: get reads the downloaded block; unstaged: get is the copy, waited for below)
+  io.get(o->error, o_err, NE * 24);
+  io.get(o->chi2, o_chi, NE * 8);
+  io.get(o->rho, o_rho, NE * 16);
+  io.get(o->j_point, o_jpt, NE * 72);
+  io.get(o->j_pose, o_jps, NE * 144);
+  io.get(o->depth_positive, o_dp, NE);
+  if (!io.staged) HIP_TRY(c, io.wait());
+  drain_timers(c);
+  return ORBFE_OK;
+}
+
+orbfe_status orbfe_ba_build_system(orbfe_ctx* c, const orbfe_ba_problem* p, const uint8_t* pose_fixed, const orbfe_ba_system_out* o) {
+  ApiLock api_lk(c);
+  if (!c || !p || !o) return fail(c, ORBFE_EBADARG, "ba_build_system: NULL argument");
+  const size_t E = (size_t)p->n_edges, NK = (size_t)p->n_poses, NP = (size_t)p->n_points;
+  if (p->n_edges < 0 || p->n_poses < 0 || p->n_points < 0) return fail(c, ORBFE_EBADARG, "ba_build_system: negative size");
+  if (!o->Hpp || !o->bp || !o->Hll || !o->bl) return fail(c, ORBFE_EBADARG, "ba_build_system: NULL output");
+  if (E && (!p->poses || !p->points || !p->edge_pose || !p->edge_point || !p->meas || !p->is_stereo || !p->info || !p->huber_delta))
+    return fail(c, ORBFE_EBADARG, "ba_build_system: NULL array");
+  TRY(ba_check_problem(c, "ba_build_system", p));
+  HIP_TRY(c, hipSetDevice(c->device));
+  TRY(join_stereo(c));
+  BaVertexLists v;
+  ba_vertex_lists(p, &v);
+  // r3: the system is built by the kernels of the device-side Levenberg-Marquardt path (k_lm.hip: every edge linearised once, eight lanes
+  // per point, a workgroup per pose -- 22 us where round 1's three kernels, each recomputing every edge's Jacobians, took 171); inputs
+  // and lists go up as ONE block through the page-locked staging buffer, the blocks come back as one
+  ScratchLayout L;
+  ScratchRegion up, zero, out;  // zero: control state (buffer 0 current) and the edge levels (all active), the tail of the upload
+  BaInputs in;
+  ba_take(L.open(up), p, pose_fixed, &v, &in);
+  const size_t o_state = L.open(zero).take(sizeof(LmState)), o_level = L.take(E), o_hpp = L.close(zero).close(up).open(out).take<double>(NK * 36),
+               o_bp = L.take<double>(NK * 6), o_hll = L.take<double>(NP * 9), o_bl = L.take<double>(NP * 3), o_hpl = L.take<double>(E * 18),
+               o_terms = L.close(out).take<double>(E * 32), o_chi = L.take<double>((NP + 31) / 32);
+  const ScratchRegion down = o->Hpl ? out : out.upto(o_hpl);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
+  ba_put(io, in);
+  std::memset(io.host<uint8_t>(zero.begin), 0, zero.bytes());
+  HIP_TRY(c, io.upload(up));
+  {
+    LmLaunch K{};
+    lm_fill_inputs(K, io, in, p);
+    K.nf = 0;
+    K.poses[1] = K.poses[0], K.points[1] = K.points[0];
+    K.terms[0] = K.terms[1] = io.dev<double>(o_terms), K.Hpl[0] = K.Hpl[1] = io.dev<double>(o_hpl);
+    K.Hpp[0] = K.Hpp[1] = io.dev<double>(o_hpp), K.bp[0] = K.bp[1] = io.dev<double>(o_bp);
+    K.Hll[0] = K.Hll[1] = io.dev<double>(o_hll), K.bl[0] = K.bl[1] = io.dev<double>(o_bl);
+    K.chi_part[0] = K.chi_part[1] = io.dev<double>(o_chi);
+    K.state = io.dev<LmState>(o_state);
+    K.info_eff = io.dev<double>(in[BA_INFO]), K.chi2_last = nullptr, K.level = io.dev<uint8_t>(o_level);
+    StageTimer tm(c, ORBFE_STAGE_BA, c->stream);
+    launch_lm_build(c->stream, K, 0, 0, 0, true);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, io.fetch(down));
+  drain_timers(c);
+  io.get(o->Hpp, o_hpp, NK * 288);
+  io.get(o->bp, o_bp, NK * 48);
+  io.get(o->Hll, o_hll, NP * 72);
+  io.get(o->bl, o_bl, NP * 24);
+  io.get(o->Hpl, o_hpl, E * 144);
+  return ORBFE_OK;
+}
+
+// Optimizer::OptimizeLocalMap's two optimize() calls (Optimizer.cc:336-362): validate, build the vertex lists, then one of the two
+// optimisers above.
+orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, const uint8_t* pose_fixed, int32_t iters_first,
+                                     int32_t iters_second, const volatile uint8_t* stop_flag, const orbfe_ba_optimize_out* o) {
+  ApiLock api_lk(c);
+  static const bool trace_host = getenv("ORBFE_LBA_TRACE") != nullptr;
+  LbaCall a{c, p, pose_fixed, iters_first, iters_second, stop_flag, o, trace_host};
+  if (!c || !p || !o) return fail(c, ORBFE_EBADARG, "ba_local_optimize: NULL argument");
+  const int E = p->n_edges, NK = p->n_poses, NP = p->n_points;
+  if (E < 0 || NK < 0 || NP < 0 || iters_first < 0 || iters_second < 0) return fail(c, ORBFE_EBADARG, "ba_local_optimize: negative size");
+  if (!o->poses || !o->points) return fail(c, ORBFE_EBADARG, "ba_local_optimize: NULL output");
+  if ((NK && !p->poses) || (NP && !p->points) ||
+      (E && (!p->edge_pose || !p->edge_point || !p->meas || !p->is_stereo || !p->info || !p->huber_delta)))
+    return fail(c, ORBFE_EBADARG, "ba_local_optimize: NULL array");
+  TRY(ba_check_problem(c, "ba_local_optimize", p));
+  a.slot.assign(NK, -1);
+  for (int k = 0; k < NK; ++k)
+    if (!(pose_fixed && pose_fixed[k])) {
+      a.slot[k] = (int32_t)a.free_pose.size();
+      a.free_pose.push_back(k);
+    }
+  a.nf = (int)a.free_pose.size();
+  // (no bound on nf: up to LBA_MAX_FREE free keyframes the reduced system is factorised by one workgroup out of LDS, beyond that by the
+  //  multi-workgroup path of k_lba.hip with its panel in global memory)
+  ba_vertex_lists(p, &a.v);
+  // The device-side Levenberg-Marquardt path (k_lm.hip) builds the pair lists of the reduced system itself, from a (pose, point) -> edge
+  // table: that needs a pose to observe a point at most once (as every map of the reference does); anything else takes the host-driven path.
+  bool single_obs = true;
+  {
+    std::vector<int32_t> seen(NK, -1);
+    for (int pt = 0; pt < NP && single_obs; ++pt)
+      for (int q = a.v.pt_off[pt]; q < a.v.pt_off[pt + 1]; ++q) {
+        const int k = p->edge_pose[a.v.pt_edges[q]];
+        if (seen[k] == pt) {
+          single_obs = false;
+          break;
+        }
+        seen[k] = pt;
+      }
+    for (int k = 0; k < NK; ++k)
+      if (a.slot[k] >= 0) a.pair_cap = std::max(a.pair_cap, a.v.ps_off[k + 1] - a.v.ps_off[k]);
+  }
+  a.mark("validate + vertex lists");
+  const bool dev_lm = c->lm_on_device && E > 0 && a.nf <= LM_BIG_MAX_NB && single_obs;
+  return dev_lm ? a.device_lm() : a.host_lm();
+}
 
 orbfe_status orbfe_pose_only_optimize(orbfe_ctx* c, int32_t n, const double* xw, const double* meas, const double* info, const float* sigma2,
                                       const double* pose_in, double fx, double fy, double cx, double cy, double bf, double* pose_out,
@@ -591,45 +567,36 @@ orbfe_status orbfe_pose_only_optimize(orbfe_ctx* c, int32_t n, const double* xw,
     return fail(c, ORBFE_EBADARG, "pose_only_optimize: NULL argument");
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
-  const size_t N = (size_t)std::max(n, 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
+  const size_t N = (size_t)n;
   // inputs as ONE upload through the page-locked staging buffer, results as one download (five copies from pageable memory up and three down
   // were a fifth of the call)
-  const size_t o_x = take(N * 24), o_m = take(N * 24), o_i = take(N * 8), o_s = take(N * 4), o_p = take(56), o_up_end = take(8),
-               o_po = take(56), o_ng = take(8), o_in = take(N), o_out_end = take(8), o_e = take(N * 24), o_l = take(N), o_r = take(N);
-  TRY(ensure_tmp(c, off));
-  TRY(ensure_stage(c, std::max(o_up_end, o_out_end - o_po)));
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* hs = c->main.h_stage;
-  if (n) {
-    std::memcpy(hs + o_x, xw, (size_t)n * 24);
-    std::memcpy(hs + o_m, meas, (size_t)n * 24);
-    std::memcpy(hs + o_i, info, (size_t)n * 8);
-    std::memcpy(hs + o_s, sigma2, (size_t)n * 4);
-  }
-  std::memcpy(hs + o_p, pose_in, 56);
-  HIP_TRY(c, hipMemcpyAsync(b, hs, o_up_end, hipMemcpyHostToDevice, c->stream));
+  ScratchLayout L;
+  ScratchRegion up, out;
+  const size_t o_x = L.open(up).take<double>(N * 3), o_m = L.take<double>(N * 3), o_i = L.take<double>(N), o_s = L.take<float>(N), o_p = L.take(56),
+               o_po = L.close(up).open(out).take(56), o_ng = L.take(8), o_in = L.take(N), o_e = L.close(out).take<double>(N * 3), o_l = L.take(N),
+               o_r = L.take(N);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, out.bytes())));
+  io.put(o_x, xw, N * 24);
+  io.put(o_m, meas, N * 24);
+  io.put(o_i, info, N * 8);
+  io.put(o_s, sigma2, N * 4);
+  io.put(o_p, pose_in, 56);
+  HIP_TRY(c, io.upload(up));
   BaParamsDev prm = {fx, fy, cx, cy, bf};
   {
     StageTimer tm(c, ORBFE_STAGE_BA, c->stream);
-    launch_pose_only(c->stream, n, (const double*)(b + o_x), (const double*)(b + o_m), (const double*)(b + o_i), (const float*)(b + o_s),
-                     (const double*)(b + o_p), prm, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), (double*)(b + o_e),
-                     b + o_l, b + o_r, b + o_in, (double*)(b + o_po), (int32_t*)(b + o_ng));
+    launch_pose_only(c->stream, n, io.dev<double>(o_x), io.dev<double>(o_m), io.dev<double>(o_i), io.dev<float>(o_s), io.dev<double>(o_p), prm,
+                     (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), io.dev<double>(o_e), io.dev<uint8_t>(o_l),
+                     io.dev<uint8_t>(o_r), io.dev<uint8_t>(o_in), io.dev<double>(o_po), io.dev<int32_t>(o_ng));
   }
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs, b + o_po, (inlier_out && n ? o_in + (size_t)n : o_in) - o_po, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.fetch(out.upto(inlier_out ? o_in + N : o_in)));  // (the inlier flags only if the caller wants them, and only n of them)
   drain_timers(c);
-  std::memcpy(pose_out, hs, 56);
-  std::memcpy(n_good, hs + (o_ng - o_po), 4);
-  if (inlier_out && n) std::memcpy(inlier_out, hs + (o_in - o_po), (size_t)n);
+  io.get(pose_out, o_po, 56);
+  io.get(n_good, o_ng, 4);
+  io.get(inlier_out, o_in, N);
   return ORBFE_OK;
 }
-
 
 }  // extern "C"

@@ -228,59 +228,49 @@ orbfe_status vocab_on_device(orbfe_ctx* c, const orbfe_vocab* v, BowVocabDev& ou
 }
 
 struct BowLayout {
-  size_t o_desc, o_wkey, o_nkey, o_wts, o_out, total;
-  size_t r_words, r_values, r_nodes, r_offsets, r_features, r_counts, r_total;  // inside the result block (device and staging alike)
+  ScratchRegion up, out;  // the descriptors a caller uploads (empty for slots) | the result block
+  size_t o_desc, o_wkey, o_nkey, o_wts;
+  size_t o_words, o_values, o_nodes, o_offsets, o_features, o_counts;  // the result block's fields
+  size_t np2, total;
 };
 BowLayout bow_layout(size_t n_img, size_t cap, size_t upload_bytes) {
-  size_t np2 = 1;
-  while (np2 < cap) np2 <<= 1;
   BowLayout l;
-  l.o_desc = 0;
-  l.o_wkey = align_up(upload_bytes, 256);
-  l.o_nkey = l.o_wkey + align_up(n_img * np2 * 8, 256);
-  l.o_wts = l.o_nkey + align_up(n_img * np2 * 8, 256);
-  l.o_out = l.o_wts + align_up(n_img * np2 * 8, 256);
-  const size_t cp = std::max<size_t>(cap, 1);
-  l.r_values = 0;
-  l.r_words = align_up(n_img * cp * 8, 256);
-  l.r_nodes = l.r_words + align_up(n_img * cp * 4, 256);
-  l.r_features = l.r_nodes + align_up(n_img * cp * 4, 256);
-  l.r_offsets = l.r_features + align_up(n_img * cp * 4, 256);
-  l.r_counts = l.r_offsets + align_up(n_img * (cap + 1) * 4, 256);
-  l.r_total = l.r_counts + align_up(n_img * 8, 256);
-  l.total = l.o_out + l.r_total;
+  for (l.np2 = 1; l.np2 < cap;) l.np2 <<= 1;
+  ScratchLayout L;
+  l.o_desc = upload_bytes ? L.open(l.up).take(upload_bytes) : 0;
+  l.o_wkey = L.close(l.up).take<uint64_t>(n_img * l.np2), l.o_nkey = L.take<uint64_t>(n_img * l.np2), l.o_wts = L.take<double>(n_img * l.np2);
+  l.o_values = L.open(l.out).take<double>(n_img * cap), l.o_words = L.take<uint32_t>(n_img * cap), l.o_nodes = L.take<uint32_t>(n_img * cap);
+  l.o_features = L.take<uint32_t>(n_img * cap);
+  l.o_offsets = L.take<int32_t>(n_img * (cap + 1));  // k_bow's node offsets: cap + 1 per image, the last one the feature count
+  l.o_counts = L.take<int32_t>(n_img * 2);
+  l.total = L.close(l.out).end();
   return l;
 }
 
-// the common tail: launch, one copy of the result block, one synchronisation, the caller's arrays
-orbfe_status run_bow(orbfe_ctx* c, const BowVocabDev& vd, const uint8_t* d_desc, size_t desc_img_stride, const int32_t* d_counts, int count_step, int n_fixed,
-                     int n_img, int cap, int levelsup, const BowLayout& l, uint8_t* hs, const orbfe_bow_out* out) {
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* r = b + l.o_out;
-  size_t np2 = 1;
-  while (np2 < (size_t)cap) np2 <<= 1;
-  launch_bow(c->stream, d_desc, desc_img_stride, d_counts, count_step, n_fixed, n_img, cap, vd, levelsup, (uint64_t*)(b + l.o_wkey), (uint64_t*)(b + l.o_nkey),
-             (double*)(b + l.o_wts), np2, (uint32_t*)(r + l.r_words), (double*)(r + l.r_values), (uint32_t*)(r + l.r_nodes),
-             (int32_t*)(r + l.r_offsets), (uint32_t*)(r + l.r_features), (int32_t*)(r + l.r_counts));
+// the common tail: launch, one copy of the result block (to `stage_at` in the staging buffer), one synchronisation, the caller's arrays
+orbfe_status run_bow(orbfe_ctx* c, StagedIo& io, const BowVocabDev& vd, const uint8_t* d_desc, size_t desc_img_stride, const int32_t* d_counts, int count_step,
+                     int n_fixed, int n_img, int cap, int levelsup, const BowLayout& l, size_t stage_at, const orbfe_bow_out* out) {
+  launch_bow(c->stream, d_desc, desc_img_stride, d_counts, count_step, n_fixed, n_img, cap, vd, levelsup, io.dev<uint64_t>(l.o_wkey),
+             io.dev<uint64_t>(l.o_nkey), io.dev<double>(l.o_wts), l.np2, io.dev<uint32_t>(l.o_words), io.dev<double>(l.o_values),
+             io.dev<uint32_t>(l.o_nodes), io.dev<int32_t>(l.o_offsets), io.dev<uint32_t>(l.o_features), io.dev<int32_t>(l.o_counts));
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs, r, l.r_total, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.fetch(l.out, stage_at));
   drain_timers(c);
   const size_t cp = std::max(cap, 1);
   for (int i = 0; i < n_img; ++i) {
     int32_t cnt[2];
-    std::memcpy(cnt, hs + l.r_counts + 8 * (size_t)i, 8);
+    io.get(cnt, l.o_counts + 8 * (size_t)i, 8);
     if (cnt[0] < 0 || cnt[0] > cap || cnt[1] < 0 || cnt[1] > cap) return fail(c, ORBFE_EDEVICE, "bow: corrupt counts %d %d", cnt[0], cnt[1]);
     int32_t kept = 0;
-    std::memcpy(&kept, hs + l.r_offsets + 4 * ((size_t)i * (cap + 1) + cnt[1]), 4);
+    io.get(&kept, l.o_offsets + 4 * ((size_t)i * (cap + 1) + cnt[1]), 4);
     if (kept < 0 || kept > cap) return fail(c, ORBFE_EDEVICE, "bow: corrupt feature count %d", kept);
     const size_t o = (size_t)i * cp;
-    if (out->words) std::memcpy(out->words + o, hs + l.r_words + 4 * o, 4 * (size_t)cnt[0]);
-    if (out->values) std::memcpy(out->values + o, hs + l.r_values + 8 * o, 8 * (size_t)cnt[0]);
+    if (out->words) io.get(out->words + o, l.o_words + 4 * o, 4 * (size_t)cnt[0]);
+    if (out->values) io.get(out->values + o, l.o_values + 8 * o, 8 * (size_t)cnt[0]);
     if (out->n_words) out->n_words[i] = cnt[0];
-    if (out->nodes) std::memcpy(out->nodes + o, hs + l.r_nodes + 4 * o, 4 * (size_t)cnt[1]);
-    if (out->node_offsets) std::memcpy(out->node_offsets + (size_t)i * (cap + 1), hs + l.r_offsets + 4 * (size_t)i * (cap + 1), 4 * ((size_t)cnt[1] + 1));
-    if (out->features) std::memcpy(out->features + o, hs + l.r_features + 4 * o, 4 * (size_t)kept);
+    if (out->nodes) io.get(out->nodes + o, l.o_nodes + 4 * o, 4 * (size_t)cnt[1]);
+    if (out->node_offsets) io.get(out->node_offsets + (size_t)i * (cap + 1), l.o_offsets + 4 * (size_t)i * (cap + 1), 4 * ((size_t)cnt[1] + 1));
+    if (out->features) io.get(out->features + o, l.o_features + 4 * o, 4 * (size_t)kept);
     if (out->n_nodes) out->n_nodes[i] = cnt[1];
   }
   return ORBFE_OK;
@@ -346,15 +336,11 @@ orbfe_status orbfe_bow_transform(orbfe_ctx* c, const orbfe_vocab* v, const uint8
   BowVocabDev vd;
   TRY(vocab_on_device(c, v, vd));
   const BowLayout l = bow_layout(1, (size_t)n, (size_t)n * 32);
-  TRY(ensure_tmp(c, l.total));
-  const size_t up = align_up((size_t)n * 32, 256);
-  TRY(ensure_stage(c, up + l.r_total));
-  uint8_t* hs = c->main.h_stage;
-  if (n) {
-    std::memcpy(hs, desc, (size_t)n * 32);
-    HIP_TRY(c, hipMemcpyAsync((uint8_t*)c->d_tmp + l.o_desc, hs, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  return run_bow(c, vd, (uint8_t*)c->d_tmp + l.o_desc, 0, nullptr, 1, n, 1, n, levelsup, l, hs + up, out);
+  StagedIo io;
+  TRY(io.reserve(c, l.total, l.up.end + l.out.bytes()));
+  io.put(l.o_desc, desc, (size_t)n * 32);
+  if (n) HIP_TRY(c, io.upload(l.up));
+  return run_bow(c, io, vd, io.dev<uint8_t>(l.o_desc), 0, nullptr, 1, n, 1, n, levelsup, l, l.up.end, out);
 }
 
 orbfe_status orbfe_bow_slots(orbfe_ctx* c, const orbfe_vocab* v, int32_t slot0, int32_t n_slots, int32_t slot_step, int32_t levelsup,
@@ -372,10 +358,10 @@ orbfe_status orbfe_bow_slots(orbfe_ctx* c, const orbfe_vocab* v, int32_t slot0, 
   TRY(vocab_on_device(c, v, vd));
   const int NF = c->cfg.n_features;
   const BowLayout l = bow_layout((size_t)n_slots, (size_t)NF, 0);
-  TRY(ensure_tmp(c, l.total));
-  TRY(ensure_stage(c, l.r_total));
-  return run_bow(c, vd, c->d_desc + (size_t)slot0 * NF * 32, (size_t)NF * slot_step, c->d_n_kp + slot0, slot_step, 0, n_slots, NF, levelsup, l,
-                 c->main.h_stage, out);
+  StagedIo io;
+  TRY(io.reserve(c, l.total, l.out.bytes()));
+  return run_bow(c, io, vd, c->d_desc + (size_t)slot0 * NF * 32, (size_t)NF * slot_step, c->d_n_kp + slot0, slot_step, 0, n_slots, NF, levelsup, l, 0,
+                 out);
 }
 
 }  // extern "C"

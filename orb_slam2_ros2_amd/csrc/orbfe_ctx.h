@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "orbfe_internal.h"
+#include "scratch_layout.h"
+#include "search_area_layout.h"
 
 namespace orbfe {
 // k_pyramid.hip
@@ -313,7 +315,8 @@ struct orbfe_ctx {
   // stop flag is mirrored into it while the call waits -- and the page-locked copy of the state record
   volatile uint8_t* h_abort = nullptr;
   LmState* h_lm_state = nullptr;
-  bool lm_on_device = true;  // ORBFE_LBA_HOST_LM=1: round 2's host-driven loop (kept for A/B runs and for > LM_CHOL_MAX_NB free keyframes)
+  bool lm_on_device = true;  // ORBFE_LBA_HOST_LM=1: round 2's host-driven loop (kept for A/B runs; also taken past LM_BIG_MAX_NB free
+                             // keyframes and when a pose observes a point twice)
 
   // profiling
   int prof = 0;  // 0 off | 1 every stage timed alone (overlaps and graphs off) | 2..: only stage (prof - 2) timed, in the production schedule
@@ -347,12 +350,7 @@ static inline int cv_floor_f(float v) {
   int i = (int)v;
   return i - (i > v);
 }
-static inline int cv_ceil_f(float v) {
-  int i = (int)v;
-  return i + (i < v);
-}
 static inline short sat_short_f(float v) { return (short)std::min(32767, std::max(-32768, cv_round_f(v))); }
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 template <typename T>
 static orbfe_status dev_alloc(orbfe_ctx* c, T** p, size_t count) {
   HIP_TRY(c, hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
@@ -378,6 +376,55 @@ static inline orbfe_status slots_idle(orbfe_ctx* c, int slot0, int n, const char
 orbfe_status ensure_tmp(orbfe_ctx* c, size_t bytes);
 orbfe_status ensure_stage(orbfe_ctx* c, orbfe_ctx::Lane& ln, size_t bytes);
 orbfe_status ensure_stage(orbfe_ctx* c, size_t bytes);
+
+// ---- one call's staged transfers: the inputs are written (put) into page-locked staging memory at the offsets of a ScratchLayout and go up
+// as ONE copy; one block of results comes down as one copy and is read field by field (get).  Bound to a context (reserve) or to a (device
+// block, staging block, stream) triple its owner has sized (orbfe_pnp, orbfe_kfdb).  Unstaged (calls too large for the staging buffer): put
+// and get are the direct asynchronous copies from / to the caller's memory, upload and download copy nothing.  The first HIP error of a put
+// or get is kept and returned by upload, download and wait.  Nothing here allocates.
+struct StagedIo {
+  uint8_t *d = nullptr, *h = nullptr;  // device block | its page-locked staging
+  hipStream_t st = nullptr;
+  bool staged = true;
+  hipError_t err = hipSuccess;
+  ptrdiff_t down_shift = 0;  // staging address of a downloaded byte = h + its offset + down_shift
+
+  StagedIo(uint8_t* dev_block = nullptr, uint8_t* stage_block = nullptr, hipStream_t s = nullptr) : d(dev_block), h(stage_block), st(s) {}
+  // scratch and staging of the context, grown as needed: only afterwards are the two base pointers valid (either may have moved)
+  orbfe_status reserve(orbfe_ctx* c, size_t dev_bytes, size_t stage_bytes, bool use_stage = true) {
+    TRY(ensure_tmp(c, dev_bytes));
+    if (use_stage) TRY(ensure_stage(c, stage_bytes));
+    d = (uint8_t*)c->d_tmp, h = use_stage ? c->main.h_stage : nullptr, st = c->stream, staged = use_stage;
+    return ORBFE_OK;
+  }
+  template <typename T>
+  T* dev(size_t off) const { return (T*)(d + off); }
+  template <typename T>
+  T* host(size_t off) const { return (T*)(h + off); }  // an input built in place in the staging buffer
+  void keep(hipError_t e) { err = err != hipSuccess ? err : e; }
+  void put(size_t off, const void* src, size_t bytes) {
+    if (!bytes) return;
+    if (staged) std::memcpy(h + off, src, bytes);
+    else keep(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, st));
+  }
+  hipError_t upload(const ScratchRegion& r) {
+    if (staged) keep(hipMemcpyAsync(d + r.begin, h + r.begin, r.bytes(), hipMemcpyHostToDevice, st));
+    return err;
+  }
+  hipError_t download(const ScratchRegion& r, size_t at = 0) {  // the region lands in the staging buffer at offset `at`
+    down_shift = (ptrdiff_t)at - (ptrdiff_t)r.begin;
+    if (staged) keep(hipMemcpyAsync(h + at, d + r.begin, r.bytes(), hipMemcpyDeviceToHost, st));
+    return err;
+  }
+  hipError_t wait() { return err != hipSuccess ? err : hipStreamSynchronize(st); }
+  hipError_t fetch(const ScratchRegion& r, size_t at = 0) { return download(r, at) != hipSuccess ? err : wait(); }
+  const uint8_t* got(size_t off) const { return h + off + down_shift; }  // field `off` of the downloaded region
+  void get(void* dst, size_t off, size_t bytes) {
+    if (!dst || !bytes) return;
+    if (staged) std::memcpy(dst, got(off), bytes);
+    else keep(hipMemcpyAsync(dst, d + off, bytes, hipMemcpyDeviceToHost, st));
+  }
+};
 
 // ---- stage timing ---------------------------------------------------------------------------------
 static inline bool timed(const orbfe_ctx* c, int stage) { return c->prof == 1 || c->prof == stage + 2; }

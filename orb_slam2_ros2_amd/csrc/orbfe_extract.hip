@@ -597,22 +597,22 @@ orbfe_status orbfe_frame_rgbd(orbfe_ctx* c, int32_t slot, const orbfe_camera* ca
   // The depth image is staged in page-locked memory and READ FROM THERE by the kernel (one 2- or 4-byte value per keypoint: uploading
   // 614 KB of a 640 x 480 16-bit image for 1000 reads was a third of the call); depth, rightU and the undistorted keypoints are written
   // to the staging buffer by the kernel as well: one 4-byte copy (the count), one synchronisation.
-  const size_t h_res = align_up(d_bytes, 256), h_ru = h_res + align_up(NF * 8, 256), h_n = h_ru + align_up(NF * 8, 256), h_k = h_n + 256,
-               h_total = h_k + align_up(NF * sizeof(orbfe_keypoint), 256);
-  TRY(ensure_stage(c, h_total));
-  uint8_t* hs = c->main.h_stage;
-  if (depth) std::memcpy(hs, depth, d_bytes);
+  ScratchLayout L;  // (of the staging buffer alone)
+  const size_t h_img = L.take(d_bytes), h_res = L.take<double>(NF), h_ru = L.take<double>(NF), h_n = L.take<int32_t>(1), h_k = L.take<orbfe_keypoint>(NF);
+  StagedIo io;
+  TRY(io.reserve(c, 0, L.end()));
+  if (depth) io.put(h_img, depth, d_bytes);
   grid_invalidate(c, slot);  // (the keypoints move: a grid kept for the slot is stale)
-  launch_frame_rgbd(c->stream, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, *cam, depth ? hs : nullptr, depth_type, depth_stride,
-                    depth_scale, (double*)(hs + h_res), (double*)(hs + h_ru), kps_out ? (orbfe_keypoint*)(hs + h_k) : nullptr);
+  launch_frame_rgbd(c->stream, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, *cam, depth ? io.h + h_img : nullptr, depth_type, depth_stride,
+                    depth_scale, (double*)(io.h + h_res), (double*)(io.h + h_ru), kps_out ? (orbfe_keypoint*)(io.h + h_k) : nullptr);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs + h_n, c->d_n_kp + slot, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(io.h + h_n, c->d_n_kp + slot, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, io.wait());
   int32_t n = 0;
-  std::memcpy(&n, hs + h_n, 4);
-  if (depth_out) std::memcpy(depth_out, hs + h_res, NF * 8);
-  if (right_u_out) std::memcpy(right_u_out, hs + h_ru, NF * 8);
-  if (kps_out && n > 0) std::memcpy(kps_out, hs + h_k, sizeof(orbfe_keypoint) * (size_t)std::min<int64_t>(n, (int64_t)NF));
+  io.get(&n, h_n, 4);
+  io.get(depth_out, h_res, NF * 8);
+  io.get(right_u_out, h_ru, NF * 8);
+  if (n > 0) io.get(kps_out, h_k, sizeof(orbfe_keypoint) * (size_t)std::min<int64_t>(n, (int64_t)NF));
   return ORBFE_OK;
 }
 
@@ -642,12 +642,12 @@ orbfe_status orbfe_stereo_match(orbfe_ctx* c, int32_t slot_left, int32_t slot_ri
   const int pair = slot_left / 2;
   // the kernel writes the requested arrays into the page-locked staging buffer itself; only the match count is copied (4 bytes)
   const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
-  const size_t o_ru = 0, o_dp = align_up(NF * 8, 256), o_br = o_dp + align_up(NF * 8, 256), o_bd = o_br + align_up(NF * 4, 256),
-               o_nm = o_bd + align_up(NF * 4, 256), total = o_nm + 256;
-  TRY(ensure_stage(c, total));
-  uint8_t* h = c->main.h_stage;
-  const StereoHostOut ho = {right_u ? (double*)(h + o_ru) : nullptr, depth ? (double*)(h + o_dp) : nullptr,
-                            best_right ? (int32_t*)(h + o_br) : nullptr, best_dist ? (int32_t*)(h + o_bd) : nullptr};
+  ScratchLayout L;  // (of the staging buffer alone)
+  const size_t o_ru = L.take<double>(NF), o_dp = L.take<double>(NF), o_br = L.take<int32_t>(NF), o_bd = L.take<int32_t>(NF), o_nm = L.take<int32_t>(1);
+  StagedIo io;
+  TRY(io.reserve(c, 0, L.end()));
+  const StereoHostOut ho = {right_u ? (double*)(io.h + o_ru) : nullptr, depth ? (double*)(io.h + o_dp) : nullptr,
+                            best_right ? (int32_t*)(io.h + o_br) : nullptr, best_dist ? (int32_t*)(io.h + o_bd) : nullptr};
   // The right image's row table: built by its extraction when that was a one- or two-image call of this (small) context -- the match
   // is then k_stereo alone; the pair's counter was zeroed there too unless an earlier match has counted into it since.
   const bool table_ready = c->slot_table_ok && c->slot_table_ok[(size_t)slot_right] != 0;
@@ -656,22 +656,22 @@ orbfe_status orbfe_stereo_match(orbfe_ctx* c, int32_t slot_left, int32_t slot_ri
   // (the count: with right_u in the staging buffer it is counted there -- k_stereo counts exactly the features it gives a right coordinate --
   //  and the 4-byte copy, a transfer of its own behind the kernel, is left out)
   const bool count_on_host = right_u != nullptr;
-  if (n_matches && !count_on_host) HIP_TRY(c, hipMemcpyAsync(h + o_nm, c->d_n_match + pair, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_matches && !count_on_host) HIP_TRY(c, hipMemcpyAsync(io.h + o_nm, c->d_n_match + pair, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, io.wait());
   drain_timers(c);
   const size_t n = (size_t)c->cfg.n_features;
-  if (right_u && n) std::memcpy(right_u, h + o_ru, sizeof(double) * n);
-  if (depth && n) std::memcpy(depth, h + o_dp, sizeof(double) * n);
-  if (best_right && n) std::memcpy(best_right, h + o_br, sizeof(int32_t) * n);
-  if (best_dist && n) std::memcpy(best_dist, h + o_bd, sizeof(int32_t) * n);
+  io.get(right_u, o_ru, sizeof(double) * n);
+  io.get(depth, o_dp, sizeof(double) * n);
+  io.get(best_right, o_br, sizeof(int32_t) * n);
+  io.get(best_dist, o_bd, sizeof(int32_t) * n);
   if (n_matches) {
     if (count_on_host) {
       int32_t nm = 0;
-      const double* ru = (const double*)(h + o_ru);
+      const double* ru = (const double*)(io.h + o_ru);
       for (size_t i = 0; i < n; ++i) nm += ru[i] >= 0.0 ? 1 : 0;
       *n_matches = nm;
     } else
-      std::memcpy(n_matches, h + o_nm, sizeof(int32_t));
+      io.get(n_matches, o_nm, sizeof(int32_t));
   }
   return ORBFE_OK;
 }

@@ -4,7 +4,6 @@
 #include "orbfe_ctx.h"
 extern "C" {
 
-
 orbfe_status orbfe_match_bruteforce(orbfe_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, const uint32_t* cand_offsets,
                                     const uint32_t* cand_idx, int32_t* best_idx, int32_t* best_dist, int32_t* second_dist) {
   ApiLock api_lk(c);
@@ -14,77 +13,47 @@ orbfe_status orbfe_match_bruteforce(orbfe_ctx* c, const uint8_t* q, int32_t nq, 
   if (nq == 0) return ORBFE_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
-  const size_t n_cand = cand_offsets ? cand_offsets[nq] : 0;
+  const size_t n_cand = cand_offsets ? cand_offsets[nq] : 0, NQ = (size_t)nq;
   if (cand_offsets)
     for (size_t i = 0; i < n_cand; ++i)
       if (cand_idx[i] >= (uint32_t)nt) return fail(c, ORBFE_EBADARG, "match_bruteforce: candidate %u >= nt %d", cand_idx[i], nt);
-  size_t o_q = 0, o_t = align_up((size_t)nq * 32, 256), o_off = o_t + align_up((size_t)std::max(nt, 1) * 32, 256);
-  size_t o_cand = o_off + align_up(((size_t)nq + 1) * 4, 256), o_bi = o_cand + align_up(std::max<size_t>(n_cand, 1) * 4, 256);
-  size_t o_bd = o_bi + align_up((size_t)nq * 4, 256), o_sd = o_bd + align_up((size_t)nq * 4, 256), total = o_sd + align_up((size_t)nq * 4, 256);
-  TRY(ensure_tmp(c, total));
-  uint8_t* base = (uint8_t*)c->d_tmp;
+  ScratchLayout L;
+  ScratchRegion up, out;
+  const size_t o_q = L.open(up).take(NQ * 32), o_t = L.take((size_t)nt * 32),
+               o_off = L.take<uint32_t>(NQ + 1),  // k_match_bruteforce reads off[i + 1] of the last query
+               o_cand = L.take<uint32_t>(n_cand), o_bi = L.close(up).open(out).take<int32_t>(NQ), o_bd = L.take<int32_t>(NQ),
+               o_sd = L.take<int32_t>(NQ);
+  L.close(out);
   // up to 8 MB: one upload and one download through the page-locked staging buffer (seven copies from / to pageable memory otherwise)
-  const bool staged = total <= ((size_t)8 << 20);
-  uint8_t* hs = nullptr;
-  if (staged) {
-    TRY(ensure_stage(c, total));
-    hs = c->main.h_stage;
-    std::memcpy(hs + o_q, q, (size_t)nq * 32);
-    if (nt) std::memcpy(hs + o_t, t, (size_t)nt * 32);
-    if (cand_offsets) {
-      std::memcpy(hs + o_off, cand_offsets, ((size_t)nq + 1) * 4);
-      if (n_cand) std::memcpy(hs + o_cand, cand_idx, n_cand * 4);
-    }
-    HIP_TRY(c, hipMemcpyAsync(base, hs, o_bi, hipMemcpyHostToDevice, c->stream));
-  } else {
-    HIP_TRY(c, hipMemcpyAsync(base + o_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-    if (nt) HIP_TRY(c, hipMemcpyAsync(base + o_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
-    if (cand_offsets) {
-      HIP_TRY(c, hipMemcpyAsync(base + o_off, cand_offsets, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, c->stream));
-      if (n_cand) HIP_TRY(c, hipMemcpyAsync(base + o_cand, cand_idx, n_cand * 4, hipMemcpyHostToDevice, c->stream));
-    }
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, out.bytes()), L.end() <= ((size_t)8 << 20)));
+  io.put(o_q, q, NQ * 32);
+  io.put(o_t, t, (size_t)nt * 32);
+  if (cand_offsets) {
+    io.put(o_off, cand_offsets, (NQ + 1) * 4);
+    io.put(o_cand, cand_idx, n_cand * 4);
   }
+  HIP_TRY(c, io.upload(up));
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, c->stream);
-    launch_match_bruteforce(c->stream, base + o_q, nq, base + o_t, nt, cand_offsets ? (const uint32_t*)(base + o_off) : nullptr,
-                            (const uint32_t*)(base + o_cand), (int32_t*)(base + o_bi), (int32_t*)(base + o_bd), (int32_t*)(base + o_sd));
+    launch_match_bruteforce(c->stream, io.dev<uint8_t>(o_q), nq, io.dev<uint8_t>(o_t), nt, cand_offsets ? io.dev<uint32_t>(o_off) : nullptr,
+                            io.dev<uint32_t>(o_cand), io.dev<int32_t>(o_bi), io.dev<int32_t>(o_bd), io.dev<int32_t>(o_sd));
   }
   HIP_TRY(c, hipGetLastError());
-  if (staged) {
-    HIP_TRY(c, hipMemcpyAsync(hs, base + o_bi, total - o_bi, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    drain_timers(c);
-    std::memcpy(best_idx, hs, (size_t)nq * 4);
-    std::memcpy(best_dist, hs + (o_bd - o_bi), (size_t)nq * 4);
-    std::memcpy(second_dist, hs + (o_sd - o_bi), (size_t)nq * 4);
-    return ORBFE_OK;
-  }
-  HIP_TRY(c, hipMemcpyAsync(best_idx, base + o_bi, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(best_dist, base + o_bd, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(second_dist, base + o_sd, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.download(out));
+  if (io.staged) HIP_TRY(c, io.wait());  // (staged: get reads the downloaded block; unstaged: get is the copy, waited for below)
+  io.get(best_idx, o_bi, NQ * 4);
+  io.get(best_dist, o_bd, NQ * 4);
+  io.get(second_dist, o_sd, NQ * 4);
+  if (!io.staged) HIP_TRY(c, io.wait());
   drain_timers(c);
   return ORBFE_OK;
 }
 
 // The grid-guided search against a feature set on the device: the features of an image slot (orbfe_search_in_area) or a set the caller
 // uploaded (orbfe_search_in_area_features: a KeyFrame's keypoints and descriptors -- keyframes are not resident in a slot).
-// grid of a frame: VirtualFrame::initGrid (Frame.cc:55-56) sizes it from the undistorted bounds, findFeaturesInArea clips the box at
-// (int)mfMaxU / (int)mfMaxV (:291-293).  bounds = {min_u, max_u, min_v, max_v}; NULL: the image itself (no distortion: 0, width, 0, height)
-struct AreaGrid {
-  int rows, cols, clip_w, clip_h;
-};
-static bool area_grid(const orbfe_ctx* c, const float* bounds, AreaGrid* g) {
-  if (!bounds) {
-    *g = {(c->cfg.height + 47) / 48, (c->cfg.width + 63) / 64, c->cfg.width, c->cfg.height};
-    return true;
-  }
-  if (!(std::isfinite(bounds[0]) && std::isfinite(bounds[1]) && std::isfinite(bounds[2]) && std::isfinite(bounds[3])) ||
-      !(bounds[1] > bounds[0]) || !(bounds[3] > bounds[2]) || bounds[1] > 65536.f || bounds[3] > 65536.f || bounds[1] < 1.f || bounds[3] < 1.f)
-    return false;
-  *g = {cv_ceil_f((float)(bounds[3] - bounds[2]) / 48), cv_ceil_f((float)(bounds[1] - bounds[0]) / 64), (int)bounds[1], (int)bounds[3]};
-  return g->rows >= 1 && g->cols >= 1;
-}
+// (AreaGrid, area_grid and the search's scratch layout: search_area_layout.h)
+static bool area_grid(const orbfe_ctx* c, const float* bounds, AreaGrid* g) { return area_grid(c->cfg.width, c->cfg.height, bounds, g); }
 
 // the grid of `slot` for the geometry ag on stream st: the one kept from the last search if the slot's keypoints are still the same
 static orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const AreaGrid& ag, const int32_t** d_off, const int32_t** d_feat) {
@@ -112,77 +81,60 @@ static orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const Area
   return ORBFE_OK;
 }
 
-static orbfe_status search_area_core(orbfe_ctx* c, const char* who, const orbfe_keypoint* d_kps, const int32_t* d_n_kp, const uint4* d_kpl,
-                                     const uint8_t* d_desc, size_t n_target, size_t tmp_used, int32_t nq, const float* qxy,
-                                     const float* radius, const int8_t* min_level, const int8_t* max_level, const uint8_t* q_desc,
-                                     const uint8_t* exclude, int32_t* best_idx, int32_t* best_dist, int32_t* second_dist, int32_t* n_cand,
-                                     const float* bounds = nullptr, int32_t* excluded_hits = nullptr, bool staged_prefix = false,
-                                     int cache_slot = -1) {
-  // staged_prefix: the caller has written the first tmp_used bytes of the scratch into the staging buffer (same offsets): they go up
-  // with the queries.  cache_slot >= 0: the target is that slot -- its grid is kept between searches (slot_grid)
+// the grid and the scratch layout of a search behind `start` bytes of the caller's own: the callers size their reservation from l->end()
+static orbfe_status search_area_plan(orbfe_ctx* c, const char* who, const float* bounds, size_t start, size_t n_target, int32_t nq,
+                                     SearchAreaLayout* l) {
   AreaGrid ag;
   if (!area_grid(c, bounds, &ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", who);
-  const int rows = ag.rows, cols = ag.cols;
-  const size_t ncells = (size_t)rows * cols;
+  const size_t ncells = (size_t)ag.rows * ag.cols;
   if ((2 * ncells + 1) * 4 > 60 * 1024) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", who, ncells);
-  const size_t NT = std::max<size_t>(n_target, 1);
-  size_t off = tmp_used;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
-  // queries first (they continue the caller's uploaded block, if any, so that everything goes up as ONE copy through the page-locked
-  // staging buffer), then the grid, then the results (one download): ten copies from / to pageable memory were most of a 0.2 ms call
-  const size_t o_q = take((size_t)nq * 8), o_r = take((size_t)nq * 4), o_lo = take((size_t)nq), o_hi = take((size_t)nq),
-               o_d = take((size_t)nq * 32), o_ex = take(NT), o_in_end = take(8), o_co = take((ncells + 1) * 4), o_cf = take(NT * 4),
-               o_bi = take((size_t)nq * 4), o_bd = take((size_t)nq * 4), o_sd = take((size_t)nq * 4), o_nc = take((size_t)nq * 4),
-               o_eh = take(NT * 4), o_out_end = take(8);
-  if (off > c->tmp_bytes) return fail(c, ORBFE_ENOMEM, "%s: scratch not reserved", who);  // (the callers reserve before they upload)
-  uint8_t* b = (uint8_t*)c->d_tmp;
+  *l = search_area_layout(start, ag, n_target, (size_t)nq);
+  return ORBFE_OK;
+}
+
+static orbfe_status search_area_core(orbfe_ctx* c, const char* who, StagedIo& io, const SearchAreaLayout& l,
+                                     const orbfe_keypoint* d_kps, const int32_t* d_n_kp, const uint4* d_kpl, const uint8_t* d_desc,
+                                     size_t n_target, int32_t nq, const float* qxy, const float* radius, const int8_t* min_level,
+                                     const int8_t* max_level, const uint8_t* q_desc, const uint8_t* exclude, int32_t* best_idx,
+                                     int32_t* best_dist, int32_t* second_dist, int32_t* n_cand, int32_t* excluded_hits = nullptr,
+                                     bool staged_prefix = false, int cache_slot = -1) {
+  // staged_prefix: the caller has written the bytes in front of the layout into the staging buffer (same offsets): they go up
+  // with the queries.  cache_slot >= 0: the target is that slot -- its grid is kept between searches (slot_grid)
+  if (l.end() > c->tmp_bytes) return fail(c, ORBFE_ENOMEM, "%s: scratch not reserved", who);  // (the callers reserve before they upload)
+  const size_t NQ = (size_t)nq;
+  const AreaGrid& ag = l.grid;
   const bool hits = exclude && excluded_hits;
-  const size_t out_bytes = (hits ? o_out_end : o_eh) - o_bi;
-  TRY(ensure_stage(c, std::max(o_in_end, out_bytes)));  // (a caller with a staged prefix has reserved at least this much already)
-  uint8_t* hs = c->main.h_stage;
-  std::memcpy(hs + o_q, qxy, (size_t)nq * 8);
-  std::memcpy(hs + o_r, radius, (size_t)nq * 4);
-  std::memcpy(hs + o_lo, min_level, (size_t)nq);
-  std::memcpy(hs + o_hi, max_level, (size_t)nq);
-  std::memcpy(hs + o_d, q_desc, (size_t)nq * 32);
-  if (exclude) std::memcpy(hs + o_ex, exclude, n_target);
-  const size_t up0 = staged_prefix ? 0 : o_q;
-  HIP_TRY(c, hipMemcpyAsync(b + up0, hs + up0, o_in_end - up0, hipMemcpyHostToDevice, c->stream));
-  if (hits) HIP_TRY(c, hipMemsetAsync(b + o_eh, 0, NT * 4, c->stream));
+  io.put(l.o_q, qxy, NQ * 8);
+  io.put(l.o_r, radius, NQ * 4);
+  io.put(l.o_lo, min_level, NQ);
+  io.put(l.o_hi, max_level, NQ);
+  io.put(l.o_d, q_desc, NQ * 32);
+  if (exclude) io.put(l.o_ex, exclude, n_target);
+  HIP_TRY(c, io.upload(staged_prefix ? ScratchRegion{0, l.in.end} : l.in));
+  if (hits && n_target) HIP_TRY(c, hipMemsetAsync(io.dev<uint8_t>(l.o_eh), 0, n_target * 4, c->stream));
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, c->stream);
-    const int32_t *g_off = (const int32_t*)(b + o_co), *g_feat = (const int32_t*)(b + o_cf);
+    const int32_t *g_off = io.dev<int32_t>(l.o_co), *g_feat = io.dev<int32_t>(l.o_cf);
     if (cache_slot >= 0)
       TRY(slot_grid(c, c->stream, cache_slot, ag, &g_off, &g_feat));
     else
-      launch_grid_build(c->stream, d_kps, d_n_kp, (int)NT, rows, cols, (int32_t*)(b + o_co), (int32_t*)(b + o_cf));
-    launch_search_area(c->stream, d_kpl, d_desc, ag.clip_w, ag.clip_h, rows, cols, g_off,
-                       g_feat, nq, (const float*)(b + o_q), (const float*)(b + o_r), (const int8_t*)(b + o_lo),
-                       (const int8_t*)(b + o_hi), b + o_d, exclude ? b + o_ex : nullptr, (int32_t*)(b + o_bi), (int32_t*)(b + o_bd),
-                       (int32_t*)(b + o_sd), (int32_t*)(b + o_nc), hits ? (int32_t*)(b + o_eh) : nullptr);
+      launch_grid_build(c->stream, d_kps, d_n_kp, (int)std::max<size_t>(n_target, 1), ag.rows, ag.cols, io.dev<int32_t>(l.o_co),
+                        io.dev<int32_t>(l.o_cf));
+    launch_search_area(c->stream, d_kpl, d_desc, ag.clip_w, ag.clip_h, ag.rows, ag.cols, g_off, g_feat, nq, io.dev<float>(l.o_q),
+                       io.dev<float>(l.o_r), io.dev<int8_t>(l.o_lo), io.dev<int8_t>(l.o_hi), io.dev<uint8_t>(l.o_d),
+                       exclude ? io.dev<uint8_t>(l.o_ex) : nullptr, io.dev<int32_t>(l.o_bi), io.dev<int32_t>(l.o_bd), io.dev<int32_t>(l.o_sd),
+                       io.dev<int32_t>(l.o_nc), hits ? io.dev<int32_t>(l.o_eh) : nullptr);
   }
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs, b + o_bi, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.fetch(hits ? l.out : l.out.upto(l.o_eh)));
   drain_timers(c);
-  std::memcpy(best_idx, hs, (size_t)nq * 4);
-  std::memcpy(best_dist, hs + (o_bd - o_bi), (size_t)nq * 4);
-  std::memcpy(second_dist, hs + (o_sd - o_bi), (size_t)nq * 4);
-  std::memcpy(n_cand, hs + (o_nc - o_bi), (size_t)nq * 4);
-  if (hits) std::memcpy(excluded_hits, hs + (o_eh - o_bi), n_target * 4);
+  io.get(best_idx, l.o_bi, NQ * 4);
+  io.get(best_dist, l.o_bd, NQ * 4);
+  io.get(second_dist, l.o_sd, NQ * 4);
+  io.get(n_cand, l.o_nc, NQ * 4);
+  if (hits) io.get(excluded_hits, l.o_eh, n_target * 4);
   else if (excluded_hits && n_target) std::memset(excluded_hits, 0, n_target * 4);
   return ORBFE_OK;
-}
-// scratch the core needs beyond `tmp_used`
-static size_t search_area_scratch(const orbfe_ctx* c, size_t n_target, int32_t nq, const float* bounds = nullptr) {
-  AreaGrid ag;
-  if (!area_grid(c, bounds, &ag)) ag = {(c->cfg.height + 47) / 48, (c->cfg.width + 63) / 64, 0, 0};
-  const size_t ncells = (size_t)ag.rows * ag.cols, NT = std::max<size_t>(n_target, 1);
-  return ((ncells + 1) * 4 + NT * 9 + (size_t)nq * (8 + 4 + 1 + 1 + 32 + 16)) + 15 * 256 + 4096;
 }
 
 orbfe_status orbfe_search_in_area(orbfe_ctx* c, int32_t slot, int32_t nq, const float* qxy, const float* radius, const int8_t* min_level,
@@ -197,10 +149,13 @@ orbfe_status orbfe_search_in_area(orbfe_ctx* c, int32_t slot, int32_t nq, const 
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
   const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
-  TRY(ensure_tmp(c, search_area_scratch(c, NF, nq)));
-  return search_area_core(c, "search_in_area", c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, c->d_kpl + (size_t)slot * NF,
-                          c->d_desc + (size_t)slot * NF * 32, NF, 0, nq, qxy, radius, min_level, max_level, q_desc, exclude, best_idx,
-                          best_dist, second_dist, n_cand, nullptr, nullptr, false, slot);
+  SearchAreaLayout l;
+  TRY(search_area_plan(c, "search_in_area", nullptr, 0, NF, nq, &l));
+  StagedIo io;
+  TRY(io.reserve(c, l.end(), std::max(l.in.end, l.out.bytes())));
+  return search_area_core(c, "search_in_area", io, l, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, c->d_kpl + (size_t)slot * NF,
+                          c->d_desc + (size_t)slot * NF * 32, NF, nq, qxy, radius, min_level, max_level, q_desc, exclude, best_idx, best_dist,
+                          second_dist, n_cand, nullptr, false, slot);
 }
 
 orbfe_status orbfe_search_in_area_features(orbfe_ctx* c, int32_t nt, const orbfe_keypoint* t_kps, const uint8_t* t_desc, int32_t nq,
@@ -224,15 +179,15 @@ orbfe_status orbfe_search_in_area_features_ex(orbfe_ctx* c, int32_t nt, const or
   if (nq == 0) return ORBFE_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
-  const size_t NT = (size_t)std::max(nt, 1);
+  const size_t NT = (size_t)nt;
   // the uploaded feature set at the front of the scratch: keypoints | octave list in the layout of the slot arrays | descriptors | count
-  const size_t o_k = 0, o_l = o_k + align_up(NT * sizeof(orbfe_keypoint), 256), o_d = o_l + align_up(NT * sizeof(uint4), 256),
-               o_n = o_d + align_up(NT * 32, 256), used = o_n + 256;
-  TRY(ensure_tmp(c, used + search_area_scratch(c, NT, nq, bounds)));
-  TRY(ensure_stage(c, used + search_area_scratch(c, NT, nq, bounds)));
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* hs = c->main.h_stage;
-  uint4* kpl = (uint4*)(hs + o_l);  // (built in the staging buffer: it goes up with everything else)
+  ScratchLayout L;
+  const size_t o_k = L.take<orbfe_keypoint>(NT), o_l = L.take<uint4>(NT), o_d = L.take(NT * 32), o_n = L.take<int32_t>(1);
+  SearchAreaLayout l;
+  TRY(search_area_plan(c, "search_in_area_features", bounds, L.end(), NT, nq, &l));
+  StagedIo io;
+  TRY(io.reserve(c, l.end(), std::max(l.in.end, l.out.bytes())));
+  uint4* kpl = io.host<uint4>(o_l);  // (built in the staging buffer: it goes up with everything else)
   std::memset(kpl, 0, NT * sizeof(uint4));
   for (int i = 0; i < nt; ++i) {
     // caller-supplied features (a KeyFrame's undistorted mvFeatsLeft): coordinates may lie outside the image or be non-finite -- the grid
@@ -241,14 +196,12 @@ orbfe_status orbfe_search_in_area_features_ex(orbfe_ctx* c, int32_t nt, const or
       return fail(c, ORBFE_EBADARG, "search_in_area_features: feature %d has octave %d (0..%d expected)", i, t_kps[i].octave, ORBFE_MAX_LEVELS - 1);
     kpl[(size_t)i].y = (uint32_t)t_kps[i].octave;  // the search reads the octave from here
   }
-  if (nt) {
-    std::memcpy(hs + o_k, t_kps, (size_t)nt * sizeof(orbfe_keypoint));
-    std::memcpy(hs + o_d, t_desc, (size_t)nt * 32);
-  }
-  std::memcpy(hs + o_n, &nt, 4);
-  return search_area_core(c, "search_in_area_features", (const orbfe_keypoint*)(b + o_k), (const int32_t*)(b + o_n), (const uint4*)(b + o_l),
-                          b + o_d, (size_t)nt, used, nq, qxy, radius, min_level, max_level, q_desc, exclude, best_idx, best_dist,
-                          second_dist, n_cand, bounds, excluded_hits, true);
+  io.put(o_k, t_kps, NT * sizeof(orbfe_keypoint));
+  io.put(o_d, t_desc, NT * 32);
+  io.put(o_n, &nt, 4);
+  return search_area_core(c, "search_in_area_features", io, l, io.dev<orbfe_keypoint>(o_k), io.dev<int32_t>(o_n), io.dev<uint4>(o_l),
+                          io.dev<uint8_t>(o_d), NT, nq, qxy, radius, min_level, max_level, q_desc, exclude, best_idx, best_dist, second_dist,
+                          n_cand, excluded_hits, true);
 }
 
 orbfe_status orbfe_project_map_points(orbfe_ctx* c, int32_t n, const float* pos, const float* view_dir, const float* max_dist,
@@ -262,43 +215,51 @@ orbfe_status orbfe_project_map_points(orbfe_ctx* c, int32_t n, const float* pos,
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
   const size_t N = (size_t)n;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
-  const size_t o_p = take(N * 12), o_v = take(N * 12), o_mx = take(N * 4), o_mn = take(N * 4), o_in_end = take(8), o_uv = take(N * 8),
-               o_d = take(N * 4), o_c = take(N * 4), o_l = take(N), o_s = take(N), o_out_end = take(8);
-  TRY(ensure_tmp(c, off));
-  TRY(ensure_stage(c, std::max(o_in_end, o_out_end - o_uv)));  // one copy up, one down, through the page-locked staging buffer
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* hs = c->main.h_stage;
-  std::memcpy(hs + o_p, pos, N * 12);
-  std::memcpy(hs + o_v, view_dir, N * 12);
-  std::memcpy(hs + o_mx, max_dist, N * 4);
-  std::memcpy(hs + o_mn, min_dist, N * 4);
-  HIP_TRY(c, hipMemcpyAsync(b, hs, o_in_end, hipMemcpyHostToDevice, c->stream));
+  ScratchLayout L;
+  ScratchRegion up, out;
+  const size_t o_p = L.open(up).take<float>(N * 3), o_v = L.take<float>(N * 3), o_mx = L.take<float>(N), o_mn = L.take<float>(N),
+               o_uv = L.close(up).open(out).take<float>(N * 2), o_d = L.take<float>(N), o_c = L.take<float>(N), o_l = L.take(N), o_s = L.take(N);
+  L.close(out);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, out.bytes())));  // one copy up, one down, through the page-locked staging buffer
+  io.put(o_p, pos, N * 12);
+  io.put(o_v, view_dir, N * 12);
+  io.put(o_mx, max_dist, N * 4);
+  io.put(o_mn, min_dist, N * 4);
+  HIP_TRY(c, io.upload(up));
   const float cam4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
   const float bounds4[4] = {pose->min_u, pose->max_u, pose->min_v, pose->max_v};
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, c->stream);
     // std::log(ORBExtractor::mfScaledFactor): float argument, float result
-    launch_project_map_points(c->stream, n, (const float*)(b + o_p), (const float*)(b + o_v), (const float*)(b + o_mx),
-                              (const float*)(b + o_mn), pose->Rcw, pose->tcw, cam4, bounds4, std::log(c->cfg.scale_factor), 7,
-                              (float*)(b + o_uv), (float*)(b + o_d), (float*)(b + o_c), (int8_t*)(b + o_l), b + o_s);
+    launch_project_map_points(c->stream, n, io.dev<float>(o_p), io.dev<float>(o_v), io.dev<float>(o_mx), io.dev<float>(o_mn), pose->Rcw,
+                              pose->tcw, cam4, bounds4, std::log(c->cfg.scale_factor), 7, io.dev<float>(o_uv), io.dev<float>(o_d),
+                              io.dev<float>(o_c), io.dev<int8_t>(o_l), io.dev<uint8_t>(o_s));
   }
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs, b + o_uv, o_out_end - o_uv, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.fetch(out));
   drain_timers(c);
-  std::memcpy(uv, hs, N * 8);
-  std::memcpy(distance, hs + (o_d - o_uv), N * 4);
-  std::memcpy(cos_theta, hs + (o_c - o_uv), N * 4);
-  std::memcpy(level, hs + (o_l - o_uv), N);
-  std::memcpy(visible, hs + (o_s - o_uv), N);
+  io.get(uv, o_uv, N * 8);
+  io.get(distance, o_d, N * 4);
+  io.get(cos_theta, o_c, N * 4);
+  io.get(level, o_l, N);
+  io.get(visible, o_s, N);
   return ORBFE_OK;
 }
+// what both tracking chains hand back from their downloaded block: the counts, the pose, the assignment and the inlier flag of every feature
+static void track_results(StagedIo& io, size_t o_cnt, size_t o_ng, size_t o_po, size_t o_asg, size_t o_eo, size_t o_in, size_t NF,
+                          const orbfe_track_output* out) {
+  const int32_t *cnt = (const int32_t*)io.got(o_cnt), *eo = (const int32_t*)io.got(o_eo);
+  const uint8_t* ein = io.got(o_in);
+  *out->n_matches = cnt[0];
+  *out->n_edges = cnt[1];
+  io.get(out->n_good, o_ng, 4);
+  io.get(out->pose_out, o_po, 56);
+  io.get(out->assigned, o_asg, NF * 4);
+  for (size_t f = 0; f < NF; ++f) out->inlier[f] = (cnt[1] >= 0 && eo[f] >= 0) ? ein[eo[f]] : 0;
+  io.get(out->edge_of, o_eo, NF * 4);
+}
+
 // Tracking::trackLocalMap's device work as ONE call (src/Tracking.cc:641-675): isInVision / predictLevel per map point
 // (MapPoint.cc:141-201), ORBMatcher::searchByProjection(frame, map points, th) (ORBMatcher.cc:561-612) against the features of `slot`,
 // and Optimizer::OptimizePoseOnly (Optimizer.cc:33-178) on what the frame holds afterwards -- one upload, seven launches, one download;
@@ -324,46 +285,40 @@ orbfe_status orbfe_track_local_map(orbfe_ctx* c, int32_t slot, const orbfe_frame
   TRY(slots_idle(c, slot, 1, "track_local_map"));
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
-  const size_t N = (size_t)std::max(n, 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
+  const size_t N = (size_t)n;
   // [ upload | claim (0x7F fill) | device-only | download ]
-  const size_t o_pos = take(N * 12), o_vd = take(N * 12), o_mx = take(N * 4), o_mn = take(N * 4), o_desc = take(N * 32), o_fl = take(N),
-               o_held = take(NF * 4), o_ru = take(NF * 8), o_s2 = take((size_t)nl * 4), o_is2 = take((size_t)nl * 4), o_p0 = take(56),
-               o_up_end = take(8), o_claim = take(NF * 4), o_claim_end = take(8), o_uv = take(N * 8), o_dist = take(N * 4), o_cos = take(N * 4),
-               o_lvl = take(N), o_vis = take(N), o_rad = take(N * 4), o_lo = take(N), o_hi = take(N),
-               o_bi = take(N * 4), o_bd = take(N * 4), o_sd = take(N * 4), o_nc = take(N * 4), o_xw = take(NF * 24),
-               o_ms = take(NF * 24), o_info = take(NF * 8), o_sig = take(NF * 4), o_err = take(NF * 24), o_l = take(NF), o_r = take(NF),
-               o_dn = take(0), o_cnt = take(16), o_ng = take(8), o_po = take(56), o_asg = take(NF * 4), o_eo = take(NF * 4), o_in = take(NF),
-               o_dn_end = take(8);
-  (void)o_dn;
-  TRY(ensure_tmp(c, off));
-  TRY(ensure_stage(c, std::max(o_up_end, o_dn_end - o_cnt)));
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* hs = c->main.h_stage;
-  if (n) {
-    std::memcpy(hs + o_pos, in->pos, (size_t)n * 12);
-    std::memcpy(hs + o_vd, in->view_dir, (size_t)n * 12);
-    std::memcpy(hs + o_mx, in->max_dist, (size_t)n * 4);
-    std::memcpy(hs + o_mn, in->min_dist, (size_t)n * 4);
-    std::memcpy(hs + o_desc, in->desc, (size_t)n * 32);
-    std::memcpy(hs + o_fl, in->flags, (size_t)n);
-  }
-  if (in->held) std::memcpy(hs + o_held, in->held, NF * 4);
-  else std::memset(hs + o_held, 0xFF, NF * 4);
-  if (in->right_u) std::memcpy(hs + o_ru, in->right_u, NF * 8);
+  ScratchLayout L;
+  ScratchRegion up, claim, down;
+  const size_t o_pos = L.open(up).take<float>(N * 3), o_vd = L.take<float>(N * 3), o_mx = L.take<float>(N), o_mn = L.take<float>(N),
+               o_desc = L.take(N * 32), o_fl = L.take(N), o_held = L.take<int32_t>(NF), o_ru = L.take<double>(NF), o_s2 = L.take<float>((size_t)nl),
+               o_is2 = L.take<float>((size_t)nl), o_p0 = L.take(56), o_claim = L.close(up).open(claim).take<int32_t>(NF),
+               o_uv = L.close(claim).take<float>(N * 2), o_dist = L.take<float>(N), o_cos = L.take<float>(N), o_lvl = L.take(N), o_vis = L.take(N),
+               o_rad = L.take<float>(N), o_lo = L.take(N), o_hi = L.take(N), o_bi = L.take<int32_t>(N), o_bd = L.take<int32_t>(N),
+               o_sd = L.take<int32_t>(N), o_nc = L.take<int32_t>(N), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3),
+               o_info = L.take<double>(NF), o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF),
+               o_cnt = L.open(down).take(16), o_ng = L.take(8), o_po = L.take(56), o_asg = L.take<int32_t>(NF), o_eo = L.take<int32_t>(NF),
+               o_in = L.take(NF);
+  L.close(down);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
+  io.put(o_pos, in->pos, N * 12);
+  io.put(o_vd, in->view_dir, N * 12);
+  io.put(o_mx, in->max_dist, N * 4);
+  io.put(o_mn, in->min_dist, N * 4);
+  io.put(o_desc, in->desc, N * 32);
+  io.put(o_fl, in->flags, N);
+  if (in->held) io.put(o_held, in->held, NF * 4);
+  else std::memset(io.host<uint8_t>(o_held), 0xFF, NF * 4);
+  if (in->right_u) io.put(o_ru, in->right_u, NF * 8);
   else
-    for (size_t f = 0; f < NF; ++f) ((double*)(hs + o_ru))[f] = -1.0;
-  std::memcpy(hs + o_s2, in->level_sigma2, (size_t)nl * 4);
-  std::memcpy(hs + o_is2, in->level_inv_sigma2, (size_t)nl * 4);
-  std::memcpy(hs + o_p0, in->pose_se3, 56);
+    for (size_t f = 0; f < NF; ++f) io.host<double>(o_ru)[f] = -1.0;
+  io.put(o_s2, in->level_sigma2, (size_t)nl * 4);
+  io.put(o_is2, in->level_inv_sigma2, (size_t)nl * 4);
+  io.put(o_p0, in->pose_se3, 56);
   hipStream_t st = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(b, hs, o_up_end, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemsetAsync(b + o_claim, 0x7F, o_claim_end - o_claim, st));
+  uint8_t* b = io.d;
+  HIP_TRY(c, io.upload(up));
+  HIP_TRY(c, hipMemsetAsync(b + claim.begin, 0x7F, claim.bytes(), st));
   const float cam4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
   const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
   {
@@ -393,20 +348,9 @@ orbfe_status orbfe_track_local_map(orbfe_ctx* c, int32_t slot, const orbfe_frame
                      b + o_r, b + o_in, (double*)(b + o_po), (int32_t*)(b + o_ng), (const int32_t*)(b + o_cnt) + 1);
   }
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(hs, b + o_cnt, o_dn_end - o_cnt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, io.fetch(down));
   drain_timers(c);
-  const int32_t* cnt = (const int32_t*)hs;
-  *out->n_matches = cnt[0];
-  *out->n_edges = cnt[1];
-  std::memcpy(out->n_good, hs + (o_ng - o_cnt), 4);
-  std::memcpy(out->pose_out, hs + (o_po - o_cnt), 56);
-  std::memcpy(out->assigned, hs + (o_asg - o_cnt), NF * 4);
-  const int32_t* eo = (const int32_t*)(hs + (o_eo - o_cnt));
-  const uint8_t* ein = hs + (o_in - o_cnt);
-  const bool optimised = cnt[1] >= 0;
-  for (size_t f = 0; f < NF; ++f) out->inlier[f] = (optimised && eo[f] >= 0) ? ein[eo[f]] : 0;
-  if (out->edge_of) std::memcpy(out->edge_of, eo, NF * 4);
+  track_results(io, o_cnt, o_ng, o_po, o_asg, o_eo, o_in, NF, out);
   return ORBFE_OK;
 }
 
@@ -436,60 +380,52 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
   TRY(slots_idle(c, slot, 1, "track_motion_model"));
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
-  const size_t N = (size_t)std::max(n, 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o2 = off;
-    off += align_up(std::max<size_t>(bytes, 8), 256);
-    return o2;
-  };
-  // [ upload once | upload per pass | claim (-1 fill), hits and counter (0 fill) | device-only | download ]
-  const size_t o_qxy = take(N * 8), o_lo = take(N), o_hi = take(N), o_desc = take(N * 32), o_pos = take(N * 12), o_fl = take(N), o_ru = take(NF * 8),
-               o_s2 = take((size_t)nl * 4), o_is2 = take((size_t)nl * 4), o_p0 = take(56), o_up1_end = take(8), o_rad = take(N * 4), o_held = take(NF * 4),
-               o_ex = take(NF), o_up2_end = take(8), o_claim = take(NF * 4), o_claim_end = take(8), o_eh = take(NF * 4), o_acc = take(16),
-               o_qa = take(N), o_zero_end = take(8), o_bi = take(N * 4), o_bd = take(N * 4), o_sd = take(N * 4),
-               o_nc = take(N * 4), o_xw = take(NF * 24), o_ms = take(NF * 24), o_info = take(NF * 8), o_sig = take(NF * 4), o_err = take(NF * 24),
-               o_l = take(NF), o_r = take(NF), o_cnt = take(16), o_ng = take(8), o_po = take(56), o_asg = take(NF * 4), o_eo = take(NF * 4), o_in = take(NF),
-               o_ehd = take(NF * 4), o_qad = take(N), o_dn_end = take(8);
-  (void)o_up1_end;
-  TRY(ensure_tmp(c, off));
-  TRY(ensure_stage(c, std::max(o_up2_end, o_dn_end - o_cnt)));
-  uint8_t* b = (uint8_t*)c->d_tmp;
-  uint8_t* hs = c->main.h_stage;
-  if (n) {
-    std::memcpy(hs + o_qxy, in->qxy, (size_t)n * 8);
-    std::memcpy(hs + o_lo, in->q_min_level, (size_t)n);
-    std::memcpy(hs + o_hi, in->q_max_level, (size_t)n);
-    std::memcpy(hs + o_desc, in->desc, (size_t)n * 32);
-    std::memcpy(hs + o_pos, in->pos, (size_t)n * 12);
-    std::memset(hs + o_fl, 3, (size_t)n);  // every query is a good map point in the map (the caller's filter, ORBMatcher.cc:286-289)
-  }
-  if (in->right_u) std::memcpy(hs + o_ru, in->right_u, NF * 8);
+  const size_t N = (size_t)n;
+  // [ upload once | upload per pass | claim (-1 fill) | hits and counter (0 fill) | device-only | download ]
+  ScratchLayout L;
+  ScratchRegion up, up_pass, claim, zero, down;
+  const size_t o_qxy = L.open(up).take<float>(N * 2), o_lo = L.take(N), o_hi = L.take(N), o_desc = L.take(N * 32), o_pos = L.take<float>(N * 3),
+               o_fl = L.take(N), o_ru = L.take<double>(NF), o_s2 = L.take<float>((size_t)nl), o_is2 = L.take<float>((size_t)nl), o_p0 = L.take(56),
+               o_rad = L.open(up_pass).take<float>(N), o_held = L.take<int32_t>(NF), o_ex = L.take(NF),
+               o_claim = L.close(up_pass).close(up).open(claim).take<int32_t>(NF), o_eh = L.close(claim).open(zero).take<int32_t>(NF),
+               o_acc = L.take(16), o_qa = L.take(N), o_bi = L.close(zero).take<int32_t>(N), o_bd = L.take<int32_t>(N), o_sd = L.take<int32_t>(N),
+               o_nc = L.take<int32_t>(N), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF),
+               o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF), o_cnt = L.open(down).take(16),
+               o_ng = L.take(8), o_po = L.take(56), o_asg = L.take<int32_t>(NF), o_eo = L.take<int32_t>(NF), o_in = L.take(NF),
+               o_ehd = L.take<int32_t>(NF), o_qad = L.take(N);
+  L.close(down);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
+  uint8_t* b = io.d;
+  io.put(o_qxy, in->qxy, N * 8);
+  io.put(o_lo, in->q_min_level, N);
+  io.put(o_hi, in->q_max_level, N);
+  io.put(o_desc, in->desc, N * 32);
+  io.put(o_pos, in->pos, N * 12);
+  std::memset(io.host<uint8_t>(o_fl), 3, N);  // every query is a good map point in the map (the caller's filter, ORBMatcher.cc:286-289)
+  if (in->right_u) io.put(o_ru, in->right_u, NF * 8);
   else
-    for (size_t f = 0; f < NF; ++f) ((double*)(hs + o_ru))[f] = -1.0;
-  std::memcpy(hs + o_s2, in->level_sigma2, (size_t)nl * 4);
-  std::memcpy(hs + o_is2, in->level_inv_sigma2, (size_t)nl * 4);
-  std::memcpy(hs + o_p0, in->pose_se3, 56);
+    for (size_t f = 0; f < NF; ++f) io.host<double>(o_ru)[f] = -1.0;
+  io.put(o_s2, in->level_sigma2, (size_t)nl * 4);
+  io.put(o_is2, in->level_inv_sigma2, (size_t)nl * 4);
+  io.put(o_p0, in->pose_se3, 56);
   std::vector<int32_t> held(NF, -1);
   if (in->held) std::memcpy(held.data(), in->held, NF * 4);
   std::vector<int32_t> hits_total(excluded_hits ? NF : 0, 0), qm_total(query_matches ? N : 0, 0);
   hipStream_t st = c->stream;
   const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
   int base_matches = 0, n_pass = 0;
-  const int32_t* cnt = (const int32_t*)hs;
+  const int32_t* cnt = nullptr;
   for (int pass = 0; pass < 2; ++pass) {
     const float th = pass == 0 ? in->th : in->th_second;
     if (pass == 1 && !(th > 0)) break;
     // the per-pass upload: radius, what the features hold, and the candidates that are excluded (a feature that holds a map point: :322-331)
-    for (int i = 0; i < n; ++i) ((float*)(hs + o_rad))[i] = th * in->level_sigma2[in->q_octave[i]];  // findFeaturesInArea: radius * getScaledFactor2(octave)
-    std::memcpy(hs + o_held, held.data(), NF * 4);
-    for (size_t f = 0; f < NF; ++f) hs[o_ex + f] = held[f] >= 0 ? 1 : 0;
-    if (pass == 0)
-      HIP_TRY(c, hipMemcpyAsync(b, hs, o_up2_end, hipMemcpyHostToDevice, st));
-    else
-      HIP_TRY(c, hipMemcpyAsync(b + o_rad, hs + o_rad, o_up2_end - o_rad, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(b + o_claim, 0xFF, o_claim_end - o_claim, st));
-    HIP_TRY(c, hipMemsetAsync(b + o_eh, 0, o_zero_end - o_eh, st));
+    for (int i = 0; i < n; ++i) io.host<float>(o_rad)[i] = th * in->level_sigma2[in->q_octave[i]];  // findFeaturesInArea: radius * getScaledFactor2(octave)
+    io.put(o_held, held.data(), NF * 4);
+    for (size_t f = 0; f < NF; ++f) io.host<uint8_t>(o_ex)[f] = held[f] >= 0 ? 1 : 0;
+    HIP_TRY(c, io.upload(pass == 0 ? up : up_pass));
+    HIP_TRY(c, hipMemsetAsync(b + claim.begin, 0xFF, claim.bytes(), st));
+    HIP_TRY(c, hipMemsetAsync(b + zero.begin, 0, zero.bytes(), st));
     {
       StageTimer tm(c, ORBFE_STAGE_MATCH, st);
       const int32_t *g_off = nullptr, *g_feat = nullptr;
@@ -514,36 +450,26 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(b + o_ehd, b + o_eh, NF * 4, hipMemcpyDeviceToDevice, st));  // (the hits sit in front of the downloaded block)
     HIP_TRY(c, hipMemcpyAsync(b + o_qad, b + o_qa, N, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(hs, b + o_cnt, o_dn_end - o_cnt, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, io.fetch(down));
+    cnt = (const int32_t*)io.got(o_cnt);
     ++n_pass;
     if (excluded_hits) {
-      const int32_t* eh = (const int32_t*)(hs + (o_ehd - o_cnt));
+      const int32_t* eh = (const int32_t*)io.got(o_ehd);
       for (size_t f = 0; f < NF; ++f) hits_total[f] += eh[f];
     }
     if (query_matches)
-      for (int i = 0; i < n; ++i) qm_total[(size_t)i] += hs[(o_qad - o_cnt) + (size_t)i];
+      for (int i = 0; i < n; ++i) qm_total[(size_t)i] += io.got(o_qad)[i];
     if (cnt[1] >= 0 || pass == 1 || !(in->th_second > 0)) break;
     // fewer than min_matches: the matches of this pass stay (setMapPoints, :344-345) and are excluded from the next one
     base_matches = cnt[0];
-    std::memcpy(held.data(), hs + (o_asg - o_cnt), NF * 4);
+    io.get(held.data(), o_asg, NF * 4);
   }
   drain_timers(c);
-  *out->n_matches = cnt[0];
-  *out->n_edges = cnt[1];
-  std::memcpy(out->n_good, hs + (o_ng - o_cnt), 4);
-  std::memcpy(out->pose_out, hs + (o_po - o_cnt), 56);
-  std::memcpy(out->assigned, hs + (o_asg - o_cnt), NF * 4);
-  const int32_t* eo = (const int32_t*)(hs + (o_eo - o_cnt));
-  const uint8_t* ein = hs + (o_in - o_cnt);
-  const bool optimised = cnt[1] >= 0;
-  for (size_t f = 0; f < NF; ++f) out->inlier[f] = (optimised && eo[f] >= 0) ? ein[eo[f]] : 0;
-  if (out->edge_of) std::memcpy(out->edge_of, eo, NF * 4);
+  track_results(io, o_cnt, o_ng, o_po, o_asg, o_eo, o_in, NF, out);
   if (excluded_hits) std::memcpy(excluded_hits, hits_total.data(), NF * 4);
   if (query_matches && n) std::memcpy(query_matches, qm_total.data(), (size_t)n * 4);
   if (passes) *passes = n_pass;
   return ORBFE_OK;
 }
-
 
 }  // extern "C"

@@ -364,31 +364,31 @@ orbfe_status orbfe_kfdb_query(orbfe_ctx* c, orbfe_kfdb* db, const orbfe_kfdb_que
   // one upload: words | values | ignored slots | header (zeros); one download: header | records
   const size_t nq = (size_t)q->n_words;
   const uint32_t rec_cap = (uint32_t)std::min<int64_t>(cap, (int64_t)db->slot_of.size());
-  const size_t o_w = 0, o_v = align_up(nq * 4, 256), o_i = o_v + align_up(nq * 8, 256), o_h = o_i + align_up(ign.size() * 4, 256);
-  const size_t o_rec = o_h + 256, total = o_rec + (size_t)rec_cap * sizeof(KfdbRec);
-  TRY(io_reserve(db, c, total));
-  uint8_t* h = db->h_io;
-  uint8_t* d = db->d_io;
-  if (nq) {
-    std::memcpy(h + o_w, q->words, nq * 4);
-    std::memcpy(h + o_v, q->values, nq * 8);
-  }
-  if (!ign.empty()) std::memcpy(h + o_i, ign.data(), ign.size() * 4);
-  std::memset(h + o_h, 0, 256);
-  HIP_TRY(c, hipMemcpyAsync(d, h, o_rec, hipMemcpyHostToDevice, c->stream));
-  launch_kfdb_query(c->stream, (const uint32_t*)(d + o_w), (const double*)(d + o_v), (int)nq, db->d_slots, n_slots, db->d_words, db->d_values,
-                    (const uint32_t*)(d + o_i), (int)ign.size(), db->d_counts, (KfdbHdr*)(d + o_h), q->min_score ? 1 : 0,
-                    q->min_score ? *q->min_score : 0.0, (KfdbRec*)(d + o_rec), rec_cap);
+  ScratchLayout L;
+  ScratchRegion up, down;
+  const size_t o_w = L.open(up).take<uint32_t>(nq), o_v = L.take<double>(nq), o_i = L.take<uint32_t>(ign.size()),
+               o_h = L.open(down).take(sizeof(KfdbHdr)),  // (goes up as zeros, comes down with the counts)
+               o_rec = L.close(up).take<KfdbRec>(rec_cap);
+  L.close(down);
+  TRY(io_reserve(db, c, L.end()));
+  StagedIo io(db->d_io, db->h_io, c->stream);
+  io.put(o_w, q->words, nq * 4);
+  io.put(o_v, q->values, nq * 8);
+  io.put(o_i, ign.data(), ign.size() * 4);
+  std::memset(io.host<uint8_t>(o_h), 0, sizeof(KfdbHdr));
+  HIP_TRY(c, io.upload(up));
+  launch_kfdb_query(c->stream, io.dev<uint32_t>(o_w), io.dev<double>(o_v), (int)nq, db->d_slots, n_slots, db->d_words, db->d_values,
+                    io.dev<uint32_t>(o_i), (int)ign.size(), db->d_counts, io.dev<KfdbHdr>(o_h), q->min_score ? 1 : 0,
+                    q->min_score ? *q->min_score : 0.0, io.dev<KfdbRec>(o_rec), rec_cap);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(h + o_h, d + o_h, total - o_h, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.fetch(down, down.begin));
   KfdbHdr hd;
-  std::memcpy(&hd, h + o_h, sizeof hd);
+  io.get(&hd, o_h, sizeof hd);
   *n_out = (int64_t)hd.n_out;
   if ((int64_t)hd.n_out > cap) return fail(c, ORBFE_ECAPACITY, "kfdb_query: %u survivors, room for %lld", hd.n_out, (long long)cap);
   if (hd.n_out > rec_cap) return fail(c, ORBFE_EDEVICE, "kfdb_query: corrupt survivor count %u", hd.n_out);
   std::vector<KfdbRec> r(hd.n_out);
-  if (hd.n_out) std::memcpy(r.data(), h + o_rec, (size_t)hd.n_out * sizeof(KfdbRec));
+  io.get(r.data(), o_rec, (size_t)hd.n_out * sizeof(KfdbRec));
   for (const KfdbRec& x : r)
     if (x.slot >= (uint32_t)n_slots || !(db->slots[x.slot].flags & KFDB_LIVE)) return fail(c, ORBFE_EDEVICE, "kfdb_query: corrupt record (slot %u)", x.slot);
   std::sort(r.begin(), r.end(), [&](const KfdbRec& a, const KfdbRec& b) { return db->slot_id[a.slot] < db->slot_id[b.slot]; });
@@ -414,23 +414,22 @@ orbfe_status orbfe_kfdb_score(orbfe_ctx* c, orbfe_kfdb* db, const orbfe_kfdb_que
   if (n == 0) return ORBFE_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t nq = (size_t)q->n_words;
-  const size_t o_w = 0, o_v = align_up(nq * 4, 256), o_l = o_v + align_up(nq * 8, 256), up = o_l + align_up((size_t)n * 4, 256);
-  const size_t o_out = up, total = o_out + (size_t)n * 8;
-  TRY(io_reserve(db, c, total));
-  uint8_t* h = db->h_io;
-  uint8_t* d = db->d_io;
-  if (nq) {
-    std::memcpy(h + o_w, q->words, nq * 4);
-    std::memcpy(h + o_v, q->values, nq * 8);
-  }
-  std::memcpy(h + o_l, list.data(), (size_t)n * 4);
-  HIP_TRY(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, c->stream));
-  launch_kfdb_score_list(c->stream, (const uint32_t*)(d + o_w), (const double*)(d + o_v), (int)nq, db->d_slots, db->d_words, db->d_values,
-                         (const uint32_t*)(d + o_l), n, (double*)(d + o_out));
+  ScratchLayout L;
+  ScratchRegion up, down;
+  const size_t o_w = L.open(up).take<uint32_t>(nq), o_v = L.take<double>(nq), o_l = L.take<uint32_t>((size_t)n),
+               o_out = L.close(up).open(down).take<double>((size_t)n);
+  L.close(down);
+  TRY(io_reserve(db, c, L.end()));
+  StagedIo io(db->d_io, db->h_io, c->stream);
+  io.put(o_w, q->words, nq * 4);
+  io.put(o_v, q->values, nq * 8);
+  io.put(o_l, list.data(), (size_t)n * 4);
+  HIP_TRY(c, io.upload(up));
+  launch_kfdb_score_list(c->stream, io.dev<uint32_t>(o_w), io.dev<double>(o_v), (int)nq, db->d_slots, db->d_words, db->d_values,
+                         io.dev<uint32_t>(o_l), n, io.dev<double>(o_out));
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(h + o_out, d + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::memcpy(scores, h + o_out, (size_t)n * 8);
+  HIP_TRY(c, io.fetch(down.upto(o_out + (size_t)n * 8), down.begin));
+  io.get(scores, o_out, (size_t)n * 8);
   return ORBFE_OK;
 }
 

@@ -184,31 +184,28 @@ orbfe_status speculate(orbfe_pnp* s, int32_t p, int32_t n, const float* pose, bo
   if (words > 0x7FFFFFFF) return fail(nullptr, ORBFE_ECAPACITY, "pnp_iterate: speculation too large");
   const size_t nh = s->hyps.size(), nc = calls.size();
   // upload: hyps | calls | entry list;  download: out | masks | refine masks;  device only: list scratch
-  const size_t o_h = 0, o_c = align_up(nh * sizeof(PnpHyp), 256), o_e = o_c + align_up(nc * sizeof(PnpCall), 256);
-  const size_t up = o_e + align_up((size_t)std::max<int64_t>(entry_len, 1) * 4, 256);
-  const size_t o_out = up, o_m = o_out + align_up(nh * sizeof(PnpOut), 256), o_rm = o_m + align_up((size_t)words * 8, 256);
-  const size_t o_l = o_rm + align_up((size_t)words * 8, 256), total = o_l + (size_t)std::max<int64_t>(list_total, 1) * 4;
-  TRY(io_reserve(s, total, o_l));
-  uint8_t* h = s->h_io;
-  uint8_t* d = s->d_io;
-  if (nh) std::memcpy(h + o_h, s->hyps.data(), nh * sizeof(PnpHyp));
-  std::memcpy(h + o_c, calls.data(), nc * sizeof(PnpCall));
-  if (entry_len) std::memcpy(h + o_e, entry, (size_t)entry_len * 4);
+  ScratchLayout L;
+  ScratchRegion up, down;
+  const size_t o_h = L.open(up).take<PnpHyp>(nh), o_c = L.take<PnpCall>(nc), o_e = L.take<int32_t>((size_t)entry_len),
+               o_out = L.close(up).open(down).take<PnpOut>(nh), o_m = L.take<uint64_t>((size_t)words), o_rm = L.take<uint64_t>((size_t)words),
+               o_l = L.close(down).take<int32_t>((size_t)list_total);
+  TRY(io_reserve(s, L.end(), down.end));
+  StagedIo io(s->d_io, s->h_io, s->stream);
+  io.put(o_h, s->hyps.data(), nh * sizeof(PnpHyp));
+  io.put(o_c, calls.data(), nc * sizeof(PnpCall));
+  io.put(o_e, entry, (size_t)entry_len * 4);
   HIP_TRY(nullptr, hipSetDevice(s->device));
-  HIP_TRY(nullptr, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s->stream));
-  launch_pnp(s->stream, (const PnpHyp*)(d + o_h), (int)nh, (const PnpCall*)(d + o_c), (int)nc, s->d_probs, s->d_xyz, s->d_uv, s->d_thr, s->cam,
-             (const int*)(d + o_e), (PnpOut*)(d + o_out), (uint64_t*)(d + o_m), (uint64_t*)(d + o_rm), (int*)(d + o_l));
+  HIP_TRY(nullptr, io.upload(up));
+  launch_pnp(s->stream, io.dev<PnpHyp>(o_h), (int)nh, io.dev<PnpCall>(o_c), (int)nc, s->d_probs, s->d_xyz, s->d_uv, s->d_thr, s->cam,
+             io.dev<int>(o_e), io.dev<PnpOut>(o_out), io.dev<uint64_t>(o_m), io.dev<uint64_t>(o_rm), io.dev<int>(o_l));
   HIP_TRY(nullptr, hipGetLastError());
-  HIP_TRY(nullptr, hipMemcpyAsync(h + o_out, d + o_out, o_l - o_out, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(nullptr, hipStreamSynchronize(s->stream));
+  HIP_TRY(nullptr, io.fetch(down, down.begin));
   s->out.resize(nh);
   s->masks.resize((size_t)words);
   s->ref_masks.resize((size_t)words);
-  if (nh) std::memcpy(s->out.data(), h + o_out, nh * sizeof(PnpOut));
-  if (words) {
-    std::memcpy(s->masks.data(), h + o_m, (size_t)words * 8);
-    std::memcpy(s->ref_masks.data(), h + o_rm, (size_t)words * 8);
-  }
+  io.get(s->out.data(), o_out, nh * sizeof(PnpOut));
+  io.get(s->masks.data(), o_m, (size_t)words * 8);
+  io.get(s->ref_masks.data(), o_rm, (size_t)words * 8);
   s->launches += 1;
   s->hypotheses += (int64_t)nh;
   return ORBFE_OK;

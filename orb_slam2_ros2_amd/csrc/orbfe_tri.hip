@@ -62,11 +62,12 @@ orbfe_status orbfe_create_new_map_points(orbfe_ctx* c, const orbfe_tri_kf* cur, 
   // the upload: [TriKf x (1 + n_nb)] | scale factors | every keyframe's arrays | cur's unprocessed flags and positions
   std::vector<TriKf> kf((size_t)n_nb + 1);
   std::vector<Piece> pieces;
-  size_t up = align_up(kf.size() * sizeof(TriKf), 256);
+  ScratchLayout L;
+  ScratchRegion up, zero, down;
+  L.open(up).take<TriKf>(kf.size());
   auto place = [&](const void* src, size_t bytes, uint32_t* off) {
-    *off = (uint32_t)up;
+    *off = (uint32_t)L.take(bytes);
     pieces.push_back({src, bytes, off});
-    up += align_up(std::max<size_t>(bytes, 1), 256);
   };
   TriParams P = {};
   int32_t n_slots = 0, max_feat = 0;
@@ -114,32 +115,26 @@ orbfe_status orbfe_create_new_map_points(orbfe_ctx* c, const orbfe_tri_kf* cur, 
 
   // device scratch behind the upload: zeroed counters | offsets, lists, slots, positions | the download (header, records, tail)
   const size_t nc = (size_t)cur->n, ns = (size_t)n_slots;
-  const size_t o_cnt = align_up(up, 256), o_fill = o_cnt + align_up(nc * 4 + 4, 256), o_acc = o_fill + align_up(nc * 4 + 4, 256);
-  const size_t z_end = o_acc + align_up(ns * 4 + 4, 256);
-  const size_t o_off = z_end, o_list = o_off + align_up(nc * 4 + 4, 256), o_slots = o_list + align_up(ns * 4 + 4, 256);
-  const size_t o_tf = o_slots + align_up(ns * sizeof(TriSlot) + 4, 256), o_pos = o_tf + align_up(nc * 4 + 4, 256);
-  const size_t o_hdr = o_pos + align_up((std::max(nc, ns) + 1) * 4, 256), o_rec = o_hdr + 256;
-  const size_t o_tail = o_rec + align_up((size_t)P.rec_cap * sizeof(TriRec) + 4, 256);
-  const size_t o_cons = o_tail + align_up((size_t)P.tail_cap * 4 + 4, 256), total = o_cons + nc + 4;
-  const size_t down = total - o_hdr;
-  TRY(ensure_tmp(c, total));
-  TRY(ensure_stage(c, up + down));
-  uint8_t* hs = c->main.h_stage;
-  uint8_t* d = (uint8_t*)c->d_tmp;
-  std::memcpy(hs, kf.data(), kf.size() * sizeof(TriKf));
-  for (const Piece& p : pieces)
-    if (p.bytes) std::memcpy(hs + *p.off, p.src, p.bytes);
-  HIP_TRY(c, hipMemcpyAsync(d, hs, up, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, z_end - o_cnt, c->stream));
-  launch_tri(c->stream, d, (const TriKf*)d, P, max_feat, (TriSlot*)(d + o_slots), (int32_t*)(d + o_cnt), (int32_t*)(d + o_off),
-             (int32_t*)(d + o_fill), (int32_t*)(d + o_list), (int32_t*)(d + o_acc), (int32_t*)(d + o_tf), (int32_t*)(d + o_pos),
-             (int32_t*)(d + o_hdr), (TriRec*)(d + o_rec), (int32_t*)(d + o_tail), d + o_cons);
+  const size_t o_cnt = L.close(up).open(zero).take<int32_t>(nc), o_fill = L.take<int32_t>(nc), o_acc = L.take<int32_t>(ns),
+               o_off = L.close(zero).take<int32_t>(nc + 1),  // k_tri_scan writes the total into off[n_cur]
+               o_list = L.take<int32_t>(ns), o_slots = L.take<TriSlot>(ns), o_tf = L.take<int32_t>(nc),
+               o_pos = L.take<int32_t>(std::max(nc, ns) + 1),  // k_tri_compact scans n_slots, then n_cur flags into pos[0 .. n]
+               o_hdr = L.open(down).take<int32_t>(2), o_rec = L.take<TriRec>((size_t)P.rec_cap), o_tail = L.take<int32_t>((size_t)P.tail_cap),
+               o_cons = L.take(nc);
+  L.close(down);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), up.end + down.bytes()));
+  io.put(0, kf.data(), kf.size() * sizeof(TriKf));
+  for (const Piece& p : pieces) io.put(*p.off, p.src, p.bytes);
+  HIP_TRY(c, io.upload(up));
+  HIP_TRY(c, hipMemsetAsync(io.dev<uint8_t>(zero.begin), 0, zero.bytes(), c->stream));
+  launch_tri(c->stream, io.d, io.dev<TriKf>(0), P, max_feat, io.dev<TriSlot>(o_slots), io.dev<int32_t>(o_cnt), io.dev<int32_t>(o_off),
+             io.dev<int32_t>(o_fill), io.dev<int32_t>(o_list), io.dev<int32_t>(o_acc), io.dev<int32_t>(o_tf), io.dev<int32_t>(o_pos),
+             io.dev<int32_t>(o_hdr), io.dev<TriRec>(o_rec), io.dev<int32_t>(o_tail), io.dev<uint8_t>(o_cons));
   HIP_TRY(c, hipGetLastError());
-  uint8_t* hd = hs + up;
-  HIP_TRY(c, hipMemcpyAsync(hd, d + o_hdr, down, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, io.fetch(down, up.end));  // (behind the staged inputs)
   int32_t h[2];
-  std::memcpy(h, hd, sizeof h);
+  io.get(h, o_hdr, sizeof h);
   *n_records = h[0];
   *n_tail = h[1];
   if (h[0] < 0 || h[0] > std::min(n_slots, cur->n) || h[1] < 0 || h[1] > cur->n)
@@ -148,9 +143,9 @@ orbfe_status orbfe_create_new_map_points(orbfe_ctx* c, const orbfe_tri_kf* cur, 
     return fail(c, ORBFE_ECAPACITY, "create_new_map_points: %d records (room for %lld), %d tail entries (room for %lld)", h[0], (long long)cap,
                 h[1], (long long)tail_cap);
   static_assert(sizeof(TriRec) == sizeof(orbfe_tri_record), "TriRec is orbfe_tri_record");
-  if (h[0]) std::memcpy(records, hd + (o_rec - o_hdr), (size_t)h[0] * sizeof(TriRec));
-  if (h[1]) std::memcpy(tail, hd + (o_tail - o_hdr), (size_t)h[1] * 4);
-  if (consumed && nc) std::memcpy(consumed, hd + (o_cons - o_hdr), nc);
+  io.get(records, o_rec, (size_t)h[0] * sizeof(TriRec));
+  io.get(tail, o_tail, (size_t)h[1] * 4);
+  io.get(consumed, o_cons, nc);
   return ORBFE_OK;
 }
 

@@ -1,0 +1,100 @@
+// test_scratch_layout.cpp -- csrc/scratch_layout.h and csrc/search_area_layout.h, host only (no HIP header, no device): the padding rule,
+// regions, and that a reservation sized from the guided search's layout is exactly what the search takes.
+#include <cstdint>
+#include <cstdio>
+#include <initializer_list>
+
+#include "../../orb_slam2_ros2_amd/csrc/search_area_layout.h"
+
+static int failures = 0;
+#define CHECK(cond)                                                   \
+  do {                                                                \
+    if (!(cond)) {                                                    \
+      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
+      ++failures;                                                     \
+    }                                                                 \
+  } while (0)
+
+static size_t padded(size_t bytes) { return ((bytes < 8 ? 8 : bytes) + 255) & ~(size_t)255; }
+
+int main() {
+  // offsets are multiples of 256, consecutive takes do not overlap, an empty take still advances
+  {
+    ScratchLayout L;
+    size_t prev_end = 0;
+    for (size_t bytes : {(size_t)0, (size_t)1, (size_t)7, (size_t)8, (size_t)9, (size_t)255, (size_t)256, (size_t)257, (size_t)100000}) {
+      const size_t o = L.take(bytes);
+      CHECK(o % 256 == 0);
+      CHECK(o == prev_end);                 // contiguous: no hole, no overlap
+      CHECK(L.end() >= o + bytes);          // the array fits
+      CHECK(L.end() > o);                   // take(0) advances too
+      CHECK(L.end() == o + padded(bytes));  // the one padding rule
+      prev_end = L.end();
+    }
+  }
+  // a layout started at a non-zero offset continues from there
+  {
+    ScratchLayout L(1024);
+    CHECK(L.end() == 1024);
+    CHECK(L.take(10) == 1024);
+    CHECK(L.take(10) == 1280);
+    CHECK(L.end() == 1536);
+  }
+  // the typed take equals the byte take
+  {
+    ScratchLayout A, B;
+    for (size_t n : {(size_t)0, (size_t)1, (size_t)63, (size_t)64, (size_t)65}) {
+      CHECK(A.take<int32_t>(n) == B.take(n * 4));
+      CHECK(A.take<double>(n) == B.take(n * 8));
+      CHECK(A.take<uint8_t>(n) == B.take(n));
+      CHECK(A.end() == B.end());
+    }
+  }
+  // a region's begin and end enclose exactly its takes
+  {
+    ScratchLayout L;
+    ScratchRegion r, empty;
+    const size_t before = L.take(300);
+    L.open(r);
+    const size_t first = L.take(1), last = L.take(600);
+    L.close(r);
+    const size_t after = L.take(5);
+    CHECK(before + padded(300) == r.begin);
+    CHECK(r.begin == first && r.end == last + padded(600) && r.end == after);
+    CHECK(r.bytes() == padded(1) + padded(600));
+    CHECK(r.upto(last).begin == r.begin && r.upto(last).bytes() == padded(1));
+    L.open(empty);
+    L.close(empty);
+    CHECK(empty.bytes() == 0 && empty.begin == L.end());
+  }
+  // the guided search: end() is reached exactly by the takes the search performs, behind any prefix, with and without frame bounds
+  {
+    const float bounds[4] = {-20.5f, 1260.25f, -12.f, 390.5f};
+    const float bad[4] = {10.f, 5.f, 0.f, 100.f};
+    AreaGrid ag = {0, 0, 0, 0};
+    CHECK(!area_grid(1241, 376, bad, &ag));
+    for (const float* b : {(const float*)nullptr, (const float*)bounds})
+      for (size_t nq : {(size_t)0, (size_t)1, (size_t)1000})
+        for (size_t nt : {(size_t)0, (size_t)1, (size_t)2000})
+          for (size_t start : {(size_t)0, (size_t)4096}) {
+            CHECK(area_grid(1241, 376, b, &ag));
+            if (!b) CHECK(ag.rows == 8 && ag.cols == 20 && ag.clip_w == 1241 && ag.clip_h == 376);
+            else CHECK(ag.rows == 9 && ag.cols == 21 && ag.clip_w == 1260 && ag.clip_h == 390);
+            const size_t ncells = (size_t)ag.rows * ag.cols;
+            const SearchAreaLayout l = search_area_layout(start, ag, nt, nq);
+            const size_t in_bytes = padded(nq * 8) + padded(nq * 4) + 2 * padded(nq) + padded(nq * 32) + padded(nt);
+            const size_t grid_bytes = padded((ncells + 1) * 4) + padded(nt * 4);
+            const size_t out_bytes = 4 * padded(nq * 4) + padded(nt * 4);
+            CHECK(l.in.begin == start && l.o_q == start && l.in.bytes() == in_bytes);
+            CHECK(l.o_co == l.in.end && l.out.begin == l.in.end + grid_bytes && l.o_bi == l.out.begin);
+            CHECK(l.out.bytes() == out_bytes && l.out.end == l.end());
+            CHECK(l.end() == start + in_bytes + grid_bytes + out_bytes);
+            CHECK(l.o_eh + padded(nt * 4) == l.end());  // the last array ends where the reservation ends
+            const size_t offs[] = {l.o_q, l.o_r, l.o_lo, l.o_hi, l.o_d, l.o_ex, l.o_co, l.o_cf, l.o_bi, l.o_bd, l.o_sd, l.o_nc, l.o_eh, l.end()};
+            for (size_t i = 0; i + 1 < sizeof offs / sizeof offs[0]; ++i) CHECK(offs[i] % 256 == 0 && offs[i] < offs[i + 1]);
+          }
+  }
+  if (failures) return 1;
+  std::printf("SCRATCH_LAYOUT_OK\n");
+  return 0;
+}

@@ -165,6 +165,16 @@ def test_dropin_header_compiles_against_the_stand_in_opencv_and_fails_loudly_wit
     assert r.returncode == 3 and r.stdout.strip() == "NO_DEVICE"
 
 
+def test_scratch_layout_host_program(tmp_path):
+    """tests/cpp/test_scratch_layout.cpp: the host entry points' scratch layout (csrc/scratch_layout.h: padding rule, regions) and the guided
+    search's layout (csrc/search_area_layout.h: the reservation equals what the search takes), compiled with the host compiler alone."""
+    import subprocess
+    exe = str(tmp_path / "test_scratch_layout")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "cpp", "test_scratch_layout.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "SCRATCH_LAYOUT_OK", r.stdout + r.stderr
+
+
 def test_no_kernel_reads_the_dispatch_packet():
     """A kernel with a private array the compiler cannot scalarise (or with blockDim / gridDim) gets the dispatch pointer: its waves then begin
     with a scalar load from the queue's ring buffer in HOST memory (r6: 13.6 us per wave of a pair's descriptor launch).  tools/check_dispatch_ptr.py
