@@ -740,6 +740,46 @@ orbfe_status orbfe_create_new_map_points(orbfe_ctx* ctx, const orbfe_tri_kf* cur
                                          const float* scale_factors, int32_t n_levels, orbfe_tri_record* records, int64_t cap,
                                          int64_t* n_records, int32_t* tail, int64_t tail_cap, int64_t* n_tail, uint8_t* consumed);
 
+/* ---- the inverse fuses of a new keyframe (LocalMapping::fuseMapPoints, src/LocalMapping.cc:352-405) ------------------------------
+ * After its forward fuse, fuseMapPoints runs ORBMatcher::fuse(pkf, cur, map) (src/ORBMatcher.cc:716-724) once per target keyframe:
+ * searchByProjection(pkf, cur, matches, 3.0f, true) (:265-347) + processFuseMps (:623-663).  With bFuse that search projects nothing:
+ * feature i of `cur` searches target k around ITS OWN position with ITS OWN descriptor, so the search result of (k, i) depends on
+ * keyframe data alone and only MapPoint::isInVision(target k) depends on the map state.  One call computes, for every target k and
+ * every feature i of `cur`:
+ *   best_idx[k][i]   the feature of target k that findFeaturesInArea(cur.kps[i], th, lo, hi) (src/Frame.cc:286-311, radius
+ *                    th * sf[octave]^2, cells clamped as orbfe_search_in_area) + getBestMatch(cur.desc[i], ..) select, if the list is
+ *                    not empty, (float)best / (float)second < ratio and best < dist_threshold (:339); -1 otherwise.  The octave window
+ *                    follows z[k] (tlc.z of :274-276, computed by the caller) against bl: z > bl: [octave, 7], z < -bl: [0, octave],
+ *                    else [octave - 1, octave + 1] clipped to 0 .. 7 (the reference hard-codes 7).  Computed for EVERY (k, i), with or
+ *                    without a point in the slot: a slot that is empty now can gain a point before its keyframe's turn.
+ *   best_dist[k][i]  the distance of that match (0 where best_idx is -1)
+ *   visible[k][i]    MapPoint::isInVision(target k) (src/MapPoint.cc:141-171) of the point in slot i, in the float / double mix of
+ *                    orbfe_project_map_points; 0 where has_point[i] is 0
+ * The caller replays the reference's sequential loop over the targets with these tables (which entries stay valid while
+ * MapPoint::replace changes the map).  One upload, three launches, one download.  n_kf == 0 or cur->n == 0: ORBFE_OK, nothing written.
+ * Errors: ORBFE_EBADARG (NULL pointers, n_kf outside 0 .. ORBFE_FUSE_MAX_KF, n outside 0 .. ORBFE_BOW_MAX_FEATURES, an octave outside
+ * 0 .. n_levels - 1, bad bounds), ORBFE_EBADSIZE (a target's grid exceeds the LDS counters), ORBFE_EDEVICE, ORBFE_ENOMEM.              */
+#define ORBFE_FUSE_MAX_KF 64
+typedef struct orbfe_fuse_kf {
+  int32_t n;                  /* features, 0 .. ORBFE_BOW_MAX_FEATURES                                       */
+  const orbfe_keypoint* kps;  /* [n] mvFeatsLeft                                                             */
+  const uint8_t* desc;        /* [n][32]                                                                     */
+  float Rcw[9], tcw[3];       /* getPose(Rcw, tcw), row-major                                                */
+  float bounds[4];            /* mfMinU mfMaxU mfMinV mfMaxV (grid + clipping, as orbfe_search_in_area_features_ex) */
+} orbfe_fuse_kf;
+typedef struct orbfe_fuse_points { /* one row per feature of `cur` */
+  const uint8_t* has_point;   /* [n] the slot holds a non-null, not-bad map point                             */
+  const float* pos;           /* [n][3] */
+  const float* view_dir;      /* [n][3] */
+  const float* max_dist;      /* [n]    */
+  const float* min_dist;      /* [n]    */
+} orbfe_fuse_points;
+orbfe_status orbfe_fuse_into_keyframes(orbfe_ctx* ctx, const orbfe_fuse_kf* cur, const orbfe_fuse_points* pts, int32_t n_kf,
+                                       const orbfe_fuse_kf* targets, const float* z /*[n_kf]*/, const orbfe_camera* cam /* fx fy cx cy */,
+                                       float bl, const float* scale_factors, int32_t n_levels, float th, float ratio,
+                                       int32_t dist_threshold, int32_t* best_idx /*[n_kf][cur->n]*/, int32_t* best_dist /*[n_kf][cur->n]*/,
+                                       uint8_t* visible /*[n_kf][cur->n]*/);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

@@ -130,6 +130,16 @@ class TriKf(C.Structure):
                 ("Tcw", C.c_float * 16), ("Twc", C.c_float * 16), ("Ow", C.c_float * 3), ("unproc", C.c_void_p), ("unproc_pos", C.c_void_p)]
 
 
+class FuseKf(C.Structure):
+    _fields_ = [("n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
+                ("bounds", C.c_float * 4)]
+
+
+class FusePoints(C.Structure):
+    _fields_ = [("has_point", C.c_void_p), ("pos", C.c_void_p), ("view_dir", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p)]
+
+
+FUSE_MAX_KF = 64
 TRI_REC_DTYPE = np.dtype([("nb", "<i4"), ("q", "<i4"), ("t", "<i4"), ("kind", "<i4"), ("xyz", "<f4", (3,))])
 TRI_MAX_NB = 64
 
@@ -150,7 +160,7 @@ EXPORTS = [
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_set_bad", "orbfe_kfdb_erase", "orbfe_kfdb_size", "orbfe_kfdb_query",
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
-    "orbfe_create_new_map_points",
+    "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates",
 ]
 BOW_MAX_FEATURES = 65535
@@ -261,6 +271,8 @@ def load() -> C.CDLL:
     L.orbfe_pnp_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.orbfe_create_new_map_points.argtypes = [vp, C.POINTER(TriKf), i32, vp, C.POINTER(Camera), vp, f32, vp, i32, vp, C.c_int64,
                                               C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64), vp]
+    L.orbfe_fuse_into_keyframes.argtypes = [vp, C.POINTER(FuseKf), C.POINTER(FusePoints), i32, vp, vp, C.POINTER(Camera), f32, vp, i32, f32, f32,
+                                            i32, vp, vp, vp]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -1226,6 +1238,60 @@ class Context:
         self.last_counts = (nr.value, nt.value)
         self._check(st)
         return recs[:nr.value].copy(), tail[:nt.value].copy(), consumed[:n].astype(bool)
+
+    # ---- the inverse fuses of a new keyframe -------------------------------------------------------------------------------------
+    def fuse_into_keyframes(self, cur, pts, targets, z, cam, bl, scale_factors, th=3.0, ratio=0.6, dist_threshold=50, out=None):
+        """The K inverse fuses of LocalMapping::fuseMapPoints as one call (orbfe_fuse_into_keyframes, include/orbfe.h).  cur and every
+        target: dict(kps [n] KP_DTYPE, desc [n, 32] uint8, Rcw [3, 3], tcw [3], bounds = (minU, maxU, minV, maxV)); pts: dict(has_point
+        [n], pos [n, 3], view_dir [n, 3], max_dist [n], min_dist [n]) per feature of cur; z [K]: tlc.z of every target
+        (ORBMatcher.cc:274-276); cam = (fx, fy, cx, cy).  Returns (best_idx int32, best_dist int32, visible uint8), each [K, n].
+        out: the three arrays to write into (C-contiguous, [K, n]) instead of fresh ones."""
+        keep = []
+
+        def arr(a, dt, shape=None):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            if shape is not None:
+                a = a.reshape(shape)
+            keep.append(a)
+            return a
+
+        def vptr(a):
+            return None if a is None else ptr(a).value
+
+        def kf(d):
+            k = FuseKf()
+            k.n = len(d["kps"])
+            k.kps = vptr(arr(d["kps"], KP_DTYPE))
+            k.desc = vptr(arr(d["desc"], np.uint8, (-1, 32)))
+            k.Rcw[:] = [float(v) for v in np.asarray(d["Rcw"], np.float32).reshape(9)]
+            k.tcw[:] = [float(v) for v in np.asarray(d["tcw"], np.float32).reshape(3)]
+            k.bounds[:] = [float(np.float32(v)) for v in d["bounds"]]
+            return k
+
+        c = kf(cur)
+        n, K = c.n, len(targets)
+        tg = (FuseKf * max(K, 1))(*[kf(d) for d in targets])
+        p = FusePoints()
+        has = pts.get("has_point")
+        p.has_point = vptr(arr(None if has is None else np.asarray(has).astype(bool), np.uint8))
+        p.pos = vptr(arr(pts.get("pos"), np.float32, (-1, 3)))
+        p.view_dir = vptr(arr(pts.get("view_dir"), np.float32, (-1, 3)))
+        p.max_dist = vptr(arr(pts.get("max_dist"), np.float32))
+        p.min_dist = vptr(arr(pts.get("min_dist"), np.float32))
+        zz = arr(z, np.float32)
+        sf = arr(scale_factors, np.float32)
+        cm = Camera(*[float(np.float32(v)) for v in cam[:4]])
+        if out is None:
+            out = (np.zeros((K, n), np.int32), np.zeros((K, n), np.int32), np.zeros((K, n), np.uint8))
+        bi, bd, vis = out
+        # (kept with the arrays behind them: tools/fuse_bench.py times the bare C call with the same arguments)
+        self._fuse_args = (self.h, C.byref(c), C.byref(p), K, C.cast(tg, C.c_void_p), ptr(zz), C.byref(cm), float(np.float32(bl)), ptr(sf), len(sf),
+                           float(np.float32(th)), float(np.float32(ratio)), int(dist_threshold), ptr(bi), ptr(bd), ptr(vis))
+        self._fuse_keep = (keep, c, p, tg, cm, bi, bd, vis)
+        self._check(self.lib.orbfe_fuse_into_keyframes(*self._fuse_args))
+        return bi, bd, vis
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -302,3 +302,20 @@ struct TriRec {
   int32_t nb, q, t, kind;
   float xyz[3];
 };
+
+// ---- inverse fuses of a new keyframe (k_fuse.hip, orbfe_fuse.hip) -------------------------------------------------------------------
+// One target keyframe of the call: byte offsets of its arrays in the scratch block (64 bit: 64 x 65535 features stay addressable), its
+// grid geometry (search_area_layout.h: AreaGrid from its bounds), its octave-window case and its pose.
+struct FuseKf {
+  uint64_t o_kps, o_desc, o_coff, o_cfeat;
+  int32_t n, rows, cols, clip_w, clip_h;
+  int32_t mode;  // 0: [octave - 1, octave + 1], 1 (up): [octave, 7], 2 (down): [0, octave]
+  int32_t in_lds, pad;  // the grid build keeps this keyframe's lists in LDS
+  float R[9], t[3];
+  float bounds[4];
+};
+struct FuseParams {
+  float fx, fy, cx, cy;
+  float th, ratio;
+  int32_t dist_threshold, n_kf, n_cur;
+};

@@ -74,6 +74,37 @@ def sim3_project(pos, max_dist, min_dist, Rcw, tcw, sim3, cam, bounds, log_sf):
     return ok, uv, octave
 
 
+def tlc_z(Rcw1, tcw1, Rcw2, tcw2):
+    """tlc.z of ORBMatcher::searchByProjection(pFrame1, pFrame2, ..) (src/ORBMatcher.cc:274-276): twc1 = -Rcw1.t() * tcw1,
+    tlc = Rcw2 * twc1 + tcw2 -- the products summed in float, alpha / beta applied in double (host/orbfe_dropin.hpp: motionDirection)"""
+    R1, t1 = np.asarray(Rcw1, F32).reshape(3, 3), np.asarray(tcw1, F32).reshape(3)
+    R2, t2 = np.asarray(Rcw2, F32).reshape(3, 3), np.asarray(tcw2, F32).reshape(3)
+    twc1 = np.array([F32(-1.0 * np.float64(s)) for s in _matvec(R1.T, t1)], F32)
+    return F32(np.float64(_matvec(R2, twc1)[2]) + np.float64(t2[2]))
+
+
+def is_in_vision(pos, view_dir, max_dist, min_dist, Rcw, tcw, cam, bounds):
+    """MapPoint::isInVision (src/MapPoint.cc:141-171) for one point in the float / double mix of csrc/k_guided.hip's k_project_map_points"""
+    pc = _affine(1.0, Rcw, np.asarray(pos, F32).reshape(3), tcw)
+    x, y, z = pc
+    if z < 0:
+        return False
+    d = F32(np.sqrt(F32(F32(F32(x * x) + F32(y * y)) + F32(z * z))))
+    if not (d < F32(max_dist) and d > F32(min_dist)):
+        return False
+    fx, fy, cx, cy = (F32(v) for v in cam[:4])
+    u, v = F32(F32(F32(x / z) * fx) + cx), F32(F32(F32(y / z) * fy) + cy)
+    min_u, max_u, min_v, max_v = (F32(b) for b in bounds)
+    if not (u < max_u and v < max_v and u > min_u and v > min_v):
+        return False
+    vd = _matvec(Rcw, np.asarray(view_dir, F32).reshape(3)).astype(np.float64)
+    vabs = F32(np.sqrt(vd[0] * vd[0] + vd[1] * vd[1] + vd[2] * vd[2]))
+    dot = vd[0] * np.float64(x) + vd[1] * np.float64(y) + vd[2] * np.float64(z)
+    with np.errstate(all="ignore"):
+        cos_theta = F32(dot / np.float64(F32(d * vabs)))
+    return not cos_theta < F32(0.5)
+
+
 class MatcherExt:
     """mixed into frontend.ORBMatcher"""
 
@@ -190,6 +221,66 @@ class MatcherExt:
                                                 z, bl, True, in_vision2, area_search=search)
         return self.processFuseMps(matches, kf1_state["good"], kf1_state["id"], kf2_state["good"], kf2_state["id"], kf1_state["obs"],
                                    kf2_state["obs"], False)
+
+    def fuseIntoKeyframes(self, ctx, model, cur_kf, target_kfs, cur, pts, targets, z, cam, bl, scale_factors, th=3.0, search_in=None,
+                          reevaluate=True):
+        """The loop `for pkf in sTargetKfs: matcher.fuse(pkf, cur, map)` of LocalMapping::fuseMapPoints (src/LocalMapping.cc:401-402) from
+        ONE batch call (Context.fuse_into_keyframes; search_in(cur, pts, targets, z, cam, bl, scale_factors, th, ratio, dist_threshold)
+        replaces it without a device) and a sequential replay on `model`, a small mutable map:
+            model.slot(kf, i) -> point id or -1        model.is_bad(pid)        model.n_obs(pid)        model.in_vision(pid, kf)
+            model.set_slot(kf, i, pid)                 model.add_observation(pid, kf, i)                model.replace(keep, drop)
+        cur_kf / target_kfs name the keyframes in the model; cur / pts / targets / z are their arrays as the binding takes them, pts
+        describing the points model.slot(cur_kf, i) at call time.
+        Why one batch is enough: with bFuse the search of (target k, feature i) uses cur's feature position and descriptor only
+        (src/ORBMatcher.cc:297-313), so no MapPoint::replace of an earlier fuse can change it.  Only isInVision depends on the map, and the
+        batch's visible[k][i] is used iff slot i still holds the point it held at call time AND that point has not survived a replace
+        since (its view direction is recomputed there, src/MapPoint.cc:229-230); otherwise the live point is re-evaluated (counted).
+        Per target, in the caller's order: the match list in ascending i from the live slots (point present and not bad, visible,
+        best_idx >= 0), then processFuseMps (:623-663) on the snapshots of both keyframes' slots with isBad / getObsNum read live, as the
+        reference's objects give them.
+        reevaluate = False uses the batch flag everywhere (what a stale flag would do; for tests).
+        Returns (nFuse per target, dict(device_flags, reevaluated))."""
+        if search_in is not None:
+            bi, bd, vis = search_in(cur, pts, targets, z, cam, bl, scale_factors, th, self.mfRatio, self.mnMinThreshold)
+        else:
+            bi, bd, vis = ctx.fuse_into_keyframes(cur, pts, targets, z, cam, bl, scale_factors, th, self.mfRatio, self.mnMinThreshold)
+        n = len(cur["kps"])
+        at_call = [model.slot(cur_kf, i) for i in range(n)]
+        survived = set()
+        stats = dict(device_flags=0, reevaluated=0)
+        n_fuse = []
+        for k, kf in enumerate(target_kfs):
+            v_ids = [model.slot(cur_kf, i) for i in range(n)]                                     # mps2 / vMapPoints (:282, :721)
+            matches = []
+            for i in range(n):
+                pid = v_ids[i]
+                if pid < 0 or model.is_bad(pid):
+                    continue
+                if not reevaluate or (pid == at_call[i] and pid not in survived):
+                    visible = bool(vis[k][i])
+                    stats["device_flags"] += 1
+                else:
+                    visible = model.in_vision(pid, kf)
+                    stats["reevaluated"] += 1
+                if visible and bi[k][i] >= 0:
+                    matches.append((int(bi[k][i]), i, int(bd[k][i])))
+            f_ids = {q: model.slot(kf, q) for q in set(m[0] for m in matches)}                    # fMapPoints (:720): the slots the loop reads
+            nf = 0
+            for q, tr, _ in matches:
+                p1, p2 = f_ids[q], v_ids[tr]
+                if p2 < 0 or model.is_bad(p2):
+                    continue
+                if p1 < 0 or model.is_bad(p1):
+                    model.set_slot(kf, q, p2)
+                    model.add_observation(p2, kf, q)
+                    nf += 1
+                elif p1 != p2:
+                    keep, drop = (p1, p2) if model.n_obs(p1) >= model.n_obs(p2) else (p2, p1)
+                    model.replace(keep, drop)
+                    survived.add(keep)
+                    nf += 1
+            n_fuse.append(nf)
+        return n_fuse, stats
 
     def searchForTriangulation(self, ctx, bow_args, kps1, kps2, pose1, pose1_inv, pose2, pose2_inv, k_inv, scale_factors):
         """ORBMatcher::searchForTriangulation (src/ORBMatcher.cc:736-787): searchByBow(pkf1, pkf2, matches, true) -- bow_args are the
