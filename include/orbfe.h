@@ -804,6 +804,11 @@ const char* orbfe_stage_name(int32_t stage);
  * FAST candidates of (slot, level) in the reference's order (cell-row-major, in-cell raster), region
  * coordinates: xyr[3*i] = x, y, response.  Returns the count through n_out even if cap is too small.  */
 orbfe_status orbfe_debug_candidates(orbfe_ctx* ctx, int32_t slot, int32_t level, float* xyr, int32_t cap, int32_t* n_out);
+/* The device exp-map update of the pose and local-BA optimisers on n independent items: out[i] = exp(upd[i]) * poses[i] with g2o's
+ * normalizeRotation (unit quaternion, w >= 0).  A pose is (qx, qy, qz, qw, tx, ty, tz), an update (omega, upsilon).  n == 0 does nothing;
+ * n < 0 or a NULL array is ORBFE_EBADARG.                                                              */
+orbfe_status orbfe_debug_se3_oplus(orbfe_ctx* ctx, int32_t n, const double* poses /*[n][7]*/, const double* upd /*[n][6]*/,
+                                   double* out /*[n][7]*/);
 
 #ifdef __cplusplus
 }

@@ -254,6 +254,8 @@ void orc_se3_oplus(const double* T, const double* upd, double* out) {
   out[0] = aw * bx + ax * bw + ay * bz - az * by;
   out[1] = aw * by + ay * bw + az * bx - ax * bz;
   out[2] = aw * bz + az * bw + ax * by - ay * bx;
+  if (out[3] < 0)  // SE3Quat::normalizeRotation: w >= 0
+    for (int i = 0; i < 4; ++i) out[i] = -out[i];
   const double n = std::sqrt(out[0] * out[0] + out[1] * out[1] + out[2] * out[2] + out[3] * out[3]);
   for (int i = 0; i < 4; ++i) out[i] /= n;
   const double Tq[7] = {ax, ay, az, aw, te[0], te[1], te[2]};

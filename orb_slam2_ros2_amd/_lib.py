@@ -161,7 +161,7 @@ EXPORTS = [
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
-    "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates",
+    "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
 ]
 BOW_MAX_FEATURES = 65535
 
@@ -278,6 +278,7 @@ def load() -> C.CDLL:
     L.orbfe_stage_name.argtypes = [i32]
     L.orbfe_stage_name.restype = C.c_char_p
     L.orbfe_debug_candidates.argtypes = [vp, i32, i32, vp, i32, vp]
+    L.orbfe_debug_se3_oplus.argtypes = [vp, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -791,6 +792,17 @@ class Context:
         out = np.zeros((max(n.value, 1), 3), np.float32)
         self._check(self.lib.orbfe_debug_candidates(self.h, slot, level, ptr(out), n.value, C.byref(n)))
         return out[:n.value]
+
+    def debug_se3_oplus(self, poses, upd) -> np.ndarray:
+        """exp(upd[i]) * poses[i] by the device's pose_oplus: poses (n, 7) = (q xyzw, t), upd (n, 6) = (omega, upsilon) -> (n, 7)"""
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        upd = np.ascontiguousarray(upd, np.float64).reshape(-1, 6)
+        if poses.shape[0] != upd.shape[0]:
+            raise ValueError("poses / upd disagree in length")
+        n = poses.shape[0]
+        out = np.zeros((max(n, 1), 7))
+        self._check(self.lib.orbfe_debug_se3_oplus(self.h, n, ptr(poses), ptr(upd), ptr(out)))
+        return out[:n]
 
     # ---- stereo -------------------------------------------------------------------------------
     def stereo_match(self, slot_left, slot_right, fx, bf):

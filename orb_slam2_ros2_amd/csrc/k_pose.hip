@@ -730,4 +730,25 @@ void launch_pose_only(hipStream_t s, int n, const double* Xw, const double* meas
                        level, robust, inlier, pose_out, n_good);
 }
 
+// orbfe_debug_se3_oplus: pose_oplus on n independent (pose, update) pairs, one thread each -- the way a test reaches every branch of the
+// exp map (the optimisers above take whatever branch their trajectory leads to)
+__global__ __launch_bounds__(64) void k_debug_se3_oplus(int n, const double* __restrict__ poses, const double* __restrict__ upd,
+                                                        double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  PoseDev T, Tn;
+  double u[6];
+  for (int k = 0; k < 4; ++k) T.q[k] = poses[(size_t)i * 7 + k];
+  for (int k = 0; k < 3; ++k) T.t[k] = poses[(size_t)i * 7 + 4 + k];
+  for (int k = 0; k < 6; ++k) u[k] = upd[(size_t)i * 6 + k];
+  pose_oplus(T, u, Tn);
+  for (int k = 0; k < 4; ++k) out[(size_t)i * 7 + k] = Tn.q[k];
+  for (int k = 0; k < 3; ++k) out[(size_t)i * 7 + 4 + k] = Tn.t[k];
+}
+
+void launch_debug_se3_oplus(hipStream_t s, int n, const double* poses, const double* upd, double* out) {
+  if (n > 0) hipLaunchKernelGGL(k_debug_se3_oplus, dim3((n + 63) / 64), dim3(64), 0, s, n, poses, upd, out);
+}
+
 }  // namespace orbfe

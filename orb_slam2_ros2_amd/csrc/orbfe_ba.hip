@@ -599,4 +599,27 @@ orbfe_status orbfe_pose_only_optimize(orbfe_ctx* c, int32_t n, const double* xw,
   return ORBFE_OK;
 }
 
+orbfe_status orbfe_debug_se3_oplus(orbfe_ctx* c, int32_t n, const double* poses, const double* upd, double* out) {
+  ApiLock api_lk(c);
+  if (!c || n < 0 || !poses || !upd || !out) return fail(c, ORBFE_EBADARG, "debug_se3_oplus: bad argument");
+  if (n == 0) return ORBFE_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  TRY(join_stereo(c));
+  const size_t N = (size_t)n;
+  ScratchLayout L;
+  ScratchRegion up, down;
+  const size_t o_p = L.open(up).take<double>(N * 7), o_u = L.take<double>(N * 6), o_o = L.close(up).open(down).take<double>(N * 7);
+  L.close(down);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
+  io.put(o_p, poses, N * 56);
+  io.put(o_u, upd, N * 48);
+  HIP_TRY(c, io.upload(up));
+  launch_debug_se3_oplus(c->stream, n, io.dev<double>(o_p), io.dev<double>(o_u), io.dev<double>(o_o));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, io.fetch(down));
+  io.get(out, o_o, N * 56);
+  return ORBFE_OK;
+}
+
 }  // extern "C"

@@ -104,12 +104,16 @@ def R_to_quat(R):
     return -q if q[3] < 0 else q
 
 
-def synth_map(seed=42, n_kf=14, n_pt=400, kf_id_step=1, mp_id0=1000, extra_kps=5, scale_factor=1.2, n_levels=8):
+def synth_map(seed=42, n_kf=14, n_pt=400, kf_id_step=1, mp_id0=1000, extra_kps=5, scale_factor=1.2, n_levels=8, gauge=None):
     """A MapData message (real protobuf) whose keyframes/points/observations are the synthetic local-BA problem of
-    orb_slam2_ros2_amd.ba_synth (perturbed estimates, noisy float measurements, 5 % gross outliers)."""
+    orb_slam2_ros2_amd.ba_synth (perturbed estimates, noisy float measurements, 5 % gross outliers).
+    gauge = (axis, angle, t_g): the same map in the world X' = R_g X + t_g (se3_reference.gauge): general keyframe rotations."""
     from orb_slam2_ros2_amd.ba_synth import make_problem
     M = messages()
     prob = make_problem(seed=seed, n_kf=n_kf, n_pt=n_pt, scale_factor=scale_factor, n_levels=n_levels)
+    if gauge is not None:
+        import se3_reference
+        prob = se3_reference.gauge(prob, *gauge)
     rng = np.random.default_rng(seed)
     sf = np.float32(scale_factor) ** np.arange(n_levels, dtype=np.float32)
     md = M["MapData"]()

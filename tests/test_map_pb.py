@@ -127,9 +127,12 @@ def test_local_graph_edge_cases(small_map):
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_local_ba_on_map_file(small_map):
+    _check_local_ba_on_map_file(*small_map)
+
+
+def _check_local_ba_on_map_file(md, cam, pb):
     from oracle import pyoracle
     from orb_slam2_ros2_amd._lib import Context
-    md, cam, pb = small_map
     ctx = Context(640, 480, 1000, 8, 1.2, 20, 7, max_images=2)
     kf_id = 10
     out_pb, rep = ctx.map_local_ba(pb, kf_id, **cam)
@@ -174,6 +177,75 @@ def test_local_ba_on_map_file(small_map):
     keep = dev["bad"] == 0
     assert dev["chi2"][keep].mean() < 3.0 and dev["chi2"][keep].max() <= 7.815
     ctx.close()
+
+
+# ---- maps whose keyframe rotations are half turns: the trace <= 0 branches of tcw_to_se3 (host/map_pb.hpp) -------------------------------
+GAUGED = {"near_x": 0, "near_y": 1, "near_z": 2}      # gauge of se3_reference.GAUGES -> the largest diagonal element of every rotation
+
+
+@pytest.fixture(scope="module")
+def gauged_maps():
+    import se3_reference as S
+    out = {}
+    for name in GAUGED:
+        md, cam = U.synth_map(n_kf=15, n_pt=500, kf_id_step=2, gauge=S.GAUGES[name])
+        out[name] = (md, cam, md.SerializeToString())
+    return out
+
+
+def _assert_half_turns(md, index):
+    """every keyframe rotation of the map has trace <= 0 and its largest diagonal element at `index`: Converter::ConvertTcw2SE3 takes that
+    one of the three largest-diagonal branches, never the trace > 0 one"""
+    for k in md.keyframes.keyframes:
+        d = np.diag(np.array(list(k.pose.rotation), np.float32).reshape(3, 3).astype(np.float64))
+        assert d.sum() <= 0 and int(np.argmax(d)) == index and np.sort(d)[2] > np.sort(d)[1] + 0.5
+
+
+@pytest.mark.parametrize("name", list(GAUGED))
+def test_local_graph_and_round_trips_of_a_half_turned_map(gauged_maps, name):
+    """tcw_to_se3 in each largest-diagonal branch (asserted on the map): orbfe_map_local_graph against the numpy restatement as
+    test_local_graph_matches_restatement does, its quaternions against the file's own matrices, and the pb -> pb and pb -> txt -> pb round
+    trips on the rotations as the round-trip tests above do."""
+    md, _, pb = gauged_maps[name]
+    _assert_half_turns(md, GAUGED[name])
+    g, r = _lib.map_local_graph(pb, 10), U.local_graph(md, 10)
+    assert g["n_group"] == r["n_group"] and g["n_group"] >= 10
+    for key, want in r.items():
+        if key == "n_group":
+            continue
+        got = np.asarray(g[key])
+        assert got.shape == np.asarray(want).shape, key
+        if got.dtype.kind == "f":
+            assert np.abs(got - want).max() < 1e-15, key
+        else:
+            assert (got == want).all(), key
+    assert np.allclose(np.linalg.norm(g["poses"][:, :4], axis=1), 1.0) and (g["poses"][:, 3] >= 0).all()
+    # the independent judge of the conversion: R(q) is the matrix of the file.  The file's entries are floats, so its matrix is a rotation
+    # only to 6e-8 per entry (half an ulp of 1); the nearest rotation is within a few of those: 5e-7
+    kfs = {int(k.id): k for k in md.keyframes.keyframes}
+    for v, kid in enumerate(g["pose_kf_id"]):
+        R = np.array(list(kfs[int(kid)].pose.rotation), np.float32).reshape(3, 3).astype(np.float64)
+        assert np.abs(U.quat_to_R(g["poses"][v, :4]) - R).max() < 5e-7
+    back = MD()
+    back.ParseFromString(_lib.map_pb_reencode(pb))
+    assert back == md
+    kf_txt, mp_txt = _lib.map_pb_to_txt(pb)
+    assert (kf_txt, mp_txt) == _txt_of(md)
+    txt = MD()
+    txt.ParseFromString(_lib.map_txt_to_pb(kf_txt, mp_txt))
+    f32 = lambda v: float(np.float32(float(_g(v))))
+    for a, b in zip(md.keyframes.keyframes, txt.keyframes.keyframes):
+        assert [f32(v) for v in a.pose.rotation] == list(b.pose.rotation) and [f32(v) for v in a.pose.translation] == list(b.pose.translation)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(GAUGED))
+def test_local_ba_on_a_half_turned_map_file(gauged_maps, name):
+    """orbfe_map_local_ba on a map whose rotations take the trace <= 0 branch of tcw_to_se3 with the largest diagonal element at x, y or z
+    (asserted on the map): everything test_local_ba_on_map_file asserts."""
+    md, cam, pb = gauged_maps[name]
+    _assert_half_turns(md, GAUGED[name])
+    _check_local_ba_on_map_file(md, cam, pb)
 
 
 @pytest.mark.gpu

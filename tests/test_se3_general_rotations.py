@@ -1,0 +1,297 @@
+"""The SE3 code on general rotations and on every branch of the exp map.
+
+Every other fp64 pose of the suite is a few degrees from the identity (ba_synth.make_problem rotates about y only, within 0.3 rad), so
+most product terms of the rotation matrix are exactly zero there, w is never small or negative and the trace of R never <= 0.  Here
+the same synthetic problems are moved into worlds X' = R_g X + t_g (se3_reference.gauge), which leaves every measurement where it was
+and gives every pose four large quaternion components, and the oracle and the device are compared with 40- to 50-digit mpmath
+references that share no spelling with them (se3_reference.mp_edge / mp_oplus).
+
+CPU part: oracle against the reference (edges, exp map), and the two optimiser restatements of the oracle through gauge covariance.
+GPU part: orbfe_debug_se3_oplus, ba_eval_edges, ba_build_system, pose_only_optimize and ba_local_optimize on gauged problems."""
+import numpy as np
+import pytest
+
+import se3_reference as S
+from orb_slam2_ros2_amd import ba_synth
+from test_local_ba import _pose_dist, _problem
+from test_pose_only import _args
+
+EDGE_KEYS = ("poses", "points", "edge_pose", "edge_point", "meas", "is_stereo", "info", "huber_delta", "fx", "fy", "cx", "cy", "bf")
+
+
+def _edge_args(p):
+    return {k: p[k] for k in EDGE_KEYS}
+
+
+def _rel(a, ref):
+    """worst |a - ref| / max(1, |ref|)"""
+    return float((np.abs(a - ref) / np.maximum(1.0, np.abs(ref))).max())
+
+
+@pytest.fixture(scope="module")
+def gauged():
+    """make_problem(seed=5, n_kf=6, n_pt=40) in the four gauged worlds, each with its 40-digit edge reference (computed once)"""
+    base = ba_synth.make_problem(seed=5, n_kf=6, n_pt=40)
+    out = {}
+    for name, g in S.GAUGES.items():
+        p = S.gauge(base, *g)
+        out[name] = (p, S.mp_edges(p))
+    out["_base"] = (base, None)
+    return out
+
+
+@pytest.fixture(scope="module")
+def oplus_table():
+    """the exp-map case table with its 50-digit reference: poses, updates, reference R and t, branch per case"""
+    poses, upd = S.oplus_cases()
+    ref = [S.mp_oplus(T, u) for T, u in zip(poses, upd)]
+    return poses, upd, np.array([r[0] for r in ref]), np.array([r[1] for r in ref]), [r[2] for r in ref]
+
+
+def _assert_general(poses, floor=0.01):
+    """the premise of every test here: no quaternion component of any pose is small"""
+    assert np.abs(np.asarray(poses).reshape(-1, 7)[:, :4]).min() > floor
+
+
+def _assert_oplus_reach(poses, upd, branches):
+    """the case table reaches the series branch, trace > 0, all three largest-diagonal branches, and both signs of the product's w"""
+    assert set(branches) == {"series", "tr>0", 0, 1, 2}
+    raw_w = np.array([S.quat_mul(S.quat_of(u[:3], np.linalg.norm(u[:3])), T[:4])[3] for T, u in zip(poses, upd)])
+    assert (raw_w < -0.01).any() and (raw_w > 0.01).any()        # the w < 0 negation of normalizeRotation is taken, and not taken
+    assert (poses[:, 3] < 0).any() and (poses[:, 3] > 0).any()
+
+
+# ---- CPU: the oracle against the references -----------------------------------------------------------------------------------------
+def test_gauge_moves_no_camera_frame_point(orc, gauged):
+    """the gauge itself: same errors in every world (to the rounding of the moved vertices: 1e-15 * 6 m * fx / z), other poses"""
+    base = gauged["_base"][0]
+    e0 = orc.ba_eval_edges(**_edge_args(base))["error"]
+    for name in S.GAUGES:
+        p = gauged[name][0]
+        assert np.abs(orc.ba_eval_edges(**_edge_args(p))["error"] - e0).max() < 1e-9
+        assert np.abs(p["poses"][:, :4] - base["poses"][:, :4]).max(1).min() > 0.5 and np.array_equal(p["meas"], base["meas"])
+
+
+def test_oracle_edges_match_the_40_digit_reference(orc, gauged):
+    """Reaches all twelve product terms of quat_to_rot and the qx, qz parts of the quaternion-vector product with non-zero factors:
+    asserted through every |q_i| > 0.01; and poses of trace <= 0 with each largest-diagonal index, computed from the quaternions.
+    Bounds (issue): 1e-11 absolute on the error, 1e-11 relative on the Jacobians."""
+    seen = set()
+    for name in S.GAUGES:
+        p, ref = gauged[name]
+        _assert_general(p["poses"])
+        for q in p["poses"][:, :4]:
+            tr, i = S.trace_branch(q)
+            if tr <= 0:
+                seen.add(i)
+        o = orc.ba_eval_edges(**_edge_args(p))
+        d = (np.abs(o["error"] - ref["error"]).max(), _rel(o["j_point"], ref["j_point"]), _rel(o["j_pose"], ref["j_pose"]))
+        print(f"oracle vs reference, {name}: error {d[0]:.2e}  j_point {d[1]:.2e}  j_pose {d[2]:.2e}")
+        assert d[0] < 1e-11 and d[1] < 1e-11 and d[2] < 1e-11, (name, d)
+        assert np.abs(ref["j_point"]).max() > 10 and (p["is_stereo"] == 0).any() and (p["is_stereo"] == 1).any()
+    assert seen == {0, 1, 2}
+
+
+def test_oracle_edges_are_blind_to_the_quaternion_sign(orc, gauged):
+    p = gauged["skew"][0]
+    a, b = orc.ba_eval_edges(**_edge_args(p)), orc.ba_eval_edges(**_edge_args(S.negate_q(p)))
+    assert (S.negate_q(p)["poses"][:, 3] < 0).all() and (p["poses"][:, 3] > 0).all()
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_oracle_se3_oplus_matches_the_50_digit_reference(orc, oplus_table):
+    """orc.se3_oplus on the whole case table (series branch, trace > 0, the three largest-diagonal branches, the w < 0 negation:
+    asserted by _assert_oplus_reach), as rotation matrices and translations.  Bound (issue): 1e-11 on both."""
+    poses, upd, R_ref, t_ref, branches = oplus_table
+    _assert_general(poses)
+    _assert_oplus_reach(poses, upd, branches)
+    worst = [0.0, 0.0]
+    for T, u, R, t in zip(poses, upd, R_ref, t_ref):
+        o = orc.se3_oplus(T, u)
+        assert abs(np.linalg.norm(o[:4]) - 1) < 1e-15 and o[3] >= 0
+        worst = [max(worst[0], np.abs(S.quat_to_R(o[:4]) - R).max()), max(worst[1], np.abs(o[4:] - t).max())]
+    print(f"oracle se3_oplus vs reference: R {worst[0]:.2e}  t {worst[1]:.2e}")
+    assert worst[0] < 1e-11 and worst[1] < 1e-11, worst
+
+
+def test_oracle_pose_only_is_gauge_covariant(orc):
+    """pose_oracle.cpp's restatement of the exp map and of the pose Jacobians, through its optimiser: the optimisation of a gauged
+    problem is the gauge image of the optimisation of the original.  Bounds (issue): pose 1e-9, identical inlier flags."""
+    p = ba_synth.make_pose_problem(seed=11, n=300)
+    g = S.GAUGES["skew"]
+    pg = S.gauge(p, *g)
+    _assert_general(pg["pose"])
+    n0, pose0, inl0 = orc.pose_only_optimize(**_args(p))
+    n1, pose1, inl1 = orc.pose_only_optimize(**_args(pg))
+    back = S.ungauge_poses(pose1, *g)
+    print(f"gauged pose-only: {n1} inliers, mapped-back pose off by {_pose_dist(back[None], pose0[None]):.2e}")
+    assert n0 == n1 and np.array_equal(inl0, inl1) and 200 < n0 < 300
+    assert _pose_dist(back[None], pose0[None]) < 1e-9
+    assert abs(np.linalg.norm(pose1[:4]) - 1) < 1e-12 and pose1[3] > 0
+
+
+def test_oracle_local_ba_is_gauge_covariant(orc):
+    """lba_oracle.cpp's restatements, through its optimiser: same Levenberg-Marquardt trajectory in the gauged world.  Bounds (issue):
+    the same (5, 10) iterations, identical level / bad flags, chi2 to rtol 1e-6."""
+    pr, fixed = _problem(3, 12, 400)
+    pg = S.gauge(pr, *S.GAUGES["skew"])
+    _assert_general(pg["poses"])
+    a, b = orc.ba_local_optimize(pr, fixed), orc.ba_local_optimize(pg, fixed)
+    print(f"gauged local BA: iterations {tuple(b['iters'])}, chi2 off by {np.abs(a['chi2'] - b['chi2']).max():.2e}")
+    assert tuple(a["iters"]) == tuple(b["iters"]) == (5, 10)
+    assert np.array_equal(a["level"], b["level"]) and np.array_equal(a["bad"], b["bad"])
+    assert np.allclose(a["chi2"], b["chi2"], rtol=1e-6, atol=1e-9)
+    back = S.ungauge_poses(b["poses"], *S.GAUGES["skew"])
+    assert _pose_dist(back, a["poses"]) < 1e-7
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture
+def ctx():
+    from orb_slam2_ros2_amd._lib import Context
+    c = Context(640, 480, n_features=500, max_images=1)
+    yield c
+    c.close()
+
+
+@pytest.mark.gpu
+def test_device_se3_oplus_matches_reference_and_oracle(orc, ctx, oplus_table):
+    """orbfe_debug_se3_oplus = the device's pose_oplus (se3_dev.h), the whole case table in one call: the theta < 1e-5 series branch,
+    trace > 0, the three hand-spelled largest-diagonal branches and the w < 0 negation (asserted by _assert_oplus_reach).
+    Bounds (issue): 1e-11 against the 50-digit reference on R and t, 1e-12 against the oracle, |q| = 1 within 1e-15, w >= 0."""
+    from orb_slam2_ros2_amd._lib import OrbfeError
+    poses, upd, R_ref, t_ref, branches = oplus_table
+    _assert_oplus_reach(poses, upd, branches)
+    out = ctx.debug_se3_oplus(poses, upd)
+    orc_out = np.array([orc.se3_oplus(T, u) for T, u in zip(poses, upd)])
+    dR = max(np.abs(S.quat_to_R(o[:4]) - R).max() for o, R in zip(out, R_ref))
+    dt = np.abs(out[:, 4:] - t_ref).max()
+    d_orc = _pose_dist(out, orc_out)
+    print(f"device se3_oplus vs reference: R {dR:.2e}  t {dt:.2e};  vs oracle {d_orc:.2e}")
+    assert dR < 1e-11 and dt < 1e-11
+    assert d_orc < 1e-12
+    assert np.abs(np.linalg.norm(out[:, :4], axis=1) - 1).max() < 1e-15 and (out[:, 3] >= 0).all()
+    # one item, 65 items (a second workgroup with one live lane), none; every item is computed alone: same bits as in the table's call
+    assert np.array_equal(ctx.debug_se3_oplus(poses[29:30], upd[29:30]), out[29:30])
+    idx = np.arange(65) % len(poses)
+    assert np.array_equal(ctx.debug_se3_oplus(poses[idx], upd[idx]), out[idx])
+    assert ctx.debug_se3_oplus(np.zeros((0, 7)), np.zeros((0, 6))).shape == (0, 7)
+    with pytest.raises(OrbfeError) as ei:
+        ctx._check(ctx.lib.orbfe_debug_se3_oplus(ctx.h, -1, poses.ctypes.data, upd.ctypes.data, out.ctypes.data))
+    assert ei.value.status == 1                                     # ORBFE_EBADARG
+    assert ctx.lib.orbfe_debug_se3_oplus(ctx.h, 4, poses.ctypes.data, None, out.ctypes.data) == 1
+    assert ctx.lib.orbfe_debug_se3_oplus(None, 4, poses.ctypes.data, upd.ctypes.data, out.ctypes.data) == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(S.GAUGES))
+def test_device_ba_edges_on_gauged_problems(orc, ctx, gauged, name):
+    """k_ba_edges / edge_terms with every product term of the rotation matrix non-zero (every |q_i| > 0.01, asserted): against the
+    oracle at the tolerances of test_ba_edges_match_oracle, against the 40-digit reference at 1e-11 (issue), and q against -q."""
+    p, ref = gauged[name]
+    _assert_general(p["poses"])
+    out, o = ctx.ba_eval_edges(**_edge_args(p)), orc.ba_eval_edges(**_edge_args(p))
+    d = (np.abs(out["error"] - ref["error"]).max(), _rel(out["j_point"], ref["j_point"]), _rel(out["j_pose"], ref["j_pose"]))
+    print(f"device vs reference, {name}: error {d[0]:.2e}  j_point {d[1]:.2e}  j_pose {d[2]:.2e}")
+    for k in ("error", "chi2", "rho", "j_point", "j_pose"):
+        assert out[k].shape == o[k].shape and np.allclose(out[k], o[k], rtol=1e-9, atol=1e-12), k
+    assert d[0] < 1e-11 and d[1] < 1e-11 and d[2] < 1e-11, d
+    assert np.array_equal(out["depth_positive"], o["depth_positive"]) and out["depth_positive"].all()
+    neg = ctx.ba_eval_edges(**_edge_args(S.negate_q(p)))
+    assert all(np.array_equal(neg[k], out[k]) for k in out)
+
+
+@pytest.mark.gpu
+def test_device_ba_build_system_on_a_gauged_problem(orc, ctx):
+    """k_ba_pose_blocks / k_ba_point_blocks on general rotations; a free pose with more than 64 edges and one with fewer (asserted):
+    both trip counts of the lane-stride loop.  Against the oracle at the tolerances of test_ba_normal_equation_blocks_match_oracle,
+    and H_ll / H_pp against blocks assembled in numpy from the 40-digit Jacobians and the oracle's rho (issue: rtol 1e-9, atol 1e-7)."""
+    p = S.gauge(ba_synth.make_problem(n_kf=6, n_pt=120), *S.GAUGES["skew"])
+    _assert_general(p["poses"])
+    nk = 6
+    fixed = np.zeros(nk, np.uint8)
+    fixed[0] = 1
+    per_pose = np.bincount(p["edge_pose"], minlength=nk)[1:]
+    assert (per_pose > 64).any() and ((per_pose < 64) & (per_pose > 0)).any(), per_pose
+    out = ctx.ba_build_system(**_edge_args(p), pose_fixed=fixed)
+    ref = orc.ba_build_system(**_edge_args(p), pose_fixed=fixed)
+    for k in ("Hpp", "bp", "Hll", "bl", "Hpl"):
+        assert np.allclose(out[k], ref[k], rtol=1e-9, atol=1e-12 * np.abs(ref[k]).max()), k
+    lean = ctx.ba_build_system(**_edge_args(p), pose_fixed=fixed, want_hpl=False)
+    assert "Hpl" not in lean and all(np.array_equal(lean[k], out[k]) for k in lean)
+    assert not out["Hpp"][0].any() and all(out["Hpp"][k].any() for k in range(1, nk))
+    m = S.mp_edges(p)
+    w = orc.ba_eval_edges(**_edge_args(p))["rho"][:, 1] * p["info"]
+    Hll, Hpp = np.zeros_like(out["Hll"]), np.zeros_like(out["Hpp"])
+    for e in range(w.size):
+        A, B = m["j_point"][e], m["j_pose"][e]
+        Hll[p["edge_point"][e]] += w[e] * A.T @ A
+        if not fixed[p["edge_pose"][e]]:
+            Hpp[p["edge_pose"][e]] += w[e] * B.T @ B
+    assert np.allclose(out["Hll"], Hll, rtol=1e-9, atol=1e-7) and np.allclose(out["Hpp"], Hpp, rtol=1e-9, atol=1e-7)
+
+
+# (seed, n) as test_device_optimiser_matches_oracle: the 256-thread register kernel up to 1024 edges, the 512-thread one up to 2048, the
+# in-memory kernel beyond
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n,kernel,gauge,variant", [
+    (10, 40, "reg256", "skew", ""), (9, 257, "reg256", "skew", ""), (13, 1025, "reg512", "skew", ""), (15, 2500, "memory", "skew", ""),
+    (9, 257, "reg256", "near_x", ""), (9, 257, "reg256", "skew", "negated"), (9, 257, "reg256", "skew", "mono")])
+def test_device_pose_only_on_gauged_problems(orc, ctx, seed, n, kernel, gauge, variant):
+    """k_pose_only_reg<256>, <512> and k_pose_only (the kernel follows from n: asserted) with a start pose of four large quaternion
+    components (asserted), w < 0 for 'negated'; rightU < 0 everywhere for 'mono'.  Asserts of test_device_optimiser_matches_oracle."""
+    assert kernel == ("reg256" if n <= 1024 else "reg512" if n <= 2048 else "memory")
+    p = S.gauge(ba_synth.make_pose_problem(seed=seed, n=n), *S.GAUGES[gauge])
+    if variant == "negated":
+        p = S.negate_q(p)
+    a = _args(p)
+    if variant == "mono":
+        a["meas"] = a["meas"].copy()
+        a["meas"][:, 2] = -1.0
+    _assert_general(a["pose"])
+    assert (a["pose"][3] < 0) == (variant == "negated")
+    n_good, pose, inl = ctx.pose_only_optimize(**a)
+    r_good, r_pose, r_inl = orc.pose_only_optimize(**a)
+    print(f"pose-only n={n} {gauge} {variant}: device vs oracle {np.abs(pose - r_pose).max():.2e}, {n_good} inliers")
+    assert np.abs(pose - r_pose).max() < 1e-6
+    assert (inl != r_inl).sum() <= 1 and abs(n_good - r_good) <= 1
+    assert not inl[p["outlier"]].any()
+    assert pose[3] > 0 and abs(np.linalg.norm(pose[:4]) - 1) < 1e-12
+    assert np.abs(pose - a["pose"]).max() > 1e-3                      # it moved
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n_kf,n_pt,n_fixed,gauge,path", [
+    (3, 12, 400, 2, "skew", "registers"), (3, 12, 400, 2, "near_y", "registers"), (14, 48, 2000, 5, "skew", "lmbig"),
+    (3, 12, 400, 2, "skew", "host_lm")])
+def test_device_local_ba_on_gauged_problems(orc, monkeypatch, seed, n_kf, n_pt, n_fixed, gauge, path):
+    """k_lba's Jacobians and pose_oplus inside the register-resident Levenberg-Marquardt (k_lm: at most 42 free keyframes), the blocked
+    one (k_lmbig: more than 42, asserted) and the host-driven loop (ORBFE_LBA_HOST_LM=1, read at orbfe_create), every pose -- the fixed
+    ones included -- with four large quaternion components (asserted).  Asserts of test_device_local_ba_matches_oracle."""
+    from orb_slam2_ros2_amd._lib import Context
+    pr, fixed = _problem(seed, n_kf, n_pt, n_fixed)
+    pr = S.gauge(pr, *S.GAUGES[gauge])
+    if gauge == "near_y":
+        # the half turn of a trajectory: every rotation has trace <= 0 with R[1][1] the largest diagonal element, and w changes sign
+        # along the arc (the keyframe next to the crossing has |w| = 0.005, so the floor on the components is lower here)
+        _assert_general(pr["poses"], 0.003)
+        assert all(S.trace_branch(q)[0] <= 0 and S.trace_branch(q)[1] == 1 for q in pr["poses"][:, :4])
+        assert (pr["poses"][:, 3] < 0).any() and (pr["poses"][:, 3] > 0).any()
+    else:
+        _assert_general(pr["poses"])
+    assert ((fixed == 0).sum() > 42) == (path == "lmbig")
+    if path == "host_lm":
+        monkeypatch.setenv("ORBFE_LBA_HOST_LM", "1")
+    c = Context(640, 480, n_features=500, max_images=1)
+    g = c.ba_local_optimize(pr, fixed)
+    o = orc.ba_local_optimize(pr, fixed)
+    print(f"local BA {path} {gauge}: iterations {tuple(g['iters'])}, poses {_pose_dist(g['poses'], o['poses']):.2e}, "
+          f"points {np.abs(g['points'] - o['points']).max():.2e}")
+    assert tuple(g["iters"]) == tuple(o["iters"])
+    assert _pose_dist(g["poses"], o["poses"]) < 1e-7 and np.abs(g["points"] - o["points"]).max() < 1e-7
+    assert np.array_equal(g["poses"][:n_fixed], pr["poses"][:n_fixed])
+    assert (g["level"] != o["level"]).sum() <= 1 and (g["bad"] != o["bad"]).sum() <= 1
+    assert np.allclose(g["chi2"], o["chi2"], rtol=1e-6, atol=1e-9)
+    again = c.ba_local_optimize(pr, fixed)
+    assert all(np.array_equal(again[k], g[k]) for k in ("poses", "points", "level", "chi2", "bad"))
+    c.close()

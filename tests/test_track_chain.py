@@ -113,7 +113,35 @@ def _reference_chain(orc, s, th=3.0, ratio=0.8, min_threshold=50, min_matches=30
 def test_track_local_map_matches_the_three_step_chain(orc, seed, th):
     from orb_slam2_ros2_amd._lib import Context
     ctx = Context(W, H, n_features=NF, max_images=2)
-    s = _scene(ctx, seed)
+    _check_track_local_map(ctx, orc, _scene(ctx, seed), th)
+    ctx.close()
+
+
+def _gauged(s, axis, angle, t_g):
+    """The scene in the world X' = R_g X + t_g (se3_reference.gauge): map points, viewing directions and the pose move, the frame does
+    not.  The float Rcw / tcw come from the gauged fp64 pose the way _scene makes them."""
+    import se3_reference as S
+    Rg = S.quat_to_R(S.quat_of(axis, angle))
+    pose = S.gauge_poses(s["pose_se3"], axis, angle, t_g)
+    return dict(s, pos=S.gauge_points(s["pos"].astype(np.float64), axis, angle, t_g).astype(np.float32),
+                view_dir=(s["view_dir"].astype(np.float64) @ Rg.T).astype(np.float32), pose_se3=pose,
+                Rcw=_quat_to_R(pose[:4]).astype(np.float32), tcw=pose[4:].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_track_local_map_with_a_general_rotation(orc):
+    """k_project_map_points and the chained k_pose on a rotation matrix with no small entry and a start pose of four large quaternion
+    components (both asserted): the scene of seed 3 behind the skew 2.9 rad gauge, everything the test above asserts."""
+    import se3_reference as S
+    from orb_slam2_ros2_amd._lib import Context
+    ctx = Context(W, H, n_features=NF, max_images=2)
+    s = _gauged(_scene(ctx, 3), *S.GAUGES["skew"])
+    assert np.abs(s["Rcw"]).min() > 0.05 and np.abs(s["pose_se3"][:4]).min() > 0.01
+    _check_track_local_map(ctx, orc, s, 3.0)
+    ctx.close()
+
+
+def _check_track_local_map(ctx, orc, s, th):
     sig2 = (SF * SF).astype(np.float32)
     inv_sig2 = (np.float32(1.0) / sig2).astype(np.float32)
     args = (0, s["pos"], s["view_dir"], s["max_dist"], s["min_dist"], s["mp_desc"], s["flags"], s["Rcw"], s["tcw"], (FX, FY, CX, CY, BF),
@@ -136,7 +164,6 @@ def test_track_local_map_matches_the_three_step_chain(orc, seed, th):
     none = ctx.track_local_map(0, np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), np.zeros((0, 32), np.uint8), np.zeros(0, np.uint8),
                                s["Rcw"], s["tcw"], (FX, FY, CX, CY, BF), (0.0, float(W), 0.0, float(H)), s["pose_se3"], sig2, inv_sig2)
     assert none["n_matches"] == 0 and (none["assigned"] == -1).all()
-    ctx.close()
 
 
 # ---- Tracking::trackMotionModel's middle as one call (orbfe_track_motion_model) -------------------------------------------------
