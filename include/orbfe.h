@@ -780,6 +780,77 @@ orbfe_status orbfe_fuse_into_keyframes(orbfe_ctx* ctx, const orbfe_fuse_kf* cur,
                                        int32_t dist_threshold, int32_t* best_idx /*[n_kf][cur->n]*/, int32_t* best_dist /*[n_kf][cur->n]*/,
                                        uint8_t* visible /*[n_kf][cur->n]*/);
 
+/* ---- keyframes resident on the device -------------------------------------------------------------------------------
+ * One orbfe_kfstore holds, on ONE device and keyed by a uint64 id (KeyFrame::getID()), what never changes after a keyframe's creation:
+ * its n features (keypoints, descriptors, depth and right_u, -1 where there is none), its frame bounds, the area grid built from them
+ * (cell_off[rows * cols + 1], cell_feat[n]: VirtualFrame::initGrid, what orbfe_fuse_into_keyframes builds per call) and, once set_bow
+ * has run, its FeatureVector in orbfe_bow_out's layout.  Poses and map points are NOT stored: they change during mapping and stay
+ * arguments of the calls below.  The store has its own lock and serves every context on its device; a context on another device:
+ * ORBFE_EBADARG.  add, add_from_slot, set_bow and erase take the lock exclusively; fetch, info, size and the two *_stored calls take
+ * it shared for their whole (synchronous) duration, so an erase never frees memory under a running kernel.  An entry never moves:
+ * memory comes in slabs of slab_bytes (0: 32 MB), an entry larger than a slab gets an allocation of its own, erased space is reused.
+ *   create         width, height: the image size a NULL `bounds` stands for (a context's config); n_levels: octaves are 0 .. n_levels - 1
+ *   add            from host arrays (loaded maps, tests).  depth / right_u NULL: every entry -1.  bounds NULL: {0, width, 0, height}.
+ *                  Errors: an id already present, an octave out of range, bad bounds: ORBFE_EBADARG, nothing changes; a grid that
+ *                  exceeds the LDS counters: ORBFE_EBADSIZE (the rule of orbfe_fuse_into_keyframes).
+ *   add_from_slot  the features of extraction slot `slot` of `ctx` (and, pair >= 0, that stereo pair's right_u and depth; pair < 0:
+ *                  -1) device to device, ordered after the slot's pending work as orbfe_fetch_features is.  Only the feature count
+ *                  comes to the host (4 bytes, so that the entry is exactly as large as it must be); ONE launch then packs the
+ *                  slot's arrays into the entry and builds its grid.  *n_out (NULL: not wanted): the count.  The context's n_levels
+ *                  must not exceed the store's.
+ *   set_bow        the FeatureVector of a present keyframe (replacing an earlier one), checked as orbfe_create_new_map_points checks
+ *                  an orbfe_tri_kf: nodes strictly ascending, offsets from 0, not decreasing, not past n, feature indices below n.
+ *   erase          unknown ids are ignored.
+ *   info / fetch   an unknown id: ORBFE_EBADARG.  fetch copies the arrays whose pointer is not NULL, sized as info says.  has_stereo says
+ *                  whether depth and right_u were supplied at insertion (add with both arrays, add_from_slot with pair >= 0).
+ * orbfe_fuse_into_keyframes_stored and orbfe_create_new_map_points_stored are orbfe_fuse_into_keyframes and
+ * orbfe_create_new_map_points with the keyframes named by id: identical outputs, rules and errors, the same kernels; only the map
+ * state goes up.  n_cur / orbfe_tri_state::n must equal the stored feature count (they size the caller's arrays).  cur_id may be among
+ * the fuse targets.  An unknown id, a keyframe without FeatureVector (create_new_map_points_stored), n_levels below the store's:
+ * ORBFE_EBADARG, nothing written.                                                                                                    */
+typedef struct orbfe_kfstore orbfe_kfstore;
+typedef struct orbfe_kfstore_info {
+  int32_t n;                  /* features                                                                     */
+  int32_t has_bow;            /* set_bow has run                                                              */
+  int32_t has_stereo;         /* depth and right_u were supplied (add with both arrays, add_from_slot with a pair) */
+  int32_t n_nodes, n_bow_features; /* sizes of the FeatureVector arrays (0 without one)                       */
+  int32_t grid_rows, grid_cols;    /* cell_off has grid_rows * grid_cols + 1 entries, cell_feat n             */
+  float bounds[4];            /* mfMinU mfMaxU mfMinV mfMaxV                                                  */
+  int64_t bytes;              /* device bytes the entry occupies                                              */
+} orbfe_kfstore_info;
+typedef struct orbfe_fuse_pose {
+  float Rcw[9], tcw[3];       /* getPose(Rcw, tcw), row-major                                                 */
+} orbfe_fuse_pose;
+typedef struct orbfe_tri_state { /* the map state of one stored keyframe */
+  int32_t n;                     /* its feature count (must equal the stored one)                             */
+  const uint8_t* flags;          /* [n] ORBFE_TRI_GOOD | ORBFE_TRI_INMAP                                      */
+  float Tcw[16], Twc[16], Ow[3]; /* as orbfe_tri_kf                                                           */
+  const uint8_t* unproc;         /* cur only: [n]                                                             */
+  const float* unproc_pos;       /* cur only: [n][3]                                                          */
+} orbfe_tri_state;
+orbfe_status orbfe_kfstore_create(int32_t device_id, int32_t width, int32_t height, int32_t n_levels, int64_t slab_bytes, orbfe_kfstore** out);
+void orbfe_kfstore_destroy(orbfe_kfstore* store);  /* no call on the store may still run */
+orbfe_status orbfe_kfstore_add(orbfe_kfstore* store, uint64_t id, int32_t n, const orbfe_keypoint* kps, const uint8_t* desc, const double* depth,
+                               const double* right_u, const float* bounds /*[4] or NULL*/);
+orbfe_status orbfe_kfstore_add_from_slot(orbfe_ctx* ctx, orbfe_kfstore* store, uint64_t id, int32_t slot, int32_t pair,
+                                         const float* bounds /*[4] or NULL*/, int32_t* n_out);
+orbfe_status orbfe_kfstore_set_bow(orbfe_kfstore* store, uint64_t id, int32_t n_nodes, const uint32_t* nodes, const int32_t* node_offsets,
+                                   const uint32_t* features);
+orbfe_status orbfe_kfstore_erase(orbfe_kfstore* store, int32_t n, const uint64_t* ids);
+orbfe_status orbfe_kfstore_size(orbfe_kfstore* store, int64_t* n_keyframes, int64_t* bytes_used, int64_t* bytes_reserved);
+orbfe_status orbfe_kfstore_info_get(orbfe_kfstore* store, uint64_t id, orbfe_kfstore_info* out);
+orbfe_status orbfe_kfstore_fetch(orbfe_kfstore* store, uint64_t id, orbfe_keypoint* kps, uint8_t* desc, double* depth, double* right_u,
+                                 int32_t* cell_off, int32_t* cell_feat, uint32_t* nodes, int32_t* node_offsets, uint32_t* features);
+orbfe_status orbfe_fuse_into_keyframes_stored(orbfe_ctx* ctx, orbfe_kfstore* store, uint64_t cur_id, int32_t n_cur, const orbfe_fuse_points* pts,
+                                              int32_t n_kf, const uint64_t* target_ids, const orbfe_fuse_pose* poses /*[n_kf]*/,
+                                              const float* z /*[n_kf]*/, const orbfe_camera* cam, float bl, const float* scale_factors,
+                                              int32_t n_levels, float th, float ratio, int32_t dist_threshold, int32_t* best_idx,
+                                              int32_t* best_dist, uint8_t* visible);
+orbfe_status orbfe_create_new_map_points_stored(orbfe_ctx* ctx, orbfe_kfstore* store, uint64_t cur_id, const orbfe_tri_state* cur, int32_t n_nb,
+                                                const uint64_t* nb_ids, const orbfe_tri_state* nbs, const orbfe_camera* cam, const float* k_inv,
+                                                float bl, const float* scale_factors, int32_t n_levels, orbfe_tri_record* records, int64_t cap,
+                                                int64_t* n_records, int32_t* tail, int64_t tail_cap, int64_t* n_tail, uint8_t* consumed);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

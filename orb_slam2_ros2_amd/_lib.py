@@ -139,6 +139,20 @@ class FusePoints(C.Structure):
     _fields_ = [("has_point", C.c_void_p), ("pos", C.c_void_p), ("view_dir", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p)]
 
 
+class KfstoreInfo(C.Structure):
+    _fields_ = [("n", C.c_int32), ("has_bow", C.c_int32), ("has_stereo", C.c_int32), ("n_nodes", C.c_int32), ("n_bow_features", C.c_int32), ("grid_rows", C.c_int32),
+                ("grid_cols", C.c_int32), ("bounds", C.c_float * 4), ("bytes", C.c_int64)]
+
+
+class FusePose(C.Structure):
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3)]
+
+
+class TriState(C.Structure):
+    _fields_ = [("n", C.c_int32), ("flags", C.c_void_p), ("Tcw", C.c_float * 16), ("Twc", C.c_float * 16), ("Ow", C.c_float * 3),
+                ("unproc", C.c_void_p), ("unproc_pos", C.c_void_p)]
+
+
 FUSE_MAX_KF = 64
 TRI_REC_DTYPE = np.dtype([("nb", "<i4"), ("q", "<i4"), ("t", "<i4"), ("kind", "<i4"), ("xyz", "<f4", (3,))])
 TRI_MAX_NB = 64
@@ -161,6 +175,9 @@ EXPORTS = [
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
+    "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
+    "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
+    "orbfe_create_new_map_points_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
 ]
 BOW_MAX_FEATURES = 65535
@@ -273,6 +290,21 @@ def load() -> C.CDLL:
                                               C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64), vp]
     L.orbfe_fuse_into_keyframes.argtypes = [vp, C.POINTER(FuseKf), C.POINTER(FusePoints), i32, vp, vp, C.POINTER(Camera), f32, vp, i32, f32, f32,
                                             i32, vp, vp, vp]
+    u64, i64 = C.c_uint64, C.c_int64
+    L.orbfe_kfstore_create.argtypes = [i32, i32, i32, i32, i64, C.POINTER(vp)]
+    L.orbfe_kfstore_destroy.argtypes = [vp]
+    L.orbfe_kfstore_destroy.restype = None
+    L.orbfe_kfstore_add.argtypes = [vp, u64, i32, vp, vp, vp, vp, vp]
+    L.orbfe_kfstore_add_from_slot.argtypes = [vp, vp, u64, i32, i32, vp, C.POINTER(i32)]
+    L.orbfe_kfstore_set_bow.argtypes = [vp, u64, i32, vp, vp, vp]
+    L.orbfe_kfstore_erase.argtypes = [vp, i32, vp]
+    L.orbfe_kfstore_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.orbfe_kfstore_info_get.argtypes = [vp, u64, C.POINTER(KfstoreInfo)]
+    L.orbfe_kfstore_fetch.argtypes = [vp, u64] + [vp] * 9
+    L.orbfe_fuse_into_keyframes_stored.argtypes = [vp, vp, u64, i32, C.POINTER(FusePoints), i32, vp, vp, vp, C.POINTER(Camera), f32, vp, i32, f32,
+                                                   f32, i32, vp, vp, vp]
+    L.orbfe_create_new_map_points_stored.argtypes = [vp, vp, u64, C.POINTER(TriState), i32, vp, vp, C.POINTER(Camera), vp, f32, vp, i32, vp, i64,
+                                                     C.POINTER(i64), vp, i64, C.POINTER(i64), vp]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -573,6 +605,104 @@ class KeyFrameDB:
         i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
         out = np.zeros(len(i))
         ctx._check(self.lib.orbfe_kfdb_score(ctx.h, self.h, C.byref(q), ptr(i), len(i), ptr(out)))
+        return out
+
+
+class KeyframeStore:
+    """Keyframes resident on one device, keyed by uint64 id (orbfe_kfstore, include/orbfe.h): features, stereo columns,
+    frame bounds, the area grid and -- after set_bow -- the FeatureVector.  Poses and map points are not stored.  Any Context on the same
+    device uses it through Context.fuse_into_keyframes_stored / create_new_map_points_stored."""
+
+    def __init__(self, width, height, n_levels=8, device_id=0, slab_bytes=0):
+        self.lib = load()
+        h = C.c_void_p(None)
+        st = self.lib.orbfe_kfstore_create(int(device_id), int(width), int(height), int(n_levels), int(slab_bytes), C.byref(h))
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+        self.h = h
+
+    def _check(self, st):
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbfe_kfstore_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _bounds(bounds):
+        return None if bounds is None else np.ascontiguousarray(bounds, np.float32).reshape(4)
+
+    def add(self, kf_id, kps, desc, depth=None, right_u=None, bounds=None):
+        """from host arrays: kps [n] KP_DTYPE, desc [n, 32] uint8, depth / right_u [n] float64 (None: -1), bounds (minU, maxU, minV, maxV)
+        (None: the image)"""
+        k = np.ascontiguousarray(kps, KP_DTYPE)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        if len(d) != len(k):
+            raise ValueError("add: kps and desc differ in length")
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float64)
+        ru = None if right_u is None else np.ascontiguousarray(right_u, np.float64)
+        if any(a is not None and len(a) != len(k) for a in (dp, ru)):
+            raise ValueError("add: depth / right_u must have one entry per feature")
+        b = self._bounds(bounds)
+        self._check(self.lib.orbfe_kfstore_add(self.h, int(kf_id), len(k), ptr(k), ptr(d), None if dp is None else ptr(dp), None if ru is None else ptr(ru),
+                                               None if b is None else ptr(b)))
+
+    def add_from_slot(self, ctx, kf_id, slot, pair=-1, bounds=None):
+        """the features of extraction slot `slot` of `ctx` (pair >= 0: with that stereo pair's right_u and depth), device to device -> n"""
+        b = self._bounds(bounds)
+        n = C.c_int32(0)
+        ctx._check(self.lib.orbfe_kfstore_add_from_slot(ctx.h, self.h, int(kf_id), int(slot), int(pair), None if b is None else ptr(b), C.byref(n)))
+        return n.value
+
+    def set_bow(self, kf_id, nodes, node_offsets, features):
+        """the FeatureVector (bow_transform's last three outputs)"""
+        nd = np.ascontiguousarray(nodes, np.uint32)
+        of = np.ascontiguousarray(node_offsets, np.int32)
+        ft = np.ascontiguousarray(features, np.uint32)
+        if len(of) != len(nd) + 1 or (len(of) and 0 <= of[-1] and of[-1] > len(ft)):
+            raise ValueError("set_bow: node_offsets must have len(nodes) + 1 entries ending inside features")
+        self._check(self.lib.orbfe_kfstore_set_bow(self.h, int(kf_id), len(nd), ptr(nd), ptr(of), ptr(ft)))
+
+    def erase(self, ids):
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        self._check(self.lib.orbfe_kfstore_erase(self.h, len(i), ptr(i)))
+
+    def __len__(self):
+        n = C.c_int64(0)
+        self._check(self.lib.orbfe_kfstore_size(self.h, C.byref(n), None, None))
+        return n.value
+
+    def bytes(self):
+        """(bytes the entries occupy, bytes of device memory reserved in slabs)"""
+        u, r = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.orbfe_kfstore_size(self.h, None, C.byref(u), C.byref(r)))
+        return u.value, r.value
+
+    def info(self, kf_id):
+        o = KfstoreInfo()
+        self._check(self.lib.orbfe_kfstore_info_get(self.h, int(kf_id), C.byref(o)))
+        return dict(n=o.n, has_bow=bool(o.has_bow), has_stereo=bool(o.has_stereo), n_nodes=o.n_nodes, n_bow_features=o.n_bow_features, grid=(o.grid_rows, o.grid_cols),
+                    bounds=np.array(list(o.bounds), np.float32), bytes=o.bytes)
+
+    def fetch(self, kf_id):
+        """the entry as dict(kps, desc, depth, right_u, bounds, cell_off, cell_feat, fv = (nodes, offsets, features) or None)"""
+        i = self.info(kf_id)
+        n = i["n"]
+        out = dict(kps=np.zeros(n, KP_DTYPE), desc=np.zeros((n, 32), np.uint8), depth=np.zeros(n, np.float64), right_u=np.zeros(n, np.float64),
+                   cell_off=np.zeros(i["grid"][0] * i["grid"][1] + 1, np.int32), cell_feat=np.zeros(n, np.int32))
+        fv = (np.zeros(i["n_nodes"], np.uint32), np.zeros(i["n_nodes"] + 1, np.int32), np.zeros(i["n_bow_features"], np.uint32)) if i["has_bow"] else None
+        p = lambda a: ptr(a) if a.size else None  # noqa: E731
+        self._check(self.lib.orbfe_kfstore_fetch(self.h, int(kf_id), p(out["kps"]), p(out["desc"]), p(out["depth"]), p(out["right_u"]), p(out["cell_off"]),
+                                                 p(out["cell_feat"]), *([None] * 3 if fv is None else [p(a) for a in fv])))
+        out["bounds"], out["fv"] = i["bounds"], fv
         return out
 
 
@@ -1304,6 +1434,107 @@ class Context:
         self._fuse_keep = (keep, c, p, tg, cm, bi, bd, vis)
         self._check(self.lib.orbfe_fuse_into_keyframes(*self._fuse_args))
         return bi, bd, vis
+
+    # ---- the same two calls over keyframes resident in a KeyframeStore ------------------------------------------------------------------
+    def fuse_into_keyframes_stored(self, store, cur_id, pts, target_ids, poses, z, cam, bl, scale_factors, th=3.0, ratio=0.6, dist_threshold=50,
+                                   out=None):
+        """fuse_into_keyframes with the keyframes named by id in `store` (orbfe_fuse_into_keyframes_stored): poses = [(Rcw, tcw)] per target
+        (or dicts with those keys); everything else, and the result, as fuse_into_keyframes."""
+        keep = []
+
+        def arr(a, dt, shape=None):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            if shape is not None:
+                a = a.reshape(shape)
+            keep.append(a)
+            return a
+
+        def vptr(a):
+            return None if a is None else ptr(a).value
+
+        K = len(target_ids)
+        n = store.info(cur_id)["n"]
+        ids = arr(target_ids, np.uint64)
+        ps = (FusePose * max(K, 1))()
+        for k, pz in enumerate(poses):
+            R, t = (pz["Rcw"], pz["tcw"]) if isinstance(pz, dict) else pz
+            ps[k].Rcw[:] = [float(v) for v in np.asarray(R, np.float32).reshape(9)]
+            ps[k].tcw[:] = [float(v) for v in np.asarray(t, np.float32).reshape(3)]
+        p = FusePoints()
+        has = pts.get("has_point")
+        rows = [arr(None if has is None else np.asarray(has).astype(bool), np.uint8), arr(pts.get("pos"), np.float32, (-1, 3)),
+                arr(pts.get("view_dir"), np.float32, (-1, 3)), arr(pts.get("max_dist"), np.float32), arr(pts.get("min_dist"), np.float32)]
+        p.has_point, p.pos, p.view_dir, p.max_dist, p.min_dist = [vptr(x) for x in rows]
+        zz = arr(z, np.float32)
+        sf = arr(scale_factors, np.float32)
+        cm = Camera(*[float(np.float32(v)) for v in cam[:4]])
+        # the library sizes every row array by the STORED feature count: arrays of another length would be read or written past their end
+        if any(x is not None and len(x) != n for x in rows) or len(poses) != K or (zz is not None and len(zz) != K):
+            raise ValueError(f"fuse_into_keyframes_stored: keyframe {cur_id} has {n} features and there are {K} targets; pts / poses / z do not match")
+        if out is None:
+            out = (np.zeros((K, n), np.int32), np.zeros((K, n), np.int32), np.zeros((K, n), np.uint8))
+        bi, bd, vis = out
+        if any(x.size < K * n or not x.flags.c_contiguous for x in out) or (bi.dtype, bd.dtype, vis.dtype) != (np.int32, np.int32, np.uint8):
+            raise ValueError("fuse_into_keyframes_stored: out must be C-contiguous int32, int32, uint8 arrays of at least [K, n]")
+        # (kept with the arrays behind them: tools/kfstore_bench.py times the bare C call with the same arguments)
+        self._fuse_stored_args = (self.h, store.h, int(cur_id), n, C.byref(p), K, vptr(ids), C.cast(ps, C.c_void_p), vptr(zz), C.byref(cm),
+                                  float(np.float32(bl)), ptr(sf), len(sf), float(np.float32(th)), float(np.float32(ratio)), int(dist_threshold),
+                                  ptr(bi), ptr(bd), ptr(vis))
+        self._fuse_stored_keep = (keep, p, ps, cm, bi, bd, vis)
+        self._check(self.lib.orbfe_fuse_into_keyframes_stored(*self._fuse_stored_args))
+        return bi, bd, vis
+
+    def create_new_map_points_stored(self, store, cur_id, cur, nb_ids, nbs, cam, k_inv, bl, scale_factors, cap=None, tail_cap=None):
+        """create_new_map_points with the keyframes named by id in `store` (orbfe_create_new_map_points_stored).  cur and every entry of nbs
+        carry only the map state: flags [n], Tcw, Twc, Ow; cur also unproc and unproc_pos (other keys are ignored, so the dicts of
+        create_new_map_points pass).  Returns what create_new_map_points returns."""
+        keep = []
+
+        def arr(a, dt, shape=None):
+            a = np.ascontiguousarray(a, dt)
+            if shape is not None:
+                a = a.reshape(shape)
+            keep.append(a)
+            return a
+
+        def state(d, with_unproc):
+            k = TriState()
+            fl = arr(d["flags"], np.uint8)
+            k.n = len(fl)
+            k.flags = ptr(fl).value
+            k.Tcw[:] = [float(v) for v in np.asarray(d["Tcw"], np.float32).reshape(16)]
+            k.Twc[:] = [float(v) for v in np.asarray(d["Twc"], np.float32).reshape(16)]
+            k.Ow[:] = [float(v) for v in np.asarray(d["Ow"], np.float32).reshape(3)]
+            if with_unproc:
+                k.unproc = ptr(arr(np.asarray(d["unproc"]).astype(bool), np.uint8)).value
+                k.unproc_pos = ptr(arr(d["unproc_pos"], np.float32, (-1, 3))).value
+            return k
+
+        c = state(cur, True)
+        nb = (TriState * max(len(nbs), 1))(*[state(d, False) for d in nbs])
+        ids = arr(nb_ids, np.uint64)
+        n = c.n
+        unproc, unproc_pos = np.asarray(cur["unproc"]), np.asarray(cur["unproc_pos"], np.float32).reshape(-1, 3)
+        if len(ids) != len(nbs) or len(unproc) != n or len(unproc_pos) != n:
+            raise ValueError("create_new_map_points_stored: one id per neighbour state, unproc / unproc_pos of cur's length")
+        cap = n if cap is None else int(cap)
+        tail_cap = n if tail_cap is None else int(tail_cap)
+        recs = np.zeros(max(cap, 1), TRI_REC_DTYPE)
+        tail = np.zeros(max(tail_cap, 1), np.int32)
+        consumed = np.zeros(max(n, 1), np.uint8)
+        cm = Camera(*[float(v) for v in cam[:4]])
+        ki = arr(k_inv, np.float32, (9,))
+        sf = arr(scale_factors, np.float32)
+        nr, nt = C.c_int64(0), C.c_int64(0)
+        self._tri_stored_args = (self.h, store.h, int(cur_id), C.byref(c), len(nbs), ptr(ids), C.cast(nb, C.c_void_p), C.byref(cm), ptr(ki), float(bl),
+                                 ptr(sf), len(sf), ptr(recs), cap, C.byref(nr), ptr(tail), tail_cap, C.byref(nt), ptr(consumed))
+        self._tri_stored_keep = (keep, c, nb, cm, recs, tail, consumed, nr, nt)
+        st = self.lib.orbfe_create_new_map_points_stored(*self._tri_stored_args)
+        self.last_counts = (nr.value, nt.value)
+        self._check(st)
+        return recs[:nr.value].copy(), tail[:nt.value].copy(), consumed[:n].astype(bool)
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -1,0 +1,104 @@
+// fuse_grid_body.h -- the area grid of one keyframe (VirtualFrame::initGrid, src/Frame.cc:53-69) by one workgroup of FUSE_GRID_NT
+// threads: the body of k_fuse_grid (k_fuse.hip), shared with k_kfstore_pack (k_kfstore.hip), which builds a stored keyframe's grid
+// once, at insertion.  The grid is sized from the keyframe's own bounds (search_area_layout.h: AreaGrid).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "orbfe_internal.h"
+
+#define FUSE_GRID_W 64
+#define FUSE_GRID_H 48
+#define FUSE_GRID_NT 1024
+
+namespace orbfe {
+
+__device__ __forceinline__ int cvfloor_f(float v) {
+  const int i = (int)v;
+  return i - (i > v);
+}
+// cell of a coordinate: cvFloor(v / size) (Frame.cc:64-65) clamped to the grid at both ends, a non-finite coordinate in cell 0
+__device__ __forceinline__ int grid_cell(float v, int size, int n) {
+  const float q = v / (float)size;
+  if (!(q > 0.0f)) return 0;
+  if (q >= (float)(n - 1)) return n - 1;
+  return cvfloor_f(q);
+}
+
+// cell_off[ncells + 1], cell_feat[n] (a cell's features in ascending index) of the n keypoints kps.  l_grid: the workgroup's dynamic
+// LDS, [ncells + 1] offsets, [ncells] counts / fill cursors, then (feat_in_lds) the [n] unordered lists and the [n] cells of the
+// features; l_scan: FUSE_GRID_NT words of LDS.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void fuse_grid_build(const orbfe_keypoint* __restrict__ kps, int n, int rows, int cols, int feat_in_lds,
+                                                int32_t* __restrict__ cell_off, int32_t* __restrict__ cell_feat, int32_t* l_grid,
+                                                int32_t* l_scan) {
+  const int tid = threadIdx.x;
+  const int ncells = rows * cols;
+  int32_t* l_off = l_grid;
+  int32_t* l_cur = l_grid + ncells + 1;
+  int32_t* feat = feat_in_lds ? l_cur + ncells : cell_feat;
+  int32_t* l_cell = feat + n;  // (feat_in_lds only)
+  for (int c = tid; c < ncells; c += FUSE_GRID_NT) l_cur[c] = 0;
+  __syncthreads();
+  for (int i = tid; i < n; i += FUSE_GRID_NT) {
+    const int cell = grid_cell(kps[i].y, FUSE_GRID_H, rows) * cols + grid_cell(kps[i].x, FUSE_GRID_W, cols);
+    if (feat_in_lds) l_cell[i] = cell;
+    atomicAdd(&l_cur[cell], 1);
+  }
+  __syncthreads();
+  // exclusive prefix over the cells: a thread sums a run of consecutive cells, the run totals are scanned, the thread writes its run's offsets
+  const int per = (ncells + FUSE_GRID_NT - 1) / FUSE_GRID_NT;
+  const int c0 = min(tid * per, ncells), c1 = min(c0 + per, ncells);
+  int local = 0;
+  for (int c = c0; c < c1; ++c) local += l_cur[c];
+  l_scan[tid] = local;
+  __syncthreads();
+  for (int o = 1; o < FUSE_GRID_NT; o <<= 1) {
+    const int v = tid >= o ? l_scan[tid - o] : 0;
+    __syncthreads();
+    l_scan[tid] += v;
+    __syncthreads();
+  }
+  {
+    int acc = l_scan[tid] - local;
+    for (int c = c0; c < c1; ++c) {
+      const int k = l_cur[c];
+      l_off[c] = acc;
+      l_cur[c] = 0;
+      acc += k;
+    }
+    if (tid == FUSE_GRID_NT - 1) l_off[ncells] = l_scan[FUSE_GRID_NT - 1];
+  }
+  __syncthreads();
+  for (int c = tid; c <= ncells; c += FUSE_GRID_NT) cell_off[c] = l_off[c];
+  for (int i = tid; i < n; i += FUSE_GRID_NT) {
+    const int cell = feat_in_lds ? l_cell[i] : grid_cell(kps[i].y, FUSE_GRID_H, rows) * cols + grid_cell(kps[i].x, FUSE_GRID_W, cols);
+    feat[l_off[cell] + atomicAdd(&l_cur[cell], 1)] = i;
+  }
+  __syncthreads();
+  // the reference pushes indices in ascending order (Frame.cc:61-68)
+  if (feat_in_lds) {
+    // every feature finds its place in its cell's list by counting the smaller indices there
+    for (int i = tid; i < n; i += FUSE_GRID_NT) {
+      const int cell = l_cell[i];
+      const int b = l_off[cell], k = l_off[cell + 1] - b;
+      int rank = 0;
+      for (int j = 0; j < k; ++j) rank += feat[b + j] < i ? 1 : 0;
+      cell_feat[b + rank] = i;
+    }
+    return;
+  }
+  for (int c = tid; c < ncells; c += FUSE_GRID_NT) {
+    int32_t* L = feat + l_off[c];
+    const int k = l_off[c + 1] - l_off[c];
+    for (int a = 1; a < k; ++a) {
+      const int32_t v = L[a];
+      int b = a - 1;
+      while (b >= 0 && L[b] > v) {
+        L[b + 1] = L[b];
+        --b;
+      }
+      L[b + 1] = v;
+    }
+  }
+}
+
+}  // namespace orbfe

@@ -14,6 +14,7 @@
 // geometry (a wave owns a query, a workgroup owns a target's grid, and the per-cell lists end up sorted).
 #include <hip/hip_runtime.h>
 
+#include "fuse_grid_body.h"
 #include "match_fold.h"
 #include "orbfe_internal.h"
 
@@ -23,101 +24,20 @@ namespace {
 
 using namespace orbfe;
 
-#define FUSE_GRID_W 64
-#define FUSE_GRID_H 48
-#define FUSE_GRID_NT 1024
-
-__device__ __forceinline__ int cvfloor_f(float v) {
-  const int i = (int)v;
-  return i - (i > v);
-}
-// cell of a coordinate: cvFloor(v / size) (Frame.cc:64-65) clamped to the grid at both ends, a non-finite coordinate in cell 0
-__device__ __forceinline__ int grid_cell(float v, int size, int n) {
-  const float q = v / (float)size;
-  if (!(q > 0.0f)) return 0;
-  if (q >= (float)(n - 1)) return n - 1;
-  return cvfloor_f(q);
+// array `off` of a target: bytes behind `base`.  The stored form (orbfe_fuse_into_keyframes_stored) passes base = nullptr and the arrays'
+// device addresses as offsets: a stored keyframe lies wherever its slab is (orbfe_kfstore.hip), and the kernels below are the same.
+template <class T>
+__device__ __forceinline__ T* at(const uint8_t* base, uint64_t off) {
+  return (T*)((uintptr_t)base + off);
 }
 
 // cell_off[ncells + 1], cell_feat[n] (a cell's features in ascending index) of target blockIdx.x
 __global__ __launch_bounds__(FUSE_GRID_NT) void k_fuse_grid(uint8_t* __restrict__ base, const FuseKf* __restrict__ kfs) {
-  // [ncells + 1] offsets, [ncells] counts / fill cursors, then (in_lds) the [n] unordered lists and the [n] cells of the features
-  extern __shared__ __attribute__((aligned(16))) int32_t l_grid[];
+  extern __shared__ __attribute__((aligned(16))) int32_t l_grid[];  // (fuse_grid_body.h)
   __shared__ int32_t l_scan[FUSE_GRID_NT];
   const FuseKf& K = kfs[blockIdx.x];
-  const orbfe_keypoint* __restrict__ kps = (const orbfe_keypoint*)(base + K.o_kps);
-  int32_t* __restrict__ cell_off = (int32_t*)(base + K.o_coff);
-  int32_t* __restrict__ cell_feat = (int32_t*)(base + K.o_cfeat);
-  const int tid = threadIdx.x;
-  const int n = K.n, rows = K.rows, cols = K.cols, feat_in_lds = K.in_lds;
-  const int ncells = rows * cols;
-  int32_t* l_off = l_grid;
-  int32_t* l_cur = l_grid + ncells + 1;
-  int32_t* feat = feat_in_lds ? l_cur + ncells : cell_feat;
-  int32_t* l_cell = feat + n;  // (feat_in_lds only)
-  for (int c = tid; c < ncells; c += FUSE_GRID_NT) l_cur[c] = 0;
-  __syncthreads();
-  for (int i = tid; i < n; i += FUSE_GRID_NT) {
-    const int cell = grid_cell(kps[i].y, FUSE_GRID_H, rows) * cols + grid_cell(kps[i].x, FUSE_GRID_W, cols);
-    if (feat_in_lds) l_cell[i] = cell;
-    atomicAdd(&l_cur[cell], 1);
-  }
-  __syncthreads();
-  // exclusive prefix over the cells: a thread sums a run of consecutive cells, the run totals are scanned, the thread writes its run's offsets
-  const int per = (ncells + FUSE_GRID_NT - 1) / FUSE_GRID_NT;
-  const int c0 = min(tid * per, ncells), c1 = min(c0 + per, ncells);
-  int local = 0;
-  for (int c = c0; c < c1; ++c) local += l_cur[c];
-  l_scan[tid] = local;
-  __syncthreads();
-  for (int o = 1; o < FUSE_GRID_NT; o <<= 1) {
-    const int v = tid >= o ? l_scan[tid - o] : 0;
-    __syncthreads();
-    l_scan[tid] += v;
-    __syncthreads();
-  }
-  {
-    int acc = l_scan[tid] - local;
-    for (int c = c0; c < c1; ++c) {
-      const int k = l_cur[c];
-      l_off[c] = acc;
-      l_cur[c] = 0;
-      acc += k;
-    }
-    if (tid == FUSE_GRID_NT - 1) l_off[ncells] = l_scan[FUSE_GRID_NT - 1];
-  }
-  __syncthreads();
-  for (int c = tid; c <= ncells; c += FUSE_GRID_NT) cell_off[c] = l_off[c];
-  for (int i = tid; i < n; i += FUSE_GRID_NT) {
-    const int cell = feat_in_lds ? l_cell[i] : grid_cell(kps[i].y, FUSE_GRID_H, rows) * cols + grid_cell(kps[i].x, FUSE_GRID_W, cols);
-    feat[l_off[cell] + atomicAdd(&l_cur[cell], 1)] = i;
-  }
-  __syncthreads();
-  // the reference pushes indices in ascending order (Frame.cc:61-68)
-  if (feat_in_lds) {
-    // every feature finds its place in its cell's list by counting the smaller indices there
-    for (int i = tid; i < n; i += FUSE_GRID_NT) {
-      const int cell = l_cell[i];
-      const int b = l_off[cell], k = l_off[cell + 1] - b;
-      int rank = 0;
-      for (int j = 0; j < k; ++j) rank += feat[b + j] < i ? 1 : 0;
-      cell_feat[b + rank] = i;
-    }
-    return;
-  }
-  for (int c = tid; c < ncells; c += FUSE_GRID_NT) {
-    int32_t* L = feat + l_off[c];
-    const int k = l_off[c + 1] - l_off[c];
-    for (int a = 1; a < k; ++a) {
-      const int32_t v = L[a];
-      int b = a - 1;
-      while (b >= 0 && L[b] > v) {
-        L[b + 1] = L[b];
-        --b;
-      }
-      L[b + 1] = v;
-    }
-  }
+  fuse_grid_build(at<const orbfe_keypoint>(base, K.o_kps), K.n, K.rows, K.cols, K.in_lds, at<int32_t>(base, K.o_coff), at<int32_t>(base, K.o_cfeat),
+                  l_grid, l_scan);
 }
 
 // MapPoint::isInVision(target k) for the point of slot i: Rcw * X + tcw as float products summed left to right, then
@@ -171,10 +91,10 @@ __global__ __launch_bounds__(256) void k_fuse_search(const uint8_t* __restrict__
   if (q >= (long long)P.n_kf * P.n_cur) return;
   const int k = (int)(q / P.n_cur), i = (int)(q - (long long)k * P.n_cur);
   const FuseKf& K = kfs[k];
-  const orbfe_keypoint* __restrict__ kps = (const orbfe_keypoint*)(base + K.o_kps);
-  const uint8_t* __restrict__ desc = base + K.o_desc;
-  const int32_t* __restrict__ cell_off = (const int32_t*)(base + K.o_coff);
-  const int32_t* __restrict__ cell_feat = (const int32_t*)(base + K.o_cfeat);
+  const orbfe_keypoint* __restrict__ kps = at<const orbfe_keypoint>(base, K.o_kps);
+  const uint8_t* __restrict__ desc = at<const uint8_t>(base, K.o_desc);
+  const int32_t* __restrict__ cell_off = at<const int32_t>(base, K.o_coff);
+  const int32_t* __restrict__ cell_feat = at<const int32_t>(base, K.o_cfeat);
   const int rows = K.rows, cols = K.cols, width = K.clip_w, height = K.clip_h, mode = K.mode;
   const float x = q_kps[i].x, y = q_kps[i].y;
   const int oct = q_kps[i].octave;
@@ -235,12 +155,13 @@ __global__ __launch_bounds__(256) void k_fuse_search(const uint8_t* __restrict__
 
 }  // namespace
 
+// build_grids false: the targets' grids are already there (stored keyframes)
 void launch_fuse(hipStream_t st, uint8_t* base, const FuseKf* kfs, const FuseParams& P, size_t grid_lds, const orbfe_keypoint* q_kps,
                  const uint8_t* q_desc, const float* sf, const uint8_t* has_point, const float* pos, const float* vdir, const float* max_dist,
-                 const float* min_dist, int32_t* best_idx, int32_t* best_dist, uint8_t* visible) {
+                 const float* min_dist, int32_t* best_idx, int32_t* best_dist, uint8_t* visible, bool build_grids) {
   const long long nq = (long long)P.n_kf * P.n_cur;
   if (nq <= 0) return;
-  hipLaunchKernelGGL(k_fuse_grid, dim3(P.n_kf), dim3(FUSE_GRID_NT), grid_lds, st, base, kfs);
+  if (build_grids) hipLaunchKernelGGL(k_fuse_grid, dim3(P.n_kf), dim3(FUSE_GRID_NT), grid_lds, st, base, kfs);
   hipLaunchKernelGGL(k_fuse_visible, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, kfs, P, has_point, pos, vdir, max_dist, min_dist, visible);
   hipLaunchKernelGGL(k_fuse_search, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, base, kfs, P, q_kps, q_desc, sf, best_idx, best_dist);
 }

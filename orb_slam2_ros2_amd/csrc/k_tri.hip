@@ -155,30 +155,46 @@ __device__ __forceinline__ float line_dist(float lx, float ly, const float* F, f
   return (float)fabs(dot) / sqrtf(prm[0] * prm[0] + prm[1] * prm[1]);
 }
 
-__global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ up, const TriKf* __restrict__ kfs, TriParams P,
+// Where a keyframe's own arrays are: behind the call's upload (TriKf: orbfe_create_new_map_points) or where the keyframe store keeps
+// them (TriKfStored: orbfe_create_new_map_points_stored).  The kernels are templates over the record and otherwise ONE text; the flags,
+// the unprocessed points and the scale factors are in the upload in both forms.
+#define TRI_KF_ARRAY(name, T, off, ptr)                                                                               \
+  __device__ __forceinline__ const T* name(const uint8_t* up, const TriKf& K) { return (const T*)(up + K.off); }      \
+  __device__ __forceinline__ const T* name(const uint8_t*, const TriKfStored& K) { return (const T*)K.ptr; }
+TRI_KF_ARRAY(kf_kps, orbfe_keypoint, o_kps, kps)
+TRI_KF_ARRAY(kf_desc, uint8_t, o_desc, desc)
+TRI_KF_ARRAY(kf_nodes, uint32_t, o_nodes, nodes)
+TRI_KF_ARRAY(kf_offs, int32_t, o_offs, offs)
+TRI_KF_ARRAY(kf_feat, uint32_t, o_feat, feat)
+TRI_KF_ARRAY(kf_depth, double, o_depth, depth)
+TRI_KF_ARRAY(kf_ru, double, o_ru, ru)
+#undef TRI_KF_ARRAY
+
+template <class KF>
+__global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ up, const KF* __restrict__ kfs, TriParams P,
                                                    TriSlot* __restrict__ slots, int32_t* __restrict__ cnt) {
   const int lane = threadIdx.x & 63;
   const int nbi = blockIdx.y;
-  const TriKf& C = kfs[0];
-  const TriKf& B = kfs[1 + nbi];
+  const KF& C = kfs[0];
+  const KF& B = kfs[1 + nbi];
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= B.n_feat) return;
   TriSlot out = {-1, 0, nbi, 0, 0, {0.f, 0.f, 0.f}};
   const uint8_t* fl_c = up + C.o_flags;
   const uint8_t* fl_b = up + B.o_flags;
-  const uint32_t pk = ((const uint32_t*)(up + B.o_feat))[j];
+  const uint32_t pk = kf_feat(up, B)[j];
   int k = -1;
   if (!B.skip && (fl_b[pk] & 3) != 3) {
     // the entry's node: the last i with offs[i] <= j
-    const int32_t* ob = (const int32_t*)(up + B.o_offs);
+    const int32_t* ob = kf_offs(up, B);
     int lo = 0, hi = B.n_nodes - 1;
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
       if (ob[mid] <= j) lo = mid;
       else hi = mid - 1;
     }
-    const uint32_t node = ((const uint32_t*)(up + B.o_nodes))[lo];
-    const uint32_t* nc = (const uint32_t*)(up + C.o_nodes);
+    const uint32_t node = kf_nodes(up, B)[lo];
+    const uint32_t* nc = kf_nodes(up, C);
     int a = 0, e = C.n_nodes;
     while (a < e) {
       const int mid = (a + e) >> 1;
@@ -188,10 +204,10 @@ __global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ u
     if (a < C.n_nodes && nc[a] == node) k = a;
   }
   if (k >= 0) {
-    const int32_t* oc = (const int32_t*)(up + C.o_offs);
-    const uint32_t* fc = (const uint32_t*)(up + C.o_feat);
-    const uint8_t* dc = up + C.o_desc;
-    const uint8_t* qd = up + B.o_desc + (size_t)pk * 32;
+    const int32_t* oc = kf_offs(up, C);
+    const uint32_t* fc = kf_feat(up, C);
+    const uint8_t* dc = kf_desc(up, C);
+    const uint8_t* qd = kf_desc(up, B) + (size_t)pk * 32;
     const uint4 a0 = *(const uint4*)qd, a1 = *(const uint4*)(qd + 16);
     const int begin = oc[k], end = oc[k + 1];
     Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
@@ -214,8 +230,8 @@ __global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ u
     const float ratio = (float)b.min_d / (float)b.second;
     if (ncand > 0 && !(b.min_d > TRI_MIN_TH || ratio > TRI_RATIO)) {
       const int q = b.min_idx;
-      const orbfe_keypoint k1 = ((const orbfe_keypoint*)(up + C.o_kps))[q];
-      const orbfe_keypoint k2 = ((const orbfe_keypoint*)(up + B.o_kps))[pk];
+      const orbfe_keypoint k1 = kf_kps(up, C)[q];
+      const orbfe_keypoint k2 = kf_kps(up, B)[pk];
       const float* sf = (const float*)(up + P.o_sf);
       // the mutual epipolar test
       float T21[16], T12[16], F21[9], F12[9];
@@ -228,12 +244,12 @@ __global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ u
       if (!(line_dist(k2.x, k2.y, F21, k1.x, k1.y) > th1) && !(line_dist(k1.x, k1.y, F12, k2.x, k2.y) > th2)) {
         out.q = q;
         out.t = (int32_t)pk;
-        const double dep1 = ((const double*)(up + C.o_depth))[q], dep2 = ((const double*)(up + B.o_depth))[pk];
+        const double dep1 = kf_depth(up, C)[q], dep2 = kf_depth(up, B)[pk];
         const float c0 = cos_theta(C.Tcw, B.Tcw, k1.x, k1.y, k2.x, k2.y, P);
         float c1 = 1.f, c2 = 1.f;
         const bool st1 = dep1 > 0, st2 = dep2 > 0;
-        if (st1) c1 = cos_theta(nullptr, nullptr, k1.x, k1.y, (float)((const double*)(up + C.o_ru))[q], k1.y, P);
-        if (st2) c2 = cos_theta(nullptr, nullptr, k2.x, k2.y, (float)((const double*)(up + B.o_ru))[pk], k2.y, P);
+        if (st1) c1 = cos_theta(nullptr, nullptr, k1.x, k1.y, (float)kf_ru(up, C)[q], k1.y, P);
+        if (st2) c2 = cos_theta(nullptr, nullptr, k2.x, k2.y, (float)kf_ru(up, B)[pk], k2.y, P);
         const float cst = c2 < c1 ? c2 : c1;  // std::min(c1, c2)
         V3 p = {0.f, 0.f, 0.f};
         if (c0 < cst && c0 > 0 && (st1 || st2 || (double)c0 < 0.9998)) {
@@ -299,7 +315,8 @@ __global__ __launch_bounds__(256) void k_tri_fill(const TriSlot* __restrict__ sl
   list[off[x.q] + pos] = s;
 }
 
-__global__ __launch_bounds__(256) void k_tri_resolve(const uint8_t* __restrict__ up, const TriKf* __restrict__ kfs, TriParams P,
+template <class KF>
+__global__ __launch_bounds__(256) void k_tri_resolve(const uint8_t* __restrict__ up, const KF* __restrict__ kfs, TriParams P,
                                                      const TriSlot* __restrict__ slots, const int32_t* __restrict__ off,
                                                      int32_t* __restrict__ list, int32_t* __restrict__ acc, int32_t* __restrict__ tail_flag,
                                                      uint8_t* __restrict__ consumed) {
@@ -333,7 +350,7 @@ __global__ __launch_bounds__(256) void k_tri_resolve(const uint8_t* __restrict__
   consumed[q] = (up[P.o_unproc + q] != 0 && !unproc) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(TRI_SCAN_WG) void k_tri_compact(const TriKf* __restrict__ kfs, TriParams P, const TriSlot* __restrict__ slots,
+__global__ __launch_bounds__(TRI_SCAN_WG) void k_tri_compact(TriParams P, const TriSlot* __restrict__ slots,
                                                              int32_t* __restrict__ acc, int32_t* __restrict__ tail_flag, int32_t* __restrict__ pos,
                                                              int32_t* __restrict__ hdr, TriRec* __restrict__ recs, int32_t* __restrict__ tail) {
   __shared__ int32_t s_w[TRI_SCAN_WG / 64];
@@ -360,14 +377,26 @@ __global__ __launch_bounds__(TRI_SCAN_WG) void k_tri_compact(const TriKf* __rest
   if (threadIdx.x == 0) hdr[1] = pos[P.n_cur];
 }
 
+template <class KF>
+void launch_tri_t(hipStream_t st, const uint8_t* up, const KF* kfs, const TriParams& P, int max_feat, TriSlot* slots, int32_t* cnt, int32_t* off,
+                  int32_t* fill, int32_t* list, int32_t* acc, int32_t* tail_flag, int32_t* pos, int32_t* hdr, TriRec* recs, int32_t* tail,
+                  uint8_t* consumed) {
+  if (P.n_nb > 0 && max_feat > 0) k_tri_match<KF><<<dim3((max_feat + 3) / 4, P.n_nb), 256, 0, st>>>(up, kfs, P, slots, cnt);
+  k_tri_scan<<<1, TRI_SCAN_WG, 0, st>>>(cnt, P.n_cur, off);
+  if (P.n_slots > 0) k_tri_fill<<<(P.n_slots + 255) / 256, 256, 0, st>>>(slots, P.n_slots, off, fill, list);
+  if (P.n_cur > 0) k_tri_resolve<KF><<<(P.n_cur + 255) / 256, 256, 0, st>>>(up, kfs, P, slots, off, list, acc, tail_flag, consumed);
+  k_tri_compact<<<1, TRI_SCAN_WG, 0, st>>>(P, slots, acc, tail_flag, pos, hdr, recs, tail);
+}
+
 }  // namespace
 
 void launch_tri(hipStream_t st, const uint8_t* up, const TriKf* kfs, const TriParams& P, int max_feat, TriSlot* slots, int32_t* cnt,
                 int32_t* off, int32_t* fill, int32_t* list, int32_t* acc, int32_t* tail_flag, int32_t* pos, int32_t* hdr, TriRec* recs,
                 int32_t* tail, uint8_t* consumed) {
-  if (P.n_nb > 0 && max_feat > 0) k_tri_match<<<dim3((max_feat + 3) / 4, P.n_nb), 256, 0, st>>>(up, kfs, P, slots, cnt);
-  k_tri_scan<<<1, TRI_SCAN_WG, 0, st>>>(cnt, P.n_cur, off);
-  if (P.n_slots > 0) k_tri_fill<<<(P.n_slots + 255) / 256, 256, 0, st>>>(slots, P.n_slots, off, fill, list);
-  if (P.n_cur > 0) k_tri_resolve<<<(P.n_cur + 255) / 256, 256, 0, st>>>(up, kfs, P, slots, off, list, acc, tail_flag, consumed);
-  k_tri_compact<<<1, TRI_SCAN_WG, 0, st>>>(kfs, P, slots, acc, tail_flag, pos, hdr, recs, tail);
+  launch_tri_t(st, up, kfs, P, max_feat, slots, cnt, off, fill, list, acc, tail_flag, pos, hdr, recs, tail, consumed);
+}
+void launch_tri(hipStream_t st, const uint8_t* up, const TriKfStored* kfs, const TriParams& P, int max_feat, TriSlot* slots, int32_t* cnt,
+                int32_t* off, int32_t* fill, int32_t* list, int32_t* acc, int32_t* tail_flag, int32_t* pos, int32_t* hdr, TriRec* recs,
+                int32_t* tail, uint8_t* consumed) {
+  launch_tri_t(st, up, kfs, P, max_feat, slots, cnt, off, fill, list, acc, tail_flag, pos, hdr, recs, tail, consumed);
 }

@@ -319,3 +319,29 @@ struct FuseParams {
   float th, ratio;
   int32_t dist_threshold, n_kf, n_cur;
 };
+
+// ---- keyframes resident on the device (k_kfstore.hip, orbfe_kfstore.hip) -----------------------------------------------------------
+// One insertion: the source arrays (an extraction slot's, or the entry's own after a host upload), the entry's arrays, the grid's size.
+struct KfPack {
+  const orbfe_keypoint* s_kps;
+  const uint8_t* s_desc;
+  const double *s_depth, *s_right_u;  // nullptr: -1 everywhere
+  orbfe_keypoint* kps;
+  uint8_t* desc;
+  double *depth, *right_u;
+  int32_t *cell_off, *cell_feat;
+  int32_t n, rows, cols, in_lds;
+  int32_t n_copy;  // workgroups that copy (0: the features are in place, only the grid is built)
+};
+// TriKf of a STORED keyframe: the keyframe's own arrays where the store keeps them, its flags at o_flags of the call's upload.
+struct TriKfStored {
+  const orbfe_keypoint* kps;
+  const uint8_t* desc;
+  const uint32_t* nodes;
+  const int32_t* offs;
+  const uint32_t* feat;
+  const double *depth, *ru;
+  uint32_t o_flags;
+  int32_t n, n_nodes, n_feat, slot0, skip, pad;
+  float Tcw[16], Twc[16];
+};

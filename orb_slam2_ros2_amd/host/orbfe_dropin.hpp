@@ -491,6 +491,11 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
     descRows(f->mvLeftDescriptor, t.desc);
     t.bounds[0] = f->mfMinU, t.bounds[1] = f->mfMaxU, t.bounds[2] = f->mfMinV, t.bounds[3] = f->mfMaxV;
   }
+  // the undistorted bounds alone (orbfe_kfstore_dropin.hpp: a keyframe whose features are already on the device)
+  template <class FramePtr>
+  static void bounds(FramePtr f, float b[4]) {
+    b[0] = f->mfMinU, b[1] = f->mfMaxU, b[2] = f->mfMinV, b[3] = f->mfMaxV;
+  }
   struct Queries {
     std::vector<int> who;
     std::vector<float> uv, radius;

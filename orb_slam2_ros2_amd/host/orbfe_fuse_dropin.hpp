@@ -69,6 +69,33 @@ void flatten(FramePtr f, FlatKf& o, int& n_levels) {
   for (const auto& kp : o.t.kps) n_levels = std::max(n_levels, kp.octave + 1);
 }
 
+// The batch call behind fuseIntoKeyframes as an object: prepare() takes the keyframes of one batch and returns the number of pyramid
+// levels the scale factors must cover, run() makes the device call.  This one uploads every keyframe's features with the call
+// (orbfe_fuse_into_keyframes); orbfe_kfstore_dropin.hpp has the one over keyframes resident in a store.
+struct UploadSearch {
+  FlatKf fc;
+  std::vector<FlatKf> ft;
+  std::vector<orbfe_fuse_kf> tk;
+  template <class KeyFramePtr>
+  int prepare(KeyFramePtr cur, const KeyFramePtr* targets, size_t K) {
+    int n_levels = 1;
+    ft.assign(K, FlatKf());
+    tk.resize(K);
+    flatten(cur, fc, n_levels);
+    for (size_t k = 0; k < K; ++k) {
+      flatten(targets[k], ft[k], n_levels);
+      tk[k] = ft[k].kf;
+    }
+    return n_levels;
+  }
+  orbfe_status run(orbfe_ctx* ctx, const orbfe_fuse_points* pts, const float* z, const orbfe_camera* cam, float bl, const float* sf, int n_levels,
+                   float ratio, int32_t* bestIdx, int32_t* bestDist, uint8_t* visible) {
+    return orbfe_fuse_into_keyframes(ctx, &fc.kf, pts, (int32_t)tk.size(), tk.data(), z, cam, bl, sf, n_levels, 3.0f, ratio,
+                                     orbfe::ORBMatcher::mnMinThreshold, bestIdx, bestDist, visible);
+  }
+  static const char* name() { return "orbfe_fuse_into_keyframes"; }
+};
+
 }  // namespace fuse_detail
 
 // what the last fuseIntoKeyframes / fuseMapPoints of the calling thread did per (target, live slot): took the batch's visibility flag, or
@@ -78,8 +105,9 @@ inline long long fuseReevaluations() { return fuse_detail::counters().reevaluate
 inline int fuseLastCount() { return fuse_detail::counters().nFuse; }
 
 // `for (auto& pkf : targets) nFuseInv += matcher.fuse(pkf, cur, map);` (src/LocalMapping.cc:401-402) in the given order -> nFuseInv
-template <class CameraT, class FrameT, class KeyFramePtr, class MapPtr>
-int fuseIntoKeyframes(KeyFramePtr cur, const std::vector<KeyFramePtr>& targets, MapPtr map, float mfRatio = 0.6f) {
+// (search: fuse_detail::UploadSearch or an object of its shape)
+template <class CameraT, class FrameT, class KeyFramePtr, class MapPtr, class Search>
+int fuseIntoKeyframes(KeyFramePtr cur, const std::vector<KeyFramePtr>& targets, MapPtr map, float mfRatio, Search& search) {
   typedef typename std::decay<decltype(cur->getMapPoints())>::type MapPoints;
   typedef typename MapPoints::value_type MapPointPtr;
   typedef typename std::decay<decltype(*std::declval<MapPointPtr>())>::type MapPointT;
@@ -91,17 +119,9 @@ int fuseIntoKeyframes(KeyFramePtr cur, const std::vector<KeyFramePtr>& targets, 
     const MapPoints atCall = cur->getMapPoints();
     const size_t n = atCall.size();
     if (!n) break;
-    int n_levels = 1;
-    fuse_detail::FlatKf fc;
-    std::vector<fuse_detail::FlatKf> ft(K);
-    fuse_detail::flatten(cur, fc, n_levels);
-    std::vector<orbfe_fuse_kf> tk(K);
+    const int n_levels = search.prepare(cur, targets.data() + k0, K);
     std::vector<float> z(K);
-    for (size_t k = 0; k < K; ++k) {
-      fuse_detail::flatten(targets[k0 + k], ft[k], n_levels);
-      tk[k] = ft[k].kf;
-      z[k] = fuse_detail::tlcZ(targets[k0 + k], cur);
-    }
+    for (size_t k = 0; k < K; ++k) z[k] = fuse_detail::tlcZ(targets[k0 + k], cur);
     std::vector<uint8_t> has(n, 0);
     std::vector<float> pos(3 * n, 0.f), view(3 * n, 0.f), mx(n, 0.f), mn(n, 0.f);
     for (size_t i = 0; i < n; ++i) {
@@ -120,9 +140,8 @@ int fuseIntoKeyframes(KeyFramePtr cur, const std::vector<KeyFramePtr>& targets, 
     std::vector<int32_t> bestIdx(K * n), bestDist(K * n);
     std::vector<uint8_t> visible(K * n);
     orbfe_ctx* ctx = matcherContext();
-    const orbfe_status st = orbfe_fuse_into_keyframes(ctx, &fc.kf, &pts, (int32_t)K, tk.data(), z.data(), &cam, CameraT::mfBl, sf.data(), n_levels, 3.0f,
-                                                      mfRatio, orbfe::ORBMatcher::mnMinThreshold, bestIdx.data(), bestDist.data(), visible.data());
-    if (st != ORBFE_OK) throw std::runtime_error(std::string("orbfe_fuse_into_keyframes: ") + orbfe_last_error(ctx));
+    const orbfe_status st = search.run(ctx, &pts, z.data(), &cam, CameraT::mfBl, sf.data(), n_levels, mfRatio, bestIdx.data(), bestDist.data(), visible.data());
+    if (st != ORBFE_OK) throw std::runtime_error(std::string(Search::name()) + ": " + orbfe_last_error(ctx));
     // the replay: per target in order, the match list from the live slots, then processFuseMps' policy (src/ORBMatcher.cc:623-663, bLoop
     // false) on the reference's own objects, remembering which point survived a replace
     std::unordered_set<MapPointPtr> survived;
@@ -173,9 +192,15 @@ int fuseIntoKeyframes(KeyFramePtr cur, const std::vector<KeyFramePtr>& targets, 
   return nFuseInv;
 }
 
-// void LocalMapping::fuseMapPoints()  (src/LocalMapping.cc:352-405)
 template <class CameraT, class FrameT, class KeyFramePtr, class MapPtr>
-void fuseMapPoints(KeyFramePtr mpCurrKeyFrame, MapPtr mpMap) {
+int fuseIntoKeyframes(KeyFramePtr cur, const std::vector<KeyFramePtr>& targets, MapPtr map, float mfRatio = 0.6f) {
+  fuse_detail::UploadSearch search;
+  return fuseIntoKeyframes<CameraT, FrameT>(cur, targets, map, mfRatio, search);
+}
+
+// void LocalMapping::fuseMapPoints()  (src/LocalMapping.cc:352-405); search: the batch call of its inverse fuses (see above)
+template <class CameraT, class FrameT, class KeyFramePtr, class MapPtr, class Search>
+void fuseMapPoints(KeyFramePtr mpCurrKeyFrame, MapPtr mpMap, Search& search) {
   typedef typename std::decay<decltype(mpCurrKeyFrame->getMapPoints())>::type::value_type MapPointPtr;
   typedef typename std::decay<decltype(*mpCurrKeyFrame)>::type KeyFrameT;
   std::unordered_set<KeyFramePtr> sTargetKfs;
@@ -214,9 +239,14 @@ void fuseMapPoints(KeyFramePtr mpCurrKeyFrame, MapPtr mpMap) {
   const float mfRatio = 0.6f;
   const int nFuse = fuse(mpCurrKeyFrame, vTargetMps, mpMap, false, 3.0f, mfRatio, ORB_SLAM2_ROS2::ORBExtractor::mnLevels);
   const std::vector<KeyFramePtr> targets(sTargetKfs.begin(), sTargetKfs.end());
-  fuseIntoKeyframes<CameraT, FrameT>(mpCurrKeyFrame, targets, mpMap, mfRatio);
+  fuseIntoKeyframes<CameraT, FrameT>(mpCurrKeyFrame, targets, mpMap, mfRatio, search);
   fuse_detail::counters().nFuse += nFuse;
   KeyFrameT::updateConnections(mpCurrKeyFrame);
+}
+template <class CameraT, class FrameT, class KeyFramePtr, class MapPtr>
+void fuseMapPoints(KeyFramePtr mpCurrKeyFrame, MapPtr mpMap) {
+  fuse_detail::UploadSearch search;
+  fuseMapPoints<CameraT, FrameT>(mpCurrKeyFrame, mpMap, search);
 }
 
 }  // namespace dropin

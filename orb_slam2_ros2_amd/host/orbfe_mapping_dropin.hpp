@@ -73,11 +73,43 @@ void flatten(const KeyFramePtr& pkf, Flat& f, int& n_levels) {
   f.kf.right_u = f.right_u.data();
 }
 
+// cur's entries of mmUnprocessMps as the call wants them
+struct Unprocessed {
+  std::vector<uint8_t> flag;
+  std::vector<float> pos;
+};
+
+// The device call behind createNewMapPoints as an object: prepare() takes the current keyframe and its neighbours and returns the number
+// of pyramid levels the scale factors must cover, run() makes the call.  This one uploads every keyframe's arrays with the call
+// (orbfe_create_new_map_points); orbfe_kfstore_dropin.hpp has the one over keyframes resident in a store.
+struct UploadCall {
+  std::vector<Flat> flat;
+  std::vector<orbfe_tri_kf> nbk;
+  template <class KeyFramePtr>
+  int prepare(const KeyFramePtr& cur, const std::vector<KeyFramePtr>& nbs) {
+    int n_levels = 1;
+    flat.assign(nbs.size() + 1, Flat());
+    flatten(cur, flat[0], n_levels);
+    for (size_t i = 0; i < nbs.size(); ++i) flatten(nbs[i], flat[i + 1], n_levels);
+    return n_levels;
+  }
+  orbfe_status run(orbfe_ctx* ctx, const Unprocessed& un, const orbfe_camera* cam, const float* k_inv, float bl, const float* sf, int n_levels,
+                   orbfe_tri_record* recs, int64_t cap, int64_t* n_rec, int32_t* tail, int64_t* n_tail, uint8_t* consumed) {
+    flat[0].kf.unproc = un.flag.data();
+    flat[0].kf.unproc_pos = un.pos.data();
+    nbk.clear();
+    for (size_t i = 1; i < flat.size(); ++i) nbk.push_back(flat[i].kf);
+    return orbfe_create_new_map_points(ctx, &flat[0].kf, (int32_t)nbk.size(), nbk.data(), cam, k_inv, bl, sf, n_levels, recs, cap, n_rec, tail, cap,
+                                       n_tail, consumed);
+  }
+  static const char* name() { return "orbfe_create_new_map_points"; }
+};
+
 }  // namespace tri_detail
 
-// void LocalMapping::createNewMapPoints()  (src/LocalMapping.cc:165-285)
-template <class CameraT, class FrameT, class KeyFramePtr, class UnprocessMps, class MapPtr, class MapPointList>
-void createNewMapPoints(KeyFramePtr curKf, UnprocessMps& mmUnprocessMps, MapPtr map, MapPointList& mlpAddedMPs) {
+// void LocalMapping::createNewMapPoints()  (src/LocalMapping.cc:165-285); call: tri_detail::UploadCall or an object of its shape
+template <class CameraT, class FrameT, class KeyFramePtr, class UnprocessMps, class MapPtr, class MapPointList, class Call>
+void createNewMapPoints(KeyFramePtr curKf, UnprocessMps& mmUnprocessMps, MapPtr map, MapPointList& mlpAddedMPs, Call& call) {
   typedef typename UnprocessMps::mapped_type MapPointPtr;
   // loop 1's neighbour selection: the std::map<KeyFrame::SharedPtr, ..> dedups and orders (T2); the baseline test is the call's (T7)
   std::map<KeyFramePtr, int> chosen;
@@ -85,23 +117,17 @@ void createNewMapPoints(KeyFramePtr curKf, UnprocessMps& mmUnprocessMps, MapPtr 
     if (pKf && !pKf->isBad()) chosen.emplace(pKf, 0);
   std::vector<KeyFramePtr> nbs;
   for (const auto& it : chosen) nbs.push_back(it.first);
-  int n_levels = 1;
-  std::vector<tri_detail::Flat> flat(nbs.size() + 1);
-  tri_detail::flatten(curKf, flat[0], n_levels);
-  for (size_t i = 0; i < nbs.size(); ++i) tri_detail::flatten(nbs[i], flat[i + 1], n_levels);
-  const size_t n = flat[0].kps.size();
-  flat[0].unproc.assign(n, 0);
-  flat[0].unproc_pos.assign(3 * n, 0.f);
+  const int n_levels = call.prepare(curKf, nbs);
+  const size_t n = curKf->getLeftKeyPoints().size();
+  tri_detail::Unprocessed un;
+  un.flag.assign(n, 0);
+  un.pos.assign(3 * n, 0.f);
   for (const auto& item : mmUnprocessMps) {
     if (item.first >= n || !item.second) continue;
     const cv::Mat p = item.second->getPos();
-    flat[0].unproc[item.first] = 1;
-    for (int a = 0; a < 3; ++a) flat[0].unproc_pos[3 * item.first + a] = p.template at<float>(a);
+    un.flag[item.first] = 1;
+    for (int a = 0; a < 3; ++a) un.pos[3 * item.first + a] = p.template at<float>(a);
   }
-  flat[0].kf.unproc = flat[0].unproc.data();
-  flat[0].kf.unproc_pos = flat[0].unproc_pos.data();
-  std::vector<orbfe_tri_kf> nbk;
-  for (size_t i = 1; i < flat.size(); ++i) nbk.push_back(flat[i].kf);
   std::vector<float> sf((size_t)n_levels);
   for (int l = 0; l < n_levels; ++l) sf[(size_t)l] = FrameT::getScaledFactor(l);
   float k_inv[9];
@@ -114,10 +140,9 @@ void createNewMapPoints(KeyFramePtr curKf, UnprocessMps& mmUnprocessMps, MapPtr 
   std::vector<uint8_t> consumed(n);
   int64_t n_rec = 0, n_tail = 0;
   orbfe_ctx* ctx = matcherContext();
-  const orbfe_status st = orbfe_create_new_map_points(ctx, &flat[0].kf, (int32_t)nbk.size(), nbk.data(), &cam, k_inv, CameraT::mfBl, sf.data(),
-                                                      n_levels, recs.data(), (int64_t)n, &n_rec, tail.data(), (int64_t)n, &n_tail,
-                                                      consumed.data());
-  if (st != ORBFE_OK) throw std::runtime_error(std::string("orbfe_create_new_map_points: ") + orbfe_last_error(ctx));
+  const orbfe_status st = call.run(ctx, un, &cam, k_inv, CameraT::mfBl, sf.data(), n_levels, recs.data(), (int64_t)n, &n_rec, tail.data(), &n_tail,
+                                   consumed.data());
+  if (st != ORBFE_OK) throw std::runtime_error(std::string(Call::name()) + ": " + orbfe_last_error(ctx));
   // loop 2, applied in processing order with the reference's own calls (LocalMapping.cc:248-262)
   for (int64_t r = 0; r < n_rec; ++r) {
     const orbfe_tri_record& x = recs[(size_t)r];
@@ -152,6 +177,11 @@ void createNewMapPoints(KeyFramePtr curKf, UnprocessMps& mmUnprocessMps, MapPtr 
     map->insertMapPoint(item.second, map);
     mlpAddedMPs.push_back(item.second);
   }
+}
+template <class CameraT, class FrameT, class KeyFramePtr, class UnprocessMps, class MapPtr, class MapPointList>
+void createNewMapPoints(KeyFramePtr curKf, UnprocessMps& mmUnprocessMps, MapPtr map, MapPointList& mlpAddedMPs) {
+  tri_detail::UploadCall call;
+  createNewMapPoints<CameraT, FrameT>(curKf, mmUnprocessMps, map, mlpAddedMPs, call);
 }
 
 }  // namespace dropin
