@@ -1,7 +1,7 @@
 // k_lba.hip -- the linear algebra of one Levenberg-Marquardt trial of the local bundle adjustment, on the device.
 //
 // Replaces what g2o runs inside optimizer.optimize() under Optimizer::OptimizeLocalMap (src/ORB_SLAM2/src/Optimizer.cc:336,361)
-// once the normal-equation blocks exist (k_ba.hip): BlockSolver_6_3::setLambda / solve with marginalised points
+// once the normal-equation blocks exist (k_lm.hip's builders): BlockSolver_6_3::setLambda / solve with marginalised points
 // (g2o core/block_solver.hpp: lambda on both diagonals, Hll^-1 per point, Schur complement Hpp - Hpl Hll^-1 Hpl^T,
 // reduced right-hand side, back-substitution), the LLT of the reduced system (solvers/eigen/linear_solver_eigen.h, here a
 // dense Cholesky by one workgroup), SparseOptimizer::update (VertexSE3Expmap / VertexPointXYZ oplus) and the scalars the
@@ -10,8 +10,8 @@
 // vertex ids and a <= 1024-row triangular factorisation are not dense contractions worth MFMA tiles.
 #include <hip/hip_runtime.h>
 
+#include "ba_edge_dev.h"
 #include "orbfe_internal.h"
-#include "se3_dev.h"
 
 namespace orbfe {
 
@@ -64,34 +64,19 @@ __global__ __launch_bounds__(1024) void k_lba_maxdiag(int n_poses, int n_points,
   if (threadIdx.x == 0) out[0] = r;
 }
 
-// (Hll + lambda I)^-1 per point (Eigen's 3x3 inverse: cofactors / determinant)
+// (Hll + lambda I)^-1 per point (inv3_damped)
 __global__ __launch_bounds__(256) void k_lba_point_inv(int n_points, const double* __restrict__ Hll, const double* __restrict__ lambda_p,
                                                        double* __restrict__ Dinv, int* __restrict__ ok) {
 #pragma clang fp contract(off)
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n_points) return;
-  const double lambda = lambda_p[0];
-  double M[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) M[i] = Hll[(size_t)p * 9 + i];
-  M[0] += lambda, M[4] += lambda, M[8] += lambda;
-  const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
-  const double det = M[0] * c00 + M[1] * c01 + M[2] * c02;
-  if (det == 0 || !isfinite(det)) {
+  double D[9];
+  if (!inv3_damped(Hll + (size_t)p * 9, lambda_p[0], D)) {
     *ok = 0;
     return;
   }
-  const double id = 1.0 / det;
-  double* R = Dinv + (size_t)p * 9;
-  R[0] = c00 * id;
-  R[1] = (M[2] * M[7] - M[1] * M[8]) * id;
-  R[2] = (M[1] * M[5] - M[2] * M[4]) * id;
-  R[3] = c01 * id;
-  R[4] = (M[0] * M[8] - M[2] * M[6]) * id;
-  R[5] = (M[2] * M[3] - M[0] * M[5]) * id;
-  R[6] = c02 * id;
-  R[7] = (M[1] * M[6] - M[0] * M[7]) * id;
-  R[8] = (M[0] * M[4] - M[1] * M[3]) * id;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) Dinv[(size_t)p * 9 + i] = D[i];
 }
 
 // W(e) = Hpl(e) * Dinv(point(e))   (6x3 per edge; zero for edges of fixed poses because their Hpl is zero)
@@ -446,8 +431,7 @@ __global__ __launch_bounds__(256) void k_lba_classify(int n_edges, const double*
                                                       double* __restrict__ info_eff, double* __restrict__ delta_eff) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= n_edges) return;
-  const double th = is_stereo[e] ? 7.815 : 5.991;
-  if (chi2_last[e] > th || !depth_pos[e]) {
+  if (ba_edge_outlier(chi2_last[e], is_stereo[e] != 0, depth_pos[e] != 0)) {
     level[e] = 1;
     info_eff[e] = 0.0;
   }
@@ -459,7 +443,7 @@ __global__ __launch_bounds__(256) void k_lba_final(int n_edges, const double* __
                                                    const uint8_t* __restrict__ is_stereo, uint8_t* __restrict__ bad) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= n_edges) return;
-  bad[e] = (chi2[e] > (is_stereo[e] ? 7.815 : 5.991) || !depth_pos[e]) ? 1 : 0;
+  bad[e] = ba_edge_outlier(chi2[e], is_stereo[e] != 0, depth_pos[e] != 0) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -24,8 +24,8 @@
 // fp64 matrix cores, gated by the same state record.
 #include <hip/hip_runtime.h>
 
+#include "ba_edge_dev.h"
 #include "orbfe_internal.h"
-#include "se3_dev.h"
 #include "wave_ops.h"
 
 namespace orbfe {
@@ -49,29 +49,12 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {  // fixe
   return r;
 }
 
-// The estimates, the edge terms and the normal-equation blocks exist twice: [cur] = the current estimate and its system,
-// [cur ^ 1] = the trial's.  `which` = 0: work on cur, 1: on cur ^ 1.
-struct LmBuffers {
-  double* poses[2];
-  double* points[2];
-  double* terms[2];   // [E][LM_TERM]
-  double* Hpl[2];     // [E][18]
-  double* Hpp[2];     // [NK][36]
-  double* bp[2];      // [NK][6]
-  double* Hll[2];     // [NP][9]
-  double* bl[2];      // [NP][3]
-  double* chi_part[2];  // per linearize block: sum of rho(chi2) over its active edges
-};
-
 __device__ __forceinline__ bool lm_gate(const LmState* st, int gate) {
   // gate 0: always | 1: run_step | 2: run_switch | 3: run_final
   if (gate == 0) return true;
   const volatile int32_t* p = gate == 1 ? &st->run_step : (gate == 2 ? &st->run_switch : &st->run_final);
   return *p != 0;
 }
-
-// (fixed tree over the 64 lanes by data-parallel-primitive moves: wave_ops.h)
-__device__ __forceinline__ double wave_sum_fixed(double v) { return wave_sum_f64(v); }
 
 __device__ void lm_ctrl_body(LmState* __restrict__ st, const LmBuffers& B, int mode, int chi_blocks, int scale_blocks,
                              const double* __restrict__ scale_part, const volatile uint8_t* __restrict__ abort_flag);
@@ -88,87 +71,22 @@ __device__ __forceinline__ double lm_linearize_edge(int e, int buf, const LmBuff
   double r0 = 0.0;
   const int kp = edge_pose[e];
   const double* T = B.poses[buf] + (size_t)kp * 7;
-  const double* X = B.points[buf] + (size_t)pt * 3;
-  const double qx = T[0], qy = T[1], qz = T[2], qw = T[3];
-  const double X0 = X[0], X1 = X[1], X2 = X[2];
-  double uvx = qy * X2 - qz * X1, uvy = qz * X0 - qx * X2, uvz = qx * X1 - qy * X0;
-  uvx += uvx;
-  uvy += uvy;
-  uvz += uvz;
-  const double x = X0 + qw * uvx + (qy * uvz - qz * uvy) + T[4];
-  const double y = X1 + qw * uvy + (qz * uvx - qx * uvz) + T[5];
-  const double z = X2 + qw * uvz + (qx * uvy - qy * uvx) + T[6];
+  double p[3], err[3], rr0, r1, Bm[18];
+  se3_map(T, T + 4, B.points[buf] + (size_t)pt * 3, p);
   const bool stq = is_stereo[e] != 0;
-  const double fx = prm.fx, fy = prm.fy, cx = prm.cx, cy = prm.cy, bf = prm.bf;
-  const double* m = meas + (size_t)e * 3;
-  const double u = x / z * fx + cx, v = y / z * fy + cy;
-  const double e0 = m[0] - u, e1 = m[1] - v;
-  const double e2 = stq ? (m[2] - (u - bf / z)) : 0.0;
+  ba_edge_error(p, meas + (size_t)e * 3, stq, prm, err);
+  const double e0 = err[0], e1 = err[1], e2 = err[2];
   const double wi = info[e];
-  const double c2 = stq ? (e0 * (wi * e0) + e1 * (wi * e1) + e2 * (wi * e2)) : (e0 * (wi * e0) + e1 * (wi * e1));
-  // RobustKernelHuber::robustify (delta <= 0: no kernel)
-  const double dl = delta[e];
-  double rr0 = c2, r1 = 1.0;
-  if (dl > 0.0) {
-    const double dsqr = dl * dl;
-    if (c2 > dsqr) {
-      const double sq = sqrt(c2);
-      rr0 = 2 * sq * dl - dsqr;
-      r1 = dl / sq;
-    }
-  }
+  const double c2 = ba_edge_chi2(err, wi, stq);
+  ba_edge_robustify(c2, delta[e], rr0, r1);
   if (level[e] == 0) {  // activeRobustChi2 + the per-edge _error bookkeeping of the ACTIVE edges (g2o evaluates only those)
     r0 = rr0;
     if (write_last) chi2_last[e] = c2;
   }
   const double w = r1 * wi;
   double* t = B.terms[buf] + (size_t)e * LM_TERM;
-  const double z_2 = z * z;
-  const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
-  const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
-  const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
-  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
-  double Bm[18];
-  if (stq) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      A[k] = -fx * R[k] / z + fx * x * R[6 + k] / z_2;
-      A[3 + k] = -fy * R[3 + k] / z + fy * y * R[6 + k] / z_2;
-      A[6 + k] = A[k] - bf * R[6 + k] / z_2;
-    }
-  } else {
-    const double t02 = -x / z * fx, t12 = -y / z * fy, s = -1. / z;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      A[k] = (s * fx) * R[k] + (s * t02) * R[6 + k];
-      A[3 + k] = (s * fy) * R[3 + k] + (s * t12) * R[6 + k];
-      A[6 + k] = 0.0;
-    }
-  }
-  Bm[0] = x * y / z_2 * fx;
-  Bm[1] = -(1 + (x * x / z_2)) * fx;
-  Bm[2] = y / z * fx;
-  Bm[3] = -1. / z * fx;
-  Bm[4] = 0;
-  Bm[5] = x / z_2 * fx;
-  Bm[6] = (1 + y * y / z_2) * fy;
-  Bm[7] = -x * y / z_2 * fy;
-  Bm[8] = -x / z * fy;
-  Bm[9] = 0;
-  Bm[10] = -1. / z * fy;
-  Bm[11] = y / z_2 * fy;
-  if (stq) {
-    Bm[12] = Bm[0] - bf * y / z_2;
-    Bm[13] = Bm[1] + bf * x / z_2;
-    Bm[14] = Bm[2];
-    Bm[15] = Bm[3];
-    Bm[16] = 0;
-    Bm[17] = Bm[5] - bf / z_2;
-  } else {
-#pragma unroll
-    for (int k = 12; k < 18; ++k) Bm[k] = 0.0;
-  }
+  ba_edge_jpoint(T, p, stq, prm, A);
+  ba_edge_jpose(p, stq, prm, Bm);
   const int rows = stq ? 3 : 2;
 #pragma unroll
   for (int k = 0; k < 9; ++k) t[k] = A[k];
@@ -298,7 +216,7 @@ __device__ __forceinline__ void lm_pose_block(int k, int n_poses, int buf, const
   }
 #pragma unroll
   for (int i = 0; i < 42; ++i) {
-    const double v = wave_sum_fixed(acc[i]);
+    const double v = wave_sum_f64(acc[i]);
     if (lane == 0) part[wv][i] = v;
   }
   __syncthreads();
@@ -344,7 +262,7 @@ __global__ __launch_bounds__(1024) void k_lm_maxdiag(int n_poses, int n_points, 
   if (threadIdx.x == 0) st->maxdiag = sh[0];
 }
 
-// per point: Dinv = (Hll + lambda I)^-1 (Eigen's 3x3 inverse: cofactors / determinant), then W(e) = Hpl(e) Dinv for the point's edges.
+// per point: Dinv = (Hll + lambda I)^-1 (inv3_damped), then W(e) = Hpl(e) Dinv for the point's edges.
 // EIGHT lanes per point (each inverts the same block and takes one edge): one dependent chain per lane instead of one per edge.
 // Blocks [pt_blocks, pt_blocks + n_poses): Hpp / bp of the CURRENT system (lm_pose_block).  The pose side of a system is only ever used
 // once its estimate is the current one (k_lm_schur, k_lm_update's scale), so it is not built with the trial's system but here, beside the
@@ -365,27 +283,11 @@ __global__ __launch_bounds__(256) void k_lm_prep(int n_points, int n_poses, int 
   if (p >= n_points) return;
   const int buf = st->cur;
   const double lambda = st->lambda;
-  double M[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) M[i] = B.Hll[buf][(size_t)p * 9 + i];
-  M[0] += lambda, M[4] += lambda, M[8] += lambda;
-  const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
-  const double det = M[0] * c00 + M[1] * c01 + M[2] * c02;
-  if (det == 0 || !isfinite(det)) {
+  double D[9];
+  if (!inv3_damped(B.Hll[buf] + (size_t)p * 9, lambda, D)) {
     if (sub == 0) st->ok = 0;
     return;
   }
-  const double id = 1.0 / det;
-  double D[9];
-  D[0] = c00 * id;
-  D[1] = (M[2] * M[7] - M[1] * M[8]) * id;
-  D[2] = (M[1] * M[5] - M[2] * M[4]) * id;
-  D[3] = c01 * id;
-  D[4] = (M[0] * M[8] - M[2] * M[6]) * id;
-  D[5] = (M[2] * M[3] - M[0] * M[5]) * id;
-  D[6] = c02 * id;
-  D[7] = (M[1] * M[6] - M[0] * M[7]) * id;
-  D[8] = (M[0] * M[4] - M[1] * M[3]) * id;
   if (sub == 0) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) Dinv[(size_t)p * 9 + i] = D[i];
@@ -486,7 +388,7 @@ __global__ __launch_bounds__(64) void k_lm_schur(int nf, LmBuffers B, const LmSt
     }
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
-      const double s = wave_sum_fixed(r[a]);
+      const double s = wave_sum_f64(r[a]);
       if (lane == a) (M ? M[(size_t)ld * ld + 6 * i + a] : rhs[6 * i + a]) = B.bp[buf][(size_t)ki * 6 + a] - s;
     }
     return;
@@ -520,7 +422,7 @@ __global__ __launch_bounds__(64) void k_lm_schur(int nf, LmBuffers B, const LmSt
   double* out = Sblk + (size_t)b * 36;
 #pragma unroll
   for (int k = 0; k < 36; ++k) {
-    const double s = wave_sum_fixed(acc[k]);
+    const double s = wave_sum_f64(acc[k]);
     if (lane == k) {
       double v = -s;
       if (i == j) {
@@ -1139,17 +1041,9 @@ __global__ __launch_bounds__(256) void k_lm_classify(int n_edges, LmBuffers B, c
   if (e >= n_edges) return;
   const int buf = st->cur;
   const double* T = B.poses[buf] + (size_t)edge_pose[e] * 7;
-  const double* X = B.points[buf] + (size_t)edge_point[e] * 3;
-  const double qx = T[0], qy = T[1], qw = T[3];
-  const double X0 = X[0], X1 = X[1], X2 = X[2];
-  double uvx = qy * X2 - T[2] * X1, uvy = T[2] * X0 - qx * X2;
-  uvx += uvx;
-  uvy += uvy;
-  double uvz = qx * X1 - qy * X0;
-  uvz += uvz;
-  const double z = X2 + qw * uvz + (qx * uvy - qy * uvx) + T[6];  // isDepthPositive: (T * X).z > 0
-  const double th = is_stereo[e] ? 7.815 : 5.991;
-  if (chi2_last[e] > th || !(z > 0.0)) {
+  double p[3];
+  se3_map(T, T + 4, B.points[buf] + (size_t)edge_point[e] * 3, p);
+  if (ba_edge_outlier(chi2_last[e], is_stereo[e] != 0, ba_depth_positive(p))) {
     level[e] = 1;
     info_eff[e] = 0.0;
   }
@@ -1170,25 +1064,13 @@ __global__ __launch_bounds__(256) void k_lm_final(int n_edges, int n_poses, int 
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e < n_edges) {
     const double* T = B.poses[buf] + (size_t)edge_pose[e] * 7;
-    const double* X = B.points[buf] + (size_t)edge_point[e] * 3;
-    const double qx = T[0], qy = T[1], qz = T[2], qw = T[3];
-    const double X0 = X[0], X1 = X[1], X2 = X[2];
-    double uvx = qy * X2 - qz * X1, uvy = qz * X0 - qx * X2, uvz = qx * X1 - qy * X0;
-    uvx += uvx;
-    uvy += uvy;
-    uvz += uvz;
-    const double x = X0 + qw * uvx + (qy * uvz - qz * uvy) + T[4];
-    const double y = X1 + qw * uvy + (qz * uvx - qx * uvz) + T[5];
-    const double z = X2 + qw * uvz + (qx * uvy - qy * uvx) + T[6];
+    double p[3], err[3];
+    se3_map(T, T + 4, B.points[buf] + (size_t)edge_point[e] * 3, p);
     const bool stq = is_stereo[e] != 0;
-    const double* m = meas + (size_t)e * 3;
-    const double u = x / z * prm.fx + prm.cx, v = y / z * prm.fy + prm.cy;
-    const double e0 = m[0] - u, e1 = m[1] - v;
-    const double e2 = stq ? (m[2] - (u - prm.bf / z)) : 0.0;
-    const double w = info[e];
-    const double c2 = stq ? (e0 * (w * e0) + e1 * (w * e1) + e2 * (w * e2)) : (e0 * (w * e0) + e1 * (w * e1));
+    ba_edge_error(p, meas + (size_t)e * 3, stq, prm, err);
+    const double c2 = ba_edge_chi2(err, info[e], stq);
     chi2_out[e] = c2;
-    bad[e] = (c2 > (stq ? 7.815 : 5.991) || !(z > 0.0)) ? 1 : 0;
+    bad[e] = ba_edge_outlier(c2, stq, ba_depth_positive(p)) ? 1 : 0;
     level_out[e] = level[e];
   }
   for (int i = e; i < n_poses * 7; i += gridDim.x * 256) poses_out[i] = B.poses[buf][i];
@@ -1199,19 +1081,10 @@ __global__ __launch_bounds__(256) void k_lm_final(int n_edges, int n_poses, int 
 void launch_lm_chol_big(hipStream_t s, const LmLaunch& L);
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-static LmBuffers lm_buffers(const LmLaunch& L) {
-  LmBuffers B;
-  for (int k = 0; k < 2; ++k) {
-    B.poses[k] = L.poses[k], B.points[k] = L.points[k], B.terms[k] = L.terms[k], B.Hpl[k] = L.Hpl[k], B.Hpp[k] = L.Hpp[k], B.bp[k] = L.bp[k];
-    B.Hll[k] = L.Hll[k], B.bl[k] = L.bl[k], B.chi_part[k] = L.chi_part[k];
-  }
-  return B;
-}
-
 // the system of buffer cur ^ which, gated: the point side and, with_poses, the pose side as a launch of its own (inside a trial it
 // rides with k_lm_prep of the NEXT trial instead)
 void launch_lm_build(hipStream_t s, const LmLaunch& L, int gate, int which, int write_last, bool with_poses) {
-  const LmBuffers B = lm_buffers(L);
+  const LmBuffers& B = L.B;
   const int pb = (L.NP + 31) / 32;
   if (pb > 0)
     hipLaunchKernelGGL(k_lm_linpoints, dim3(pb), dim3(256), 0, s, L.NP, B, L.state, gate, which, L.pt_off, L.pt_edges, L.edge_pose, L.meas,
@@ -1227,15 +1100,15 @@ void launch_lm_pairs(hipStream_t s, const LmLaunch& L) {
                      L.pair_table, L.pairs, L.pair_cnt);
 }
 void launch_lm_maxdiag(hipStream_t s, const LmLaunch& L, int gate) {
-  hipLaunchKernelGGL(k_lm_maxdiag, dim3(1), dim3(1024), 0, s, L.NK, L.NP, lm_buffers(L), L.state, gate, L.fixed);
+  hipLaunchKernelGGL(k_lm_maxdiag, dim3(1), dim3(1024), 0, s, L.NK, L.NP, L.B, L.state, gate, L.fixed);
 }
 void launch_lm_ctrl(hipStream_t s, const LmLaunch& L, int mode) {
-  hipLaunchKernelGGL(k_lm_ctrl, dim3(1), dim3(64), 0, s, L.state, lm_buffers(L), mode, (L.NP + 31) / 32, (L.NP + 31) / 32 + (L.NK + 255) / 256, L.scale_part, L.abort_flag,
+  hipLaunchKernelGGL(k_lm_ctrl, dim3(1), dim3(64), 0, s, L.state, L.B, mode, (L.NP + 31) / 32, (L.NP + 31) / 32 + (L.NK + 255) / 256, L.scale_part, L.abort_flag,
                      mode == 4 ? L.state_out : (LmState*)nullptr);
 }
 // one trial: solve + update + the system at the trial estimate (the control step that decides it is the caller's next launch)
 void launch_lm_step(hipStream_t s, const LmLaunch& L) {
-  const LmBuffers B = lm_buffers(L);
+  const LmBuffers& B = L.B;
   const int pb = (L.NP + 31) / 32;
   if (pb + L.NK > 0)
     hipLaunchKernelGGL(k_lm_prep, dim3(pb + L.NK), dim3(256), 0, s, L.NP, L.NK, pb, B, L.state, L.pt_off, L.pt_edges, L.Dinv, L.W, L.fixed, L.ps_off,
@@ -1262,7 +1135,7 @@ void launch_lm_steps(hipStream_t s, const LmLaunch& L, int n) {
   }
 }
 void launch_lm_switch(hipStream_t s, const LmLaunch& L) {
-  const LmBuffers B = lm_buffers(L);
+  const LmBuffers& B = L.B;
   launch_lm_ctrl(s, L, 1);
   if (L.E > 0)
     hipLaunchKernelGGL(k_lm_classify, dim3((L.E + 255) / 256), dim3(256), 0, s, L.E, B, L.state, L.edge_pose, L.edge_point, L.chi2_last, L.is_stereo,
@@ -1272,7 +1145,7 @@ void launch_lm_switch(hipStream_t s, const LmLaunch& L) {
   launch_lm_ctrl(s, L, 2);
 }
 void launch_lm_final(hipStream_t s, const LmLaunch& L) {
-  const LmBuffers B = lm_buffers(L);
+  const LmBuffers& B = L.B;
   launch_lm_ctrl(s, L, 3);
   const int n = std::max(L.E, 1);
   hipLaunchKernelGGL(k_lm_final, dim3((n + 255) / 256), dim3(256), 0, s, L.E, L.NK, L.NP, B, L.state, L.edge_pose, L.edge_point, L.meas, L.is_stereo,

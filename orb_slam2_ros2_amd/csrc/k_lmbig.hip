@@ -18,7 +18,7 @@
 // blocks below it and the rank-16 updates run on the matrix cores) and solves X L^T = A for its own 48 rows by blocked substitution,
 // X_b = (A_b - sum X_c L_bc^T) inv_bb^T, every product an MFMA (a column-at-a-time substitution by one wave was 14 us a tile, the
 // 48-column factorisation 24 us: tools/exp/lmb_bench.hip).  No workgroup waits for another.  After the last launch L and y are
-// complete; k_lmb_back_mw solves L^T x = y with one workgroup per tile column (k_lmb_back: the one-workgroup version, kept for tools/exp/lmb_bench.hip).
+// complete; k_lmb_back_mw solves L^T x = y with one workgroup per tile column.
 // Fixed summation order everywhere: run-to-run identical.  A non-positive pivot clears LmState::ok (g2o: the linear solver fails, the
 // trial is rejected) and x = 0.
 #include <hip/hip_runtime.h>
@@ -305,116 +305,16 @@ __global__ __launch_bounds__(192) void k_lmb_step(int k, int KT, int ld, double*
   }
 }
 
-// L^T x = y (y = row ld of M after the factorisation), one workgroup; resets the column flags for the next trial.
-// Per tile column, from the last: x_k = L_kk^-T y_k by blocked backward substitution with the three 16 x 16 inverses the factorisation
-// left behind (five 16 x 16 matrix-vector products, sixteen lanes each), then y_j -= L_kj^T x_k for every column left of the tile
-// (one column per thread, its 48 loads in flight at once); the next diagonal tile is requested before the panel update and lands under it.
-// (First version: a 48-step substitution straight from global memory, 1.75 ms at 300 keyframes; from LDS 0.40 ms.)
-__global__ __launch_bounds__(1024) void k_lmb_back(int n, int KT, int ld, const double* __restrict__ M, const double* __restrict__ Linv,
-                                                   LmState* __restrict__ st, int32_t* __restrict__ flags, double* __restrict__ x) {
-#pragma clang fp contract(fast)
-  extern __shared__ double lmb_y[];  // [ld] y -> x | [48] x of the current tile | [48][49] its diagonal tile | [3][16][17] the inverses
-  if (!lmb_gate(st)) return;
-  const int t = threadIdx.x;
-  const bool failed = *(volatile int32_t*)&flags[KT] != 0;
-  if (failed) {
-    for (int c = t; c < n; c += 1024) x[c] = 0.0;
-    __syncthreads();
-    for (int q = t; q <= KT; q += 1024) flags[q] = 0;
-    return;
-  }
-  double* xs = lmb_y + ld;
-  double* Lt = xs + LMB_T;
-  double* Iv = Lt + LMB_T * LMB_LS;
-  for (int c = t; c < ld; c += 1024) lmb_y[c] = M[(size_t)ld * ld + c];
-  // (tile elements of thread t: e = t, t + 1024, t + 2048 of 2304; inverse elements e = t of 768)
-  auto tile_fetch = [&](int kt, double (&v)[3], double& iv) {
-    const double* Lkk = M + (size_t)kt * LMB_T * ld + (size_t)kt * LMB_T;
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int e = t + 1024 * u;
-      v[u] = e < LMB_T * LMB_T ? Lkk[(size_t)(e / LMB_T) * ld + e % LMB_T] : 0.0;
-    }
-    iv = t < 768 ? Linv[(size_t)kt * 768 + t] : 0.0;
-  };
-  auto tile_store = [&](const double (&v)[3], double iv) {
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int e = t + 1024 * u;
-      if (e < LMB_T * LMB_T) Lt[(e / LMB_T) * LMB_LS + e % LMB_T] = v[u];
-    }
-    if (t < 768) Iv[(t >> 8) * 16 * LMB_IS + ((t & 255) >> 4) * LMB_IS + (t & 15)] = iv;
-  };
-  double tv[3], tiv;
-  tile_fetch(KT - 1, tv, tiv);
-  tile_store(tv, tiv);
-  __syncthreads();
-  for (int kt = KT - 1; kt >= 0; --kt) {
-    if (kt > 0) tile_fetch(kt - 1, tv, tiv);  // lands under this step's work
-    if (t < 64) {
-      // out[i] = sum_k Mx[k][i] v[k] over a 16 x 16 block (transposed product), lanes 0..15
-      const int i = t & 15;
-      double* yk = lmb_y + kt * LMB_T;
-      auto mv_t = [&](const double* Mx, int pitch, const double* v) {
-        double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-        for (int k2 = 0; k2 < 16; k2 += 2) {
-          s0 = fma(Mx[k2 * pitch + i], v[k2], s0);
-          s1 = fma(Mx[(k2 + 1) * pitch + i], v[k2 + 1], s1);
-        }
-        return s0 + s1;
-      };
-      const double x3 = mv_t(Iv + 2 * 16 * LMB_IS, LMB_IS, yk + 32);
-      if (t < 16) xs[32 + i] = x3;
-      lmb_wave_sync();
-      const double y2 = yk[16 + i] - mv_t(Lt + 32 * LMB_LS + 16, LMB_LS, xs + 32);
-      lmb_wave_sync();
-      if (t < 16) yk[16 + i] = y2;
-      lmb_wave_sync();
-      const double x2 = mv_t(Iv + 16 * LMB_IS, LMB_IS, yk + 16);
-      if (t < 16) xs[16 + i] = x2;
-      lmb_wave_sync();
-      const double y1 = yk[i] - (mv_t(Lt + 32 * LMB_LS, LMB_LS, xs + 32) + mv_t(Lt + 16 * LMB_LS, LMB_LS, xs + 16));
-      lmb_wave_sync();
-      if (t < 16) yk[i] = y1;
-      lmb_wave_sync();
-      const double x1 = mv_t(Iv, LMB_IS, yk);
-      if (t < 16) {
-        xs[i] = x1;
-        yk[i] = x1, yk[16 + i] = x2, yk[32 + i] = x3;
-      }
-    }
-    __syncthreads();
-    // y_j -= L_kj^T x_k for every column left of the tile: row panel kt of L, one column per thread
-    for (int c = t; c < kt * LMB_T; c += 1024) {
-      const double* col = M + (size_t)kt * LMB_T * ld + c;
-      double lv[LMB_T];
-#pragma unroll
-      for (int r = 0; r < LMB_T; ++r) lv[r] = col[(size_t)r * ld];  // (all requested before the first is used: one round trip)
-      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-      for (int r = 0; r < LMB_T; r += 4) {
-        s0 = fma(lv[r], xs[r], s0);
-        s1 = fma(lv[r + 1], xs[r + 1], s1);
-        s2 = fma(lv[r + 2], xs[r + 2], s2);
-        s3 = fma(lv[r + 3], xs[r + 3], s3);
-      }
-      lmb_y[c] -= (s0 + s1) + (s2 + s3);
-    }
-    if (kt > 0) tile_store(tv, tiv);  // (the tile solve of this step is over: the barrier above)
-    __syncthreads();
-  }
-  for (int c = t; c < n; c += 1024) x[c] = lmb_y[c];
-  for (int q = t; q <= KT; q += 1024) flags[q] = 0;
-}
-
-// The same over MANY CUs: one workgroup per tile column, column KT - 1 first (workgroup 0).  Workgroup j owns y_j: it subtracts
+// L^T x = y (y = row ld of M after the factorisation).  Per tile column, from the last: x_k = L_kk^-T y_k by blocked backward
+// substitution with the three 16 x 16 inverses the factorisation left behind (five 16 x 16 matrix-vector products, sixteen lanes
+// each), and y_j -= L_kj^T x_k for every column left of the tile.
+// Over MANY CUs: one workgroup per tile column, column KT - 1 first (workgroup 0).  Workgroup j owns y_j: it subtracts
 // L_kj^T x_k for k = KT - 1 ... j + 1 as the x_k become available (the 48 x 48 tile of the next k is requested BEFORE the wait, so a
 // column's critical path is flag -> 48 doubles of x -> one tile's matrix-vector product -> the 16-wide block solves -> publish), solves
 // its own tile and raises xready[j].  A workgroup waits only for workgroups of SMALLER index (dispatched before it; workgroup 0 waits for
 // nobody), so the waits cannot deadlock.  xready[] is zeroed by the first launch of the NEXT factorisation (k_lmb_step, k = -1): no
-// workgroup of this kernel may reset a flag another one is still polling.  The one-workgroup version moved the whole 13 MB of an
-// 1800-row factor through one CU: 0.44 ms; this one 0.15.
+// workgroup of this kernel may reset a flag another one is still polling.  (A one-workgroup version, dropped since, moved the whole
+// 13 MB of an 1800-row factor through one CU: 0.44 ms; this one 0.15.)
 __global__ __launch_bounds__(192) void k_lmb_back_mw(int n, int KT, int ld, const double* __restrict__ M, const double* __restrict__ Linv,
                                                      LmState* __restrict__ st, int32_t* __restrict__ flags, int32_t* __restrict__ xready,
                                                      double* __restrict__ x) {
@@ -465,7 +365,7 @@ __global__ __launch_bounds__(192) void k_lmb_back_mw(int n, int KT, int ld, cons
     if (t < LMB_T) yj[t] -= (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
     __syncthreads();
   }
-  if (t < 64) {  // x_j = L_jj^-T y_j by the block inverses (as k_lmb_back)
+  if (t < 64) {  // x_j = L_jj^-T y_j by the block inverses
     const int i = t & 15;
     auto mv_t = [&](const double* Mx, int pitch, const double* v) {
       double a0 = 0.0, a1 = 0.0;

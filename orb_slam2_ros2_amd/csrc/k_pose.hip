@@ -9,8 +9,8 @@
 // (fixed tree => deterministic), solve a 6x6 system on one lane.  No host round trip per iteration.
 #include <hip/hip_runtime.h>
 
+#include "ba_edge_dev.h"
 #include "orbfe_internal.h"
-#include "se3_dev.h"
 #include "wave_ops.h"
 
 namespace orbfe {
@@ -129,22 +129,13 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_only(int n, const double*
   }
   __syncthreads();
 
+  // (an edge is mono when rightU < 0: Edge(Stereo)SE3ProjectXYZOnlyPose share error and chi2 with the BA edges, ba_edge_dev.h)
   auto edge_error = [&](int i, const PoseDev& T, double* e) {
     double p[3];
-    quat_rotate(T.q, Xw + 3 * i, p);
-    const double x = p[0] + T.t[0], y = p[1] + T.t[1], z = p[2] + T.t[2];
-    const double* m = meas + 3 * i;
-    const double u = x / z * prm.fx + prm.cx, v = y / z * prm.fy + prm.cy;
-    e[0] = m[0] - u;
-    e[1] = m[1] - v;
-    e[2] = (m[2] < 0) ? 0.0 : m[2] - (u - prm.bf / z);
+    se3_map(T.q, T.t, Xw + 3 * i, p);
+    ba_edge_error(p, meas + 3 * i, !(meas[3 * i + 2] < 0), prm, e);
   };
-  auto edge_chi2 = [&](int i, const double* e) {
-    const double w = info[i];
-    double c = e[0] * (w * e[0]) + e[1] * (w * e[1]);
-    if (!(meas[3 * i + 2] < 0)) c += e[2] * (w * e[2]);
-    return c;
-  };
+  auto edge_chi2 = [&](int i, const double* e) { return ba_edge_chi2(e, info[i], !(meas[3 * i + 2] < 0)); };
   // computeActiveErrors + activeRobustChi2 at the current S.T
   auto eval_chi = [&]() {
     const PoseDev T = S.T;
@@ -157,12 +148,9 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_only(int n, const double*
       err[3 * i + 1] = e[1];
       err[3 * i + 2] = e[2];
       const double c = edge_chi2(i, e);
-      if (robust[i]) {
-        const double dl = (meas[3 * i + 2] < 0) ? d_mono : d_stereo;
-        const double dsqr = dl * dl;
-        part += (c <= dsqr) ? c : (2 * sqrt(c) * dl - dsqr);
-      } else
-        part += c;
+      double r0 = c, r1;
+      if (robust[i]) huber_robustify(c, (meas[3 * i + 2] < 0) ? d_mono : d_stereo, r0, r1);
+      part += r0;
     }
     return block_sum(part, S.red, 27);
   };
@@ -174,44 +162,20 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_only(int n, const double*
     for (int k = 0; k < 27; ++k) acc[k] = 0;
     for (int i = tid; i < n; i += POSE_THREADS) {
       if (level[i] != 0) continue;
-      double p[3];
-      quat_rotate(T.q, Xw + 3 * i, p);
-      const double x = p[0] + T.t[0], y = p[1] + T.t[1], z = p[2] + T.t[2];
-      const double invz = 1.0 / z, invz_2 = invz * invz;
+      double p[3], J[18];
+      se3_map(T.q, T.t, Xw + 3 * i, p);
       const bool st = !(meas[3 * i + 2] < 0);
-      double J[3][6];
-      J[0][0] = x * y * invz_2 * prm.fx;
-      J[0][1] = -(1 + (x * x * invz_2)) * prm.fx;
-      J[0][2] = y * invz * prm.fx;
-      J[0][3] = -invz * prm.fx;
-      J[0][4] = 0;
-      J[0][5] = x * invz_2 * prm.fx;
-      J[1][0] = (1 + y * y * invz_2) * prm.fy;
-      J[1][1] = -x * y * invz_2 * prm.fy;
-      J[1][2] = -x * invz * prm.fy;
-      J[1][3] = 0;
-      J[1][4] = -invz * prm.fy;
-      J[1][5] = y * invz_2 * prm.fy;
-      J[2][0] = st ? J[0][0] - prm.bf * y * invz_2 : 0.0;
-      J[2][1] = st ? J[0][1] + prm.bf * x * invz_2 : 0.0;
-      J[2][2] = st ? J[0][2] : 0.0;
-      J[2][3] = st ? J[0][3] : 0.0;
-      J[2][4] = 0;
-      J[2][5] = st ? J[0][5] - prm.bf * invz_2 : 0.0;
+      pose_edge_jpose(p, st, prm, J);
       const double e[3] = {err[3 * i], err[3 * i + 1], st ? err[3 * i + 2] : 0.0};
       const double w = info[i];
-      double r1 = 1.0;
-      if (robust[i]) {
-        const double c = edge_chi2(i, e);
-        const double dl = st ? d_stereo : d_mono;
-        if (c > dl * dl) r1 = dl / sqrt(c);
-      }
+      double r0, r1 = 1.0;
+      if (robust[i]) huber_robustify(edge_chi2(i, e), st ? d_stereo : d_mono, r0, r1);
       int k = 0;
 #pragma unroll
       for (int a = 0; a < 6; ++a) {
-        acc[21 + a] -= r1 * (J[0][a] * (w * e[0]) + J[1][a] * (w * e[1]) + J[2][a] * (w * e[2]));
+        acc[21 + a] -= r1 * (J[a] * (w * e[0]) + J[6 + a] * (w * e[1]) + J[12 + a] * (w * e[2]));
 #pragma unroll
-        for (int c2 = a; c2 < 6; ++c2) acc[k++] += J[0][a] * (r1 * w) * J[0][c2] + J[1][a] * (r1 * w) * J[1][c2] + J[2][a] * (r1 * w) * J[2][c2];
+        for (int c2 = a; c2 < 6; ++c2) acc[k++] += J[a] * (r1 * w) * J[c2] + J[6 + a] * (r1 * w) * J[6 + c2] + J[12 + a] * (r1 * w) * J[12 + c2];
       }
     }
     double tot[27];
@@ -327,7 +291,7 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_only(int n, const double*
           err[3 * i + 2] = e[2];
         }
         const double c = edge_chi2(i, e);
-        const double th = (st ? 7.815 : 5.991) * (double)sigma2[i];
+        const double th = ba_chi2_threshold(st) * (double)sigma2[i];
         if (c > th) {
           inlier[i] = 0;
           level[i] = 1;
@@ -426,7 +390,7 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
     for (int k = 0; k < 3; ++k) X[u][k] = (n > 0) ? Xw[3 * ii + k] : 0.0, M[u][k] = (n > 0) ? meas[3 * ii + k] : 0.0;
     W[u] = (n > 0) ? info[ii] : 0.0;
     st[u] = !(M[u][2] < 0);
-    TH[u] = (st[u] ? 7.815 : 5.991) * (double)((n > 0) ? sigma2[ii] : 0.f);
+    TH[u] = ba_chi2_threshold(st[u]) * (double)((n > 0) ? sigma2[ii] : 0.f);
     lvl0[u] = have[u], rob[u] = true, inl[u] = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) E[u][k] = 0.0;
@@ -439,18 +403,10 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
 
   auto edge_error = [&](int u, const PoseDev& T, double* e) {
     double p[3];
-    quat_rotate(T.q, X[u], p);
-    const double x = p[0] + T.t[0], y = p[1] + T.t[1], z = p[2] + T.t[2];
-    const double uu = x / z * prm.fx + prm.cx, v = y / z * prm.fy + prm.cy;
-    e[0] = M[u][0] - uu;
-    e[1] = M[u][1] - v;
-    e[2] = (M[u][2] < 0) ? 0.0 : M[u][2] - (uu - prm.bf / z);
+    se3_map(T.q, T.t, X[u], p);
+    ba_edge_error(p, M[u], st[u], prm, e);
   };
-  auto edge_chi2 = [&](int u, const double* e) {
-    double c = e[0] * (W[u] * e[0]) + e[1] * (W[u] * e[1]);
-    if (st[u]) c += e[2] * (W[u] * e[2]);
-    return c;
-  };
+  auto edge_chi2 = [&](int u, const double* e) { return ba_edge_chi2(e, W[u], st[u]); };
 
   // edge->computeError() at construction (Optimizer.cc:90,111) -- (with the state machine below this is the only other use of edge_error
   // besides the evaluation site and the re-classification)
@@ -512,12 +468,9 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
             if (!lvl0[u]) continue;
             edge_error(u, Te, E[u]);
             const double c = edge_chi2(u, E[u]);
-            if (rob[u]) {
-              const double dl = st[u] ? d_stereo : d_mono;
-              const double dsqr = dl * dl;
-              part += (c <= dsqr) ? c : (2 * sqrt(c) * dl - dsqr);
-            } else
-              part += c;
+            double r0 = c, r1;
+            if (rob[u]) huber_robustify(c, st[u] ? d_stereo : d_mono, r0, r1);
+            part += r0;
           }
           chi = block_sum_alt(part);
         }
@@ -574,44 +527,20 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
 #pragma unroll
           for (int u = 0; u < POSE_EPT; ++u) {
             if (!lvl0[u]) continue;
-            double p[3];
-            quat_rotate(T.q, X[u], p);
-            const double x = p[0] + T.t[0], y = p[1] + T.t[1], z = p[2] + T.t[2];
-            const double invz = 1.0 / z, invz_2 = invz * invz;
+            double p[3], J[18];
+            se3_map(T.q, T.t, X[u], p);
             const bool s3 = st[u];
-            double J[3][6];
-            J[0][0] = x * y * invz_2 * prm.fx;
-            J[0][1] = -(1 + (x * x * invz_2)) * prm.fx;
-            J[0][2] = y * invz * prm.fx;
-            J[0][3] = -invz * prm.fx;
-            J[0][4] = 0;
-            J[0][5] = x * invz_2 * prm.fx;
-            J[1][0] = (1 + y * y * invz_2) * prm.fy;
-            J[1][1] = -x * y * invz_2 * prm.fy;
-            J[1][2] = -x * invz * prm.fy;
-            J[1][3] = 0;
-            J[1][4] = -invz * prm.fy;
-            J[1][5] = y * invz_2 * prm.fy;
-            J[2][0] = s3 ? J[0][0] - prm.bf * y * invz_2 : 0.0;
-            J[2][1] = s3 ? J[0][1] + prm.bf * x * invz_2 : 0.0;
-            J[2][2] = s3 ? J[0][2] : 0.0;
-            J[2][3] = s3 ? J[0][3] : 0.0;
-            J[2][4] = 0;
-            J[2][5] = s3 ? J[0][5] - prm.bf * invz_2 : 0.0;
+            pose_edge_jpose(p, s3, prm, J);
             const double e[3] = {E[u][0], E[u][1], s3 ? E[u][2] : 0.0};
             const double w = W[u];
-            double r1 = 1.0;
-            if (rob[u]) {
-              const double c = edge_chi2(u, e);
-              const double dl = s3 ? d_stereo : d_mono;
-              if (c > dl * dl) r1 = dl / sqrt(c);
-            }
+            double r0, r1 = 1.0;
+            if (rob[u]) huber_robustify(edge_chi2(u, e), s3 ? d_stereo : d_mono, r0, r1);
             int k = 0;
 #pragma unroll
             for (int a = 0; a < 6; ++a) {
-              acc[21 + a] -= r1 * (J[0][a] * (w * e[0]) + J[1][a] * (w * e[1]) + J[2][a] * (w * e[2]));
+              acc[21 + a] -= r1 * (J[a] * (w * e[0]) + J[6 + a] * (w * e[1]) + J[12 + a] * (w * e[2]));
 #pragma unroll
-              for (int c2 = a; c2 < 6; ++c2) acc[k++] += J[0][a] * (r1 * w) * J[0][c2] + J[1][a] * (r1 * w) * J[1][c2] + J[2][a] * (r1 * w) * J[2][c2];
+              for (int c2 = a; c2 < 6; ++c2) acc[k++] += J[a] * (r1 * w) * J[c2] + J[6 + a] * (r1 * w) * J[6 + c2] + J[12 + a] * (r1 * w) * J[12 + c2];
             }
           }
           PS(5)  // build: per-edge arithmetic

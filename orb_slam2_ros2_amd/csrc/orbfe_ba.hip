@@ -48,7 +48,7 @@ void ba_take(ScratchLayout& L, const orbfe_ba_problem* p, const uint8_t* pose_fi
   const BaInputs::Field f[BA_FIELDS] = {
       {p->poses, NK * 56, 0}, {p->points, NP * 24, 0}, {p->edge_pose, E * 4, 0}, {p->edge_point, E * 4, 0}, {p->meas, E * 24, 0},
       {p->is_stereo, E, 0}, {p->info, E * 8, 0}, {p->huber_delta, E * 8, 0}, {pose_fixed, NK, 0},
-      // (k_lm_linpoints / k_lm_pose_block, k_lba_solve and k_ba_system read pt_off[point + 1] and ps_off[pose + 1] of the last vertex)
+      // (k_lm_linpoints / lm_pose_block and k_lba_solve read pt_off[point + 1] and ps_off[pose + 1] of the last vertex)
       {v ? v->pt_off.data() : nullptr, (NP + 1) * 4, 0}, {v ? v->pt_edges.data() : nullptr, E * 4, 0},
       {v ? v->ps_off.data() : nullptr, (NK + 1) * 4, 0}, {v ? v->ps_edges.data() : nullptr, E * 4, 0}};
   in->n = v ? BA_FIELDS : BA_FIX;
@@ -62,13 +62,29 @@ void ba_put(StagedIo& io, const BaInputs& in) {
 // what the system build and the device-side optimiser tell the k_lm kernels in the same way: sizes, inputs, lists, camera
 void lm_fill_inputs(LmLaunch& L, const StagedIo& io, const BaInputs& in, const orbfe_ba_problem* p) {
   L.NK = p->n_poses, L.NP = p->n_points, L.E = p->n_edges;
-  L.poses[0] = io.dev<double>(in[BA_POSE]), L.points[0] = io.dev<double>(in[BA_PT]);
+  L.B.poses[0] = io.dev<double>(in[BA_POSE]), L.B.points[0] = io.dev<double>(in[BA_PT]);
   L.edge_pose = io.dev<int32_t>(in[BA_EP]), L.edge_point = io.dev<int32_t>(in[BA_ET]);
   L.pt_off = io.dev<int32_t>(in[BA_PTO]), L.pt_edges = io.dev<int32_t>(in[BA_PTE]);
   L.ps_off = io.dev<int32_t>(in[BA_PSO]), L.ps_edges = io.dev<int32_t>(in[BA_PSE]);
   L.meas = io.dev<double>(in[BA_MEAS]), L.info = io.dev<double>(in[BA_INFO]), L.is_stereo = io.dev<uint8_t>(in[BA_ST]);
   L.fixed = io.dev<uint8_t>(in[BA_FIX]), L.delta_eff = io.dev<double>(in[BA_DELTA]);
   L.prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
+}
+// One system at one estimate, outside the device-side optimiser (orbfe_ba_build_system, the host-driven loop): both buffer sets are the
+// one given, the control state is zeros (buffer 0 current), then launch_lm_build(s, L, 0, 0, 0, true).
+struct LmSystemAt {
+  size_t state, level, info_eff, hpp, bp, hll, bl, hpl, terms /* [E][32] */, chi /* [(NP + 31) / 32] */;
+};
+void lm_fill_one_system(LmLaunch& L, const StagedIo& io, const LmSystemAt& o) {
+  LmBuffers& B = L.B;
+  L.nf = 0;
+  B.poses[1] = B.poses[0], B.points[1] = B.points[0];
+  B.terms[0] = B.terms[1] = io.dev<double>(o.terms), B.Hpl[0] = B.Hpl[1] = io.dev<double>(o.hpl);
+  B.Hpp[0] = B.Hpp[1] = io.dev<double>(o.hpp), B.bp[0] = B.bp[1] = io.dev<double>(o.bp);
+  B.Hll[0] = B.Hll[1] = io.dev<double>(o.hll), B.bl[0] = B.bl[1] = io.dev<double>(o.bl);
+  B.chi_part[0] = B.chi_part[1] = io.dev<double>(o.chi);
+  L.state = io.dev<LmState>(o.state);
+  L.info_eff = io.dev<double>(o.info_eff), L.chi2_last = nullptr, L.level = io.dev<uint8_t>(o.level);
 }
 
 // one orbfe_ba_local_optimize call: the arguments, what the entry point derived from them, and its ORBFE_LBA_TRACE marks
@@ -149,10 +165,11 @@ orbfe_status LbaCall::device_lm() {
   LmLaunch K{};
   lm_fill_inputs(K, io, in, p);
   K.nf = nf;
-  K.poses[1] = io.dev<double>(o_pose1), K.points[1] = io.dev<double>(o_pt1);
+  K.B.poses[1] = io.dev<double>(o_pose1), K.B.points[1] = io.dev<double>(o_pt1);
   for (int k = 0; k < 2; ++k)
-    K.terms[k] = io.dev<double>(o_terms[k]), K.Hpl[k] = io.dev<double>(o_hpl[k]), K.Hpp[k] = io.dev<double>(o_hpp[k]), K.bp[k] = io.dev<double>(o_bp[k]),
-    K.Hll[k] = io.dev<double>(o_hll[k]), K.bl[k] = io.dev<double>(o_bl[k]), K.chi_part[k] = io.dev<double>(o_chi[k]);
+    K.B.terms[k] = io.dev<double>(o_terms[k]), K.B.Hpl[k] = io.dev<double>(o_hpl[k]), K.B.Hpp[k] = io.dev<double>(o_hpp[k]),
+    K.B.bp[k] = io.dev<double>(o_bp[k]), K.B.Hll[k] = io.dev<double>(o_hll[k]), K.B.bl[k] = io.dev<double>(o_bl[k]),
+    K.B.chi_part[k] = io.dev<double>(o_chi[k]);
   K.state = io.dev<LmState>(o_lmstate);
   K.free_pose = io.dev<int32_t>(o_free), K.pose_slot = io.dev<int32_t>(o_slot);
   K.pairs = io.dev<int2>(o_pairs), K.pair_cnt = io.dev<int32_t>(o_paircnt), K.pair_table = io.dev<int32_t>(o_ptable), K.pair_cap = pair_cap;
@@ -271,8 +288,11 @@ orbfe_status LbaCall::host_lm() {
                o_bl = L.take<double>(NPs * 3), o_hpl = L.take<double>(NE * 18), o_w = L.take<double>(NE * 18), o_s = L.take<double>(n * n),
                o_rhs = L.take<double>(n), o_x = L.take<double>(n), o_dxp = L.take<double>(NKs * 6), o_dxl = L.take<double>(NPs * 3),
                o_err = L.take<double>(NE * 3), o_chi2 = L.take<double>(NE), o_rho = L.take<double>(NE * 2),
-               // zero: one block that starts as zeros (ONE fill): edge levels | chi2 of the last linearisation | point inverses
-               o_level = L.open(zero).take(NE), o_last = L.take<double>(NE), o_dinv = L.take<double>(NPs * 9), o_depth = L.close(zero).take(NE),
+               o_terms = L.take<double>(NE * 32), o_chipart = L.take<double>((NPs + 31) / 32),  // the system builder's (k_lm_linpoints)
+               // zero: one block that starts as zeros (ONE fill): edge levels | chi2 of the last linearisation | point inverses | the
+               // system builder's control state (buffer 0 current)
+               o_level = L.open(zero).take(NE), o_last = L.take<double>(NE), o_dinv = L.take<double>(NPs * 9), o_lmstate = L.take(sizeof(LmState)),
+               o_depth = L.close(zero).take(NE),
                o_bad = L.take(NE), o_sc = L.take<double>(5),
                o_big = L.take(nf > LBA_MAX_FREE ? ((n + 1) * 6 + (size_t)nf * 36 + n) * 8 : 8);  // launch_lba_solve's panel in global memory
   const size_t o_pose = in[BA_POSE], o_pt = in[BA_PT], o_meas = in[BA_MEAS], o_st = in[BA_ST], o_info = in[BA_INFO], o_delta = in[BA_DELTA],
@@ -292,6 +312,10 @@ orbfe_status LbaCall::host_lm() {
   HIP_TRY(c, hipMemsetAsync(b + zero.begin, 0, zero.bytes(), st));  // (every memset is a launch of 4.6 us: six of them preceded the first kernel)
 
   const BaParamsDev prm = {p->fx, p->fy, p->cx, p->cy, p->bf};
+  // buildSystem: the builders of the device-side path (k_lm.hip) at the one estimate this loop keeps
+  LmLaunch K{};
+  lm_fill_inputs(K, io, in, p);
+  lm_fill_one_system(K, io, {o_lmstate, o_level, o_info_eff, o_hpp, o_bp, o_hll, o_bl, o_hpl, o_terms, o_chipart});
   double* d_poses = (double*)(b + o_pose);
   double* d_points = (double*)(b + o_pt);
   const int32_t* d_ek = (const int32_t*)(b + in[BA_EP]);
@@ -325,10 +349,7 @@ orbfe_status LbaCall::host_lm() {
       if (stopped()) break;
       ++done;
       evaluate();
-      launch_ba_system(st, NK, NP, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, (const double*)(b + o_info_eff),
-                       (const double*)(b + o_delta), prm, b + o_fix, (const int32_t*)(b + o_pto), (const int32_t*)(b + o_pte),
-                       (const int32_t*)(b + o_pso), (const int32_t*)(b + o_pse), (double*)(b + o_hpp), (double*)(b + o_bp),
-                       (double*)(b + o_hll), (double*)(b + o_bl), (double*)(b + o_hpl));
+      launch_lm_build(st, K, 0, 0, 0, true);
       if (it == 0) launch_lba_maxdiag(st, NK, NP, (const double*)(b + o_hpp), (const double*)(b + o_hll), b + o_fix, d_sc + 1);
       HostScalars h;
       HIP_TRY(c, read_scalars(h));
@@ -490,14 +511,7 @@ orbfe_status orbfe_ba_build_system(orbfe_ctx* c, const orbfe_ba_problem* p, cons
   {
     LmLaunch K{};
     lm_fill_inputs(K, io, in, p);
-    K.nf = 0;
-    K.poses[1] = K.poses[0], K.points[1] = K.points[0];
-    K.terms[0] = K.terms[1] = io.dev<double>(o_terms), K.Hpl[0] = K.Hpl[1] = io.dev<double>(o_hpl);
-    K.Hpp[0] = K.Hpp[1] = io.dev<double>(o_hpp), K.bp[0] = K.bp[1] = io.dev<double>(o_bp);
-    K.Hll[0] = K.Hll[1] = io.dev<double>(o_hll), K.bl[0] = K.bl[1] = io.dev<double>(o_bl);
-    K.chi_part[0] = K.chi_part[1] = io.dev<double>(o_chi);
-    K.state = io.dev<LmState>(o_state);
-    K.info_eff = io.dev<double>(in[BA_INFO]), K.chi2_last = nullptr, K.level = io.dev<uint8_t>(o_level);
+    lm_fill_one_system(K, io, {o_state, o_level, in[BA_INFO], o_hpp, o_bp, o_hll, o_bl, o_hpl, o_terms, o_chi});
     StageTimer tm(c, ORBFE_STAGE_BA, c->stream);
     launch_lm_build(c->stream, K, 0, 0, 0, true);
   }

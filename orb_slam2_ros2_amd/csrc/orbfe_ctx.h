@@ -108,11 +108,6 @@ void launch_ba_edges(hipStream_t s, int n_edges, const double* d_poses, const do
                      const int32_t* d_edge_point, const double* d_meas, const uint8_t* d_is_stereo, const double* d_info,
                      const double* d_delta, BaParamsDev prm, double* d_error, double* d_chi2, double* d_rho, double* d_jpoint,
                      double* d_jpose, uint8_t* d_depth_pos);
-void launch_ba_system(hipStream_t s, int n_poses, int n_points, int n_edges, const double* poses, const double* points,
-                      const int32_t* edge_pose, const int32_t* edge_point, const double* meas, const uint8_t* is_stereo,
-                      const double* info, const double* delta, BaParamsDev prm, const uint8_t* pose_fixed, const int32_t* pt_off,
-                      const int32_t* pt_edges, const int32_t* ps_off, const int32_t* ps_edges, double* Hpp, double* bp, double* Hll,
-                      double* bl, double* Hpl);
 void launch_project_map_points(hipStream_t s, int n, const float* d_pos, const float* d_vdir, const float* d_max, const float* d_min,
                                const float* R, const float* t, const float* cam4, const float* bounds4, float log_sf, int max_level,
                                float* d_uv, float* d_dist, float* d_cos, int8_t* d_level, uint8_t* d_vis);

@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "../../include/orbfe.h"
+#include "ba_edge_dev.h"
 
 #define ORBFE_MAX_STRIPS 16  // Quadtree::initSplit root strips, round(w/h)  (ORBExtractor.cc:85)
 #define ORBFE_BORDER 19      // ORBExtractor::mnBorderSize (ORBExtractor.cc:523)
@@ -161,13 +162,14 @@ struct StereoRowsBuf {
 // local BA: non-fixed keyframes the dense reduced solver takes (its panel, right-hand side and diagonal blocks live in 64 KB of LDS)
 #define LBA_MAX_FREE 100
 
-struct BaParamsDev {
-  double fx, fy, cx, cy, bf;
-};
+// (BaParamsDev, the camera of the edge model: ba_edge_dev.h)
 
 // ---- device-side Levenberg-Marquardt control of the local BA (k_lm.hip) -------------------------------------------------------------
 #define LM_CHOL_MAX_NB 42  // free keyframes the register-resident Cholesky takes: 42 * 41 / 2 = 861 off-diagonal blocks, two per thread of 448
-#define LM_BIG_MAX_NB 1000 // free keyframes the blocked multi-workgroup Cholesky takes (k_lmbig.hip: the back substitution keeps y in 48 KB of LDS)
+// free keyframes the device-side path takes; past it the host-driven loop runs.  The value is kept from r4, when a one-workgroup back
+// substitution held y in 48 KB of LDS; k_lmb_back_mw has no such limit and nothing structural enforces 1000 now -- what bounds the
+// device path is memory (the dense (ld + 48) x ld system, the nf x NP pair table) and 32-bit products such as b * pair_cap in k_lm_schur.
+#define LM_BIG_MAX_NB 1000
 
 // The state record one control lane advances between the trials (device memory; the host reads it once per call).
 struct LmState {
@@ -187,9 +189,23 @@ struct LmState {
   int32_t pad;
 };
 
+// The estimates, the edge terms and the normal-equation blocks exist twice: [cur] = the current estimate and its system,
+// [cur ^ 1] = the trial's.  The kernels of k_lm.hip take this record by value.
+struct LmBuffers {
+  double* poses[2];
+  double* points[2];
+  double* terms[2];     // [E][32]: the per-edge terms of one linearisation (k_lm.hip, LM_TERM)
+  double* Hpl[2];       // [E][18]
+  double* Hpp[2];       // [NK][36]
+  double* bp[2];        // [NK][6]
+  double* Hll[2];       // [NP][9]
+  double* bl[2];        // [NP][3]
+  double* chi_part[2];  // per linearize block: sum of rho(chi2) over its active edges
+};
+
 struct LmLaunch {
   int NK, NP, E, nf;
-  double *poses[2], *points[2], *terms[2], *Hpl[2], *Hpp[2], *bp[2], *Hll[2], *bl[2], *chi_part[2];
+  LmBuffers B;
   LmState* state;
   LmState* state_out;  // copy of the state after the last control step of a pass, inside the result block (one download)
   const int32_t *edge_pose, *edge_point, *pt_off, *pt_edges, *ps_off, *ps_edges, *free_pose, *pose_slot;

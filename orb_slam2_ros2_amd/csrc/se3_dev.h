@@ -1,7 +1,23 @@
-// se3_dev.h -- device-side SE3 helpers shared by the pose-only and local-BA kernels (g2o types/slam3d/se3quat.h restated:
+// se3_dev.h -- SE3 helpers shared by the pose-only and local-BA kernels (g2o types/slam3d/se3quat.h restated:
 // Eigen quaternion-vector product, SE3Quat::exp, operator*, normalizeRotation).  fp64, no FMA contraction.
+// Host + device: a plain C++ compiler takes this header too (tests/cpp/test_ba_edge.cpp runs it on the CPU, with -ffp-contract=off).
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define ORBFE_HD __host__ __device__
+#define ORBFE_HD_INLINE __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#define ORBFE_HD
+#define ORBFE_HD_INLINE inline __attribute__((always_inline))
+#endif
+#ifdef __clang__
+#define ORBFE_FP_STRICT _Pragma("clang fp contract(off)")
+#define ORBFE_UNROLL _Pragma("unroll")
+#else
+#define ORBFE_FP_STRICT
+#define ORBFE_UNROLL
+#endif
 
 namespace orbfe {
 
@@ -9,7 +25,8 @@ struct PoseDev {
   double q[4], t[3];
 };
 
-__device__ __forceinline__ void quat_rotate(const double* q, const double* v, double* out) {
+ORBFE_HD_INLINE void quat_rotate(const double* q, const double* v, double* out) {
+  ORBFE_FP_STRICT
   const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
   double ux = qy * v[2] - qz * v[1], uy = qz * v[0] - qx * v[2], uz = qx * v[1] - qy * v[0];
   ux += ux;
@@ -21,7 +38,8 @@ __device__ __forceinline__ void quat_rotate(const double* q, const double* v, do
 }
 
 // SE3Quat::exp(update) * T, normalizeRotation (g2o se3quat.h); update = (omega, upsilon)
-__device__ inline void pose_oplus(const PoseDev& T, const double* upd, PoseDev& out) {
+ORBFE_HD inline void pose_oplus(const PoseDev& T, const double* upd, PoseDev& out) {
+  ORBFE_FP_STRICT
   const double wx = upd[0], wy = upd[1], wz = upd[2];
   const double theta = sqrt(wx * wx + wy * wy + wz * wz);
   const double Om[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
@@ -98,6 +116,5 @@ __device__ inline void pose_oplus(const PoseDev& T, const double* upd, PoseDev& 
   const double n = sqrt(out.q[0] * out.q[0] + out.q[1] * out.q[1] + out.q[2] * out.q[2] + out.q[3] * out.q[3]);
   for (int i = 0; i < 4; ++i) out.q[i] /= n;
 }
-
 
 }  // namespace orbfe

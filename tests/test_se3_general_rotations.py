@@ -6,8 +6,14 @@ the same synthetic problems are moved into worlds X' = R_g X + t_g (se3_referenc
 and gives every pose four large quaternion components, and the oracle and the device are compared with 40- to 50-digit mpmath
 references that share no spelling with them (se3_reference.mp_edge / mp_oplus).
 
-CPU part: oracle against the reference (edges, exp map), and the two optimiser restatements of the oracle through gauge covariance.
+CPU part: oracle against the reference (edges, exp map), the two optimiser restatements of the oracle through gauge covariance, and the
+kernels' own edge model (csrc/ba_edge_dev.h, csrc/se3_dev.h) compiled for the host and run as a stand-alone program.
 GPU part: orbfe_debug_se3_oplus, ba_eval_edges, ba_build_system, pose_only_optimize and ba_local_optimize on gauged problems."""
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -16,6 +22,7 @@ from orb_slam2_ros2_amd import ba_synth
 from test_local_ba import _pose_dist, _problem
 from test_pose_only import _args
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EDGE_KEYS = ("poses", "points", "edge_pose", "edge_point", "meas", "is_stereo", "info", "huber_delta", "fx", "fy", "cx", "cy", "bf")
 
 
@@ -145,6 +152,84 @@ def test_oracle_local_ba_is_gauge_covariant(orc):
     assert _pose_dist(back, a["poses"]) < 1e-7
 
 
+# ---- CPU: the kernels' edge model, compiled by the host compiler ------------------------------------------------------------------------
+def _doubles(p):
+    """one problem in the layout tests/cpp/test_ba_edge.cpp reads"""
+    nk, npt, ne = len(p["poses"]), len(p["points"]), len(p["edge_pose"])
+    parts = [[nk, npt, ne], [p[k] for k in ("fx", "fy", "cx", "cy", "bf")]]
+    parts += [np.asarray(p[k], np.float64).ravel() for k in ("poses", "points", "edge_pose", "edge_point", "meas", "is_stereo", "info", "huber_delta")]
+    return np.concatenate([np.asarray(a, np.float64) for a in parts])
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_edge_model_stand_alone(orc, gauged, oplus_table, tmp_path):
+    """tests/cpp/test_ba_edge.cpp: ba_edge_dev.h and se3_dev.h have no HIP in them for a host compiler, so the source lines the kernels
+    inline run here, under the host compiler's address and undefined-behaviour sanitizers when this g++ has their runtimes (a stand-alone
+    program; nothing of it is loaded into python).  Problems: the four gauged worlds, 'skew' with every quaternion negated, 'skew' with
+    per-edge Huber widths either side of every chi2; and the exp-map case table.  Bounds (issue): error 1e-11 absolute, j_point / j_pose /
+    the pose-only j_pose 1e-11 relative to the 40-digit reference; q and -q the same bits; rho against the oracle at rtol 1e-9, atol 1e-12
+    with both Huber branches taken (asserted); pose_oplus 1e-11 on R and t against the 50-digit reference, |q| = 1 within 1e-15, w >= 0.
+    The damped 3x3 inverse is checked inside the program."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_ba_edge.cpp")
+    exe = str(tmp_path / "t")
+    base = ["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-g", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "orb_slam2_ros2_amd", "csrc"), "-o", exe, src]
+    mode = "address + undefined-behaviour sanitizers"
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        # only a g++ WITHOUT the sanitizers' runtimes (the link step cannot find libasan / libubsan) may run the program plain
+        assert re.search(r"cannot find -l(asan|ubsan)|cannot find lib(asan|ubsan)|lib(asan|ubsan)\S* ?: No such file", r.stderr), r.stderr[-3000:]
+        mode = "no sanitizer runtime on this machine: plain build"
+        subprocess.check_call(base, timeout=300)
+    print("test_ba_edge.cpp:", mode)
+    names = list(S.GAUGES)
+    skew = gauged["skew"][0]
+    # Huber widths from the oracle's chi2: half of it (the sqrt branch), twice it plus one (the quadratic branch), none (delta <= 0)
+    chi2 = orc.ba_eval_edges(**_edge_args(skew))["chi2"]
+    hub = dict(skew)
+    hub["huber_delta"] = np.where(np.arange(chi2.size) % 3 == 0, 0.5 * np.sqrt(chi2), np.where(np.arange(chi2.size) % 3 == 1, 2 * np.sqrt(chi2) + 1, -1.0))
+    probs = [gauged[n][0] for n in names] + [S.negate_q(skew), hub]
+    poses, upd, R_ref, t_ref, branches = oplus_table
+    _assert_oplus_reach(poses, upd, branches)
+    blob = np.concatenate([[len(probs)]] + [_doubles(p) for p in probs] + [[len(poses)], poses.ravel(), upd.ravel()]).astype("<f8")
+    blob.tofile(str(tmp_path / "in.bin"))
+    r = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("OK"), (r.stdout + r.stderr)[-2000:]
+    res = np.fromfile(str(tmp_path / "out.bin"), "<f8")
+    at, outs = 0, []
+    for p in probs:
+        ne, o = len(p["edge_pose"]), {}
+        for k, shape in (("error", (3,)), ("chi2", ()), ("rho", (2,)), ("j_point", (3, 3)), ("j_pose", (3, 6)), ("pose_j", (3, 6)),
+                         ("depth_positive", ()), ("bad", ())):
+            n = ne * int(np.prod(shape, dtype=int))
+            o[k] = res[at:at + n].reshape((ne,) + shape)
+            at += n
+        outs.append(o)
+    oplus = res[at:].reshape(-1, 7)
+    assert oplus.shape == poses.shape
+    for name, p, o in zip(names, probs, outs):
+        ref = gauged[name][1]
+        _assert_general(p["poses"])
+        d = (np.abs(o["error"] - ref["error"]).max(), _rel(o["j_point"], ref["j_point"]), _rel(o["j_pose"], ref["j_pose"]), _rel(o["pose_j"], ref["j_pose"]))
+        print(f"edge model vs reference, {name}: error {d[0]:.2e}  j_point {d[1]:.2e}  j_pose {d[2]:.2e}  pose-only j_pose {d[3]:.2e}")
+        assert all(v < 1e-11 for v in d), (name, d)
+        assert (p["is_stereo"] == 0).any() and (p["is_stereo"] == 1).any() and o["depth_positive"].all()
+        th = np.where(p["is_stereo"] != 0, 7.815, 5.991)
+        assert np.array_equal(o["bad"] != 0, o["chi2"] > th)
+    neg, hb = outs[len(names)], outs[len(names) + 1]
+    assert (probs[len(names)]["poses"][:, 3] < 0).all() and (skew["poses"][:, 3] > 0).all()
+    assert all(np.array_equal(neg[k], outs[names.index("skew")][k]) for k in neg)
+    rho = orc.ba_eval_edges(**_edge_args(hub))["rho"]
+    d_hub = hub["huber_delta"]
+    assert ((hb["rho"][:, 1] < 1) & (d_hub > 0)).any() and ((hb["rho"][:, 1] == 1) & (d_hub > 0)).any() and (d_hub <= 0).any()
+    assert np.array_equal(hb["rho"][d_hub <= 0], np.stack([hb["chi2"][d_hub <= 0], np.ones((d_hub <= 0).sum())], 1))
+    assert np.allclose(hb["rho"], rho, rtol=1e-9, atol=1e-12)
+    dR = max(np.abs(S.quat_to_R(o[:4]) - R).max() for o, R in zip(oplus, R_ref))
+    dt = np.abs(oplus[:, 4:] - t_ref).max()
+    print(f"host pose_oplus vs reference: R {dR:.2e}  t {dt:.2e}")
+    assert dR < 1e-11 and dt < 1e-11
+    assert np.abs(np.linalg.norm(oplus[:, :4], axis=1) - 1).max() < 1e-15 and (oplus[:, 3] >= 0).all()
+
+
 # ---- GPU ------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture
 def ctx():
@@ -186,7 +271,7 @@ def test_device_se3_oplus_matches_reference_and_oracle(orc, ctx, oplus_table):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(S.GAUGES))
 def test_device_ba_edges_on_gauged_problems(orc, ctx, gauged, name):
-    """k_ba_edges / edge_terms with every product term of the rotation matrix non-zero (every |q_i| > 0.01, asserted): against the
+    """k_ba_edges (the edge model of ba_edge_dev.h) with every product term of the rotation matrix non-zero (every |q_i| > 0.01, asserted): against the
     oracle at the tolerances of test_ba_edges_match_oracle, against the 40-digit reference at 1e-11 (issue), and q against -q."""
     p, ref = gauged[name]
     _assert_general(p["poses"])
@@ -203,8 +288,8 @@ def test_device_ba_edges_on_gauged_problems(orc, ctx, gauged, name):
 
 @pytest.mark.gpu
 def test_device_ba_build_system_on_a_gauged_problem(orc, ctx):
-    """k_ba_pose_blocks / k_ba_point_blocks on general rotations; a free pose with more than 64 edges and one with fewer (asserted):
-    both trip counts of the lane-stride loop.  Against the oracle at the tolerances of test_ba_normal_equation_blocks_match_oracle,
+    """k_lm_linpoints / k_lm_poseblocks (k_lm.hip, what orbfe_ba_build_system launches) on general rotations; a free pose with more than
+    64 edges and one with fewer (asserted).  Against the oracle at the tolerances of test_ba_normal_equation_blocks_match_oracle,
     and H_ll / H_pp against blocks assembled in numpy from the 40-digit Jacobians and the oracle's rho (issue: rtol 1e-9, atol 1e-7)."""
     p = S.gauge(ba_synth.make_problem(n_kf=6, n_pt=120), *S.GAUGES["skew"])
     _assert_general(p["poses"])
@@ -229,6 +314,55 @@ def test_device_ba_build_system_on_a_gauged_problem(orc, ctx):
         if not fixed[p["edge_pose"][e]]:
             Hpp[p["edge_pose"][e]] += w[e] * B.T @ B
     assert np.allclose(out["Hll"], Hll, rtol=1e-9, atol=1e-7) and np.allclose(out["Hpp"], Hpp, rtol=1e-9, atol=1e-7)
+
+
+def _skew_with_pose_0_fixed(gauged):
+    """the 'skew' world (6 keyframes, 40 points, mono and stereo edges: asserted), pose 0 fixed -> problem, stereo mask, fixed flags"""
+    p = gauged["skew"][0]
+    st = p["is_stereo"] != 0
+    assert st.any() and (~st).any()
+    fixed = np.zeros(len(p["poses"]), np.uint8)
+    fixed[0] = 1
+    return p, st, fixed
+
+
+@pytest.mark.gpu
+def test_device_entry_points_share_one_edge_model(ctx, gauged):
+    """k_lm_linpoints (ba_build_system) and k_ba_edges (ba_eval_edges) run the same edge arithmetic (ba_edge_dev.h): Hpl(e) = B^T W A of
+    the system equals, bit for bit, the block assembled here from ba_eval_edges' Jacobians, rho' and the information in the kernel's own
+    order, h = 0; for r < rows: h += (j_pose[e, r, a] * w) * j_point[e, r, c]; and it is zero for the fixed pose's edges."""
+    p, st, fixed = _skew_with_pose_0_fixed(gauged)
+    ev = ctx.ba_eval_edges(**_edge_args(p))
+    Hpl = ctx.ba_build_system(**_edge_args(p), pose_fixed=fixed)["Hpl"]
+    w = ev["rho"][:, 1] * p["info"]
+    rows = np.where(st, 3, 2)
+    ref = np.zeros_like(Hpl)
+    for a in range(6):
+        for c in range(3):
+            h = np.zeros(w.size)
+            for r in range(3):
+                h = np.where(r < rows, h + (ev["j_pose"][:, r, a] * w) * ev["j_point"][:, r, c], h)
+            ref[:, a, c] = h
+    of_fixed = fixed[p["edge_pose"]] != 0
+    assert of_fixed.any() and (~of_fixed & st).any() and (~of_fixed & ~st).any()
+    ref[of_fixed] = 0.0
+    off = (Hpl != ref).any((1, 2))
+    print(f"Hpl vs blocks from ba_eval_edges: {int(off.sum())} of {w.size} edges differ ({int((off & ~st).sum())} mono), "
+          f"worst {np.abs(Hpl - ref).max():.2e}")
+    assert np.array_equal(Hpl, ref) and not Hpl[of_fixed].any() and all(Hpl[e].any() for e in np.flatnonzero(~of_fixed))
+
+
+@pytest.mark.gpu
+def test_device_final_report_is_the_edge_evaluation(ctx, gauged):
+    """k_lm_final against k_ba_edges: with no iterations the report of ba_local_optimize is ba_eval_edges' chi2 bit for bit, and
+    bad == (chi2 > 7.815 / 5.991) | ~depth_positive; the estimates come back untouched."""
+    p, st, fixed = _skew_with_pose_0_fixed(gauged)
+    ev = ctx.ba_eval_edges(**_edge_args(p))
+    g = ctx.ba_local_optimize(p, fixed, 0, 0)
+    assert tuple(g["iters"]) == (0, 0)
+    assert np.array_equal(g["chi2"], ev["chi2"])
+    assert np.array_equal(g["bad"] != 0, (ev["chi2"] > np.where(st, 7.815, 5.991)) | (ev["depth_positive"] == 0))
+    assert np.array_equal(g["poses"], p["poses"]) and np.array_equal(g["points"], p["points"])
 
 
 # (seed, n) as test_device_optimiser_matches_oracle: the 256-thread register kernel up to 1024 edges, the 512-thread one up to 2048, the
@@ -265,8 +399,9 @@ def test_device_pose_only_on_gauged_problems(orc, ctx, seed, n, kernel, gauge, v
     (3, 12, 400, 2, "skew", "registers"), (3, 12, 400, 2, "near_y", "registers"), (14, 48, 2000, 5, "skew", "lmbig"),
     (3, 12, 400, 2, "skew", "host_lm")])
 def test_device_local_ba_on_gauged_problems(orc, monkeypatch, seed, n_kf, n_pt, n_fixed, gauge, path):
-    """k_lba's Jacobians and pose_oplus inside the register-resident Levenberg-Marquardt (k_lm: at most 42 free keyframes), the blocked
-    one (k_lmbig: more than 42, asserted) and the host-driven loop (ORBFE_LBA_HOST_LM=1, read at orbfe_create), every pose -- the fixed
+    """k_lm_linpoints' Jacobians (ba_edge_dev.h) and pose_oplus inside the register-resident Levenberg-Marquardt (k_lm: at most 42 free
+    keyframes), the blocked one (k_lmbig: more than 42, asserted) and the host-driven loop (ORBFE_LBA_HOST_LM=1, read at orbfe_create: the
+    same builders, k_lba's solve and k_lba_update's pose_oplus), every pose -- the fixed
     ones included -- with four large quaternion components (asserted).  Asserts of test_device_local_ba_matches_oracle."""
     from orb_slam2_ros2_amd._lib import Context
     pr, fixed = _problem(seed, n_kf, n_pt, n_fixed)

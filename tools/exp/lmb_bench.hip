@@ -112,19 +112,6 @@ int main(int argc, char** argv) {
     }
     printf("  back substitution, one workgroup per tile column %.3f ms\n", bb);
   }
-  {  // the back substitution alone (L and y are in place; it only reads them)
-    float bb = 1e9;
-    for (int rep = 0; rep < 5; ++rep) {
-      hipEventRecord(e0, 0);
-      hipLaunchKernelGGL(k_lmb_back, dim3(1), dim3(1024), (size_t)(ld + LMB_T + LMB_T * LMB_LS + 3 * 16 * LMB_IS) * sizeof(double), 0, n, KT, ld, dM, dinv, dst, dfl, dx);
-      hipEventRecord(e1, 0);
-      hipEventSynchronize(e1);
-      float ms;
-      hipEventElapsedTime(&ms, e0, e1);
-      bb = std::min(bb, ms);
-    }
-    printf("  back substitution alone %.3f ms\n", bb);
-  }
   std::vector<double> xg(n);
   hipMemcpy(xg.data(), dx, n * 8, hipMemcpyDeviceToHost);
   hipMemcpy(&st, dst, sizeof st, hipMemcpyDeviceToHost);
