@@ -851,6 +851,50 @@ orbfe_status orbfe_create_new_map_points_stored(orbfe_ctx* ctx, orbfe_kfstore* s
                                                 float bl, const float* scale_factors, int32_t n_levels, orbfe_tri_record* records, int64_t cap,
                                                 int64_t* n_records, int32_t* tail, int64_t tail_cap, int64_t* n_tail, uint8_t* consumed);
 
+/* ---- searchByBow over stored keyframes --------------------------------------------------------------------------------
+ * ORBMatcher::searchByBow(pFrame, pKframe, matches, bAddMPs, bLoop) (src/ORBMatcher.cc:170-253) with verifyAngle (:1013-1051) of ONE
+ * query frame against n_kf keyframes of a store in one call: what Tracking::filterKFByBow (src/Tracking.cc:446-490) runs once per
+ * relocalisation candidate and LoopClosing::computeSim3 (src/LoopClosing.cc:308-326) once per loop candidate.  The candidates are named
+ * by id and read where the store keeps them (features, angles, FeatureVector); the query is a stored keyframe too (from_store) or host
+ * arrays (a Frame).  Map state is an argument: one flag byte per feature on either side.
+ * For every candidate k, matches[match_offsets[k] .. match_offsets[k + 1]) is exactly the std::vector<cv::DMatch> the reference leaves,
+ * element for element and in its order:
+ *   walk        common nodes ascending; inside a node the keyframe's features in FeatureVector order
+ *   filter      by mode (ORBFE_BOW_*), on the keyframe feature and on the node's query features; an empty candidate list: no match
+ *   best match  getBestMatch (:967-990): first minimum (strict <); the second best is never an earlier record, INT_MAX with one candidate
+ *   test        rejected iff best > dist_threshold || (float)best / (float)second > ratio (0 / 0 is accepted)
+ *   queryIdx    no uniqueness check: several matches may name one query feature
+ *   orientation check_orientation: diff = angle_q - angle_t in float, negative: 360 + diff; bin (int)(diff / 12.f), bin 30 -> 0; three
+ *               rounds of "first strictly largest remaining bin" (empty bins never); output: the chosen bins ascending, inside a bin
+ *               the order above.  (Angles no extractor gives -- NaN, a difference of 360 and more -- count as bin 0.)
+ * Side effects on map points (setMapPoints, addMatchInTrack) stay with the caller.
+ * match_offsets [n_kf + 1] is always set in full; a total beyond cap: ORBFE_ECAPACITY, nothing written to matches.  ORBFE_EBADARG, nothing
+ * written: an unknown id, a keyframe without FeatureVector, n_kf outside 0 .. ORBFE_BOW_SEARCH_MAX_KF, an unknown mode, a malformed query
+ * FeatureVector (orbfe_kfstore_set_bow's checks), n unequal to the stored count.  n_kf == 0: ORBFE_OK.  An id may appear twice, and the
+ * query's own id may be among the candidates.  Locks: the context's, then the store's (shared) for the whole synchronous duration.  One
+ * upload (records, flags, a host query's arrays), three launches, one download.                                                      */
+#define ORBFE_BOW_SEARCH_MAX_KF 64
+#define ORBFE_BOW_TRACK 0  /* bAddMPs = false, bLoop = false: keyframe features with a good point, frame features WITHOUT one */
+#define ORBFE_BOW_LOOP  1  /* bLoop: no filter on either side                                                                */
+#define ORBFE_BOW_ADD   2  /* bAddMPs: on both sides, features whose point is good AND in the map are left out             */
+typedef struct orbfe_bow_query {
+  int32_t from_store;          /* 1: the stored keyframe `id` (it needs a FeatureVector); desc / angle / the CSR below are ignored */
+  uint64_t id;
+  int32_t n;                   /* features; from_store: must equal the stored count                                       */
+  const uint8_t* desc;         /* [n][32]                                                                                 */
+  const float* angle;          /* [n] cv::KeyPoint::angle; may be NULL when check_orientation is 0                        */
+  int32_t n_nodes;             /* the FeatureVector in orbfe_bow_out's layout                                             */
+  const uint32_t* nodes;
+  const int32_t* node_offsets;
+  const uint32_t* features;
+  const uint8_t* flags;        /* [n] ORBFE_TRI_GOOD | ORBFE_TRI_INMAP; NULL: all 0 (setMapPointsNull())                  */
+} orbfe_bow_query;
+typedef struct orbfe_bow_match { int32_t query, train, distance; } orbfe_bow_match;   /* cv::DMatch(queryIdx, trainIdx, distance) */
+orbfe_status orbfe_search_by_bow_stored(orbfe_ctx* ctx, orbfe_kfstore* store, const orbfe_bow_query* q, int32_t n_kf,
+                                        const uint64_t* kf_ids, const uint8_t* const* kf_flags /*[n_kf], each [n_k] or NULL = all 0*/,
+                                        int32_t mode, float ratio, int32_t dist_threshold, int32_t check_orientation,
+                                        orbfe_bow_match* matches, int64_t cap, int64_t* match_offsets /*[n_kf + 1]*/);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

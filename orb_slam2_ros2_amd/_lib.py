@@ -153,6 +153,14 @@ class TriState(C.Structure):
                 ("unproc", C.c_void_p), ("unproc_pos", C.c_void_p)]
 
 
+class BowQuery(C.Structure):
+    _fields_ = [("from_store", C.c_int32), ("id", C.c_uint64), ("n", C.c_int32), ("desc", C.c_void_p), ("angle", C.c_void_p),
+                ("n_nodes", C.c_int32), ("nodes", C.c_void_p), ("node_offsets", C.c_void_p), ("features", C.c_void_p), ("flags", C.c_void_p)]
+
+
+BOW_MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4")])
+BOW_SEARCH_MAX_KF = 64
+BOW_TRACK, BOW_LOOP, BOW_ADD = 0, 1, 2
 FUSE_MAX_KF = 64
 TRI_REC_DTYPE = np.dtype([("nb", "<i4"), ("q", "<i4"), ("t", "<i4"), ("kind", "<i4"), ("xyz", "<f4", (3,))])
 TRI_MAX_NB = 64
@@ -177,7 +185,7 @@ EXPORTS = [
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
-    "orbfe_create_new_map_points_stored",
+    "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
 ]
 BOW_MAX_FEATURES = 65535
@@ -305,6 +313,7 @@ def load() -> C.CDLL:
                                                    f32, i32, vp, vp, vp]
     L.orbfe_create_new_map_points_stored.argtypes = [vp, vp, u64, C.POINTER(TriState), i32, vp, vp, C.POINTER(Camera), vp, f32, vp, i32, vp, i64,
                                                      C.POINTER(i64), vp, i64, C.POINTER(i64), vp]
+    L.orbfe_search_by_bow_stored.argtypes = [vp, vp, C.POINTER(BowQuery), i32, vp, vp, i32, f32, i32, i32, vp, i64, vp]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -1535,6 +1544,74 @@ class Context:
         self.last_counts = (nr.value, nt.value)
         self._check(st)
         return recs[:nr.value].copy(), tail[:nt.value].copy(), consumed[:n].astype(bool)
+
+    def search_by_bow_stored(self, store, query, kf_ids, kf_flags, mode, ratio, dist_threshold, check_orientation, cap=None):
+        """ORBMatcher::searchByBow of one query against the keyframes kf_ids of `store` in one call (orbfe_search_by_bow_stored).
+        query: an int (the id of a stored keyframe) or a dict(id=..., flags=...) for a stored query, else dict(desc [n, 32], fv = (nodes,
+        offsets, features), angle [n] (needed with check_orientation), flags [n] or None).  kf_flags: None or one entry per candidate
+        ([n_k] uint8 ORBFE_TRI_GOOD | ORBFE_TRI_INMAP, or None = all 0).  mode: BOW_TRACK / BOW_LOOP / BOW_ADD.  cap None: room for
+        every FeatureVector entry of the candidates.  Returns a list of per-candidate BOW_MATCH_DTYPE arrays; self.last_bow_offsets
+        holds match_offsets (also after an ECAPACITY failure)."""
+        keep = []
+
+        def arr(a, dt, shape=None):
+            a = np.ascontiguousarray(a, dt)
+            if shape is not None:
+                a = a.reshape(shape)
+            keep.append(a)
+            return a
+
+        q = BowQuery()
+        if not isinstance(query, dict):
+            query = dict(id=int(query))
+        fl = None if query.get("flags") is None else arr(query["flags"], np.uint8)
+        if "desc" not in query:
+            q.from_store, q.id = 1, int(query["id"])
+            q.n = len(fl) if fl is not None else store.info(q.id)["n"]
+        else:
+            d = arr(query["desc"], np.uint8, (-1, 32))
+            nodes, offs, feats = query["fv"]
+            nd, of, ft = arr(nodes, np.uint32), arr(offs, np.int32), arr(feats, np.uint32)
+            if len(of) != len(nd) + 1 or (0 <= of[-1] and of[-1] > len(ft)):
+                raise ValueError("search_by_bow_stored: node_offsets must have len(nodes) + 1 entries ending inside features")
+            q.from_store, q.n, q.desc = 0, len(d), ptr(d).value
+            if query.get("angle") is not None:
+                an = arr(query["angle"], np.float32)
+                if len(an) != len(d):
+                    raise ValueError("search_by_bow_stored: one angle per query feature")
+                q.angle = ptr(an).value
+            q.n_nodes, q.nodes, q.node_offsets, q.features = len(nd), ptr(nd).value, ptr(of).value, ptr(ft).value
+            if fl is not None and len(fl) != len(d):
+                raise ValueError("search_by_bow_stored: one flag per query feature")
+        if fl is not None:
+            q.flags = ptr(fl).value
+        ids = arr(kf_ids, np.uint64).reshape(-1)
+        K = len(ids)
+        kf_flags = [None] * K if kf_flags is None else list(kf_flags)
+        if len(kf_flags) != K:
+            raise ValueError("search_by_bow_stored: one flags entry (or None) per candidate")
+        fp = (C.c_void_p * max(K, 1))()
+        for i, f in enumerate(kf_flags):
+            fp[i] = None if f is None else ptr(arr(f, np.uint8)).value
+        if cap is None:
+            cap = 0
+            if K <= BOW_SEARCH_MAX_KF:                       # (more: the call refuses; nothing to size)
+                sizes = {}
+                for i in ids.tolist():
+                    if i not in sizes:
+                        o = KfstoreInfo()
+                        sizes[i] = o.n_bow_features if self.lib.orbfe_kfstore_info_get(store.h, i, C.byref(o)) == ORBFE_OK else 0
+                cap = sum(sizes[i] for i in ids.tolist())
+        cap = int(cap)
+        out = np.zeros(max(cap, 1), BOW_MATCH_DTYPE)
+        offs = np.full(K + 1, -1, np.int64)
+        self._bow_search_args = (self.h, store.h, C.byref(q), K, ptr(ids), C.cast(fp, C.c_void_p), int(mode), float(ratio), int(dist_threshold),
+                                 int(bool(check_orientation)), ptr(out), cap, ptr(offs))
+        self._bow_search_keep = (keep, q, ids, fp, out, offs)
+        st = self.lib.orbfe_search_by_bow_stored(*self._bow_search_args)
+        self.last_bow_offsets, self.last_bow_matches = offs, out
+        self._check(st)
+        return [out[offs[k]:offs[k + 1]].copy() for k in range(K)]
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

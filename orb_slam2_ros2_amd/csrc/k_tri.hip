@@ -1,7 +1,7 @@
 // k_tri.hip -- LocalMapping::createNewMapPoints (src/LocalMapping.cc:165-285) for one current keyframe and its neighbours.
 //
 // k_tri_match    one wave per (neighbour, FeatureVector entry j): the entry's node in the current keyframe's FeatureVector, the
-//                bAddMPs filters, getBestMatch over the node's current features (match_fold.h), the threshold / ratio test
+//                bAddMPs filters, getBestMatch over the node's current features (bow_walk.h, match_fold.h), the threshold / ratio test
 //                (searchByBow, ORBMatcher.cc:170-253), the mutual epipolar test (searchForTriangulation, :736-793), then the parallax
 //                cosines, the three-way branch, triangulate / unProject and checkMapPoint.  Out: one TriSlot per entry; a slot that
 //                can change the map state counts itself for its current feature.
@@ -15,7 +15,7 @@
 // products summed left to right; dots and norms in double; the SVD decision: Jacobi eigen-decomposition of A^T A in double (jacobi_dev.h).
 #include <hip/hip_runtime.h>
 
-#include "match_fold.h"
+#include "bow_walk.h"
 #include "orbfe_internal.h"
 #include "wave_ops.h"
 
@@ -185,23 +185,8 @@ __global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ u
   const uint32_t pk = kf_feat(up, B)[j];
   int k = -1;
   if (!B.skip && (fl_b[pk] & 3) != 3) {
-    // the entry's node: the last i with offs[i] <= j
-    const int32_t* ob = kf_offs(up, B);
-    int lo = 0, hi = B.n_nodes - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (ob[mid] <= j) lo = mid;
-      else hi = mid - 1;
-    }
-    const uint32_t node = kf_nodes(up, B)[lo];
-    const uint32_t* nc = kf_nodes(up, C);
-    int a = 0, e = C.n_nodes;
-    while (a < e) {
-      const int mid = (a + e) >> 1;
-      if (nc[mid] < node) a = mid + 1;
-      else e = mid;
-    }
-    if (a < C.n_nodes && nc[a] == node) k = a;
+    const uint32_t node = kf_nodes(up, B)[bow_entry_node(kf_offs(up, B), B.n_nodes, j)];
+    k = bow_find_node(kf_nodes(up, C), C.n_nodes, node);
   }
   if (k >= 0) {
     const int32_t* oc = kf_offs(up, C);
@@ -211,22 +196,8 @@ __global__ __launch_bounds__(256) void k_tri_match(const uint8_t* __restrict__ u
     const uint4 a0 = *(const uint4*)qd, a1 = *(const uint4*)(qd + 16);
     const int begin = oc[k], end = oc[k + 1];
     Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
-    int ncand = 0;
-    for (int c0 = begin; c0 < end; c0 += 64) {
-      const int c = c0 + lane;
-      int d = ORB_INT_MAX, idx = 0;
-      bool has = false;
-      if (c < end) {
-        const uint32_t f = fc[c];
-        if ((fl_c[f] & 3) != 3) {  // bAddMPs: current features with a good in-map point are no candidates
-          idx = (int)f;
-          d = hamming256(a0, a1, dc + (size_t)f * 32);
-          has = true;
-        }
-      }
-      ncand += __popcll(__ballot(has));
-      fold_chunk(b, d, idx, lane);
-    }
+    // bAddMPs: current features with a good in-map point are no candidates
+    const int ncand = bow_fold_node(b, a0, a1, fc, begin, end, dc, fl_c, SkipGoodInMap(), lane);
     const float ratio = (float)b.min_d / (float)b.second;
     if (ncand > 0 && !(b.min_d > TRI_MIN_TH || ratio > TRI_RATIO)) {
       const int q = b.min_idx;

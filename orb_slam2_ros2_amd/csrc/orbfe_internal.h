@@ -361,3 +361,42 @@ struct TriKfStored {
   int32_t n, n_nodes, n_feat, slot0, skip, pad;
   float Tcw[16], Twc[16];
 };
+
+// ---- searchByBow over stored keyframes (k_bowsearch.hip, orbfe_bowsearch.hip) -------------------------------------------------------
+// One candidate keyframe of the call: its arrays where the keyframe store keeps them, its flags at o_flags of the call's upload; its
+// FeatureVector entry j is match slot slot0 + j.
+struct BowKf {
+  const orbfe_keypoint* kps;
+  const uint8_t* desc;
+  const uint32_t* nodes;
+  const int32_t* offs;
+  const uint32_t* feat;
+  uint32_t o_flags;
+  int32_t n_nodes, n_feat, slot0;
+};
+// The query in its two forms: host arrays behind the call's upload, or a stored keyframe.  The flags are in the upload in both.
+struct BowQuery {
+  uint32_t o_desc, o_angle, o_nodes, o_offs, o_feat, o_flags;
+  int32_t n_nodes;
+};
+struct BowQueryStored {
+  const orbfe_keypoint* kps;
+  const uint8_t* desc;
+  const uint32_t* nodes;
+  const int32_t* offs;
+  const uint32_t* feat;
+  uint32_t o_flags;
+  int32_t n_nodes;
+};
+struct BowParams {
+  int32_t mode, dist_threshold, check_orientation, n_kf;
+  float ratio;
+  int32_t cap;  // matches the download has room for
+};
+// a match slot after k_bow_match: q = the query feature (-1: no match), the keyframe feature, the distance, verifyAngle's bin (0 without it)
+struct BowSlot {
+  int32_t q, t, d, bin;
+};
+struct BowMatch {
+  int32_t q, t, d;
+};

@@ -252,6 +252,14 @@ class ORBMatcher(MatcherExt):
             matches = self.verifyAngle(matches, angles_f, angles_kf)
         return matches
 
+    def searchByBowStored(self, ctx, store, query, kf_ids, kf_flags, bAddMPs=False, bLoop=False):
+        """searchByBow of one query against the stored keyframes kf_ids in ONE device call (Context.search_by_bow_stored; what
+        Tracking::filterKFByBow and LoopClosing::computeSim3 run once per candidate), with this matcher's mfRatio, mnMinThreshold and
+        mbCheckOri.  Returns one list [(frame idx, keyframe idx, distance)] per candidate, each equal to searchByBow's."""
+        mode = _lib.BOW_ADD if bAddMPs else _lib.BOW_LOOP if bLoop else _lib.BOW_TRACK
+        out = ctx.search_by_bow_stored(store, query, kf_ids, kf_flags, mode, self.mfRatio, self.mnMinThreshold, self.mbCheckOri)
+        return [[(int(m["query"]), int(m["train"]), int(m["distance"])) for m in a] for a in out]
+
     @classmethod
     def verifyAngle(cls, matches, angles1, angles2):
         """ORBMatcher::verifyAngle (ORBMatcher.cc:1013-1051): 30-bin histogram of angle differences (float arithmetic), the three

@@ -195,6 +195,11 @@ template <class FramePtr>
 static const auto& featVec(const FramePtr& f) {
   return f->mFeatVec;
 }
+// the map-point slots of a frame (VirtualFrame::mvpMapPoints), which setMapPoints writes, for the batched searchByBow (orbfe_reloc_dropin.hpp)
+template <class FramePtr>
+static auto& mapPointSlots(const FramePtr& f) {
+  return f->mvpMapPoints;
+}
 
 // int ORBMatcher::searchByStereo(Frame::SharedPtr pFrame)  (src/ORBMatcher.cc:18-81).  Uses pFrame->mvFeatsLeft, mvDepths, mvFeatsRightU,
 // mpExtractorLeft / mpExtractorRight (ORBMatcher is a friend of Frame, Frame.h:302-303) and Camera::mfFx / mfBf.

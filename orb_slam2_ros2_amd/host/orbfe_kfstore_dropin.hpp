@@ -137,6 +137,17 @@ class KeyframeStore {
     }
     if (!i.has_bow) setBow(pKf);
   }
+  // present with its FeatureVector, for the batched searchByBow (orbfe_reloc_dropin.hpp), which reads no stereo column: an entry the fuse
+  // inserted only gets its FeatureVector
+  template <class KeyFramePtr>
+  void ensureBow(const KeyFramePtr& pKf) {
+    orbfe_kfstore_info i;
+    if (!info(pKf, &i)) {
+      addMapping(pKf);
+      i.has_bow = 0;
+    }
+    if (!i.has_bow) setBow(pKf);
+  }
 
  private:
   static void check(orbfe_status st, const char* what, orbfe_ctx* ctx) {
