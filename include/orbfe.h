@@ -692,6 +692,50 @@ orbfe_status orbfe_pnp_iterate(orbfe_pnp* set, int32_t problem, int32_t n_iterat
 orbfe_status orbfe_pnp_engine(uint32_t* get, const uint32_t* set);
 orbfe_status orbfe_pnp_stats(orbfe_pnp* set, int64_t* launches, int64_t* hypotheses);
 
+/* ---- Sim3 RANSAC (Sim3Solver + Ransac<Sim3Ret>, src/Sim3Solver.cc, include/ORB_SLAM2/Sim3Solver.h, Ransac.hpp) ---------------------
+ * One orbfe_sim3 set holds the Sim3 problems of one LoopClosing::computeSim3 call (src/LoopClosing.cc:300-415) -- one per loop
+ * candidate, in the order its first loop creates the solvers -- on ONE device: problem i has the correspondences
+ * [offsets[i], offsets[i + 1]) (0 .. ORBFE_BOW_MAX_FEATURES of them) of pos_p / pos_q (the world positions of the two map points),
+ * octave_p / octave_q (the two keypoints' octaves, 0 .. n_levels - 1, the thresholds (float)(9.210 * level_sigma2[octave])) and the
+ * keyframe poses pose_p[i] / pose_q[i] (Rpw row-major, then tpw; likewise q).  create is Sim3Solver's constructor
+ * (Sim3Solver.cc:162-206) after its vbChoose filter, which stays with the caller (:173-182): p3d = Rpw * pos + tpw, Camera::project,
+ * setRansacParams.  params NULL: max 100 iterations, ratio 0.4, probability 0.99; min_set must be 3 and the scale is fixed, as
+ * Sim3Solver::create forces both (Sim3Solver.h:71-76, S1).  One upload.
+ *   iterate  Ransac::iterate(n_iterations, modelRet, bNoMore, vnInlierIndices) (Ransac.hpp:63-103) of one problem, exactly (DESIGN 4.21,
+ *            S1-S7) over Sim3Solver::modelFunc (:24-148, Horn) and checkInliers / computeError (:215-259): model (Rqp row-major, then
+ *            tqp; mfS is 1) and has_model (0: the empty cv::Mats) are in / out, as are inliers[0 .. *n_inliers) (problem-local
+ *            indices); both end as the reference leaves them -- untouched when no hypothesis ran.  *no_more is only ever set to 1;
+ *            *ret the return value.  cap: room in inliers; a longer result is ORBFE_ECAPACITY with *n_inliers the size needed and
+ *            nothing changed.  A call that is not the predicted one (another problem or n, an engine moved since) starts a new
+ *            speculation: the schedule computeSim3 runs -- round-robin over the live problems, ascending, n_iterations each, no
+ *            refine success -- in one upload, ONE launch and one download, replayed call by call from then on.  A problem the caller
+ *            leaves out where the schedule had it (a candidate computeSim3 discards after making its solver) is left out of later
+ *            schedules until it is called.  Speculation only changes the speed, never a result.
+ *   engine   Ransac<Sim3Ret>'s own static std::default_random_engine (default seed: state 1), apart from orbfe_pnp_engine's: get and
+ *            / or set its state (1 .. 2^31 - 2).  One lock serialises this engine and every Sim3 set's iterate.
+ *   stats    launch sequences and hypotheses evaluated on the device so far.
+ *   profile  enable > 0 puts two events around every launch from then on, 0 stops that, < 0 leaves it; device_us (NULL: not wanted) is
+ *            the time between those events so far, bytes_uploaded (NULL: not wanted) what create and every speculation sent up.
+ * Errors: ORBFE_EBADARG (NULL pointers, problem out of range, octave out of range, min_set != 3, engine state out of range),
+ * ORBFE_EDEVICE (no device, HIP failure), ORBFE_ENOMEM, ORBFE_ECAPACITY (inliers too small).                                          */
+typedef struct orbfe_sim3 orbfe_sim3;
+typedef struct orbfe_sim3_params {
+  int32_t min_set;        /* mnMinSet (3)          */
+  int32_t max_iterations; /* nMaxIterations (100)  */
+  float ratio;            /* fRatio (0.4)          */
+  float prob;             /* fProb (0.99)          */
+} orbfe_sim3_params;
+orbfe_status orbfe_sim3_create(int32_t device_id, int32_t n_problems, const int64_t* offsets /*[n_problems + 1]*/, const float* pos_p /*[N][3]*/,
+                               const float* pos_q /*[N][3]*/, const int32_t* octave_p /*[N]*/, const int32_t* octave_q /*[N]*/,
+                               const float* pose_p /*[n_problems][12]*/, const float* pose_q /*[n_problems][12]*/, const float* level_sigma2,
+                               int32_t n_levels, const orbfe_camera* cam /* fx fy cx cy */, const orbfe_sim3_params* params, orbfe_sim3** out);
+void orbfe_sim3_destroy(orbfe_sim3* set);  /* no call on the set may still run */
+orbfe_status orbfe_sim3_iterate(orbfe_sim3* set, int32_t problem, int32_t n_iterations, float* model /*[12] in/out*/, int32_t* has_model,
+                                int32_t* inliers, int64_t* n_inliers, int64_t cap, int32_t* ret, int32_t* no_more);
+orbfe_status orbfe_sim3_engine(uint32_t* get, const uint32_t* set);
+orbfe_status orbfe_sim3_stats(orbfe_sim3* set, int64_t* launches, int64_t* hypotheses);
+orbfe_status orbfe_sim3_profile(orbfe_sim3* set, int32_t enable, double* device_us, int64_t* bytes_uploaded);
+
 /* ---- new map points of a keyframe (LocalMapping::createNewMapPoints, src/LocalMapping.cc:165-285) ---------------------------------
  * One call runs loop 1 and loop 2 of createNewMapPoints for the current keyframe `cur` against the neighbours nbs[0 .. n_nb) IN THE
  * GIVEN ORDER (the reference's std::map order, T2): searchForTriangulation (searchByBow with bAddMPs, ratio 0.6, threshold 50, no

@@ -182,6 +182,7 @@ EXPORTS = [
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_set_bad", "orbfe_kfdb_erase", "orbfe_kfdb_size", "orbfe_kfdb_query",
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
+    "orbfe_sim3_create", "orbfe_sim3_destroy", "orbfe_sim3_iterate", "orbfe_sim3_engine", "orbfe_sim3_stats", "orbfe_sim3_profile",
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
@@ -294,6 +295,13 @@ def load() -> C.CDLL:
     L.orbfe_pnp_iterate.argtypes = [vp, i32, i32, vp, C.POINTER(i32), vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(i32), C.POINTER(i32)]
     L.orbfe_pnp_engine.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.orbfe_pnp_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.orbfe_sim3_create.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(Camera), C.POINTER(Sim3Params), C.POINTER(vp)]
+    L.orbfe_sim3_destroy.argtypes = [vp]
+    L.orbfe_sim3_destroy.restype = None
+    L.orbfe_sim3_iterate.argtypes = [vp, i32, i32, vp, C.POINTER(i32), vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(i32), C.POINTER(i32)]
+    L.orbfe_sim3_engine.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.orbfe_sim3_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.orbfe_sim3_profile.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.orbfe_create_new_map_points.argtypes = [vp, C.POINTER(TriKf), i32, vp, C.POINTER(Camera), vp, f32, vp, i32, vp, C.c_int64,
                                               C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64), vp]
     L.orbfe_fuse_into_keyframes.argtypes = [vp, C.POINTER(FuseKf), C.POINTER(FusePoints), i32, vp, vp, C.POINTER(Camera), f32, vp, i32, f32, f32,
@@ -526,6 +534,100 @@ def pnp_engine(state=None):
     g = C.c_uint32(0)
     s = None if state is None else C.c_uint32(int(state))
     st = L.orbfe_pnp_engine(C.byref(g), None if s is None else C.byref(s))
+    if st != ORBFE_OK:
+        raise OrbfeError(st, L.orbfe_last_error(None).decode())
+    return g.value
+
+
+class Sim3Params(C.Structure):
+    _fields_ = [("min_set", C.c_int32), ("max_iterations", C.c_int32), ("ratio", C.c_float), ("prob", C.c_float)]
+
+
+class Sim3Set:
+    """The Sim3Solvers of one LoopClosing::computeSim3 call on one device (orbfe_sim3, include/orbfe.h): problem i has the
+    correspondences [offsets[i], offsets[i + 1]) of pos_p / pos_q (world positions of the two map points) and octave_p / octave_q, and
+    the keyframe poses pose_p[i] / pose_q[i] (12 floats: R row-major, then t).  cam = (fx, fy, cx, cy); params = (min_set,
+    max_iterations, ratio, prob) or None for Sim3Solver::create's defaults (min_set must be 3)."""
+
+    def __init__(self, offsets, pos_p, pos_q, octave_p, octave_q, pose_p, pose_q, level_sigma2, cam, params=None, device_id=0):
+        self.lib = load()
+        o = np.ascontiguousarray(offsets, np.int64)
+        xp = np.ascontiguousarray(pos_p, np.float32).reshape(-1, 3)
+        xq = np.ascontiguousarray(pos_q, np.float32).reshape(-1, 3)
+        op = np.ascontiguousarray(octave_p, np.int32).reshape(-1)
+        oq = np.ascontiguousarray(octave_q, np.int32).reshape(-1)
+        tp = np.ascontiguousarray(pose_p, np.float32).reshape(-1, 12)
+        tq = np.ascontiguousarray(pose_q, np.float32).reshape(-1, 12)
+        s2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(o) < 1 or o[-1] != len(xp) or len(xq) != len(xp) or len(op) != len(xp) or len(oq) != len(xp):
+            raise ValueError("Sim3Set: offsets must end at len(pos_p) == len(pos_q) == len(octave_p) == len(octave_q)")
+        if len(tp) != len(o) - 1 or len(tq) != len(o) - 1:
+            raise ValueError("Sim3Set: one pose_p and one pose_q per problem")
+        self.sizes = np.diff(o)
+        cm = Camera(*(float(v) for v in cam), 0, 0, 0, 0, 0, 0)
+        pp = None if params is None else C.byref(Sim3Params(*params))
+        h = C.c_void_p(None)
+        st = self.lib.orbfe_sim3_create(int(device_id), len(o) - 1, ptr(o), ptr(xp), ptr(xq), ptr(op), ptr(oq), ptr(tp), ptr(tq), ptr(s2),
+                                        len(s2), C.byref(cm), pp, C.byref(h))
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+        self.h = h
+
+    def _check(self, st):
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbfe_sim3_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def iterate(self, problem, n, model=None, inliers=None, cap=None):
+        """Ransac::iterate(n, modelRet, bNoMore, vnInlierIndices) of one problem: (ret, no_more, model float32[12] (Rqp row-major, then
+        tqp; the scale is 1) or None, inliers int32).  model / inliers: the entry state, returned untouched when no hypothesis ran."""
+        ent = np.zeros(0, np.int32) if inliers is None else np.ascontiguousarray(inliers, np.int32).reshape(-1)
+        size = int(self.sizes[problem]) if 0 <= int(problem) < len(self.sizes) else 0  # out of range: the library refuses it
+        cap = max(len(ent), size) + 1 if cap is None else int(cap)
+        buf = np.zeros(max(cap, 1), np.int32)
+        buf[:len(ent)] = ent
+        mz = np.zeros(12, np.float32)
+        has = C.c_int32(0)
+        if model is not None:
+            mz[:] = np.asarray(model, np.float32).reshape(12)
+            has.value = 1
+        k = C.c_int64(len(ent))
+        ret, nm = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.orbfe_sim3_iterate(self.h, int(problem), int(n), ptr(mz), C.byref(has), ptr(buf), C.byref(k), cap, C.byref(ret),
+                                                C.byref(nm)))
+        return bool(ret.value), bool(nm.value), (mz.copy() if has.value else None), buf[:k.value].copy()
+
+    def stats(self):
+        """(launch sequences, hypotheses evaluated on the device)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.orbfe_sim3_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def profile(self, enable=None):
+        """(device microseconds between the events around the launches, bytes uploaded by create and the speculations) so far;
+        enable True / False first starts / stops recording the events (None: leave)"""
+        t, b = C.c_double(0), C.c_int64(0)
+        self._check(self.lib.orbfe_sim3_profile(self.h, -1 if enable is None else int(bool(enable)), C.byref(t), C.byref(b)))
+        return t.value, b.value
+
+
+def sim3_engine(state=None):
+    """the process-wide Sim3 sampling engine's state (Ransac<Sim3Ret>'s own minstd_rand0, apart from pnp_engine's); with `state`, set
+    it first and return the old one"""
+    L = load()
+    g = C.c_uint32(0)
+    s = None if state is None else C.c_uint32(int(state))
+    st = L.orbfe_sim3_engine(C.byref(g), None if s is None else C.byref(s))
     if st != ORBFE_OK:
         raise OrbfeError(st, L.orbfe_last_error(None).decode())
     return g.value

@@ -1,5 +1,5 @@
 // jacobi_dev.h -- cyclic trig-free Jacobi for small symmetric matrices in fp64 on one lane (registers).  Restated bit for bit by
-// tests/pnp_restatement.py (jacobi); shared by k_pnp.hip and k_tri.hip.  Include inside the including file's namespace, with contraction off.
+// tests/pnp_restatement.py (jacobi); shared by k_pnp.hip, k_tri.hip and k_sim3.hip.  Include inside the including file's namespace, with contraction off.
 #pragma once
 
 #define JAC_SWEEPS 50      // Jacobi sweeps at most

@@ -294,6 +294,27 @@ struct PnpOut {
   float ref_pose[12];
 };
 
+// ---- Sim3 RANSAC (k_sim3.hip, orbfe_sim3.hip) -------------------------------------------------------------------------------------
+// One problem (Sim3Solver) of a set: its correspondences at [off, off + n) of the set's arrays, an inlier mask of `words` uint64 words,
+// mnMinInlier.
+struct Sim3Prob {
+  int32_t off, n, words, min_inlier;
+};
+// One hypothesis of a speculated schedule: three problem-local sample indices.  Its inlier mask sits at mask_off (in words) of the
+// hypothesis masks, its refine mask at the same place of the refine masks.
+struct Sim3Hyp {
+  int32_t prob, mask_off;
+  int32_t idx[3];
+  int32_t pad[3];
+};
+// What the device found for one hypothesis: the model (Rqp row-major, then tqp) and its count; where the count exceeds mnMinInlier
+// (refined = 1), refine's model and count.
+struct Sim3Out {
+  float model[12];
+  float ref_model[12];
+  int32_t count, refined, ref_count, pad;
+};
+
 // ---- new map points (k_tri.hip, orbfe_tri.hip) -----------------------------------------------------------------------------------
 // One keyframe of the call inside the upload: byte offsets of its arrays, its sizes and poses.  kf[0] is the current keyframe,
 // kf[1 + i] neighbour i; a neighbour's FeatureVector entry j is match slot slot0 + j.

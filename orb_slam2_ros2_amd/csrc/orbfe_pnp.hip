@@ -1,9 +1,8 @@
 // orbfe_pnp.hip -- host side of the EPnP RANSAC sets (include/orbfe.h): setRansacParams, the process-wide sampling engine, the speculated
 // schedule (one upload, two launches, one download) and the exact replay of every Ransac<PnPRet>::iterate call from its records.
 // The kernels: k_pnp.hip.
-#include <emmintrin.h>
-
 #include "orbfe_ctx.h"
+#include "ransac_host.h"
 
 void launch_pnp(hipStream_t st, const PnpHyp* hyps, int n_hyp, const PnpCall* calls, int n_calls, const PnpProb* probs, const float* xyz,
                 const float* uv, const float* thr, const float cam[4], const int* entry, PnpOut* out, uint64_t* masks, uint64_t* ref_masks,
@@ -15,41 +14,6 @@ namespace {
 // also serialises every set's iterate.
 std::mutex g_pnp_mu;
 uint32_t g_engine = 1;
-
-// minstd_rand0 and libstdc++'s uniform_int_distribution<size_t>(0, n - 1) (the scaling path: minstd's range is not 2^32 - 1)
-inline uint32_t minstd(uint32_t& x) {
-  x = (uint32_t)((uint64_t)x * 16807u % 2147483647u);
-  return x;
-}
-inline uint32_t uniform_int(uint32_t& x, uint32_t n) {
-  const uint64_t urngrange = 2147483645u, uerange = n;
-  const uint64_t scaling = urngrange / uerange, past = uerange * scaling;
-  uint64_t r;
-  do r = (uint64_t)minstd(x) - 1u;
-  while (r >= past);
-  return (uint32_t)(r / scaling);
-}
-void random_sample(uint32_t& x, uint32_t n, int32_t out[4]) {
-  int k = 0;
-  while (k != 4) {
-    const int32_t r = (int32_t)uniform_int(x, n);
-    bool seen = false;
-    for (int i = 0; i < k; ++i) seen |= out[i] == r;
-    if (!seen) out[k++] = r;
-  }
-}
-
-// setRansacParams(): its float / double mix, cvRound as cvtsd2si
-void ransac_params(int32_t N, const orbfe_pnp_params& p, int32_t* min_inlier, int32_t* max_it) {
-  *min_inlier = (int32_t)std::max((float)p.min_set, (float)N * p.ratio);
-  const float r = (float)*min_inlier / (float)N;
-  if (r >= 1) {
-    *max_it = 0;
-    return;
-  }
-  const double q = std::log(1 - p.prob) / std::log(1 - std::pow(r, p.min_set));
-  *max_it = std::min(p.max_iterations, _mm_cvtsd_si32(_mm_set_sd(q)));
-}
 
 struct Prob {
   int32_t off = 0, n = 0, words = 0, min_inlier = 0, max_it = 0;
@@ -76,10 +40,7 @@ struct orbfe_pnp {
   // device: the problems' points, thresholds and records
   float *d_xyz = nullptr, *d_uv = nullptr, *d_thr = nullptr;
   PnpProb* d_probs = nullptr;
-  uint8_t* d_io = nullptr;  // a speculation's upload, results and list scratch
-  size_t io_bytes = 0;
-  uint8_t* h_io = nullptr;  // its page-locked staging
-  size_t h_bytes = 0;
+  ransac::Io io;  // a speculation's upload, results and list scratch, and its page-locked staging
   // the speculation being replayed
   std::vector<CallRec> recs;
   size_t next = 0;
@@ -91,27 +52,7 @@ struct orbfe_pnp {
 
 namespace {
 
-orbfe_status io_reserve(orbfe_pnp* s, size_t dev_bytes, size_t host_bytes) {
-  if (s->io_bytes < dev_bytes) {
-    if (s->d_io) (void)hipFree(s->d_io);
-    s->d_io = nullptr;
-    s->io_bytes = 0;
-    const size_t b = std::max<size_t>(dev_bytes + dev_bytes / 2, 1 << 20);
-    HIP_TRY(nullptr, hipMalloc((void**)&s->d_io, b));
-    s->io_bytes = b;
-  }
-  if (s->h_bytes < host_bytes) {
-    if (s->h_io) (void)hipHostFree(s->h_io);
-    s->h_io = nullptr;
-    s->h_bytes = 0;
-    const size_t b = std::max<size_t>(host_bytes + host_bytes / 2, 1 << 20);
-    HIP_TRY(nullptr, hipHostMalloc((void**)&s->h_io, b, hipHostMallocDefault));
-    s->h_bytes = b;
-  }
-  return ORBFE_OK;
-}
-
-bool alive(const Prob& p, int32_t cur, bool called) { return p.n >= 4 ? (cur < p.max_it || !called) : !called; }
+bool alive(const Prob& p, int32_t cur, bool called) { return ransac::alive(p.n, 4, cur, p.max_it, called); }
 
 constexpr size_t kMaxHyps = 1 << 17;  // one speculation covers at most this many hypotheses (the rest: a later one)
 
@@ -148,7 +89,7 @@ orbfe_status speculate(orbfe_pnp* s, int32_t p, int32_t n, const float* pose, bo
     for (int32_t i = 0; i < k; ++i) {
       PnpHyp h{};
       h.prob = q;
-      random_sample(eng, (uint32_t)pr.n, h.idx);
+      ransac::random_sample(eng, (uint32_t)pr.n, 4, h.idx);
       r.after.push_back(eng);
       s->hyps.push_back(h);
     }
@@ -163,18 +104,8 @@ orbfe_status speculate(orbfe_pnp* s, int32_t p, int32_t n, const float* pose, bo
     s->recs.push_back(std::move(r));
     calls.push_back(c);
   };
-  add_call(p, true);
-  // the rest of this round, then whole rounds, while a problem is live
-  for (int q = p + 1; q < P && s->hyps.size() < kMaxHyps; ++q)
-    if (alive(s->probs[q], cur[q], called[q])) add_call(q, false);
-  for (bool any = true; any && s->hyps.size() < kMaxHyps;) {
-    any = false;
-    for (int q = 0; q < P && s->hyps.size() < kMaxHyps; ++q)
-      if (alive(s->probs[q], cur[q], called[q])) {
-        add_call(q, false);
-        any = true;
-      }
-  }
+  ransac::round_robin(
+      P, p, [&](int q) { return alive(s->probs[q], cur[q], called[q]); }, add_call, [&] { return s->hyps.size() >= kMaxHyps; });
   // mask offsets
   int64_t words = 0;
   for (PnpHyp& h : s->hyps) {
@@ -189,12 +120,12 @@ orbfe_status speculate(orbfe_pnp* s, int32_t p, int32_t n, const float* pose, bo
   const size_t o_h = L.open(up).take<PnpHyp>(nh), o_c = L.take<PnpCall>(nc), o_e = L.take<int32_t>((size_t)entry_len),
                o_out = L.close(up).open(down).take<PnpOut>(nh), o_m = L.take<uint64_t>((size_t)words), o_rm = L.take<uint64_t>((size_t)words),
                o_l = L.close(down).take<int32_t>((size_t)list_total);
-  TRY(io_reserve(s, L.end(), down.end));
-  StagedIo io(s->d_io, s->h_io, s->stream);
+  HIP_TRY(nullptr, hipSetDevice(s->device));  // before the block is (re)allocated: it belongs to the set's device
+  TRY(ransac::io_reserve(&s->io, L.end(), down.end));
+  StagedIo io(s->io.d_io, s->io.h_io, s->stream);
   io.put(o_h, s->hyps.data(), nh * sizeof(PnpHyp));
   io.put(o_c, calls.data(), nc * sizeof(PnpCall));
   io.put(o_e, entry, (size_t)entry_len * 4);
-  HIP_TRY(nullptr, hipSetDevice(s->device));
   HIP_TRY(nullptr, io.upload(up));
   launch_pnp(s->stream, io.dev<PnpHyp>(o_h), (int)nh, io.dev<PnpCall>(o_c), (int)nc, s->d_probs, s->d_xyz, s->d_uv, s->d_thr, s->cam,
              io.dev<int>(o_e), io.dev<PnpOut>(o_out), io.dev<uint64_t>(o_m), io.dev<uint64_t>(o_rm), io.dev<int>(o_l));
@@ -211,10 +142,7 @@ orbfe_status speculate(orbfe_pnp* s, int32_t p, int32_t n, const float* pose, bo
   return ORBFE_OK;
 }
 
-void append_bits(const uint64_t* m, int32_t words, std::vector<int32_t>& list) {
-  for (int32_t w = 0; w < words; ++w)
-    for (uint64_t b = m[w]; b; b &= b - 1) list.push_back(w * 64 + __builtin_ctzll(b));
-}
+using ransac::append_bits;
 
 }  // namespace
 
@@ -257,7 +185,7 @@ orbfe_status orbfe_pnp_create(int32_t device_id, int32_t n_problems, const int64
     p.off = (int32_t)offsets[i];
     p.n = (int32_t)(offsets[i + 1] - offsets[i]);
     p.words = (p.n + 63) / 64;
-    ransac_params(p.n, prm, &p.min_inlier, &p.max_it);
+    ransac::ransac_params(p.n, prm.min_set, prm.max_iterations, prm.ratio, prm.prob, &p.min_inlier, &p.max_it);
     dp[(size_t)i] = PnpProb{p.off, p.n, p.words, p.min_inlier};
   }
   // mvfErrors: (float)(5.991 * Frame::getScaledFactor2(octave))
@@ -292,9 +220,9 @@ void orbfe_pnp_destroy(orbfe_pnp* s) {
   int cur = -1;
   const bool have_cur = hipGetDevice(&cur) == hipSuccess;
   (void)hipSetDevice(s->device);
-  for (void* p : {(void*)s->d_xyz, (void*)s->d_uv, (void*)s->d_thr, (void*)s->d_probs, (void*)s->d_io})
+  for (void* p : {(void*)s->d_xyz, (void*)s->d_uv, (void*)s->d_thr, (void*)s->d_probs})
     if (p) (void)hipFree(p);
-  if (s->h_io) (void)hipHostFree(s->h_io);
+  ransac::io_release(&s->io);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   if (have_cur) (void)hipSetDevice(cur);
   delete s;
@@ -455,13 +383,7 @@ orbfe_status orbfe_pnp_iterate(orbfe_pnp* s, int32_t problem, int32_t n_iteratio
 }
 
 orbfe_status orbfe_pnp_engine(uint32_t* get, const uint32_t* set) {
-  std::lock_guard<std::mutex> lk(g_pnp_mu);
-  if (get) *get = g_engine;
-  if (set) {
-    if (*set == 0 || *set >= 2147483647u) return fail(nullptr, ORBFE_EBADARG, "orbfe_pnp_engine: state %u outside 1 .. 2^31 - 2", *set);
-    g_engine = *set;
-  }
-  return ORBFE_OK;
+  return ransac::engine_access(g_pnp_mu, g_engine, get, set, "orbfe_pnp_engine");
 }
 
 orbfe_status orbfe_pnp_stats(orbfe_pnp* s, int64_t* launches, int64_t* hypotheses) {
