@@ -302,8 +302,14 @@ orbfe_status orbfe_ba_build_system(orbfe_ctx* ctx, const orbfe_ba_problem* prob,
  * 7.815 (stereo) or non-positive depth goes to level 1 and ALL robust kernels are dropped (:338-359), optimize(iters_second = 10)
  * on level 0, final computeError() + the same test on every edge (:364-391).  BlockSolver_6_3 + OptimizationAlgorithmLevenberg
  * semantics (lambda0 = 1e-5 max diag, gain ratio, <= 10 trials per iteration, points marginalised by Schur complement); the
- * reduced system is factorised densely (6x6-blocked Cholesky: by one workgroup out of LDS up to 100 non-fixed keyframes, by a multi-workgroup
- * path beyond -- no bound on their number, as Optimizer.cc:232 has none).  stop_flag (nullable) is polled like g2o's
+ * reduced system is factorised densely, by one of four Cholesky solvers -- no bound on the number of non-fixed keyframes, as
+ * Optimizer.cc:232 has none:
+ *   Levenberg-Marquardt control on the device, 1..42 non-fixed keyframes      one workgroup, the matrix in registers
+ *   Levenberg-Marquardt control on the device, 43..1000                       48x48 tiles on the fp64 matrix cores, many workgroups
+ *   host-driven Levenberg-Marquardt loop, up to 100                           one workgroup out of LDS, 6x6 blocks
+ *   host-driven Levenberg-Marquardt loop, beyond 100                          the same with its panel in global memory, many workgroups
+ * (the host-driven loop runs when a pose observes a point twice, beyond 1000 non-fixed keyframes, or with ORBFE_LBA_HOST_LM=1 in the
+ * environment at orbfe_create; orbfe_debug_reduced_solve reaches each solver directly).  stop_flag (nullable) is polled like g2o's
  * forceStopFlag (Optimizer.cc:230): it points at ONE BYTE, the reference's `bool mbAbortBA` (include/ORB_SLAM2/LocalMapping.h:185) passed as
  * `bool& isStop` (Optimizer.h:69) -- only that byte is read, non-zero = stop.  The map bookkeeping of :393-441 stays with the caller.                               */
 typedef struct orbfe_ba_optimize_out {
@@ -968,6 +974,15 @@ orbfe_status orbfe_debug_candidates(orbfe_ctx* ctx, int32_t slot, int32_t level,
  * n < 0 or a NULL array is ORBFE_EBADARG.                                                              */
 orbfe_status orbfe_debug_se3_oplus(orbfe_ctx* ctx, int32_t n, const double* poses /*[n][7]*/, const double* upd /*[n][6]*/,
                                    double* out /*[n][7]*/);
+/* One dense symmetric positive-definite system S x = rhs of nb 6x6 block rows through one of the four reduced-system solvers of
+ * orbfe_ba_local_optimize, in the layout and through the launch code the optimiser gives that solver.  solver 0: registers (nb 1..42),
+ * 1: blocked, matrix cores (43..1000), 2: LDS (1..100), 3: panel in global memory (>= 101); any other nb, a NULL argument or nb < 1 is
+ * ORBFE_EBADARG.  Only the lower triangle (i >= j) of S bears on the result.  *ok = 0 and x = 0 when a pivot is not positive and finite
+ * (the optimiser rejects such a trial); that is ORBFE_OK.  Callable any number of times on one context: for solver 1 the state the
+ * blocked solver keeps between the trials of one optimisation (its bad-pivot flag among it) is kept between calls of one nb.         */
+orbfe_status orbfe_debug_reduced_solve(orbfe_ctx* ctx, int32_t solver, int32_t nb,
+                                       const double* S /*[6nb][6nb] row-major, symmetric; only i >= j is read*/,
+                                       const double* rhs /*[6nb]*/, double* x /*[6nb]*/, int32_t* ok);
 
 #ifdef __cplusplus
 }

@@ -188,6 +188,7 @@ EXPORTS = [
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
+    "orbfe_debug_reduced_solve",
 ]
 BOW_MAX_FEATURES = 65535
 
@@ -328,6 +329,7 @@ def load() -> C.CDLL:
     L.orbfe_stage_name.restype = C.c_char_p
     L.orbfe_debug_candidates.argtypes = [vp, i32, i32, vp, i32, vp]
     L.orbfe_debug_se3_oplus.argtypes = [vp, i32, vp, vp, vp]
+    L.orbfe_debug_reduced_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1044,6 +1046,19 @@ class Context:
         out = np.zeros((max(n, 1), 7))
         self._check(self.lib.orbfe_debug_se3_oplus(self.h, n, ptr(poses), ptr(upd), ptr(out)))
         return out[:n]
+
+    def debug_reduced_solve(self, solver, S, rhs):
+        """S x = rhs (S (6 nb, 6 nb) symmetric positive definite, only its lower triangle counts) by one of local BA's four reduced-system
+        solvers: 0 registers (nb 1..42), 1 blocked (43..1000), 2 LDS (1..100), 3 panel (>= 101) -> (x, ok); ok == 0: bad pivot, x = 0"""
+        S = np.ascontiguousarray(S, np.float64)
+        rhs = np.ascontiguousarray(rhs, np.float64).reshape(-1)
+        n = rhs.shape[0]
+        if S.shape != (n, n) or n % 6:
+            raise ValueError("S must be (6 nb, 6 nb) and rhs (6 nb,)")
+        x = np.zeros(max(n, 1))
+        ok = C.c_int32(-1)
+        self._check(self.lib.orbfe_debug_reduced_solve(self.h, solver, n // 6, ptr(S), ptr(rhs), ptr(x), C.byref(ok)))
+        return x[:n], ok.value
 
     # ---- stereo -------------------------------------------------------------------------------
     def stereo_match(self, slot_left, slot_right, fx, bf):

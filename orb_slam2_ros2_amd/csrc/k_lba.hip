@@ -454,6 +454,26 @@ void launch_lba_chi2_sum(hipStream_t s, int n_edges, const double* chi2, const d
 void launch_lba_maxdiag(hipStream_t s, int n_poses, int n_points, const double* Hpp, const double* Hll, const uint8_t* fixed, double* out) {
   hipLaunchKernelGGL(k_lba_maxdiag, dim3(1), dim3(1024), 0, s, n_poses, n_points, Hpp, Hll, fixed, out);
 }
+// The factorisation and both substitutions of the reduced system S x = rhs (S column-major, n = 6 nf; *ok set by the caller): the
+// LDS-resident solver up to LBA_MAX_FREE free keyframes, the panel solver past it.  big_scratch (panel solver only): panel [(n + 1) * 6] |
+// diagonal blocks [nf * 36] | right-hand side [n].  launch_lba_solve's solver step, and what orbfe_debug_reduced_solve runs.
+void launch_lba_chol(hipStream_t s, int nf, double* S, double* rhs, double* x, int* ok, double* big_scratch) {
+  if (nf <= LBA_MAX_FREE) {
+    hipLaunchKernelGGL(k_lba_chol_solve, dim3(1), dim3(1024), 0, s, 6 * nf, S, rhs, x, ok);
+  } else {
+    const int n = 6 * nf;
+    double* Pg = big_scratch;
+    double* Ldg = Pg + (size_t)(n + 1) * 6;
+    double* yg = Ldg + (size_t)nf * 36;
+    (void)hipMemcpyAsync(yg, rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, s);
+    for (int kb = 0; kb < nf; ++kb) {
+      hipLaunchKernelGGL(k_lba_chol_panel, dim3(1), dim3(1024), 0, s, n, kb, S, Pg, Ldg, yg, ok);
+      const int cols = n - 6 * kb - 6;
+      if (cols > 0) hipLaunchKernelGGL(k_lba_chol_trail, dim3((cols + 15) / 16), dim3(1024), 0, s, n, kb, S, Pg, yg, ok);
+    }
+    hipLaunchKernelGGL(k_lba_chol_back, dim3(1), dim3(1024), 0, s, n, S, Ldg, yg, x, ok);
+  }
+}
 void launch_lba_solve(hipStream_t s, int n_poses, int n_points, int n_edges, int nf, const int32_t* free_pose, const int32_t* pose_slot,
                       const int32_t* pair_off, const int2* pairs, const int32_t* ps_off, const int32_t* ps_edges, const int32_t* pt_off,
                       const int32_t* pt_edges, const int32_t* edge_pose, const int32_t* edge_point, const uint8_t* fixed, const double* Hpp,
@@ -465,21 +485,7 @@ void launch_lba_solve(hipStream_t s, int n_poses, int n_points, int n_edges, int
   if (nf > 0) {
     hipLaunchKernelGGL(k_lba_schur, dim3(nf, nf), dim3(64), 0, s, nf, free_pose, pair_off, pairs, ps_off, ps_edges, edge_point, Hpp, bp, bl,
                        Hpl, W, lambda_p, S, rhs);
-    if (nf <= LBA_MAX_FREE) {
-      hipLaunchKernelGGL(k_lba_chol_solve, dim3(1), dim3(1024), 0, s, 6 * nf, S, rhs, x, ok);
-    } else {  // big_scratch: panel [(n + 1) * 6] | diagonal blocks [nf * 36] | right-hand side [n]
-      const int n = 6 * nf;
-      double* Pg = big_scratch;
-      double* Ldg = Pg + (size_t)(n + 1) * 6;
-      double* yg = Ldg + (size_t)nf * 36;
-      (void)hipMemcpyAsync(yg, rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, s);
-      for (int kb = 0; kb < nf; ++kb) {
-        hipLaunchKernelGGL(k_lba_chol_panel, dim3(1), dim3(1024), 0, s, n, kb, S, Pg, Ldg, yg, ok);
-        const int cols = n - 6 * kb - 6;
-        if (cols > 0) hipLaunchKernelGGL(k_lba_chol_trail, dim3((cols + 15) / 16), dim3(1024), 0, s, n, kb, S, Pg, yg, ok);
-      }
-      hipLaunchKernelGGL(k_lba_chol_back, dim3(1), dim3(1024), 0, s, n, S, Ldg, yg, x, ok);
-    }
+    launch_lba_chol(s, nf, S, rhs, x, ok, big_scratch);
   }
   const int nt = n_points + n_poses;
   if (nt > 0)

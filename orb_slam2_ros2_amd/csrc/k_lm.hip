@@ -1106,6 +1106,14 @@ void launch_lm_ctrl(hipStream_t s, const LmLaunch& L, int mode) {
   hipLaunchKernelGGL(k_lm_ctrl, dim3(1), dim3(64), 0, s, L.state, L.B, mode, (L.NP + 31) / 32, (L.NP + 31) / 32 + (L.NK + 255) / 256, L.scale_part, L.abort_flag,
                      mode == 4 ? L.state_out : (LmState*)nullptr);
 }
+// the solver of a trial (gated by LmState::run_step): the blocked multi-workgroup Cholesky when the launch carries its dense system, the
+// register-resident one otherwise.  launch_lm_step's solver step, and what orbfe_debug_reduced_solve runs.
+void launch_lm_chol(hipStream_t s, const LmLaunch& L) {
+  if (L.M)
+    launch_lm_chol_big(s, L);
+  else
+    hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(LM_CHOL_THREADS), 0, s, L.nf, L.state, L.Sblk, L.rhs, L.x);
+}
 // one trial: solve + update + the system at the trial estimate (the control step that decides it is the caller's next launch)
 void launch_lm_step(hipStream_t s, const LmLaunch& L) {
   const LmBuffers& B = L.B;
@@ -1116,10 +1124,7 @@ void launch_lm_step(hipStream_t s, const LmLaunch& L) {
   if (L.nf > 0) {
     hipLaunchKernelGGL(k_lm_schur, dim3(L.nf * (L.nf + 1) / 2 + L.nf), dim3(64), 0, s, L.nf, B, L.state, L.free_pose, L.pair_cnt, L.pair_cap, L.pairs, L.ps_off,
                        L.ps_edges, L.edge_point, L.W, L.Sblk, L.rhs, L.M, L.ld);
-    if (L.M)
-      launch_lm_chol_big(s, L);
-    else
-      hipLaunchKernelGGL(k_lm_chol, dim3(1), dim3(LM_CHOL_THREADS), 0, s, L.nf, L.state, L.Sblk, L.rhs, L.x);
+    launch_lm_chol(s, L);
   }
   const int ub = pb + (L.NK + 255) / 256;
   if (ub > 0)

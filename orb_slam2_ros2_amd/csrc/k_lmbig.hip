@@ -19,7 +19,7 @@
 // X_b = (A_b - sum X_c L_bc^T) inv_bb^T, every product an MFMA (a column-at-a-time substitution by one wave was 14 us a tile, the
 // 48-column factorisation 24 us: tools/exp/lmb_bench.hip).  No workgroup waits for another.  After the last launch L and y are
 // complete; k_lmb_back_mw solves L^T x = y with one workgroup per tile column.
-// Fixed summation order everywhere: run-to-run identical.  A non-positive pivot clears LmState::ok (g2o: the linear solver fails, the
+// Fixed summation order everywhere: run-to-run identical.  A pivot that is not positive and finite clears LmState::ok (g2o: the linear solver fails, the
 // trial is rejected) and x = 0.
 #include <hip/hip_runtime.h>
 
@@ -92,8 +92,13 @@ __device__ __forceinline__ bool lmb_potrf16(double* D, double* inv, int lane) {
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     const double piv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(a[c]), c), __builtin_amdgcn_readlane(__double2loint(a[c]), c));
-    if (!(piv > 0.0)) ok = false;  // (uniform)
-    const double d = piv > 0.0 ? piv : 1.0;
+    // (uniform.  +inf is a bad pivot as in k_lm_chol: 1 / sqrt gives 0, the correction NaN, and where it is the LAST pivot of the system
+    //  -- 6 nf a multiple of 48, no padding row behind it -- no later pivot would notice: ok stayed 1 with x all NaN.
+    //  ONE class test, +normal | +subnormal, in the place of `piv > 0.0`: a second compare per pivot on this lone wave was 1.5 % of a call
+    //  at 300 free keyframes)
+    const bool good = __builtin_amdgcn_class(piv, 0x180);
+    if (!good) ok = false;
+    const double d = good ? piv : 1.0;
     const double y0 = __builtin_amdgcn_rsq(d);
     const double e = fma(-(d * y0), y0, 1.0);
     y[c] = fma(y0 * e, fma(0.375, e, 0.5), y0);

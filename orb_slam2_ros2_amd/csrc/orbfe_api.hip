@@ -590,6 +590,7 @@ void orbfe_destroy(orbfe_ctx* c) {
   if (c->h_counts) (void)hipHostFree(c->h_counts);
   if (c->h_abort) (void)hipHostFree((void*)c->h_abort);
   if (c->h_lm_state) (void)hipHostFree(c->h_lm_state);
+  if (c->d_dbg_lmb_flags) (void)hipFree(c->d_dbg_lmb_flags);
   if (c->hs.h2d) (void)hipStreamSynchronize(c->hs.h2d);
   if (c->hs.d2h) (void)hipStreamSynchronize(c->hs.d2h);
   for (int b = 0; b < orbfe_ctx::HostStream::kDepth; ++b) {

@@ -548,8 +548,12 @@ orbfe_status orbfe_ba_local_optimize(orbfe_ctx* c, const orbfe_ba_problem* p, co
       a.free_pose.push_back(k);
     }
   a.nf = (int)a.free_pose.size();
-  // (no bound on nf: up to LBA_MAX_FREE free keyframes the reduced system is factorised by one workgroup out of LDS, beyond that by the
-  //  multi-workgroup path of k_lba.hip with its panel in global memory)
+  // (no bound on nf.  The reduced system is factorised by one of four solvers:
+  //    device-side control, 1..LM_CHOL_MAX_NB free keyframes             k_lm_chol (k_lm.hip): one workgroup, the matrix in registers
+  //    device-side control, LM_CHOL_MAX_NB + 1..LM_BIG_MAX_NB            k_lmb_step / k_lmb_back_mw (k_lmbig.hip): 48 x 48 tiles, fp64 MFMA
+  //    host-driven loop, up to LBA_MAX_FREE                              k_lba_chol_solve (k_lba.hip): one workgroup out of LDS
+  //    host-driven loop, past LBA_MAX_FREE                               k_lba_chol_panel / _trail / _back: the panel in global memory
+  //  the host-driven loop runs when a pose observes a point twice, past LM_BIG_MAX_NB free keyframes, or under ORBFE_LBA_HOST_LM=1)
   ba_vertex_lists(p, &a.v);
   // The device-side Levenberg-Marquardt path (k_lm.hip) builds the pair lists of the reduced system itself, from a (pose, point) -> edge
   // table: that needs a pose to observe a point at most once (as every map of the reference does); anything else takes the host-driven path.
@@ -633,6 +637,83 @@ orbfe_status orbfe_debug_se3_oplus(orbfe_ctx* c, int32_t n, const double* poses,
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, io.fetch(down));
   io.get(out, o_o, N * 56);
+  return ORBFE_OK;
+}
+
+// One reduced camera system through one of the four Cholesky solvers of the local BA, each in the layout and through the launch code
+// orbfe_ba_local_optimize gives it (launch_lm_chol: k_lm_chol | k_lmbig; launch_lba_chol: LDS-resident | panel).
+orbfe_status orbfe_debug_reduced_solve(orbfe_ctx* c, int32_t solver, int32_t nb, const double* S, const double* rhs, double* x, int32_t* ok) {
+  ApiLock api_lk(c);
+  if (!c || !S || !rhs || !x || !ok) return fail(c, ORBFE_EBADARG, "debug_reduced_solve: NULL argument");
+  // the block rows production gives each solver (solver 3: as many as 6 nb indexes as an int)
+  static const int32_t lo[4] = {1, LM_CHOL_MAX_NB + 1, 1, LBA_MAX_FREE + 1};
+  static const int32_t hi[4] = {LM_CHOL_MAX_NB, LM_BIG_MAX_NB, LBA_MAX_FREE, std::numeric_limits<int32_t>::max() / 6};
+  if (solver < 0 || solver > 3) return fail(c, ORBFE_EBADARG, "debug_reduced_solve: solver %d (0 registers, 1 blocked, 2 LDS, 3 panel)", solver);
+  if (nb < lo[solver] || nb > hi[solver])
+    return fail(c, ORBFE_EBADARG, "debug_reduced_solve: solver %d takes %d..%d block rows, not %d", solver, lo[solver], hi[solver], nb);
+  HIP_TRY(c, hipSetDevice(c->device));
+  TRY(join_stereo(c));
+  const size_t NB = (size_t)nb, n = 6 * NB;
+  const bool lm = solver < 2, big = solver == 1, panel = solver == 3;
+  const size_t ld = big ? (size_t)lm_big_ld(nb) : 0, KT = ld / 48;
+  // the system as the solver's Schur kernel leaves it.  Solvers 0 and 1 (k_lm_schur): the 6x6 blocks (I, J), I >= J, whole -- packed
+  // row-major for solver 0; for solver 1 an n x n row-major square (blocks above the diagonal zero) that is copied into the zero-filled,
+  // padded matrix.  Solvers 2 and 3 (k_lba_schur): all of S, column-major.
+  std::vector<double> pack(solver == 0 ? NB * (NB + 1) / 2 * 36 : n * n, 0.0);
+  for (size_t I = 0; I < NB; ++I)
+    for (size_t J = 0; J < (lm ? I + 1 : NB); ++J)
+      for (size_t a = 0; a < 6; ++a)
+        for (size_t b = 0; b < 6; ++b) {
+          const size_t r = 6 * I + a, q = 6 * J + b;
+          pack[solver == 0 ? (I * (I + 1) / 2 + J) * 36 + 6 * a + b : (big ? r * n + q : r + q * n)] = S[r * n + q];
+        }
+  ScratchLayout L;
+  ScratchRegion up, down;
+  const size_t o_s = L.open(up).take<double>(pack.size()), o_rhs = L.take<double>(n),
+               o_st = L.open(down).take(lm ? sizeof(LmState) : sizeof(int32_t)),  // the control state | the host-driven loop's ok word
+               o_x = L.close(up).take<double>(big ? KT * 48 : n),                 // (k_lmb_back_mw writes the ld entries of the padded system)
+               o_m = L.close(down).take(big ? lm_big_bytes(nb) : 8), o_inv = L.take(big ? lm_big_inv_bytes(nb) : 8),
+               o_panel = L.take(panel ? ((n + 1) * 6 + NB * 36 + n) * 8 : 8);
+  StagedIo io;
+  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes()), up.end + down.bytes() <= ((size_t)16 << 20)));
+  hipStream_t st = c->stream;
+  LmState init{};
+  init.run_step = 1, init.ok = 1;
+  const int32_t ok_init = 1;
+  LmState fin{};
+  int32_t ok_fin = 0;
+  io.put(o_s, pack.data(), pack.size() * 8);
+  io.put(o_rhs, rhs, n * 8);
+  if (lm) io.put(o_st, &init, sizeof init);
+  else io.put(o_st, &ok_init, sizeof ok_init);
+  HIP_TRY(c, io.upload(up));
+  if (lm) {
+    LmLaunch K{};
+    K.nf = nb, K.state = io.dev<LmState>(o_st), K.Sblk = io.dev<double>(o_s), K.rhs = io.dev<double>(o_rhs), K.x = io.dev<double>(o_x);
+    if (big) {
+      // the flags outlive the call: a bad pivot's flag is cleared by the first launch of the NEXT factorisation, here as between two trials
+      if (!c->d_dbg_lmb_flags) TRY(dev_alloc(c, &c->d_dbg_lmb_flags, (size_t)2 * (lm_big_ld(LM_BIG_MAX_NB) / 48) + 1));
+      if (c->dbg_lmb_kt != (int)KT) HIP_TRY(c, hipMemsetAsync(c->d_dbg_lmb_flags, 0, (2 * KT + 1) * 4, st));
+      c->dbg_lmb_kt = (int)KT;
+      K.M = io.dev<double>(o_m), K.ld = (int)ld, K.lmb_flags = c->d_dbg_lmb_flags, K.lmb_inv = io.dev<double>(o_inv);
+      // as device_lm: zero fill, unit padding diagonal; then what k_lm_schur writes: the blocks into rows [0, n), the right-hand side into row ld
+      HIP_TRY(c, hipMemsetAsync(K.M, 0, lm_big_bytes(nb), st));
+      launch_lm_big_init(st, K);
+      HIP_TRY(c, hipMemcpy2DAsync(K.M, ld * 8, io.dev<double>(o_s), n * 8, n * 8, n, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(K.M + ld * ld, K.rhs, n * 8, hipMemcpyDeviceToDevice, st));
+    }
+    launch_lm_chol(st, K);
+  } else {
+    launch_lba_chol(st, nb, io.dev<double>(o_s), io.dev<double>(o_rhs), io.dev<double>(o_x), io.dev<int>(o_st), io.dev<double>(o_panel));
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, io.download(big ? down.upto(o_x + n * 8) : down));
+  if (io.staged) HIP_TRY(c, io.wait());
+  if (lm) io.get(&fin, o_st, sizeof fin);
+  else io.get(&ok_fin, o_st, sizeof ok_fin);
+  io.get(x, o_x, n * 8);
+  if (!io.staged) HIP_TRY(c, io.wait());
+  *ok = lm ? fin.ok : ok_fin;
   return ORBFE_OK;
 }
 

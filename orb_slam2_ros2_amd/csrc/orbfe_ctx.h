@@ -95,6 +95,7 @@ void launch_lba_solve(hipStream_t s, int n_poses, int n_points, int n_edges, int
                       const double* bp, const double* Hll, const double* bl, const double* Hpl, const double* lambda_p, double* Dinv, double* W,
                       double* S, double* rhs, double* x, int* ok, double* poses, double* points, double* dxp, double* dxl, double* scale_out,
                       double* big_scratch);
+void launch_lba_chol(hipStream_t s, int nf, double* S, double* rhs, double* x, int* ok, double* big_scratch);
 // k_lmbig.hip
 size_t lm_big_bytes(int nf);
 size_t lm_big_inv_bytes(int nf);
@@ -120,6 +121,7 @@ void launch_search_area(hipStream_t s, const uint4* d_kpl, const uint8_t* d_desc
 void launch_lm_build(hipStream_t s, const LmLaunch& L, int gate, int which, int write_last, bool with_poses);
 void launch_lm_maxdiag(hipStream_t s, const LmLaunch& L, int gate);
 void launch_lm_pairs(hipStream_t s, const LmLaunch& L);
+void launch_lm_chol(hipStream_t s, const LmLaunch& L);
 void launch_lm_steps(hipStream_t s, const LmLaunch& L, int n);
 void launch_lm_switch(hipStream_t s, const LmLaunch& L);
 void launch_lm_final(hipStream_t s, const LmLaunch& L);
@@ -311,6 +313,10 @@ struct orbfe_ctx {
   // stop flag is mirrored into it while the call waits -- and the page-locked copy of the state record
   volatile uint8_t* h_abort = nullptr;
   LmState* h_lm_state = nullptr;
+  // orbfe_debug_reduced_solve, solver 1: the blocked solver's flags live across calls as they live across the trials of one optimisation
+  // (zeroed when the tile count changes, as the one zero fill of a new optimisation would); dbg_lmb_kt: the tile count they belong to
+  int32_t* d_dbg_lmb_flags = nullptr;
+  int dbg_lmb_kt = 0;
   bool lm_on_device = true;  // ORBFE_LBA_HOST_LM=1: round 2's host-driven loop (kept for A/B runs; also taken past LM_BIG_MAX_NB free
                              // keyframes and when a pose observes a point twice)
 

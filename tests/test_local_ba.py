@@ -94,6 +94,51 @@ def test_device_local_ba_host_driven_loop_agrees(monkeypatch):
     assert (got["level"] != ref["level"]).sum() <= 1
 
 
+def _assert_matches_oracle(g, o, pr, fixed):
+    """the asserts of test_device_local_ba_matches_oracle"""
+    n_fixed = int(fixed.sum())
+    assert tuple(g["iters"]) == tuple(o["iters"])
+    assert _pose_dist(g["poses"], o["poses"]) < 1e-7 and np.abs(g["points"] - o["points"]).max() < 1e-7
+    assert np.array_equal(g["poses"][:n_fixed], pr["poses"][:n_fixed])
+    assert (g["level"] != o["level"]).sum() <= 1 and (g["bad"] != o["bad"]).sum() <= 1   # an edge exactly on a threshold may flip
+    assert np.allclose(g["chi2"], o["chi2"], rtol=1e-6, atol=1e-9)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n_free,n_pt,n_fixed", [(31, 43, 1500, 4), (32, 100, 2000, 5), (33, 101, 2000, 5), (34, 171, 2500, 6)])
+def test_device_local_ba_host_driven_loop_sizes(orc, monkeypatch, seed, n_free, n_pt, n_fixed):
+    """ORBFE_LBA_HOST_LM=1 at the sizes the host-driven loop's two solvers were built for: the LDS-resident Cholesky up to its limit of 100
+    free keyframes (43, 100), the panel solver past it (101; 171: 1026 unknowns, the 1024-thread row loops take a second trip).  Which
+    solver runs is a function of the inputs alone: the switch and the number of free keyframes.  (The switch is read at orbfe_create.)"""
+    from orb_slam2_ros2_amd._lib import Context
+    pr, fixed = _problem(seed, n_free + n_fixed, n_pt, n_fixed)
+    assert (fixed == 0).sum() == n_free and (n_free <= 100) == (n_free in (43, 100))     # <= 100: k_lba_chol_solve, else the panel solver
+    monkeypatch.setenv("ORBFE_LBA_HOST_LM", "1")
+    ctx = Context(640, 480, n_features=500, max_images=1)
+    g = ctx.ba_local_optimize(pr, fixed)
+    again = ctx.ba_local_optimize(pr, fixed)
+    ctx.close()
+    _assert_matches_oracle(g, orc.ba_local_optimize(pr, fixed), pr, fixed)
+    assert all(np.array_equal(again[k], g[k]) for k in ("poses", "points", "level", "chi2", "bad"))   # fixed summation orders
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n_free,n_pt,n_fixed", [(35, 45, 1500, 4), (36, 105, 2000, 5)])
+def test_device_local_ba_duplicate_edges_past_42_and_100(orc, seed, n_free, n_pt, n_fixed):
+    """How production reaches the host-driven loop and its solvers: a pose that observes a point twice (no environment switch).  45 free
+    keyframes: past the register-resident solver of the device-side control, the LDS solver here; 105: the panel solver."""
+    from orb_slam2_ros2_amd._lib import Context
+    pr, fixed = _problem(seed, n_free + n_fixed, n_pt, n_fixed)
+    pr, fixed = _mutate(pr, fixed, "duplicate_edges", np.random.default_rng(seed))
+    obs = np.stack([pr["edge_pose"], pr["edge_point"]], 1)
+    assert len(np.unique(obs, axis=0)) < len(obs)             # the premise: at least one pose observes a point twice
+    assert (fixed == 0).sum() == n_free
+    ctx = Context(640, 480, n_features=500, max_images=1)
+    g = ctx.ba_local_optimize(pr, fixed)
+    ctx.close()
+    _assert_matches_oracle(g, orc.ba_local_optimize(pr, fixed), pr, fixed)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,n_kf,n_pt,n_fixed", [(14, 48, 2000, 5), (15, 74, 3000, 10), (11, 155, 2500, 5), (12, 101, 1500, 0), (13, 310, 4000, 10)])
 def test_device_local_ba_beyond_100_free_keyframes(orc, seed, n_kf, n_pt, n_fixed):
@@ -234,8 +279,8 @@ def test_device_local_ba_stop_flag(orc):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_kf,n_fixed", [(3, 2), (44, 2), (45, 2), (10, 10), (10, 0)])
 def test_device_local_ba_around_the_device_lm_limit(orc, n_kf, n_fixed):
-    """1, 42 (the last size of the register-resident Cholesky: Levenberg-Marquardt control on the device), 43 (the first of the host-driven
-    loop), no free and no fixed keyframe at all: same iteration counts and trajectory as the oracle."""
+    """1, 42 (the last size of the register-resident Cholesky), 43 (the first of the blocked solver of k_lmbig.hip, under the same
+    device-side control), no free and no fixed keyframe at all: same iteration counts and trajectory as the oracle."""
     from orb_slam2_ros2_amd._lib import Context
     pr, fixed = _problem(20 + n_kf, n_kf, 300, n_fixed)
     ctx = Context(640, 480, n_features=500, max_images=1)
