@@ -742,6 +742,29 @@ orbfe_status orbfe_sim3_engine(uint32_t* get, const uint32_t* set);
 orbfe_status orbfe_sim3_stats(orbfe_sim3* set, int64_t* launches, int64_t* hypotheses);
 orbfe_status orbfe_sim3_profile(orbfe_sim3* set, int32_t enable, double* device_us, int64_t* bytes_uploaded);
 
+/* ---- Sim3 optimisation (Optimizer::OptimizeSim3, src/Optimizer.cc:464-619) -----------------------------------------------------------
+ * The last step of LoopClosing::computeSim3 (src/LoopClosing.cc:300-415) for one candidate, from the point where the graph is built
+ * (:509-553): pair i is one match that passed the vbIsInlier filter of :492-508, which stays with the caller as map state does
+ * everywhere -- pc[i] = cPc = Rcw * cPw + tcw and pm[i] = mPc (float, :511-512), uv_c[i] / uv_m[i] the two key points (:535, :545),
+ * info_c[i] = pCurr->getScaledFactorInv2(ckp.octave) and info_m[i] = pCurr->getScaledFactorInv2(mkp.octave) (:536, :546: pCurr for
+ * both).  One VertexSim3Expmap with the scale FIXED (the reference's only caller passes bFixedScale = true; there is no free-scale
+ * mode), an EdgeSim3ProjectXYZ and an EdgeInverseSim3ProjectXYZ per pair with Huber sqrt(9.210), both cameras (fx, fy, cx, cy);
+ * optimize(5), pairs with a chi2 > 9.210 dropped, optimize(nBad ? 10 : 5), pairs with both chi2 <= 9.210 are the inliers (:565-607).
+ * g2o differentiates these edges numerically and so does the device.
+ *   model       in / out, orbfe_sim3_iterate's layout (Rqp row-major, then tqp; mfS is 1): ConvertSim3G2o on entry, ConvertG2o2Sim3 on
+ *               return (:474, :617).
+ *   inlier_out  [n]: 1 for the pairs that stay in the match list, in order (:608-616).
+ *   n_inliers   the return value.  0 with fewer than 20 pairs left after the first round (:584): model is untouched and inlier_out all
+ *               1, as the reference returns before it swaps the list.  n < 20 gets there without a launch.
+ *   est_out     NULL or [8]: the final estimate in double (qx qy qz qw tx ty tz s), the start estimate on the early return.
+ * One upload, ONE launch, one download; 0 <= n <= ORBFE_BOW_MAX_FEATURES.  Errors: ORBFE_EBADARG (NULL context or model, n out of
+ * range, NULL arrays with n > 0, a model entry that is not finite: nothing is launched), ORBFE_EDEVICE.                              */
+orbfe_status orbfe_sim3_optimize(orbfe_ctx* ctx, int32_t n, const float* pc /*[n][3] cPc*/, const float* pm /*[n][3] mPc*/,
+                                 const float* uv_c /*[n][2]*/, const float* uv_m /*[n][2]*/, const double* info_c /*[n]*/,
+                                 const double* info_m /*[n]*/, float fx, float fy, float cx, float cy,
+                                 float* model /*[12] in/out: R row-major, t -- orbfe_sim3_iterate's layout*/,
+                                 uint8_t* inlier_out /*[n]*/, int32_t* n_inliers, double* est_out /*[8] qx qy qz qw tx ty tz s, nullable*/);
+
 /* ---- new map points of a keyframe (LocalMapping::createNewMapPoints, src/LocalMapping.cc:165-285) ---------------------------------
  * One call runs loop 1 and loop 2 of createNewMapPoints for the current keyframe `cur` against the neighbours nbs[0 .. n_nb) IN THE
  * GIVEN ORDER (the reference's std::map order, T2): searchForTriangulation (searchByBow with bAddMPs, ratio 0.6, threshold 50, no
@@ -983,6 +1006,14 @@ orbfe_status orbfe_debug_se3_oplus(orbfe_ctx* ctx, int32_t n, const double* pose
 orbfe_status orbfe_debug_reduced_solve(orbfe_ctx* ctx, int32_t solver, int32_t nb,
                                        const double* S /*[6nb][6nb] row-major, symmetric; only i >= j is read*/,
                                        const double* rhs /*[6nb]*/, double* x /*[6nb]*/, int32_t* ok);
+
+/* The edges of orbfe_sim3_optimize as the optimiser sees them, at the estimate est (qx qy qz qw tx ty tz s): err[i] = the errors of
+ * pair i's EdgeSim3ProjectXYZ (u, v) and EdgeInverseSim3ProjectXYZ (u, v), chi2[i] their two chi2, jac[i][edge][row][d] the numeric
+ * Jacobians (d: omega, upsilon; the scale column is 0 and is left out).  n == 0 does nothing; n < 0 or a NULL array is ORBFE_EBADARG. */
+orbfe_status orbfe_debug_sim3_edges(orbfe_ctx* ctx, int32_t n, const float* pc /*[n][3]*/, const float* pm /*[n][3]*/,
+                                    const float* uv_c /*[n][2]*/, const float* uv_m /*[n][2]*/, const double* info_c /*[n]*/,
+                                    const double* info_m /*[n]*/, float fx, float fy, float cx, float cy, const double* est /*[8]*/,
+                                    double* err /*[n][4]*/, double* chi2 /*[n][2]*/, double* jac /*[n][2][2][6]*/);
 
 #ifdef __cplusplus
 }

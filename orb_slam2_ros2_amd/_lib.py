@@ -183,12 +183,13 @@ EXPORTS = [
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
     "orbfe_sim3_create", "orbfe_sim3_destroy", "orbfe_sim3_iterate", "orbfe_sim3_engine", "orbfe_sim3_stats", "orbfe_sim3_profile",
+    "orbfe_sim3_optimize",
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
-    "orbfe_debug_reduced_solve",
+    "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges",
 ]
 BOW_MAX_FEATURES = 65535
 
@@ -330,6 +331,8 @@ def load() -> C.CDLL:
     L.orbfe_debug_candidates.argtypes = [vp, i32, i32, vp, i32, vp]
     L.orbfe_debug_se3_oplus.argtypes = [vp, i32, vp, vp, vp]
     L.orbfe_debug_reduced_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.orbfe_sim3_optimize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
+    L.orbfe_debug_sim3_edges.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1379,6 +1382,42 @@ class Context:
         self._check(self.lib.orbfe_pose_only_optimize(self.h, n, ptr(Xw), ptr(meas), ptr(info), ptr(sigma2), ptr(pose), fx, fy, cx, cy,
                                                       bf, ptr(out), ptr(inl), C.byref(ng)))
         return ng.value, out, inl[:n].astype(bool)
+
+    @staticmethod
+    def _sim3_pairs(pc, pm, uv_c, uv_m, info_c, info_m):
+        pc = np.ascontiguousarray(pc, np.float32).reshape(-1, 3)
+        pm = np.ascontiguousarray(pm, np.float32).reshape(-1, 3)
+        uv_c = np.ascontiguousarray(uv_c, np.float32).reshape(-1, 2)
+        uv_m = np.ascontiguousarray(uv_m, np.float32).reshape(-1, 2)
+        info_c = np.ascontiguousarray(info_c, np.float64).reshape(-1)
+        info_m = np.ascontiguousarray(info_m, np.float64).reshape(-1)
+        n = pc.shape[0]
+        if not all(a.shape[0] == n for a in (pm, uv_c, uv_m, info_c, info_m)):
+            raise ValueError("the pair arrays disagree in length")
+        return n, (pc, pm, uv_c, uv_m, info_c, info_m)
+
+    def sim3_optimize(self, pc, pm, uv_c, uv_m, info_c, info_m, cam, model):
+        """Optimizer::OptimizeSim3 on n matches (orbfe_sim3_optimize): pc = cPc, pm = mPc (n, 3), uv_c, uv_m (n, 2) the key points,
+        info_c, info_m (n,) the edges' information, cam = (fx, fy, cx, cy), model float32[12] (R row-major, t: sim3_iterate's layout)
+        -> (n_inliers, model float32[12], flags bool (n,), est float64[8] = qx qy qz qw tx ty tz s).  n_inliers == 0 with fewer than 20
+        pairs left: the model comes back untouched and every flag set."""
+        n, arrs = self._sim3_pairs(pc, pm, uv_c, uv_m, info_c, info_m)
+        model = np.array(model, np.float32).reshape(12)
+        flags = np.zeros(max(n, 1), np.uint8)
+        est = np.zeros(8)
+        ni = C.c_int32(-1)
+        self._check(self.lib.orbfe_sim3_optimize(self.h, n, *(ptr(a) for a in arrs), *(float(v) for v in cam), ptr(model), ptr(flags),
+                                                 C.byref(ni), ptr(est)))
+        return ni.value, model, flags[:n].astype(bool), est
+
+    def debug_sim3_edges(self, pc, pm, uv_c, uv_m, info_c, info_m, cam, est):
+        """the edges of sim3_optimize at the estimate est (8 doubles) -> (err (n, 4), chi2 (n, 2), jac (n, 2, 2, 6))"""
+        n, arrs = self._sim3_pairs(pc, pm, uv_c, uv_m, info_c, info_m)
+        est = np.ascontiguousarray(est, np.float64).reshape(8)
+        err, chi2, jac = np.zeros((max(n, 1), 4)), np.zeros((max(n, 1), 2)), np.zeros((max(n, 1), 2, 2, 6))
+        self._check(self.lib.orbfe_debug_sim3_edges(self.h, n, *(ptr(a) for a in arrs), *(float(v) for v in cam), ptr(est), ptr(err),
+                                                    ptr(chi2), ptr(jac)))
+        return err[:n], chi2[:n], jac[:n]
 
     # ---- frame glue ------------------------------------------------------------------------------
     def extract_color(self, img: np.ndarray, order: int):

@@ -130,3 +130,50 @@ def make_pose_problem(seed=7, n=1000, scale_factor=1.2, n_levels=8, outlier_ever
     pose0 = np.concatenate([q0, t_true + np.array([0.05, -0.04, 0.06])])
     return dict(Xw=X, meas=meas, info=info, sigma2=sigma2, pose=pose0, fx=FX, fy=FY, cx=CX, cy=CY, bf=BF,
                 truth=np.concatenate([q_true, t_true]), outlier=out)
+
+
+def _rot_from_rotvec(w):
+    w = np.asarray(w, np.float64)
+    th = float(np.linalg.norm(w))
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th < 1e-12:
+        return np.eye(3) + K
+    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / (th * th) * (K @ K)
+
+
+def make_sim3_problem(seed=11, n=200, n_outliers=20, noise_px=0.5, scale_factor=1.2, n_levels=8):
+    """One loop candidate for Optimizer::OptimizeSim3 (Optimizer.cc:464-619): n matched map points of two keyframes related by a known
+    rigid motion p_c = R p_m + t (scale 1), all in front of both cameras; key points with octave-scaled noise of noise_px pixels at
+    octave 0, exactly n_outliers pairs with a gross error of tens of pixels in the current image, the matched one, or both; the
+    information of both edges from the octaves; the start model the truth moved by about two degrees and a few centimetres, as a
+    RANSAC result is.  Returns the arrays of orbfe_sim3_optimize plus truth_R, truth_t and the outlier mask."""
+    idx = np.arange(n)
+    z = 3.0 + _u(seed, 3, idx) * 9.0
+    Pm = np.stack([(_u(seed, 1, idx) - 0.5) * 0.7 * z, (_u(seed, 2, idx) - 0.5) * 0.5 * z, z], 1)
+    R = _rot_from_rotvec([0.05, -0.12, 0.03])
+    t = np.array([0.30, -0.05, 0.15])
+    Pc = Pm @ R.T + t
+    cam = np.array([FX, FY, CX, CY])
+
+    def proj(P):
+        return np.stack([FX * P[:, 0] / P[:, 2] + CX, FY * P[:, 1] / P[:, 2] + CY], 1)
+    oct_c = (hash_u64(seed, 4, idx) % np.uint64(n_levels)).astype(np.int64)
+    oct_m = (hash_u64(seed, 5, idx) % np.uint64(n_levels)).astype(np.int64)
+    sig_c = (np.float32(scale_factor) ** oct_c.astype(np.float32)).astype(np.float32)
+    sig_m = (np.float32(scale_factor) ** oct_m.astype(np.float32)).astype(np.float32)
+    nz_c = np.stack([_irwin_hall(seed, 10, idx), _irwin_hall(seed, 30, idx)], 1) * sig_c[:, None] * noise_px
+    nz_m = np.stack([_irwin_hall(seed, 50, idx), _irwin_hall(seed, 70, idx)], 1) * sig_m[:, None] * noise_px
+    order = np.argsort(hash_u64(seed, 6, idx), kind="stable")
+    out = np.zeros(n, bool)
+    out[order[:n_outliers]] = True
+    kind = np.zeros(n, np.int64)
+    kind[order[:n_outliers]] = np.arange(n_outliers) % 3                       # 0: current image, 1: matched image, 2: both
+    gross = np.stack([30.0 + 40.0 * _u(seed, 7, idx), -(25.0 + 30.0 * _u(seed, 8, idx))], 1)
+    nz_c[out & (kind != 1)] += gross[out & (kind != 1)]
+    nz_m[out & (kind != 0)] -= gross[out & (kind != 0)]
+    inv2 = lambda s: ((np.float32(1.0) / s).astype(np.float32) ** 2).astype(np.float64)   # getScaledFactorInv2
+    R0 = _rot_from_rotvec([0.02, 0.025, -0.015]) @ R
+    t0 = t + np.array([0.04, -0.03, 0.05])
+    return dict(pc=Pc.astype(np.float32), pm=Pm.astype(np.float32), uv_c=(proj(Pc) + nz_c).astype(np.float32),
+                uv_m=(proj(Pm) + nz_m).astype(np.float32), info_c=inv2(sig_c), info_m=inv2(sig_m), cam=tuple(float(v) for v in cam),
+                model=np.concatenate([R0.reshape(9), t0]).astype(np.float32), truth_R=R, truth_t=t, outlier=out)

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_edge_dev.h"
+#include "lm6_dev.h"
 #include "orbfe_internal.h"
 #include "wave_ops.h"
 
@@ -40,49 +41,6 @@ __device__ bool solve6(const double* A /*6x6 row-major*/, const double* b, doubl
     double s = y[i];
     for (int k = i + 1; k < 6; ++k) s -= L[6 * k + i] * x[k];
     x[i] = s / L[6 * i + i];
-  }
-  return true;
-}
-
-// (H + lambda I) x = b with H and b where they are (LDS), for the register-resident kernel, where this lane-0 solve and the pose update
-// behind it are the longest serial piece of a pass (9 k of its ~20 k cycles: ~33 fp64 divisions and square roots of ~100 dependent cycles
-// each): one reciprocal square root per pivot -- v_rsq_f64 and a third-order correction y0 (1 + e / 2 + 3 e^2 / 8), e = 1 - s y0^2, error
-// below double rounding -- L_ii = s y, and every division by L_ii a multiplication by y.
-__device__ __forceinline__ bool solve6_lambda(const double* H, double lambda, const double* b, double* x) {
-#pragma clang fp contract(off)
-  double L[36], inv[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      double s = (i == j) ? H[6 * i + j] + lambda : H[6 * i + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[6 * i + k] * L[6 * j + k];
-      if (i == j) {
-        if (!(s > 0) || !isfinite(s)) return false;
-        const double y0 = __builtin_amdgcn_rsq(s);
-        const double e = fma(-(s * y0), y0, 1.0);
-        const double y = fma(y0 * e, fma(0.375, e, 0.5), y0);
-        L[6 * i + i] = s * y;
-        inv[i] = y;
-      } else
-        L[6 * i + j] = s * inv[j];
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s -= L[6 * i + k] * y[k];
-    y[i] = s * inv[i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) s -= L[6 * k + i] * x[k];
-    x[i] = s * inv[i];
   }
   return true;
 }
@@ -344,8 +302,8 @@ __device__ long long g_pose_stamps[8];
 #define PS(k)
 #define PS_COUNT(k)
 #endif
-#define POSE_TRIALS 10  // g2o's Levenberg-Marquardt gives an iteration at most 10 trial steps (qmax)
-#define POSE_STAGE_LD(NT) ((NT) + 8)  // doubles per row of the staged sums: rows 8 double-banks apart => the readers of a wave 2 per bank pair
+#define POSE_TRIALS LM6_TRIALS
+#define POSE_STAGE_LD(NT) LM6_STAGE_LD(NT)
 template <int NT>
 struct PoseSharedR {
   PoseDev T0;
@@ -545,38 +503,7 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
           }
           PS(5)  // build: per-edge arithmetic
           // (the previous system's b and trial table are rewritten only behind the barrier below: every thread has read them by then)
-          {
-            // every thread stages its 27 partial sums; NT / 32 threads per sum add 32 staged values each (ascending), a fixed tree joins
-            // them: 27 + 32 LDS accesses and ~36 additions per thread, where 27 wave trees of data-parallel-primitive moves took as long as
-            // the edges' arithmetic (6.7 k of a build's 13.5 k cycles with 256 threads)
-            constexpr int PARTS = NT / 32, LD = POSE_STAGE_LD(NT);
-#pragma unroll
-            for (int k = 0; k < 27; ++k) S.stage[k * LD + tid] = acc[k];
-            __syncthreads();
-            if (tid < 27 * PARTS) {
-              const int k = tid / PARTS, part = tid % PARTS;
-              const double* row = S.stage + k * LD + part;
-              double sm = 0;
-#pragma unroll
-              for (int j = 0; j < 32; ++j) sm += row[PARTS * j];
-              sm += dpp_f64<ORBFE_DPP_ROW_SHR(1), 0xf>(sm);  // the last lane of each group of PARTS (8: half a row of 16, 16: a row) ends up with the group's sum
-              sm += dpp_f64<ORBFE_DPP_ROW_SHR(2), 0xf>(sm);
-              sm += dpp_f64<ORBFE_DPP_ROW_SHR(4), 0xf>(sm);
-              if (PARTS == 16) sm += dpp_f64<ORBFE_DPP_ROW_SHR(8), 0xf>(sm);
-              if (part == PARTS - 1) {
-                if (k >= 21) {
-                  S.b[k - 21] = sm;
-                } else {  // k -> (a, c2), a <= c2, in the order the sums were laid out
-                  int a = 0, rem = k;
-                  while (rem >= 6 - a) rem -= 6 - a, ++a;
-                  const int c2 = a + rem;
-                  S.H[6 * a + c2] = sm;
-                  S.H[6 * c2 + a] = sm;
-                }
-              }
-            }
-            __syncthreads();
-          }
+          LM6_STAGE_REDUCE(NT, acc, S, tid)
         }
         PS(4)  // build
         current_chi = chi_cur;
@@ -593,8 +520,7 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
         // beside the others (one instruction stream; a call of 28 iterations takes ~59 trials, most of the rejected ones in the runs of ten
         // that end a converged round).  Same recurrence, same solve, same update as taking them one by one.
         if (tid < POSE_TRIALS) {
-          double lam = lambda, nu = ni;
-          for (int q = 0; q < tid; ++q) lam *= nu, nu *= 2;
+          const double lam = lm6_trial_lambda(lambda, ni, tid);
           double xs[6] = {0, 0, 0, 0, 0, 0};
           const bool ok = solve6_lambda(S.H, lam, S.b, xs);
           PoseDev Tn;

@@ -7,6 +7,7 @@
 //   orbfe_stream.hip   page-locked allocation and the host-image stream (orbfe_stream_*)
 //   orbfe_guided.hip   brute-force and grid-guided matching, map-point projection, the fused tracking chains
 //   orbfe_ba.hip       g2o edge evaluation, normal equations, local BA, pose-only optimisation
+//   orbfe_sim3opt.hip  OptimizeSim3 and its edge probe
 //   orbfe_map.hip      map.pb / text maps
 #pragma once
 #include <hip/hip_runtime.h>
@@ -129,6 +130,13 @@ void launch_pose_only(hipStream_t s, int n, const double* Xw, const double* meas
                       const double* pose_in, BaParamsDev prm, double d_mono, double d_stereo, double* err, uint8_t* level,
                       uint8_t* robust, uint8_t* inlier, double* pose_out, int32_t* n_good, const int32_t* n_dev = nullptr);
 void launch_debug_se3_oplus(hipStream_t s, int n, const double* poses, const double* upd, double* out);
+// k_sim3opt.hip
+void launch_sim3_optimize(hipStream_t s, int n, const float* pc, const float* pm, const float* uvc, const float* uvm, const double* wc,
+                          const double* wm, const float* model_in, BaParamsDev prm, double delta, double* scratch_e, uint8_t* scratch_act,
+                          float* model_out, uint8_t* inlier_out, int32_t* ret, double* est_out);
+int sim3_optimize_register_capacity();
+void launch_debug_sim3_edges(hipStream_t s, int n, const float* pc, const float* pm, const float* uvc, const float* uvm, const double* wc,
+                             const double* wm, BaParamsDev prm, const double* est, double* err, double* chi2, double* jac);
 void launch_track_queries(hipStream_t s, int n, const uint8_t* d_flags, const uint8_t* d_visible, const float* d_cos, const int8_t* d_level, float th,
                           const float* d_sigma2, int n_levels, float* d_radius, int8_t* d_min_level, int8_t* d_max_level);
 void launch_track_claim(hipStream_t s, int n, const int32_t* d_n_cand, const int32_t* d_best_idx, const int32_t* d_best_dist, const int32_t* d_second,

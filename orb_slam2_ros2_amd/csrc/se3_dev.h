@@ -37,33 +37,10 @@ ORBFE_HD_INLINE void quat_rotate(const double* q, const double* v, double* out) 
   out[2] = v[2] + qw * uz + (qx * uy - qy * ux);
 }
 
-// SE3Quat::exp(update) * T, normalizeRotation (g2o se3quat.h); update = (omega, upsilon)
-ORBFE_HD inline void pose_oplus(const PoseDev& T, const double* upd, PoseDev& out) {
+// Eigen's Quaternion(Matrix3): q = (x, y, z, w) of the rotation matrix R, the trace branch or the largest-diagonal one (g2o's SE3Quat::exp
+// and Sim3::exp both end in it; sim3_edge_dev.h also converts an estimate given as a matrix with it)
+ORBFE_HD_INLINE void rot_to_quat(const double (*R)[3], double* q) {
   ORBFE_FP_STRICT
-  const double wx = upd[0], wy = upd[1], wz = upd[2];
-  const double theta = sqrt(wx * wx + wy * wy + wz * wz);
-  const double Om[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
-  double Om2[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double a = 0;
-      for (int k = 0; k < 3; ++k) a += Om[i][k] * Om[k][j];
-      Om2[i][j] = a;
-    }
-  double R[3][3], V[3][3];
-  const double st = sin(theta), ct = cos(theta);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double I = (i == j) ? 1.0 : 0.0;
-      if (theta < 0.00001) {
-        R[i][j] = I + Om[i][j] + 0.5 * Om2[i][j];
-        V[i][j] = I + 0.5 * Om[i][j] + (1. / 6.) * Om2[i][j];
-      } else {
-        R[i][j] = I + st / theta * Om[i][j] + (1 - ct) / (theta * theta) * Om2[i][j];
-        V[i][j] = I + (1 - ct) / (theta * theta) * Om[i][j] + (theta - st) / (theta * theta * theta) * Om2[i][j];
-      }
-    }
-  double q[4];
   const double tr = R[0][0] + R[1][1] + R[2][2];
   if (tr > 0) {
     double t = sqrt(tr + 1.0);
@@ -100,6 +77,36 @@ ORBFE_HD inline void pose_oplus(const PoseDev& T, const double* upd, PoseDev& ou
       q[1] = (R[1][2] + R[2][1]) * t;
     }
   }
+}
+
+// SE3Quat::exp(update) * T, normalizeRotation (g2o se3quat.h); update = (omega, upsilon)
+ORBFE_HD inline void pose_oplus(const PoseDev& T, const double* upd, PoseDev& out) {
+  ORBFE_FP_STRICT
+  const double wx = upd[0], wy = upd[1], wz = upd[2];
+  const double theta = sqrt(wx * wx + wy * wy + wz * wz);
+  const double Om[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
+  double Om2[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double a = 0;
+      for (int k = 0; k < 3; ++k) a += Om[i][k] * Om[k][j];
+      Om2[i][j] = a;
+    }
+  double R[3][3], V[3][3];
+  const double st = sin(theta), ct = cos(theta);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double I = (i == j) ? 1.0 : 0.0;
+      if (theta < 0.00001) {
+        R[i][j] = I + Om[i][j] + 0.5 * Om2[i][j];
+        V[i][j] = I + 0.5 * Om[i][j] + (1. / 6.) * Om2[i][j];
+      } else {
+        R[i][j] = I + st / theta * Om[i][j] + (1 - ct) / (theta * theta) * Om2[i][j];
+        V[i][j] = I + (1 - ct) / (theta * theta) * Om[i][j] + (theta - st) / (theta * theta * theta) * Om2[i][j];
+      }
+    }
+  double q[4];
+  rot_to_quat(R, q);
   double te[3];
   for (int i = 0; i < 3; ++i) te[i] = V[i][0] * upd[3] + V[i][1] * upd[4] + V[i][2] * upd[5];
   const double ax = q[0], ay = q[1], az = q[2], aw = q[3];

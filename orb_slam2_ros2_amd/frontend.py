@@ -336,6 +336,12 @@ class Optimizer:
         return ctx.pose_only_optimize(Xw, meas, info, sigma2, pose, fx, fy, cx, cy, bf)
 
     @staticmethod
+    def OptimizeSim3(ctx: Context, pc, pm, uv_c, uv_m, info_c, info_m, cam, model):
+        """Optimizer::OptimizeSim3 (Optimizer.cc:464-619) from the point where the graph is built, scale fixed: returns
+        (nInliers, model float32[12], which pairs stay in the match list, the estimate in double); see Context.sim3_optimize."""
+        return ctx.sim3_optimize(pc, pm, uv_c, uv_m, info_c, info_m, cam, model)
+
+    @staticmethod
     def OptimizeLocalMap(ctx: Context, problem, pose_fixed=None, iters_first=5, iters_second=10):
         """The g2o part of Optimizer::OptimizeLocalMap (Optimizer.cc:336-391) on the graph `problem` describes (the arrays of
         orbfe_ba_problem): optimize(5) with Huber, level-1 / kernel-off re-classification, optimize(10), final chi2 test.

@@ -11,6 +11,8 @@
 //   orbfe::dropin::OptimizePoseOnly       the body of `static int Optimizer::OptimizePoseOnly(Frame::SharedPtr)` (Optimizer.h:72, src/Optimizer.cc:33-203)
 //   orbfe::dropin::OptimizeLocalMap       the body of `static void Optimizer::OptimizeLocalMap(KeyFrame::SharedPtr, bool&)` (Optimizer.h:69,
 //                                         src/Optimizer.cc:225-442)
+//   orbfe::dropin::OptimizeSim3           the body of `static int Optimizer::OptimizeSim3(KeyFramePtr, KeyFramePtr, Matches&, Sim3Ret&, bool)`
+//                                         (Optimizer.h:75, src/Optimizer.cc:464-619)
 //   orbfe::dropin::searchByBow            the body of `int ORBMatcher::searchByBow(VirtualFrame::SharedPtr, VirtualFrame::SharedPtr,
 //                                         std::vector<cv::DMatch>&, bool, bool)` (ORBMatcher.h:42, src/ORBMatcher.cc:170-253)
 //   orbfe::dropin::searchByProjection x2  frame <- frame (ORBMatcher.h:49, src/ORBMatcher.cc:265-347) and frame <- map points (ORBMatcher.h:52,
@@ -142,7 +144,8 @@ namespace dropin {
 
 // Contexts for the solver entry points: one per calling thread role, since OptimizePoseOnly runs on the Tracking thread while
 // OptimizeLocalMap runs on the LocalMapping thread (System.cc:128) and one context serves one thread at a time.
-inline orbfe_ctx* solverContext(int role /*0: tracking, 1: local mapping*/) {
+// (OptimizeSim3 runs on the LoopClosing thread, System.cc:129: role 2.)
+inline orbfe_ctx* solverContext(int role /*0: tracking, 1: local mapping, 2: loop closing*/) {
   return ContextPool::get(160, 120, 16, 1, 1.2f, 20, 7, "", 0, 1 + role);  // a token geometry; the BA calls only use its stream and scratch
 }
 
@@ -281,6 +284,68 @@ static int OptimizePoseOnly(FramePtr pFrame) {
   }
   pFrame->setPose(poseToMat(out));
   return edges - nBad;
+}
+
+// static int Optimizer::OptimizeSim3(KeyFramePtr pCurr, KeyFramePtr pMatch, Matches& inLier, Sim3Ret& g2oScm, bool bFixedScale)
+// (src/Optimizer.cc:464-619), the whole body.  What stays here is map state (O8 of DESIGN 4.22): the vbIsInlier filter of :492-508 --
+// whose second test asks the CURRENT point's isInMap() again, not the matched one's, and so does this one (pMp1 is the reference's cP,
+// pMp2 its mP, mpMatch its pMatch) --, cPc = Rcw * cPw + tcw in float the way cv::Mat's product and sum round it
+// ((float)((double)(float row sum) + (double)t)), and the information of BOTH edges from pCurr->getScaledFactorInv2, the second with
+// pMatch's key point's octave (:546).  A free scale is not on the device: bFixedScale == false throws, and so does a g2oScm whose mfS
+// is not 1 (the solver that feeds it fixes the scale).
+template <class CameraT, class KeyFramePtr, class MatchesT, class Sim3RetT>
+static int OptimizeSim3(KeyFramePtr pCurr, KeyFramePtr mpMatch, MatchesT& inLier, Sim3RetT& g2oScm, bool bFixedScale = true) {
+  if (!bFixedScale || g2oScm.mfS != 1.0f) throw std::invalid_argument("OptimizeSim3: only the fixed-scale optimisation (mfS == 1) is on the device");
+  cv::Mat Rcw, tcw, Rmw, tmw;
+  pCurr->getPose(Rcw, tcw);
+  mpMatch->getPose(Rmw, tmw);
+  auto toCamera = [](const cv::Mat& R, const cv::Mat& t, const cv::Mat& Pw, std::vector<float>& out) {
+    for (int r = 0; r < 3; ++r) {
+      const float s = (R.template at<float>(r, 0) * Pw.template at<float>(0) + R.template at<float>(r, 1) * Pw.template at<float>(1)) +
+                      R.template at<float>(r, 2) * Pw.template at<float>(2);
+      out.push_back((float)((double)s + (double)t.template at<float>(r)));
+    }
+  };
+  std::vector<float> pc, pm, uvC, uvM;
+  std::vector<double> infoC, infoM;
+  MatchesT newInlier;
+  for (std::size_t idx = 0; idx < inLier.size(); ++idx) {
+    const auto& match = inLier[idx];
+    auto pMp1 = pCurr->getMapPoint(match.queryIdx);
+    auto pMp2 = mpMatch->getMapPoint(match.trainIdx);
+    if (!pMp1 || pMp1->isBad() || !pMp1->isInMap()) continue;
+    if (!pMp2 || pMp2->isBad() || !pMp1->isInMap()) continue;
+    toCamera(Rcw, tcw, pMp1->getPos(), pc);
+    toCamera(Rmw, tmw, pMp2->getPos(), pm);
+    const auto& ckp = pCurr->getLeftKeyPoint(match.queryIdx);
+    const auto& mkp = mpMatch->getLeftKeyPoint(match.trainIdx);
+    uvC.push_back(ckp.pt.x), uvC.push_back(ckp.pt.y);
+    uvM.push_back(mkp.pt.x), uvM.push_back(mkp.pt.y);
+    infoC.push_back((double)pCurr->getScaledFactorInv2(ckp.octave));
+    infoM.push_back((double)pCurr->getScaledFactorInv2(mkp.octave));
+    newInlier.push_back(match);
+  }
+  float model[12];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) model[3 * r + c] = g2oScm.mRqp.template at<float>(r, c);
+    model[9 + r] = g2oScm.mtqp.template at<float>(r);
+  }
+  std::vector<uint8_t> keep;
+  const int nInliers = orbfe::Optimizer::OptimizeSim3(solverContext(2), pc, pm, uvC, uvM, infoC, infoM, CameraT::mfFx, CameraT::mfFy,
+                                                      CameraT::mfCx, CameraT::mfCy, model, keep);
+  if (nInliers == 0 && std::all_of(keep.begin(), keep.end(), [](uint8_t k) { return k != 0; }))
+    return 0;  // :584-585: fewer than 20 pairs were left, nothing changes (an optimisation that ran and found no inlier clears every flag)
+  MatchesT kept;
+  for (std::size_t i = 0; i < newInlier.size(); ++i)
+    if (keep[i]) kept.push_back(newInlier[i]);
+  std::swap(kept, inLier);
+  cv::Mat Rn(3, 3, CV_32F), tn(3, 1, CV_32F);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) Rn.template at<float>(r, c) = model[3 * r + c];
+    tn.template at<float>(r) = model[9 + r];
+  }
+  Sim3RetT(Rn, tn, 1.0f).copyTo(g2oScm);
+  return nInliers;
 }
 
 // static void Optimizer::OptimizeLocalMap(KeyFrame::SharedPtr pkframe, bool& isStop)  (src/Optimizer.cc:225-442).
@@ -1192,6 +1257,10 @@ int OptimizePoseOnly(FramePtr pFrame) {
 template <class CameraT, class KeyFramePtr>
 void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
   Bodies::template OptimizeLocalMap<CameraT>(pkframe, isStop);
+}
+template <class CameraT, class KeyFramePtr, class MatchesT, class Sim3RetT>
+int OptimizeSim3(KeyFramePtr pCurr, KeyFramePtr pMatch, MatchesT& inLier, Sim3RetT& g2oScm, bool bFixedScale = true) {
+  return Bodies::template OptimizeSim3<CameraT>(pCurr, pMatch, inLier, g2oScm, bFixedScale);
 }
 template <class CameraT, class KeyFramePtr, class Sim3T>
 int searchBySim3(KeyFramePtr mpCurr, KeyFramePtr mpMatch, std::vector<cv::DMatch>& matches, Sim3T& g2oScm, float th, float mfRatio = 0.6f) {

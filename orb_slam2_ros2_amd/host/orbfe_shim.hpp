@@ -824,6 +824,22 @@ class Optimizer {
     inlier.resize(n);
     return good;
   }
+  // Optimizer::OptimizeSim3 (src/Optimizer.cc:464-619) from the point where the graph is built, scale fixed: pc / pm = cPc / mPc of every
+  // match ([n][3]), uvC / uvM the two key points ([n][2]), infoC / infoM the information of the two edges; model (R row-major, t) in /
+  // out; keep[i] = 1 for the matches that stay in the list.  Returns nInliers; 0 with fewer than 20 pairs left (model untouched, keep all 1).
+  static int OptimizeSim3(orbfe_ctx* ctx, const std::vector<float>& pc, const std::vector<float>& pm, const std::vector<float>& uvC,
+                          const std::vector<float>& uvM, const std::vector<double>& infoC, const std::vector<double>& infoM, float fx,
+                          float fy, float cx, float cy, float model[12], std::vector<uint8_t>& keep) {
+    const size_t n = infoC.size();
+    if (pc.size() != 3 * n || pm.size() != 3 * n || uvC.size() != 2 * n || uvM.size() != 2 * n || infoM.size() != n)
+      throw std::invalid_argument("OptimizeSim3: the pair arrays disagree in length");
+    keep.assign(std::max<size_t>(n, 1), 0);
+    int32_t nInliers = 0;
+    check(ctx, orbfe_sim3_optimize(ctx, (int32_t)n, pc.data(), pm.data(), uvC.data(), uvM.data(), infoC.data(), infoM.data(), fx, fy, cx, cy,
+                                   model, keep.data(), &nInliers, nullptr));
+    keep.resize(n);
+    return nInliers;
+  }
 };
 
 }  // namespace orbfe
