@@ -968,6 +968,60 @@ orbfe_status orbfe_search_by_bow_stored(orbfe_ctx* ctx, orbfe_kfstore* store, co
                                         int32_t mode, float ratio, int32_t dist_threshold, int32_t check_orientation,
                                         orbfe_bow_match* matches, int64_t cap, int64_t* match_offsets /*[n_kf + 1]*/);
 
+/* ---- searchBySim3 over stored keyframes --------------------------------------------------------------------------------
+ * Both overloads of ORBMatcher::searchBySim3 (src/ORBMatcher.cc:370-559), the step of LoopClosing::computeSim3 between the Sim3 RANSAC
+ * and OptimizeSim3 and its last step over the loop group's map points.  The keyframes are named by id and read where the store keeps
+ * them (features, descriptors, bounds, area grid); only map state goes up: flags, positions, distance ranges, poses, the similarity.
+ * model / s: orbfe_sim3_iterate's layout, R row-major then t, p_c = s R p_m + t (the points overload: p_c = s R p_w + t).
+ *   arithmetic   a 3x3 row times a vector is the float sum a0 b0 + a1 b1 + a2 b2 left to right; alpha A x + t is
+ *                (float)((double)alpha * sum + (double)t); Sim3Ret::inv: s' = 1.f / s, R^T, t' = -s' * (R^T t) in float
+ *   project      u = fx * (x / z) + cx, v = fy * (y / z) + cy; rejected: z <= 0, not (u < maxU && v < maxV && u > minU && v > minV),
+ *                not (d < max_dist && d > min_dist)
+ *   window       octave o = predictLevel(max_dist, d) clamped to [0, min(7, n_levels - 1)]; radius th * sf[o]^2; octaves o - 1 .. o + 1
+ *                (not clamped); findFeaturesInArea over the TARGET's grid: rows outer, columns inner, index order inside a cell
+ *   best match   getBestMatch (:967-990): first minimum; the second best is never an earlier record, INT_MAX with one candidate
+ *   accepted     the list is not empty && best <= dist_threshold && (float)best / (float)second <= ratio (0 / 0 is rejected)
+ * orbfe_search_by_sim3_stored (the pair, :424-484), one launch of n_c + n_m waves:
+ *   A (:446-461) feature ic of cur named by no input match, GOOD and INMAP: Rcw_C, then Scm.inv(); isInImage on CUR's bounds (the
+ *                reference asks the keyframe the point comes from); d = sqrtf(x*x + y*y + z*z) / s'; target match, its features
+ *                without GOOD and INMAP left out
+ *   B (:463-475) feature im of match named by no input match, GOOD: Rcw_M, then Scm; MATCH's bounds; / s; target cur, same filter
+ *   merge        std::map::insert: A's (ic, best), then B's (best, im) in ascending im where the key is absent; new_matches gets the
+ *                new pairs in ascending query (distance 0).  A key may repeat the query of an input match (the reference does not check).
+ * orbfe_search_by_sim3_points_stored (:501-549), one launch of m waves: point j with usable[j] (the caller clears it for points that
+ * are null, bad, not in the map or already in vMatchedMps); isInImage on the keyframe's bounds; dWithS = (float)sqrt of the double sum,
+ * d = dWithS / s; view test: rv = R * view_dir in float, rejected iff the double dot rv . p < 0.5 * (double)dWithS; no filter on the
+ * keyframe's features.  best_idx[j] = the feature or -1, best_dist[j] its distance (0 with -1); the caller applies
+ * vMatchedMps[best_idx[j]] = point j in ascending j (a later point overwrites an earlier one, every accept counts).
+ * cur->id == match->id is allowed; n, m or n_matches of 0: ORBFE_OK; m <= 2^20.  More new pairs than cap: ORBFE_ECAPACITY with *n_new set,
+ * nothing written.  ORBFE_EBADARG, nothing written: an unknown id, n unequal to the stored count, a match index out of range, s or a model
+ * entry not finite or s <= 0, n_levels below the store's, a NULL array with a non-zero count, a context on another device.  Locks: the
+ * context's, then the store's (shared) for the whole synchronous duration.  One upload, one launch, one download.                  */
+typedef struct orbfe_sim3_side {      /* one keyframe of the pair: its id in the store and its map state                             */
+  uint64_t id;
+  int32_t n;                          /* must equal the stored count                                                                 */
+  const uint8_t* flags;               /* [n] ORBFE_TRI_GOOD | ORBFE_TRI_INMAP of the feature's map point; NULL: all 0                */
+  const float* pos;                   /* [n][3] world positions (with flags NULL not read)                                           */
+  const float *max_dist, *min_dist;   /* [n] MapPoint::getDistance                                                                   */
+  float Rcw[9], tcw[3];
+} orbfe_sim3_side;
+typedef struct orbfe_sim3_points {    /* vLoopGroupMps as arrays                                                                     */
+  int32_t m;
+  const uint8_t* usable;              /* [m]                                                                                         */
+  const float *pos, *view_dir;        /* [m][3]                                                                                      */
+  const float *max_dist, *min_dist;   /* [m]                                                                                         */
+  const uint8_t* desc;                /* [m][32] MapPoint::getDesc()                                                                 */
+} orbfe_sim3_points;
+orbfe_status orbfe_search_by_sim3_stored(orbfe_ctx* ctx, orbfe_kfstore* store, const orbfe_sim3_side* cur, const orbfe_sim3_side* match,
+                                         const float* model /*[12]*/, float s, int32_t n_matches,
+                                         const orbfe_bow_match* matches /*query in cur, train in match; distance not read*/,
+                                         const orbfe_camera* cam, const float* scale_factors, int32_t n_levels, float th, float ratio,
+                                         int32_t dist_threshold, orbfe_bow_match* new_matches, int32_t cap, int32_t* n_new);
+orbfe_status orbfe_search_by_sim3_points_stored(orbfe_ctx* ctx, orbfe_kfstore* store, uint64_t id, const orbfe_sim3_points* pts,
+                                                const float* model /*[12]*/, float s, const orbfe_camera* cam, const float* scale_factors,
+                                                int32_t n_levels, float th, float ratio, int32_t dist_threshold, int32_t* best_idx /*[m]*/,
+                                                int32_t* best_dist /*[m]*/);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

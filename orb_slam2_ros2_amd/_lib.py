@@ -166,6 +166,16 @@ TRI_REC_DTYPE = np.dtype([("nb", "<i4"), ("q", "<i4"), ("t", "<i4"), ("kind", "<
 TRI_MAX_NB = 64
 
 
+class Sim3Side(C.Structure):
+    _fields_ = [("id", C.c_uint64), ("n", C.c_int32), ("flags", C.c_void_p), ("pos", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3)]
+
+
+class Sim3Points(C.Structure):
+    _fields_ = [("m", C.c_int32), ("usable", C.c_void_p), ("pos", C.c_void_p), ("view_dir", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("desc", C.c_void_p)]
+
+
 class BaEdgeOut(C.Structure):
     _fields_ = [("error", C.c_void_p), ("chi2", C.c_void_p), ("rho", C.c_void_p), ("j_point", C.c_void_p),
                 ("j_pose", C.c_void_p), ("depth_positive", C.c_void_p)]
@@ -187,7 +197,7 @@ EXPORTS = [
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
-    "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored",
+    "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges",
 ]
@@ -324,6 +334,9 @@ def load() -> C.CDLL:
     L.orbfe_create_new_map_points_stored.argtypes = [vp, vp, u64, C.POINTER(TriState), i32, vp, vp, C.POINTER(Camera), vp, f32, vp, i32, vp, i64,
                                                      C.POINTER(i64), vp, i64, C.POINTER(i64), vp]
     L.orbfe_search_by_bow_stored.argtypes = [vp, vp, C.POINTER(BowQuery), i32, vp, vp, i32, f32, i32, i32, vp, i64, vp]
+    L.orbfe_search_by_sim3_stored.argtypes = [vp, vp, C.POINTER(Sim3Side), C.POINTER(Sim3Side), vp, f32, i32, vp, C.POINTER(Camera), vp, i32, f32,
+                                              f32, i32, vp, i32, C.POINTER(i32)]
+    L.orbfe_search_by_sim3_points_stored.argtypes = [vp, vp, u64, C.POINTER(Sim3Points), vp, f32, C.POINTER(Camera), vp, i32, f32, f32, i32, vp, vp]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -1768,6 +1781,78 @@ class Context:
         self.last_bow_offsets, self.last_bow_matches = offs, out
         self._check(st)
         return [out[offs[k]:offs[k + 1]].copy() for k in range(K)]
+
+    @staticmethod
+    def _sim3_side(side, keep):
+        """dict(id, flags [n] or None, pos [n, 3], max_dist, min_dist, Rcw, tcw; n: the count when flags is None) -> Sim3Side"""
+        o = Sim3Side()
+        o.id = int(side["id"])
+        if side.get("flags") is None:
+            o.n = int(side["n"])
+        else:
+            fl = np.ascontiguousarray(side["flags"], np.uint8).reshape(-1)
+            pos = np.ascontiguousarray(side["pos"], np.float32).reshape(-1, 3)
+            mx, mn = np.ascontiguousarray(side["max_dist"], np.float32), np.ascontiguousarray(side["min_dist"], np.float32)
+            if not len(fl) == len(pos) == len(mx) == len(mn):
+                raise ValueError("search_by_sim3_stored: the arrays of a side differ in length")
+            keep += [fl, pos, mx, mn]
+            o.n, o.flags, o.pos, o.max_dist, o.min_dist = len(fl), ptr(fl).value, ptr(pos).value, ptr(mx).value, ptr(mn).value
+        o.Rcw[:] = np.asarray(side["Rcw"], np.float32).reshape(9).tolist()
+        o.tcw[:] = np.asarray(side["tcw"], np.float32).reshape(3).tolist()
+        return o
+
+    @staticmethod
+    def _sim3_model(model, s):
+        """(R [3, 3], t [3]) or 12 floats -> the [12] array of the C call"""
+        if isinstance(model, (tuple, list)) and len(model) == 2:
+            model = np.concatenate([np.asarray(model[0], np.float32).reshape(9), np.asarray(model[1], np.float32).reshape(3)])
+        return np.ascontiguousarray(model, np.float32).reshape(12), float(np.float32(s))
+
+    def search_by_sim3_stored(self, store, cur, match, model, s, matches, cam, scale_factors, th, ratio, dist_threshold, cap=None):
+        """ORBMatcher::searchBySim3(mpCurr, mpMatch, matches, g2oScm, th) over two stored keyframes in one call
+        (orbfe_search_by_sim3_stored).  cur / match: dict(id, flags [n] uint8 ORBFE_TRI_GOOD | ORBFE_TRI_INMAP or None (then n), pos [n, 3],
+        max_dist [n], min_dist [n], Rcw, tcw); model: (R, t) or 12 floats, p_c = s R p_m + t; matches: [(query in cur, train in match)];
+        cam: (fx, fy, cx, cy).  Returns the NEW pairs [(query, train)] in ascending query; self.last_sim3_new holds *n_new (also after an
+        ECAPACITY failure)."""
+        keep = []
+        c_side, m_side = self._sim3_side(cur, keep), self._sim3_side(match, keep)
+        mdl, s = self._sim3_model(model, s)
+        pairs = np.asarray([(m[0], m[1]) for m in matches], np.int32).reshape(-1, 2)
+        mt = np.zeros(len(pairs), BOW_MATCH_DTYPE)
+        mt["query"], mt["train"] = pairs[:, 0], pairs[:, 1]
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        cm = Camera(float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), 0.0)
+        cap = min(c_side.n, 1 << 30) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), BOW_MATCH_DTYPE)
+        n_new = C.c_int32(-1)
+        self._sim3_search_args = (self.h, store.h, C.byref(c_side), C.byref(m_side), ptr(mdl), s, len(mt), ptr(mt) if len(mt) else None, C.byref(cm),
+                                  ptr(sf), len(sf), float(th), float(ratio), int(dist_threshold), ptr(out), cap, C.byref(n_new))
+        self._sim3_search_keep = (keep, c_side, m_side, mdl, mt, cm, sf, out, n_new)
+        st = self.lib.orbfe_search_by_sim3_stored(*self._sim3_search_args)
+        self.last_sim3_new, self.last_sim3_out = n_new.value, out
+        self._check(st)
+        return list(zip(out["query"][:n_new.value].tolist(), out["train"][:n_new.value].tolist()))
+
+    def search_by_sim3_points_stored(self, store, kf_id, pts, model, s, cam, scale_factors, th, ratio, dist_threshold):
+        """ORBMatcher::searchBySim3(pCurr, vLoopGroupMps, vMatchedMps, g2oScw, th) against the stored keyframe kf_id in one call
+        (orbfe_search_by_sim3_points_stored).  pts: dict(usable [m], pos [m, 3], view_dir [m, 3], max_dist [m], min_dist [m], desc [m, 32]);
+        model: (R, t) or 12 floats, p_c = s R p_w + t.  Returns (best_idx [m] (-1: none), best_dist [m])."""
+        us = np.ascontiguousarray(pts["usable"], np.uint8).reshape(-1)
+        pos = np.ascontiguousarray(pts["pos"], np.float32).reshape(-1, 3)
+        vd = np.ascontiguousarray(pts["view_dir"], np.float32).reshape(-1, 3)
+        mx, mn = np.ascontiguousarray(pts["max_dist"], np.float32), np.ascontiguousarray(pts["min_dist"], np.float32)
+        d = np.ascontiguousarray(pts["desc"], np.uint8).reshape(-1, 32)
+        m = len(us)
+        if not m == len(pos) == len(vd) == len(mx) == len(mn) == len(d):
+            raise ValueError("search_by_sim3_points_stored: the point arrays differ in length")
+        p = Sim3Points(m, *[ptr(a).value if m else None for a in (us, pos, vd, mx, mn, d)])
+        mdl, s = self._sim3_model(model, s)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        cm = Camera(float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), 0.0)
+        bi, bd = np.full(max(m, 1), -1, np.int32), np.zeros(max(m, 1), np.int32)
+        self._check(self.lib.orbfe_search_by_sim3_points_stored(self.h, store.h, int(kf_id), C.byref(p), ptr(mdl), s, C.byref(cm), ptr(sf), len(sf),
+                                                                float(th), float(ratio), int(dist_threshold), ptr(bi), ptr(bd)))
+        return bi[:m], bd[:m]
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

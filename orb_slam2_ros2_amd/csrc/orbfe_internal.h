@@ -421,3 +421,31 @@ struct BowSlot {
 struct BowMatch {
   int32_t q, t, d;
 };
+
+// ---- searchBySim3 over stored keyframes (k_sim3search.hip, orbfe_sim3search.hip) -----------------------------------------------------
+// One keyframe of the pair as the device reads it: its arrays where the keyframe store keeps them, its map state at offsets of the
+// call's upload, its pose, and the similarity that takes a point of ITS camera frame into the other keyframe's (direction A, source C:
+// Scm.inv(); direction B, source M: Scm).  state[i] = the flag byte of feature i | SIM3S_NAMED if an input match names the feature.
+#define SIM3S_NAMED 4
+struct Sim3Kf {
+  const orbfe_keypoint* kps;
+  const uint8_t* desc;
+  const int32_t *cell_off, *cell_feat;
+  int32_t n, rows, cols, clip_w, clip_h;
+  uint32_t o_state, o_pos, o_max, o_min;
+  float bounds[4];
+  float Rcw[9], tcw[3];
+  float s, R[9], t[3];
+};
+struct Sim3SearchParams {
+  float fx, fy, cx, cy;
+  float th, ratio, log_sf;
+  int32_t dist_threshold, max_level;
+  uint32_t o_sf;
+};
+// the points overload: the loop group's map points at offsets of the upload, the similarity Scw
+struct Sim3Points {
+  uint32_t o_usable, o_pos, o_vdir, o_max, o_min, o_desc;
+  int32_t m;
+  float s, R[9], t[3];
+};

@@ -260,6 +260,36 @@ class ORBMatcher(MatcherExt):
         out = ctx.search_by_bow_stored(store, query, kf_ids, kf_flags, mode, self.mfRatio, self.mnMinThreshold, self.mbCheckOri)
         return [[(int(m["query"]), int(m["train"]), int(m["distance"])) for m in a] for a in out]
 
+    @staticmethod
+    def _sim3_flags(kf):
+        # ORBFE_TRI_GOOD | ORBFE_TRI_INMAP
+        return (np.asarray(kf["good"], bool) * 1 | np.asarray(kf["inmap"], bool) * 2).astype(np.uint8)
+
+    def searchBySim3Stored(self, ctx, store, matches, Scm, poseC, poseM, idC, idM, kfC, kfM, th, cam, scale_factors):
+        """searchBySim3Frames over the stored keyframes idC / idM in ONE device call (Context.search_by_sim3_stored): kfC / kfM carry map
+        state only, dict(pos, good, inmap, max_dist, min_dist); the isInImage bounds and the search grids are the store's.  Returns what
+        searchBySim3Frames returns: the input matches followed by the new pairs in ascending queryIdx."""
+        s, R, t = Scm
+        sides = [dict(id=i, flags=self._sim3_flags(kf), pos=kf["pos"], max_dist=kf["max_dist"], min_dist=kf["min_dist"], Rcw=p[0], tcw=p[1])
+                 for i, kf, p in ((idC, kfC, poseC), (idM, kfM, poseM))]
+        pairs = [(int(m[0]), int(m[1])) for m in matches]
+        new = ctx.search_by_sim3_stored(store, sides[0], sides[1], (R, t), s, pairs, cam, scale_factors, th, self.mfRatio, self.mnMinThreshold)
+        return list(matches) + new
+
+    def searchBySim3PointsStored(self, ctx, store, kf_id, loop_mps, matched, Scw, th, cam, scale_factors):
+        """searchBySim3MapPoints against the stored keyframe kf_id in ONE device call (Context.search_by_sim3_points_stored); loop_mps and
+        matched as there.  Returns (assignments [(featIdx, loop map point index)] in loop order, nMatches)."""
+        s, R, t = Scw
+        matched = np.asarray(matched, np.int64)
+        already = set(int(v) for v in matched if v >= 0)
+        n_matches = int((matched >= 0).sum())
+        ids = np.asarray(loop_mps["id"], np.int64)
+        usable = np.array([bool(u) and int(i) not in already for u, i in zip(loop_mps["usable"], ids)], bool)
+        bi, _ = ctx.search_by_sim3_points_stored(store, kf_id, dict(loop_mps, usable=usable), (R, t), s, cam, scale_factors, th, self.mfRatio,
+                                                 self.mnMinThreshold)
+        out = [(int(bi[j]), int(j)) for j in np.flatnonzero(bi >= 0)]
+        return out, n_matches + len(out)
+
     @classmethod
     def verifyAngle(cls, matches, angles1, angles2):
         """ORBMatcher::verifyAngle (ORBMatcher.cc:1013-1051): 30-bin histogram of angle differences (float arithmetic), the three

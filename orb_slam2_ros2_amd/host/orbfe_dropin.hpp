@@ -745,6 +745,10 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
   static orbfe::ORBMatcher::Intrinsics intrinsics(FramePtr f) {
     return {CameraT::mfFx, CameraT::mfFy, CameraT::mfCx, CameraT::mfCy, f->mfMinU, f->mfMaxU, f->mfMinV, f->mfMaxV};
   }
+  template <class FramePtr>
+  static const std::vector<float>& scaleFactors(FramePtr f) {  // VirtualFrame::mvfScaledFactors (protected: through the friend line)
+    return f->mvfScaledFactors;
+  }
   static void poseFloats(const cv::Mat& Rcw, const cv::Mat& tcw, float* R, float* t) {
     for (int r = 0; r < 3; ++r) {
       for (int c = 0; c < 3; ++c) R[3 * r + c] = Rcw.template at<float>(r, c);

@@ -10,10 +10,15 @@
 // which gives, per candidate, the std::vector<cv::DMatch> the reference's searchByBow (src/ORBMatcher.cc:170-253) leaves -- ONE device
 // call per 64 candidates instead of one per candidate.  A candidate the store does not hold yet is inserted from its host arrays on
 // first use (KeyframeStore::ensureBow).  A Frame goes up as arrays; a current KEYFRAME (queryStored) is named by its id.
+// At the end of the file, INTEGRATION.md section 16: both ORBMatcher::searchBySim3 overloads over the same store
+// (orbfe_search_by_sim3_stored / orbfe_search_by_sim3_points_stored),
+//     orbfe::dropin::searchBySim3<Camera>(store, mpCurr, mpMatch, matches, g2oScm, th, mfRatio)
+//     orbfe::dropin::searchBySim3<Camera>(store, pCurr, vLoopGroupMps, vMatchedMps, g2oScw, th, mfRatio)
 #pragma once
 
 #include <algorithm>
 #include <map>
+#include <set>
 
 #include "orbfe_kfstore_dropin.hpp"
 
@@ -208,6 +213,93 @@ int sim3Candidates(KeyframeStore<Access>& store, KeyFramePtr mpCurrKeyFrame, con
     }
   }
   return nCandidates;
+}
+
+// ---- ORBMatcher::searchBySim3 over stored keyframes (orbfe_search_by_sim3_stored / _points_stored) ----
+namespace sim3_detail {
+
+// the map state of a keyframe's n features (the part of Bodies::keyFrameView the stored call reads)
+template <class KeyFramePtr>
+inline void mapState(KeyFramePtr kf, size_t n, orbfe::ORBMatcher::KeyFrameView& v) {
+  auto mps = kf->getMapPoints();
+  v.pos.assign(3 * n, 0.f), v.good.assign(n, 0), v.inMap.assign(n, 0), v.maxDist.assign(n, 0.f), v.minDist.assign(n, 0.f);
+  for (size_t i = 0; i < n && i < mps.size(); ++i) {
+    const auto& p = mps[i];
+    if (!p || p->isBad()) continue;
+    v.good[i] = 1, v.inMap[i] = p->isInMap() ? 1 : 0;
+    const cv::Mat X = p->getPos();
+    for (int a = 0; a < 3; ++a) v.pos[3 * i + a] = X.template at<float>(a);
+    p->getDistance(v.maxDist[i], v.minDist[i]);
+  }
+}
+template <class KeyFramePtr, class Access>
+inline size_t storedCount(KeyframeStore<Access>& store, const KeyFramePtr& kf) {
+  store.ensureFeatures(kf);
+  orbfe_kfstore_info i;
+  store.info(kf, &i);
+  return (size_t)i.n;
+}
+
+}  // namespace sim3_detail
+
+// int ORBMatcher::searchBySim3(KeyFramePtr mpCurr, KeyFramePtr mpMatch, std::vector<cv::DMatch>& matches, Sim3Ret& g2oScm, float th)
+// (ORBMatcher.h:55, src/ORBMatcher.cc:424-484): both SIM3Project sweeps and the merge in ONE device call; only map state goes up
+template <class CameraT, class KeyFramePtr, class Sim3T, class Access>
+int searchBySim3(KeyframeStore<Access>& store, KeyFramePtr mpCurr, KeyFramePtr mpMatch, std::vector<cv::DMatch>& matches, Sim3T& g2oScm, float th,
+                 float mfRatio = 0.6f) {
+  orbfe::ORBMatcher::KeyFrameView C, M;
+  sim3_detail::mapState(mpCurr, sim3_detail::storedCount(store, mpCurr), C);
+  sim3_detail::mapState(mpMatch, sim3_detail::storedCount(store, mpMatch), M);
+  cv::Mat Rcw, tcw, Rmw, tmw;
+  mpCurr->getPose(Rcw, tcw), mpMatch->getPose(Rmw, tmw);
+  float Rc[9], tc[3], Rm[9], tm[3];
+  Bodies::poseFloats(Rcw, tcw, Rc, tc), Bodies::poseFloats(Rmw, tmw, Rm, tm);
+  std::vector<std::pair<int, int>> pairs;
+  for (const auto& m : matches) pairs.emplace_back(m.queryIdx, m.trainIdx);
+  const size_t had = pairs.size();
+  orbfe::ORBMatcher(mfRatio).searchBySim3(matcherContext(), store.get(), store.id(mpCurr), store.id(mpMatch), C, M, pairs, Bodies::toSim3(g2oScm), Rc, tc,
+                                          Rm, tm, th, Bodies::template intrinsics<CameraT>(mpCurr), Bodies::scaleFactors(mpCurr));
+  for (size_t k = had; k < pairs.size(); ++k) {
+    cv::DMatch m;
+    m.queryIdx = pairs[k].first, m.trainIdx = pairs[k].second;
+    matches.push_back(m);
+  }
+  return (int)matches.size();
+}
+
+// int ORBMatcher::searchBySim3(KeyFramePtr pCurr, const std::vector<MapPointPtr>& vLoopGroupMps, std::vector<MapPointPtr>& vMatchedMps,
+//                              Sim3Ret& g2oScw, float th)   (ORBMatcher.h:58, src/ORBMatcher.cc:501-559): the projection tests too run on
+// the device; the loop group goes up as arrays, pCurr is read where the store keeps it
+template <class CameraT, class KeyFramePtr, class MapPointPtr, class Sim3T, class Access>
+int searchBySim3(KeyframeStore<Access>& store, KeyFramePtr pCurr, const std::vector<MapPointPtr>& vLoopGroupMps, std::vector<MapPointPtr>& vMatchedMps,
+                 Sim3T& g2oScw, float th, float mfRatio = 0.6f) {
+  int nMatches = 0;
+  std::set<MapPointPtr> sAlreadyMatched;
+  for (const auto& p : vMatchedMps)
+    if (p && !p->isBad() && p->isInMap()) sAlreadyMatched.insert(p), ++nMatches;
+  const size_t m = vLoopGroupMps.size();
+  orbfe::ORBMatcher::LoopPoints pts;
+  pts.usable.assign(m, 0), pts.pos.assign(3 * m, 0.f), pts.viewDir.assign(3 * m, 0.f), pts.maxDist.assign(m, 0.f), pts.minDist.assign(m, 0.f);
+  pts.desc.resize(m);
+  for (size_t i = 0; i < m; ++i) {
+    const auto& pMp = vLoopGroupMps[i];
+    if (!pMp || pMp->isBad() || !pMp->isInMap() || sAlreadyMatched.count(pMp)) continue;
+    pts.usable[i] = 1;
+    const cv::Mat Xw = pMp->getPos(), vd = pMp->getViewDirection(), d = pMp->getDesc();
+    for (int a = 0; a < 3; ++a) pts.pos[3 * i + a] = Xw.template at<float>(a), pts.viewDir[3 * i + a] = vd.template at<float>(a);
+    pMp->getDistance(pts.maxDist[i], pts.minDist[i]);
+    std::memcpy(pts.desc[i].data(), d.data, 32);
+  }
+  store.ensureFeatures(pCurr);
+  std::vector<int32_t> bestIdx, bestDist;
+  orbfe::ORBMatcher(mfRatio).searchBySim3(matcherContext(), store.get(), store.id(pCurr), pts, Bodies::toSim3(g2oScw), th,
+                                          Bodies::template intrinsics<CameraT>(pCurr), Bodies::scaleFactors(pCurr), bestIdx, bestDist);
+  for (size_t i = 0; i < m; ++i)
+    if (bestIdx[i] >= 0) {
+      vMatchedMps[(size_t)bestIdx[i]] = vLoopGroupMps[i];
+      ++nMatches;
+    }
+  return nMatches;
 }
 
 }  // namespace dropin

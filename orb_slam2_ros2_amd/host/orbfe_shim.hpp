@@ -721,6 +721,65 @@ class ORBMatcher {
     for (const auto& m : fresh) matches.push_back(m);
     return (int)matches.size();
   }
+  // ... over two keyframes of a keyframe store (orbfe_search_by_sim3_stored): ONE device call; of C and M only the map state
+  // is read (good, inMap, pos, maxDist, minDist), the features, the isInImage bounds and the grids are the store's
+  int searchBySim3(orbfe_ctx* ctx, orbfe_kfstore* store, uint64_t idC, uint64_t idM, const KeyFrameView& C, const KeyFrameView& M,
+                   std::vector<std::pair<int, int>>& matches, const Sim3& Scm, const float* RcwC, const float* tcwC, const float* RcwM,
+                   const float* tcwM, float th, const Intrinsics& K, const std::vector<float>& scaleFactors) const {
+    std::vector<uint8_t> flags[2];
+    orbfe_sim3_side side[2];
+    const KeyFrameView* kf[2] = {&C, &M};
+    const uint64_t id[2] = {idC, idM};
+    const float *R[2] = {RcwC, RcwM}, *t[2] = {tcwC, tcwM};
+    for (int k = 0; k < 2; ++k) {
+      const size_t n = kf[k]->good.size();
+      flags[k].resize(n);
+      for (size_t i = 0; i < n; ++i)
+        flags[k][i] = (uint8_t)((kf[k]->good[i] ? ORBFE_TRI_GOOD : 0) | (kf[k]->good[i] && kf[k]->inMap[i] ? ORBFE_TRI_INMAP : 0));
+      side[k] = orbfe_sim3_side();
+      side[k].id = id[k], side[k].n = (int32_t)n;
+      side[k].flags = flags[k].data(), side[k].pos = kf[k]->pos.data(), side[k].max_dist = kf[k]->maxDist.data(), side[k].min_dist = kf[k]->minDist.data();
+      for (int a = 0; a < 9; ++a) side[k].Rcw[a] = R[k][a];
+      for (int a = 0; a < 3; ++a) side[k].tcw[a] = t[k][a];
+    }
+    std::vector<orbfe_bow_match> in(matches.size()), fresh(std::max<size_t>(C.good.size(), 1));
+    for (size_t k = 0; k < matches.size(); ++k) in[k] = {matches[k].first, matches[k].second, 0};
+    float model[12];
+    sim3Model(Scm, model);
+    const orbfe_camera cam = {K.fx, K.fy, K.cx, K.cy, 0, 0, 0, 0, 0, 0};
+    int32_t nNew = 0;
+    check(ctx, orbfe_search_by_sim3_stored(ctx, store, &side[0], &side[1], model, Scm.s, (int32_t)in.size(), in.data(), &cam, scaleFactors.data(),
+                                           (int32_t)scaleFactors.size(), th, mfRatio, mnMinThreshold, fresh.data(), (int32_t)C.good.size(), &nNew));
+    for (int32_t k = 0; k < nNew; ++k) matches.emplace_back(fresh[(size_t)k].query, fresh[(size_t)k].train);
+    return (int)matches.size();
+  }
+  // ORBMatcher::searchBySim3(pCurr, vLoopGroupMps, vMatchedMps, g2oScw, th) (src/ORBMatcher.cc:501-549) against the stored keyframe `id`
+  // (orbfe_search_by_sim3_points_stored): bestIdx[j] = the feature loop point j matches or -1; the caller applies
+  // vMatchedMps[bestIdx[j]] = point j in ascending j.  usable[j] = non-null, not bad, in the map, not in vMatchedMps already.
+  struct LoopPoints {
+    std::vector<uint8_t> usable;
+    std::vector<float> pos, viewDir, maxDist, minDist;  // [m][3], [m][3], [m], [m]
+    std::vector<Descriptor> desc;
+  };
+  void searchBySim3(orbfe_ctx* ctx, orbfe_kfstore* store, uint64_t id, const LoopPoints& pts, const Sim3& Scw, float th, const Intrinsics& K,
+                    const std::vector<float>& scaleFactors, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) const {
+    const size_t m = pts.usable.size();
+    bestIdx.assign(std::max<size_t>(m, 1), -1), bestDist.assign(std::max<size_t>(m, 1), 0);
+    orbfe_sim3_points p = orbfe_sim3_points();
+    p.m = (int32_t)m;
+    p.usable = pts.usable.data(), p.pos = pts.pos.data(), p.view_dir = pts.viewDir.data(), p.max_dist = pts.maxDist.data(), p.min_dist = pts.minDist.data();
+    p.desc = m ? pts.desc[0].data() : nullptr;
+    float model[12];
+    sim3Model(Scw, model);
+    const orbfe_camera cam = {K.fx, K.fy, K.cx, K.cy, 0, 0, 0, 0, 0, 0};
+    check(ctx, orbfe_search_by_sim3_points_stored(ctx, store, id, &p, model, Scw.s, &cam, scaleFactors.data(), (int32_t)scaleFactors.size(), th, mfRatio,
+                                                  mnMinThreshold, bestIdx.data(), bestDist.data()));
+    bestIdx.resize(m), bestDist.resize(m);
+  }
+  static void sim3Model(const Sim3& S, float model[12]) {  // orbfe_sim3_iterate's layout: R row-major, then t
+    for (int a = 0; a < 9; ++a) model[a] = S.R[a];
+    for (int a = 0; a < 3; ++a) model[9 + a] = S.t[a];
+  }
   // ORBMatcher::processFuseMps (src/ORBMatcher.cc:623-661): the decision per match; the caller applies it to its map
   struct FuseAction {
     enum Kind { Add, Replace } kind;
