@@ -5,144 +5,27 @@
 // ORBMatcher.cc:265-347, map points to frame :561-612): candidates of a query = the features of the 64x48-px grid cells that
 // overlap its search box, rows outer / columns inner / index order inside a cell, filtered by octave range and an exclusion
 // mask, scanned with the reference's order-dependent best / second-best rule.  SURVEY 8f, row f1.
+// The kernels here are thin: the grid build is area_grid_body.h, the area loop and the fold area_search_body.h (this file's filter: the
+// octave of the packed record, then the exclusion mask and its hit counts), isInVision / predictLevel map_point_dev.h.
 #include <hip/hip_runtime.h>
 
+#include "area_search_body.h"
+#include "map_point_dev.h"
 #include "orbfe_internal.h"
-#include "wave_ops.h"
+#include "search_area_layout.h"
 
 namespace orbfe {
 
-#define GRID_W 64
-#define GRID_H 48
-#define ORB_INT_MAX 2147483647
-
-__device__ __forceinline__ int cvfloor_f(float v) {
-  const int i = (int)v;
-  return i - (i > v);
-}
-
-// cell of a coordinate: cvFloor(v / size) as Frame.cc:64-65, clamped to the grid at BOTH ends.  The reference indexes its vector of
-// cells unchecked (a negative or too large undistorted coordinate is undefined behaviour there); here such a feature lands in the
-// border cell, and a non-finite coordinate in cell 0, so that no index leaves the LDS counters or the scratch lists.
-__device__ __forceinline__ int grid_cell(float v, int size, int n) {
-  const float q = v / (float)size;
-  if (!(q > 0.0f)) return 0;          // negative, -0, NaN
-  if (q >= (float)(n - 1)) return n - 1;  // beyond the last cell, +inf
-  return cvfloor_f(q);
-}
-
-// ---------------------------------------------------------------------------------------------
-// grid build: one workgroup per call.  cell_off[ncells+1], cell_feat[n] (features of a cell in ascending index).
-// ---------------------------------------------------------------------------------------------
-#define GRID_NT 1024
-__global__ __launch_bounds__(GRID_NT) void k_grid_build(const orbfe_keypoint* __restrict__ kps, const int32_t* __restrict__ n_kp_ptr,
-                                                        int rows, int cols, int feat_in_lds, int32_t* __restrict__ cell_off,
-                                                        int32_t* __restrict__ cell_feat) {
-  // [ncells + 1] offsets, [ncells] counts / fill cursors, then (feat_in_lds) the [n] unordered feature lists and the [n] cells of the features
+// grid build: one workgroup per call (area_grid_body.h).  cell_off[ncells+1], cell_feat[n] (features of a cell in ascending index).
+__global__ __launch_bounds__(AREA_GRID_NT) void k_grid_build(const orbfe_keypoint* __restrict__ kps, const int32_t* __restrict__ n_kp_ptr,
+                                                             int rows, int cols, int feat_in_lds, int32_t* __restrict__ cell_off,
+                                                             int32_t* __restrict__ cell_feat) {
   extern __shared__ int32_t l_grid[];
-  __shared__ int32_t l_scan[GRID_NT];
-  const int tid = threadIdx.x;
-  const int n = *n_kp_ptr;
-  const int ncells = rows * cols;
-  int32_t* l_off = l_grid;
-  int32_t* l_cur = l_grid + ncells + 1;
-  int32_t* feat = feat_in_lds ? l_cur + ncells : cell_feat;
-  int32_t* l_cell = feat + n;  // (feat_in_lds only)
-  for (int c = tid; c < ncells; c += GRID_NT) l_cur[c] = 0;
-  __syncthreads();
-  // The coordinates are read ONCE (a thread's loads independent of each other) and the cell kept in LDS: with 256 threads each of the
-  // three passes below walked eight dependent trips to memory, ~1 us each -- 24 of this kernel's 27 us.
-  for (int i = tid; i < n; i += GRID_NT) {
-    const int cell = grid_cell(kps[i].y, GRID_H, rows) * cols + grid_cell(kps[i].x, GRID_W, cols);
-    if (feat_in_lds) l_cell[i] = cell;
-    atomicAdd(&l_cur[cell], 1);
-  }
-  __syncthreads();
-  // exclusive prefix over the cells: a thread sums a run of consecutive cells, the run totals are scanned, the thread writes its run's offsets
-  const int per = (ncells + GRID_NT - 1) / GRID_NT;
-  const int c0 = min(tid * per, ncells), c1 = min(c0 + per, ncells);
-  int local = 0;
-  for (int c = c0; c < c1; ++c) local += l_cur[c];
-  l_scan[tid] = local;
-  __syncthreads();
-  for (int o = 1; o < GRID_NT; o <<= 1) {
-    const int v = tid >= o ? l_scan[tid - o] : 0;
-    __syncthreads();
-    l_scan[tid] += v;
-    __syncthreads();
-  }
-  {
-    int acc = l_scan[tid] - local;
-    for (int c = c0; c < c1; ++c) {
-      const int k = l_cur[c];
-      l_off[c] = acc;
-      l_cur[c] = 0;
-      acc += k;
-    }
-    if (tid == GRID_NT - 1) l_off[ncells] = l_scan[GRID_NT - 1];
-  }
-  __syncthreads();
-  for (int c = tid; c <= ncells; c += GRID_NT) cell_off[c] = l_off[c];
-  for (int i = tid; i < n; i += GRID_NT) {
-    const int cell = feat_in_lds ? l_cell[i] : grid_cell(kps[i].y, GRID_H, rows) * cols + grid_cell(kps[i].x, GRID_W, cols);
-    feat[l_off[cell] + atomicAdd(&l_cur[cell], 1)] = i;
-  }
-  __syncthreads();
-  // the reference pushes indices in ascending order (Frame.cc:61-68)
-  if (feat_in_lds) {
-    // every feature finds its place in its cell's list by counting the smaller indices there: the work of a sort, spread over the threads
-    // (one thread sorting the densest cell of a clustered frame was the long pole of the per-cell sort below)
-    for (int i = tid; i < n; i += GRID_NT) {
-      const int cell = l_cell[i];
-      const int base = l_off[cell], k = l_off[cell + 1] - base;
-      int rank = 0;
-      for (int j = 0; j < k; ++j) rank += feat[base + j] < i ? 1 : 0;
-      cell_feat[base + rank] = i;
-    }
-    return;
-  }
-  for (int c = tid; c < ncells; c += GRID_NT) {
-    int32_t* L = feat + l_off[c];
-    const int k = l_off[c + 1] - l_off[c];
-    for (int a = 1; a < k; ++a) {
-      const int32_t v = L[a];
-      int b = a - 1;
-      while (b >= 0 && L[b] > v) {
-        L[b + 1] = L[b];
-        --b;
-      }
-      L[b + 1] = v;
-    }
-  }
+  __shared__ int32_t l_scan[AREA_GRID_NT];
+  area_grid_build(kps, *n_kp_ptr, rows, cols, feat_in_lds, cell_off, cell_feat, l_grid, l_scan);
 }
 
-// ---------------------------------------------------------------------------------------------
-// search: one wave per query
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int hamming256w(const uint4 a0, const uint4 a1, const uint8_t* __restrict__ p) {
-  const uint4 b0 = *(const uint4*)p;
-  const uint4 b1 = *(const uint4*)(p + 16);
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-         __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-struct Best2g {
-  int min_d, second, min_idx;
-};
-__device__ __forceinline__ void fold_chunk_g(Best2g& b, int d, int idx) {
-  const int incl = wave_incl_scan_dpp<OpMinI>(d);
-  const int excl = __builtin_amdgcn_update_dpp(ORB_INT_MAX, incl, ORBFE_DPP_WAVE_SHR1, 0xf, 0xf, false);
-  const int pre = min(b.min_d, excl);
-  const bool record = d < pre;
-  b.second = min(b.second, wave_reduce_dpp<OpMinI>(record ? ORB_INT_MAX : d));
-  const int cmin = __builtin_amdgcn_readlane(incl, 63);
-  if (cmin < b.min_d) {
-    const unsigned long long m = __ballot(d == cmin);
-    b.min_d = cmin;
-    b.min_idx = __builtin_amdgcn_readlane(idx, __ffsll((long long)m) - 1);
-  }
-}
-
+// search: one wave per query (area_search_body.h).  A candidate's octave is byte 0 of word 1 of its packed record.
 __global__ __launch_bounds__(256) void k_search_area(const uint4* __restrict__ kpl, const uint8_t* __restrict__ desc, int width,
                                                      int height, int rows, int cols, const int32_t* __restrict__ cell_off,
                                                      const int32_t* __restrict__ cell_feat, int nq, const float* __restrict__ qxy,
@@ -153,7 +36,6 @@ __global__ __launch_bounds__(256) void k_search_area(const uint4* __restrict__ k
                                                      int32_t* __restrict__ n_cand, int32_t* __restrict__ excluded_hits) {
   __shared__ int32_t stage_all[4][128];  // per wave: filtered candidates waiting to fill a 64-lane chunk (order preserved)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int32_t* stage = stage_all[wv];
   const int q = blockIdx.x * 4 + wv;
   if (q >= nq) return;
   const float x = qxy[2 * q], y = qxy[2 * q + 1], rad = radius[q];
@@ -162,55 +44,21 @@ __global__ __launch_bounds__(256) void k_search_area(const uint4* __restrict__ k
     return;
   }
   const int lo = min_level[q], hi = max_level[q];
-  const int min_x = max(0, __float2int_rn(x - rad)), max_x = min(width, __float2int_rn(x + rad));
-  const int min_y = max(0, __float2int_rn(y - rad)), max_y = min(height, __float2int_rn(y + rad));
-  const int c0 = max(0, min(cols - 1, cvfloor_f((float)min_x / (float)GRID_W))), c1 = min(cols - 1, cvfloor_f((float)max_x / (float)GRID_W));
-  const int r0 = max(0, min(rows - 1, cvfloor_f((float)min_y / (float)GRID_H))), r1 = min(rows - 1, cvfloor_f((float)max_y / (float)GRID_H));
   const uint4 a0 = *(const uint4*)(q_desc + (size_t)q * 32);
   const uint4 a1 = *(const uint4*)(q_desc + (size_t)q * 32 + 16);
-  Best2g b = {ORB_INT_MAX, ORB_INT_MAX, 0};
-  int staged = 0, total = 0;
-  auto flush = [&](int count) {  // process stage[0..count) (count <= 64) as one chunk
-    const int idx = (lane < count) ? stage[lane] : 0;
-    const int d = (lane < count) ? hamming256w(a0, a1, desc + (size_t)idx * 32) : ORB_INT_MAX;
-    fold_chunk_g(b, d, idx);
-  };
-  for (int r = r0; r <= r1; ++r)
-    for (int c = c0; c <= c1; ++c) {
-      const int beg = cell_off[r * cols + c], end = cell_off[r * cols + c + 1];
-      for (int i0 = beg; i0 < end; i0 += 64) {
-        const int i = i0 + lane;
-        int id = 0;
-        bool pass = false;
-        if (i < end) {
-          id = cell_feat[i];
-          const int oc = (int)(kpl[id].y & 0xFFu);
-          pass = oc <= hi && oc >= lo;
-          if (pass && exclude && exclude[id]) {
-            // a feature the caller excluded WAS in this query's window: searchByProjection bumps MapPoint::addMatchInTrack once per such
-            // (query, feature) occurrence while it filters the candidates (src/ORBMatcher.cc:321-331) -- the counts let the caller do the same
-            pass = false;
-            if (excluded_hits) atomicAdd(&excluded_hits[id], 1);
-          }
-        }
-        const unsigned long long m = __ballot(pass);
-        if (pass) stage[staged + __popcll(m & ((1ull << lane) - 1ull))] = id;
-        staged += __popcll(m);
-        total += __popcll(m);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (staged >= 64) {
-          flush(64);
-          const int keep = (lane < staged - 64) ? stage[64 + lane] : 0;
-          __builtin_amdgcn_wave_barrier();
-          if (lane < staged - 64) stage[lane] = keep;
-          staged -= 64;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
+  Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
+  const AreaTarget T = {desc, cell_off, cell_feat, rows, cols, width, height};
+  const int total = area_fold(T, x, y, rad, a0, a1, stage_all[wv], lane, b, [&](int id) {
+    const int oc = (int)(kpl[id].y & 0xFFu);
+    if (!(oc <= hi && oc >= lo)) return false;
+    if (exclude && exclude[id]) {
+      // a feature the caller excluded WAS in this query's window: searchByProjection bumps MapPoint::addMatchInTrack once per such
+      // (query, feature) occurrence while it filters the candidates (src/ORBMatcher.cc:321-331) -- the counts let the caller do the same
+      if (excluded_hits) atomicAdd(&excluded_hits[id], 1);
+      return false;
     }
-  if (staged > 0) flush(staged);
+    return true;
+  });
   if (lane == 0) {
     n_cand[q] = total;
     best_idx[q] = total ? b.min_idx : -1;
@@ -222,16 +70,14 @@ __global__ __launch_bounds__(256) void k_search_area(const uint4* __restrict__ k
 // ---------------------------------------------------------------------------------------------
 // MapPoint::isInVision + MapPoint::predictLevel (src/MapPoint.cc:141-201) for n map points against one frame: what
 // ORBMatcher::searchByProjection(frame, mapPoints) evaluates per point before the area search (src/ORBMatcher.cc:575-580).
-// One thread per map point; the float / double mix follows the cv::Mat expressions of the reference:
-//   Rcw * X + tcw      3x3 * 3x1 gemm: float products summed left to right, then (float)(s * 1.0 + c * 1.0) in double
-//   cv::norm, Mat::dot double accumulation of float elements
-// Early exits keep the reference's order (z < 0, distance range, image bounds, cos < 0.5); a point that fails leaves visible = 0.
+// One thread per map point over map_point_dev.h (the float / double mix and the order of the tests are stated there); a point that
+// fails leaves visible = 0, level = 0 and the values its tests got to.
 // ---------------------------------------------------------------------------------------------
 struct ProjectParams {
   float R[9], t[3];
   float fx, fy, cx, cy;
-  float min_u, max_u, min_v, max_v;
-  float log_sf;  // std::log(ORBExtractor::mfScaledFactor) as float
+  float bounds[4];  // min_u, max_u, min_v, max_v
+  float log_sf;     // std::log(ORBExtractor::mfScaledFactor) as float
   int max_level;
 };
 
@@ -242,43 +88,12 @@ __global__ __launch_bounds__(256) void k_project_map_points(int n, const float* 
                                                             uint8_t* __restrict__ visible) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float X0 = pos[3 * i], X1 = pos[3 * i + 1], X2 = pos[3 * i + 2];
-  float pc[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const float s = P.R[3 * r] * X0 + P.R[3 * r + 1] * X1 + P.R[3 * r + 2] * X2;
-    pc[r] = (float)((double)s + (double)P.t[r]);
-  }
-  uint8_t vis = 0;
-  float u = 0.f, v = 0.f, distance = 0.f, cos_theta = 0.f;
-  int level = 0;
-  do {
-    if (pc[2] < 0.f) break;
-    const float x = pc[0], y = pc[1], z = pc[2];
-    distance = sqrtf(x * x + y * y + z * z);  // (correctly rounded; __fsqrt_rn maps to the native approximation)
-    if (!(distance < max_dist[i] && distance > min_dist[i])) break;  // isGoodDistance
-    u = x / z * P.fx + P.cx;
-    v = y / z * P.fy + P.cy;
-    if (!(u < P.max_u && v < P.max_v && u > P.min_u && v > P.min_v)) break;  // VirtualFrame::isInImage
-    const float D0 = vdir[3 * i], D1 = vdir[3 * i + 1], D2 = vdir[3 * i + 2];
-    float vd[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) vd[r] = P.R[3 * r] * D0 + P.R[3 * r + 1] * D1 + P.R[3 * r + 2] * D2;
-    const double nn = (double)vd[0] * (double)vd[0] + (double)vd[1] * (double)vd[1] + (double)vd[2] * (double)vd[2];
-    const float vabs = (float)sqrt(nn);
-    const double dot = (double)vd[0] * (double)pc[0] + (double)vd[1] * (double)pc[1] + (double)vd[2] * (double)pc[2];
-    cos_theta = (float)(dot / (double)(distance * vabs));
-    if (cos_theta < 0.5f) break;
-    vis = 1;
-    // predictLevel: cvRound(std::log(nMaxDis / distance) / std::log(mfScaledFactor)), clamped to [0, 7] in the reference (max_level here)
-    const float lr = (float)log((double)(max_dist[i] / distance));
-    level = __float2int_rn(lr / P.log_sf);
-    level = level < 0 ? 0 : (level > P.max_level ? P.max_level : level);
-  } while (false);
-  uv[2 * i] = u, uv[2 * i + 1] = v;
-  dist_out[i] = distance, cos_out[i] = cos_theta;
-  level_out[i] = (int8_t)level;
-  visible[i] = vis;
+  MapPointView w;
+  const bool vis = is_in_vision(P.R, P.t, pos + 3 * i, vdir + 3 * i, max_dist[i], min_dist[i], P.fx, P.fy, P.cx, P.cy, P.bounds, w);
+  uv[2 * i] = w.u, uv[2 * i + 1] = w.v;
+  dist_out[i] = w.distance, cos_out[i] = w.cos_theta;
+  level_out[i] = (int8_t)(vis ? predict_level(max_dist[i], w.distance, P.log_sf, P.max_level) : 0);  // ([0, 7] in the reference)
+  visible[i] = vis ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -422,7 +237,7 @@ void launch_project_map_points(hipStream_t s, int n, const float* d_pos, const f
   for (int k = 0; k < 9; ++k) P.R[k] = R[k];
   for (int k = 0; k < 3; ++k) P.t[k] = t[k];
   P.fx = cam4[0], P.fy = cam4[1], P.cx = cam4[2], P.cy = cam4[3];
-  P.min_u = bounds4[0], P.max_u = bounds4[1], P.min_v = bounds4[2], P.max_v = bounds4[3];
+  for (int k = 0; k < 4; ++k) P.bounds[k] = bounds4[k];
   P.log_sf = log_sf, P.max_level = max_level;
   hipLaunchKernelGGL(k_project_map_points, dim3((n + 255) / 256), dim3(256), 0, s, n, d_pos, d_vdir, d_max, d_min, P, d_uv, d_dist, d_cos,
                      d_level, d_vis);
@@ -430,12 +245,10 @@ void launch_project_map_points(hipStream_t s, int n, const float* d_pos, const f
 
 void launch_grid_build(hipStream_t s, const orbfe_keypoint* d_kps, const int32_t* d_n_kp, int n_cap, int rows, int cols,
                        int32_t* d_cell_off, int32_t* d_cell_feat) {
-  // n_cap: upper bound of *d_n_kp; the cells' lists are filled and ordered in LDS when they fit there
-  const size_t base = (size_t)(2 * rows * cols + 1) * sizeof(int32_t);
-  const size_t lists = (size_t)n_cap * 2 * sizeof(int32_t);
-  const bool in_lds = base + lists <= 56 * 1024;
-  hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(GRID_NT), in_lds ? base + lists : base, s, d_kps, d_n_kp, rows, cols, in_lds ? 1 : 0,
-                     d_cell_off, d_cell_feat);
+  // n_cap: upper bound of *d_n_kp; the cells' lists are filled and ordered in LDS when they fit there (the callers refuse a grid
+  // whose counters do not)
+  const AreaGridLds g = area_grid_lds((size_t)rows * cols, (size_t)n_cap);
+  hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(AREA_GRID_NT), g.bytes, s, d_kps, d_n_kp, rows, cols, g.in_lds, d_cell_off, d_cell_feat);
 }
 
 void launch_search_area(hipStream_t s, const uint4* d_kpl, const uint8_t* d_desc, int width, int height, int rows, int cols,

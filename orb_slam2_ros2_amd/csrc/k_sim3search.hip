@@ -9,11 +9,11 @@
 //                       the world position, cv::norm in double, the viewing-angle test, no filter on the target's features.
 // The projection is wave-uniform and every lane computes it; a point that fails a test writes -1 and its wave leaves.  No wave waits on
 // another; every loop is bounded by a grid size or a feature count (area_search_body.h); a wave owns its point, so the results do not
-// depend on the launch geometry.  Float arithmetic: a matrix-vector row is the float sum a0 b0 + a1 b1 + a2 b2 left to right,
-// `alpha A x + t` is (float)((double)alpha * sum + t) (cv::gemm's alpha / beta), no contraction.
+// depend on the launch geometry.  Float arithmetic: map_point_dev.h's rows and `alpha A x + t`, its predictLevel; no contraction.
 #include <hip/hip_runtime.h>
 
 #include "area_search_body.h"
+#include "map_point_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -21,23 +21,8 @@ namespace {
 
 using namespace orbfe;
 
-__device__ __forceinline__ void affine(float alpha, const float* R, const float* x, const float* t, float* out) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const float sm = R[3 * r] * x[0] + R[3 * r + 1] * x[1] + R[3 * r + 2] * x[2];
-    out[r] = (float)((double)alpha * (double)sm + (double)t[r]);
-  }
-}
-
-// MapPoint::predictLevel (src/MapPoint.cc:188-199) in the expression of k_guided.hip's k_project_map_points
-__device__ __forceinline__ int predict_level(float max_dist, float d, const Sim3SearchParams& P) {
-  const float lr = (float)log((double)(max_dist / d));
-  const int level = __float2int_rn(lr / P.log_sf);
-  return level < 0 ? 0 : (level > P.max_level ? P.max_level : level);
-}
-
 __device__ __forceinline__ AreaTarget target_of(const Sim3Kf& K) {
-  return {K.kps, K.desc, K.cell_off, K.cell_feat, K.rows, K.cols, K.clip_w, K.clip_h};
+  return {K.desc, K.cell_off, K.cell_feat, K.rows, K.cols, K.clip_w, K.clip_h};
 }
 
 // the acceptance of :408-414: a non-empty list, best <= threshold and (float)best / (float)second <= ratio (0 / 0 is NaN: rejected)
@@ -72,14 +57,17 @@ __global__ __launch_bounds__(256) void k_sim3_search_pair(const uint8_t* __restr
     const float d = sqrtf(pm[0] * pm[0] + pm[1] * pm[1] + pm[2] * pm[2]) / S.s;
     const float mx = ((const float*)(up + S.o_max))[i], mn = ((const float*)(up + S.o_min))[i];
     if (!(d < mx && d > mn)) break;  // isGoodDistance
-    const int o = predict_level(mx, d, P);
+    const int o = predict_level(mx, d, P.log_sf, P.max_level);
     const float sf = ((const float*)(up + P.o_sf))[o];
     const uint4 a0 = *(const uint4*)(S.desc + (size_t)i * 32);
     const uint4 a1 = *(const uint4*)(S.desc + (size_t)i * 32 + 16);
     const uint8_t* __restrict__ t_state = up + T.o_state;
     Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
-    const int total = area_fold(target_of(T), u, v, P.th * (sf * sf), o - 1, o + 1, a0, a1, stage_all[wv], lane, b, [&](int id) {
-      return (t_state[id] & (ORBFE_TRI_GOOD | ORBFE_TRI_INMAP)) == (ORBFE_TRI_GOOD | ORBFE_TRI_INMAP);  // vGoodIndices (:396-405)
+    const orbfe_keypoint* __restrict__ t_kps = T.kps;
+    const int total = area_fold(target_of(T), u, v, P.th * (sf * sf), a0, a1, stage_all[wv], lane, b, [&](int id) {
+      const int oc = t_kps[id].octave;
+      return oc <= o + 1 && oc >= o - 1 &&
+             (t_state[id] & (ORBFE_TRI_GOOD | ORBFE_TRI_INMAP)) == (ORBFE_TRI_GOOD | ORBFE_TRI_INMAP);  // vGoodIndices (:396-405)
     });
     if (accepted(total, b, P)) best = b.min_idx;
   } while (false);
@@ -109,18 +97,21 @@ __global__ __launch_bounds__(256) void k_sim3_search_points(const uint8_t* __res
     if (!(d < mx && d > mn)) break;
     // the viewing angle (:534-536): (R * viewDirection) . p3dC >= 0.5 * |p3dC|, Mat::dot in double
     const float* vd = (const float*)(up + L.o_vdir) + 3 * j;
-    float rv[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) rv[r] = L.R[3 * r] * vd[0] + L.R[3 * r + 1] * vd[1] + L.R[3 * r + 2] * vd[2];
+    const float vw[3] = {vd[0], vd[1], vd[2]};
+    const float rv[3] = {mat3_row(L.R, 0, vw), mat3_row(L.R, 1, vw), mat3_row(L.R, 2, vw)};
     const double dot = (double)rv[0] * (double)pc[0] + (double)rv[1] * (double)pc[1] + (double)rv[2] * (double)pc[2];
     if (dot < 0.5 * (double)d_with_s) break;
-    const int o = predict_level(mx, d, P);
+    const int o = predict_level(mx, d, P.log_sf, P.max_level);
     const float sf = ((const float*)(up + P.o_sf))[o];
     const uint8_t* qd = up + L.o_desc + j * 32;
     const uint4 a0 = *(const uint4*)qd;
     const uint4 a1 = *(const uint4*)(qd + 16);
     Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
-    const int total = area_fold(target_of(T), u, v, P.th * (sf * sf), o - 1, o + 1, a0, a1, stage_all[wv], lane, b, [](int) { return true; });
+    const orbfe_keypoint* __restrict__ t_kps = T.kps;
+    const int total = area_fold(target_of(T), u, v, P.th * (sf * sf), a0, a1, stage_all[wv], lane, b, [&](int id) {
+      const int oc = t_kps[id].octave;
+      return oc <= o + 1 && oc >= o - 1;
+    });
     if (accepted(total, b, P)) best = b.min_idx, dist = b.min_d;
   } while (false);
   if (lane == 0) best_idx[q] = best, best_dist[q] = dist;

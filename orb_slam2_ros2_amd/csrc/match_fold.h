@@ -1,30 +1,24 @@
 // match_fold.h -- getBestMatch's (ORBMatcher.cc:967-990) best / second-best fold over a candidate list, 64 candidates at a time in list
-// order (k_match.hip's header comment states the order-free form), and the Hamming-256 distance.  Shared by k_match.hip and k_tri.hip.
+// order (k_match.hip's header comment states the order-free form), and the Hamming-256 distance.  The one fold: k_match.hip, k_tri.hip,
+// bow_walk.h and the area search of every guided matcher (area_search_body.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "wave_ops.h"
 
 namespace orbfe {
 
 #define ORB_INT_MAX 2147483647
 
+// one step of a min scan (k_match.hip's row-of-16 scan takes the first four); lanes without a source keep INT_MAX
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int dpp_min_step(int v) {
-  // lanes without a source keep INT_MAX (the identity of min)
-  return min(v, __builtin_amdgcn_update_dpp(ORB_INT_MAX, v, CTRL, ROW_MASK, 0xf, false));
+  return dpp_step<OpMinI, CTRL, ROW_MASK>(v);
 }
-// inclusive prefix-min over the 64 lanes (all lanes active): Hillis-Steele inside each row of 16 with DPP row
-// shifts, then the row totals are broadcast into the following rows.  Lane 63 holds the wave minimum.
-__device__ __forceinline__ int wave_incl_prefix_min(int v) {
-  v = dpp_min_step<0x111, 0xf>(v);  // row_shr:1
-  v = dpp_min_step<0x112, 0xf>(v);  // row_shr:2
-  v = dpp_min_step<0x114, 0xf>(v);  // row_shr:4
-  v = dpp_min_step<0x118, 0xf>(v);  // row_shr:8
-  v = dpp_min_step<0x142, 0xa>(v);  // row_bcast:15 -> rows 1,3
-  v = dpp_min_step<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3
-  return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) { return __builtin_amdgcn_readlane(wave_incl_prefix_min(v), 63); }
+// inclusive prefix-min over the 64 lanes (all lanes active; wave_ops.h: the one DPP scan).  Lane 63 holds the wave minimum.
+__device__ __forceinline__ int wave_incl_prefix_min(int v) { return wave_incl_scan_dpp<OpMinI>(v); }
+__device__ __forceinline__ int wave_min_i(int v) { return wave_reduce_dpp<OpMinI>(v); }
 
 struct Best2 {
   int min_d, second, min_idx;
@@ -34,7 +28,7 @@ struct Best2 {
 // d = distance of this lane's candidate or INT_MAX if the lane holds none; idx = its train index.
 __device__ __forceinline__ void fold_chunk(Best2& b, int d, int idx, int lane) {
   const int incl = wave_incl_prefix_min(d);
-  const int excl = __builtin_amdgcn_update_dpp(ORB_INT_MAX, incl, 0x138, 0xf, 0xf, false);  // wave_shr:1, lane 0 <- INT_MAX
+  const int excl = __builtin_amdgcn_update_dpp(ORB_INT_MAX, incl, ORBFE_DPP_WAVE_SHR1, 0xf, 0xf, false);  // lane 0 <- INT_MAX
   const int pre = min(b.min_d, excl);
   const bool record = d < pre;  // strict prefix-minimum record: becomes the new best, never the second best
   b.second = min(b.second, wave_min_i(record ? ORB_INT_MAX : d));

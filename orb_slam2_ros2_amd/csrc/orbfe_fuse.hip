@@ -120,13 +120,14 @@ orbfe_status orbfe_fuse_into_keyframes(orbfe_ctx* c, const orbfe_fuse_kf* cur, c
     FuseKf& d = kf[k];
     AreaGrid ag;
     if (!area_grid(c->cfg.width, c->cfg.height, t.bounds, &ag)) return fail(c, ORBFE_EBADARG, "fuse_into_keyframes: target %zu: bad frame bounds", k);
-    const size_t ncells = (size_t)ag.rows * ag.cols, lds_base = (2 * ncells + 1) * sizeof(int32_t), lds_lists = (size_t)t.n * 2 * sizeof(int32_t);
-    if (lds_base > 60 * 1024) return fail(c, ORBFE_EBADSIZE, "fuse_into_keyframes: target %zu: %zu grid cells exceed the LDS counters", k, ncells);
+    const size_t ncells = (size_t)ag.rows * ag.cols;
+    const AreaGridLds g = area_grid_lds(ncells, (size_t)t.n);
+    if (g.refused) return fail(c, ORBFE_EBADSIZE, "fuse_into_keyframes: target %zu: %zu grid cells exceed the LDS counters", k, ncells);
     d.n = t.n, d.rows = ag.rows, d.cols = ag.cols, d.clip_w = ag.clip_w, d.clip_h = ag.clip_h;
     fuse_pose(d, z[k], bl, t.Rcw, t.tcw);
-    d.in_lds = lds_base + lds_lists <= 56 * 1024 ? 1 : 0;
+    d.in_lds = g.in_lds;
     d.pad = 0;
-    grid_lds = std::max(grid_lds, d.in_lds ? lds_base + lds_lists : lds_base);
+    grid_lds = std::max(grid_lds, g.bytes);
     std::memcpy(d.bounds, t.bounds, sizeof d.bounds);
     d.o_coff = L.take<int32_t>(ncells + 1);  // k_fuse_grid writes cell_off[0 .. ncells], k_fuse_search reads cell_off[cell + 1]
     d.o_cfeat = L.take<int32_t>((size_t)t.n);

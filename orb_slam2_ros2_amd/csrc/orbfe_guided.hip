@@ -87,7 +87,7 @@ static orbfe_status search_area_plan(orbfe_ctx* c, const char* who, const float*
   AreaGrid ag;
   if (!area_grid(c, bounds, &ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", who);
   const size_t ncells = (size_t)ag.rows * ag.cols;
-  if ((2 * ncells + 1) * 4 > 60 * 1024) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", who, ncells);
+  if (area_grid_lds(ncells, n_target).refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", who, ncells);
   *l = search_area_layout(start, ag, n_target, (size_t)nq);
   return ORBFE_OK;
 }
@@ -281,7 +281,7 @@ orbfe_status orbfe_track_local_map(orbfe_ctx* c, int32_t slot, const orbfe_frame
   AreaGrid ag;
   if (!area_grid(c, bounds, &ag)) return fail(c, ORBFE_EBADARG, "track_local_map: bad frame bounds");
   const size_t ncells = (size_t)ag.rows * ag.cols;
-  if ((2 * ncells + 1) * 4 > 60 * 1024) return fail(c, ORBFE_EBADSIZE, "track_local_map: %zu grid cells exceed the LDS counters", ncells);
+  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "track_local_map: %zu grid cells exceed the LDS counters", ncells);
   TRY(slots_idle(c, slot, 1, "track_local_map"));
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
@@ -376,7 +376,7 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
   AreaGrid ag;
   if (!area_grid(c, bounds4, &ag)) return fail(c, ORBFE_EBADARG, "track_motion_model: bad frame bounds");
   const size_t ncells = (size_t)ag.rows * ag.cols;
-  if ((2 * ncells + 1) * 4 > 60 * 1024) return fail(c, ORBFE_EBADSIZE, "track_motion_model: %zu grid cells exceed the LDS counters", ncells);
+  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "track_motion_model: %zu grid cells exceed the LDS counters", ncells);
   TRY(slots_idle(c, slot, 1, "track_motion_model"));
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));

@@ -65,10 +65,11 @@ orbfe_status stage_reserve(orbfe_kfstore* s, size_t bytes) {
 orbfe_status plan_entry(orbfe_ctx* c, const orbfe_kfstore* s, const char* fn, int32_t n, const float* bounds, KfEntry* e, size_t* total, size_t* grid_lds,
                         int* in_lds) {
   if (!area_grid(s->width, s->height, bounds, &e->ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", fn);
-  const size_t ncells = e->ncells(), lds_base = (2 * ncells + 1) * sizeof(int32_t), lds_lists = (size_t)n * 2 * sizeof(int32_t);
-  if (lds_base > 60 * 1024) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", fn, ncells);
-  *in_lds = lds_base + lds_lists <= 56 * 1024 ? 1 : 0;
-  *grid_lds = *in_lds ? lds_base + lds_lists : lds_base;
+  const size_t ncells = e->ncells();
+  const AreaGridLds g = area_grid_lds(ncells, (size_t)n);
+  if (g.refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", fn, ncells);
+  *in_lds = g.in_lds;
+  *grid_lds = g.bytes;
   e->n = n;
   const float whole[4] = {0.f, (float)s->width, 0.f, (float)s->height};
   std::memcpy(e->bounds, bounds ? bounds : whole, sizeof e->bounds);

@@ -1,5 +1,5 @@
-// search_area_layout.h -- the grid geometry and the scratch layout of the grid-guided search (orbfe_guided.hip: search_area_core and the
-// callers that reserve for it).  Host only, like scratch_layout.h: tests/cpp/test_scratch_layout.cpp checks that a reservation sized from
+// search_area_layout.h -- the grid geometry, the LDS rule of the grid build (every host file that launches one) and the scratch layout of
+// the grid-guided search (orbfe_guided.hip: search_area_core and the callers that reserve for it).  Host only, like scratch_layout.h: tests/cpp/test_scratch_layout.cpp checks that a reservation sized from
 // the layout is exactly what the search then takes.
 #pragma once
 #include <cmath>
@@ -23,6 +23,21 @@ static inline bool area_grid(int width, int height, const float* bounds, AreaGri
     return false;
   *g = {cv_ceil_f((float)(bounds[3] - bounds[2]) / 48), cv_ceil_f((float)(bounds[1] - bounds[0]) / 64), (int)bounds[1], (int)bounds[3]};
   return g->rows >= 1 && g->cols >= 1;
+}
+
+// The LDS of the grid build (area_grid_body.h: one workgroup per grid), the one rule of every caller: the [ncells + 1] offsets and
+// [ncells] counters always live there -- a grid whose counters exceed 60 KB is refused; the [n] unordered lists and the [n] cells of
+// the features join them while everything fits 56 KB, else the lists are filled and sorted in the scratch block.  bytes: the dynamic
+// LDS of the launch (the 4 KB scan array of the kernel is static).
+struct AreaGridLds {
+  bool refused;
+  int in_lds;
+  size_t bytes;
+};
+static inline AreaGridLds area_grid_lds(size_t ncells, size_t n) {
+  const size_t counters = (2 * ncells + 1) * sizeof(int32_t), lists = n * 2 * sizeof(int32_t);
+  const bool in_lds = counters + lists <= 56 * 1024;
+  return {counters > 60 * 1024, in_lds ? 1 : 0, in_lds ? counters + lists : counters};
 }
 
 // Queries first (they continue the caller's uploaded block, if any, so that everything goes up as ONE copy through the page-locked

@@ -1,5 +1,5 @@
 // test_scratch_layout.cpp -- csrc/scratch_layout.h and csrc/search_area_layout.h, host only (no HIP header, no device): the padding rule,
-// regions, and that a reservation sized from the guided search's layout is exactly what the search takes.
+// regions, that a reservation sized from the guided search's layout is exactly what the search takes, and the grid build's LDS rule.
 #include <cstdint>
 #include <cstdio>
 #include <initializer_list>
@@ -93,6 +93,35 @@ int main() {
             const size_t offs[] = {l.o_q, l.o_r, l.o_lo, l.o_hi, l.o_d, l.o_ex, l.o_co, l.o_cf, l.o_bi, l.o_bd, l.o_sd, l.o_nc, l.o_eh, l.end()};
             for (size_t i = 0; i + 1 < sizeof offs / sizeof offs[0]; ++i) CHECK(offs[i] % 256 == 0 && offs[i] < offs[i + 1]);
           }
+  }
+  // the grid build's LDS rule: counters (2 ncells + 1) words, lists 2 n words; lists in LDS up to 56 KB in all, counters over 60 KB refused.
+  // Both sums are 4 mod 8 bytes, so neither limit is met exactly by any (ncells, n): the cases are the nearest sizes on either side.
+  {
+    const size_t KB56 = 56 * 1024, KB60 = 60 * 1024;
+    for (size_t ncells : {(size_t)1, (size_t)160, (size_t)189, (size_t)7000})
+      for (size_t n : {(size_t)0, (size_t)1, (size_t)2000, (size_t)7167, (size_t)8000}) {
+        const AreaGridLds g = area_grid_lds(ncells, n);
+        const size_t counters = (2 * ncells + 1) * 4, all = counters + n * 8;
+        CHECK(all % 8 == 4 && counters % 8 == 4);
+        CHECK(!g.refused);
+        CHECK(g.in_lds == (all <= KB56 ? 1 : 0));
+        CHECK(g.bytes == (g.in_lds ? all : counters));
+      }
+    // 56 KB: ncells + n = 7167 is 4 bytes under it (the most that fits), one feature or one cell more is 4 bytes over
+    const AreaGridLds fit = area_grid_lds(160, 7007), over_n = area_grid_lds(160, 7008), over_c = area_grid_lds(161, 7007);
+    CHECK(fit.in_lds == 1 && fit.bytes == KB56 - 4 && !fit.refused);
+    CHECK(over_n.in_lds == 0 && over_n.bytes == (2 * 160 + 1) * 4 && !over_n.refused);
+    CHECK(over_c.in_lds == 0 && over_c.bytes == (2 * 161 + 1) * 4 && !over_c.refused);
+    // 60 KB of counters: 7679 cells are 4 bytes under it (the largest grid accepted), one cell more is refused, whatever n is
+    for (size_t n : {(size_t)0, (size_t)1, (size_t)2000}) {
+      const AreaGridLds last = area_grid_lds(7679, n), refused = area_grid_lds(7680, n);
+      CHECK(!last.refused && last.in_lds == 0 && last.bytes == KB60 - 4);
+      CHECK(refused.refused);
+    }
+    // n = 0: the counters alone, in LDS while they fit 56 KB
+    CHECK(area_grid_lds(160, 0).in_lds == 1 && area_grid_lds(160, 0).bytes == 1284 && !area_grid_lds(160, 0).refused);
+    CHECK(area_grid_lds(7167, 0).in_lds == 1 && area_grid_lds(7167, 0).bytes == KB56 - 4);
+    CHECK(area_grid_lds(7168, 0).in_lds == 0 && area_grid_lds(7168, 0).bytes == KB56 + 4);
   }
   if (failures) return 1;
   std::printf("SCRATCH_LAYOUT_OK\n");

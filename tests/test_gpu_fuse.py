@@ -56,9 +56,11 @@ def test_borders(ctx, orc):
     same(ctx, orc, fs.border_scene())
 
 
-def test_equals_the_per_keyframe_device_calls(ctx):
-    """what the parent's entry points need 2 K calls for: project_map_points + search_in_area_features per target"""
-    sc = fs.gpu_scene("mid")
+@pytest.mark.parametrize("name", ["mid", "dense63", "dense64", "dense65", "dense200"])
+def test_equals_the_per_keyframe_device_calls(ctx, name):
+    """what the parent's entry points need 2 K calls for: project_map_points + search_in_area_features per target.  The two kernels
+    share one area loop and differ in their filters: the dense cells put the chunk boundary, the carry and a third chunk under both"""
+    sc = fs.gpu_scene("mid") if name == "mid" else fs.dense_cell_scene(int(name[5:]))
     cur, pts = sc["cur"], sc["pts"]
     bi, bd, vis = run(ctx, sc)
     octave = cur["kps"]["octave"].astype(np.int32)

@@ -103,3 +103,59 @@ def test_kept_grid_follows_the_slots_keypoints(orc):
         assert all(np.array_equal(g, r) for g, r in zip(got_u, ref_u)), f
         assert not all(np.array_equal(g, r) for g, r in zip(got_u, ref))      # ... and the answers with them
     ctx.close()
+
+
+# ---- exclusion at the fold boundaries ----------------------------------------------------------------------------------------------------
+# The target of fuse_scenes.dense_cell_scene(200): one cell with 200 features inside the queries' octave window and 40 outside it; the
+# mask excludes so many of the 200 that 63 / 64 / 65 / 129 candidates remain (a chunk less one, a full chunk, the carry, a third chunk),
+# and half of the 40 others, which no query has in its window: they must collect no hit.
+_DENSE, _REMAIN, _FOLD_CASES = 200, (63, 64, 65, 129), {}
+
+
+def _fold_boundary_case(orc, remain):
+    """-> (inputs of search_in_area_features, the excluded in-window features, the oracle's five outputs); computed once per case"""
+    if remain not in _FOLD_CASES:
+        import os
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import fuse_restatement as fr
+        import fuse_scenes as fs
+        sc = fs.dense_cell_scene(_DENSE)
+        t, cur = sc["targets"][0], sc["cur"]
+        octave = cur["kps"]["octave"].astype(np.int32)
+        lo, hi = fr.octave_window(octave, sc["z"][0], fs.BL)
+        radius = (np.float32(3.0) * (fs.SF[octave] * fs.SF[octave])).astype(np.float32)
+        qxy = np.stack([cur["kps"]["x"], cur["kps"]["y"]], 1)
+        t_oct = t["kps"]["octave"]
+        inside, outside = np.flatnonzero((t_oct >= lo[0]) & (t_oct <= hi[0])), np.flatnonzero((t_oct < lo[0]) | (t_oct > hi[0]))
+        assert len(inside) == _DENSE and len(outside) == 40 and (lo == lo[0]).all() and (hi == hi[0]).all()
+        gone = np.random.default_rng(remain).permutation(inside)[:_DENSE - remain]
+        ex = np.zeros(len(t_oct), np.uint8)
+        ex[gone] = 1
+        ex[outside[::2]] = 1
+        args = (t["kps"], t["desc"], qxy, radius, lo, hi, cur["desc"], ex)
+        want = orc.search_in_area_ex(t["kps"], t["desc"], t["bounds"], qxy, radius, lo, hi, cur["desc"], ex)
+        _FOLD_CASES[remain] = (args, t["bounds"], gone, want)
+    return _FOLD_CASES[remain]
+
+
+@pytest.mark.parametrize("remain", _REMAIN)
+def test_oracle_exclusion_leaves_the_fold_boundary_counts(orc, remain):
+    (t_kps, _, qxy, *_), _, gone, (bi, bd, sd, nc, hits) = _fold_boundary_case(orc, remain)
+    assert len(qxy) == 6 and np.array_equal(nc, np.full(6, remain))          # every query: exactly the candidates the mask leaves
+    want_hits = np.zeros(len(t_kps), np.int32)
+    want_hits[gone] = 6                                                      # once per (query, excluded feature in its window) ...
+    assert np.array_equal(hits, want_hits)                                   # ... and none outside the octave window
+    assert not np.isin(bi, gone).any() and (bi >= 0).all() and (bd <= sd).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("remain", _REMAIN)
+def test_device_exclusion_at_the_fold_boundaries(orc, remain):
+    from orb_slam2_ros2_amd._lib import Context
+    args, bounds, _, want = _fold_boundary_case(orc, remain)
+    ctx = Context(640, 480, n_features=1000, max_images=1)
+    got = ctx.search_in_area_features(*args, bounds=bounds, want_hits=True)
+    ctx.close()
+    for g, w, name in zip(got, want, ("best_idx", "best_dist", "second_dist", "n_cand", "excluded_hits")):
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), name
