@@ -765,6 +765,39 @@ orbfe_status orbfe_sim3_optimize(orbfe_ctx* ctx, int32_t n, const float* pc /*[n
                                  float* model /*[12] in/out: R row-major, t -- orbfe_sim3_iterate's layout*/,
                                  uint8_t* inlier_out /*[n]*/, int32_t* n_inliers, double* est_out /*[8] qx qy qz qw tx ty tz s, nullable*/);
 
+/* ---- pose graph over the essential graph (Optimizer::optimizeEssentialGraph, src/Optimizer.cc:746-920) -----------------------------
+ * The step LoopClosing::correctLoop (src/LoopClosing.cc:432-541) ends in, from the point where the graph is built (:767-877): vertex v
+ * is one good keyframe with its VertexSim3Expmap estimate (the corrected Sim3 of the loop group, ConvertSim3G2o of the pose otherwise),
+ * fixed where it is the loop keyframe; edge e is one EdgeSim3 (:804-877: loop connections, spanning tree, loop edges, covisibility)
+ * from vertex edge_v0[e] to vertex edge_v1[e] with the measurement meas[e] = S_v1w * S_wv0 and the identity as information.  The scale
+ * is FIXED: the reference's only caller passes bFixedScale = true and every Sim3 it passes has scale 1; there is no free-scale mode and
+ * an s other than 1 is refused.  err = log(meas * S_v0 * S_v1^-1); g2o differentiates this edge numerically for both vertices and so
+ * does the device; Levenberg-Marquardt as optimizer.optimize(iterations) runs it (the reference: 20), lambda_0 = 1e-5 max |diag|, at
+ * most 10 trials per iteration.  Several edges may join one pair of vertices, in either orientation; a vertex
+ * without an edge keeps its bytes.
+ *   estimates_out  [n_vertices][8]: every estimate after the last accepted trial (fixed ones unchanged).
+ *   chi2_out       NULL or [n_edges]: err . err of every edge at estimates_out.
+ *   stats          NULL or [2]: iterations run, trials run.
+ * One upload, a host-driven loop of a few scalars per trial, one download.  The system of the nf non-fixed vertices is dense, 6 nf
+ * square in double: nf <= ORBFE_PG_MAX_FREE (288 nf^2 bytes: 302 MB at the bound, what the panel solver of the local bundle adjustment
+ * factorises in place).
+ * ORBFE_OK with nothing launched and the estimates copied through (chi2_out is not written): n_edges == 0, iterations == 0, every
+ * vertex fixed.  Errors, with nothing written: ORBFE_EBADARG (a NULL context, graph or estimates_out; a negative count or iterations
+ * < 0; a NULL array with a non-zero count; an edge index out of range; edge_v0[e] == edge_v1[e]; an entry that is not finite; an s
+ * other than 1 on a vertex or a measurement), ORBFE_EBADSIZE (more than ORBFE_PG_MAX_FREE non-fixed vertices), ORBFE_EDEVICE.        */
+#define ORBFE_PG_MAX_FREE 1024
+typedef struct orbfe_pose_graph {
+  int32_t n_vertices, n_edges;
+  const double* estimates;   /* [n_vertices][8] qx qy qz qw tx ty tz s (s must be 1) */
+  const uint8_t* fixed;      /* [n_vertices] */
+  const int32_t* edge_v0;    /* [n_edges] vertex 0 (pkf1) */
+  const int32_t* edge_v1;    /* [n_edges] vertex 1 (pkf2) */
+  const double* meas;        /* [n_edges][8] */
+} orbfe_pose_graph;
+orbfe_status orbfe_pose_graph_optimize(orbfe_ctx* ctx, const orbfe_pose_graph* graph, int32_t iterations,
+                                       double* estimates_out /*[n_vertices][8]*/, double* chi2_out /*[n_edges], nullable*/,
+                                       int32_t* stats /*[2] iterations run, trials run; nullable*/);
+
 /* ---- new map points of a keyframe (LocalMapping::createNewMapPoints, src/LocalMapping.cc:165-285) ---------------------------------
  * One call runs loop 1 and loop 2 of createNewMapPoints for the current keyframe `cur` against the neighbours nbs[0 .. n_nb) IN THE
  * GIVEN ORDER (the reference's std::map order, T2): searchForTriangulation (searchByBow with bAddMPs, ratio 0.6, threshold 50, no
@@ -1068,6 +1101,18 @@ orbfe_status orbfe_debug_sim3_edges(orbfe_ctx* ctx, int32_t n, const float* pc /
                                     const float* uv_c /*[n][2]*/, const float* uv_m /*[n][2]*/, const double* info_c /*[n]*/,
                                     const double* info_m /*[n]*/, float fx, float fy, float cx, float cy, const double* est /*[8]*/,
                                     double* err /*[n][4]*/, double* chi2 /*[n][2]*/, double* jac /*[n][2][2][6]*/);
+
+/* The edges of orbfe_pose_graph_optimize as the optimiser sees them, at the graph's own estimates: err[e] = log(meas * S_v0 * S_v1^-1)
+ * (omega, upsilon; the scale entry is 0 and is left out), chi2[e] = err . err, jac[e][v][row][d] the numeric Jacobians of vertex 0 and
+ * vertex 1 (d: omega, upsilon), all zero for a fixed vertex.  The graph is checked as orbfe_pose_graph_optimize checks it (any number
+ * of non-fixed vertices); n_edges == 0 does nothing; a NULL output is ORBFE_EBADARG.                                                 */
+orbfe_status orbfe_debug_pose_graph_edges(orbfe_ctx* ctx, const orbfe_pose_graph* graph, double* err /*[n_edges][6]*/,
+                                          double* chi2 /*[n_edges]*/, double* jac /*[n_edges][2][6][6]*/);
+/* Where the last orbfe_pose_graph_optimize of this process spent its time, in milliseconds of wall time with the stream synchronised
+ * after every phase: ms[0] build (errors, Jacobians, per-edge blocks, chi2), ms[1] assemble (zero fill and block assembly), ms[2] solve
+ * (launch_lba_chol), ms[3] evaluate (update, chi2, the sums and the scalars' download).  Only calls made with ORBFE_PG_PHASES set in the
+ * environment are measured (and slowed down by the synchronisations); all zero otherwise.  For tools/essential_graph_bench.py.          */
+orbfe_status orbfe_debug_pose_graph_phases(double* ms /*[4]*/);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,11 @@ class BaProblem(C.Structure):
                 ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double)]
 
 
+class PoseGraph(C.Structure):
+    _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("estimates", C.c_void_p), ("fixed", C.c_void_p),
+                ("edge_v0", C.c_void_p), ("edge_v1", C.c_void_p), ("meas", C.c_void_p)]
+
+
 class BaSystemOut(C.Structure):
     _fields_ = [("Hpp", C.c_void_p), ("bp", C.c_void_p), ("Hll", C.c_void_p), ("bl", C.c_void_p), ("Hpl", C.c_void_p)]
 
@@ -193,13 +198,13 @@ EXPORTS = [
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
     "orbfe_sim3_create", "orbfe_sim3_destroy", "orbfe_sim3_iterate", "orbfe_sim3_engine", "orbfe_sim3_stats", "orbfe_sim3_profile",
-    "orbfe_sim3_optimize",
+    "orbfe_sim3_optimize", "orbfe_pose_graph_optimize",
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
-    "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges",
+    "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
 ]
 BOW_MAX_FEATURES = 65535
 
@@ -346,6 +351,9 @@ def load() -> C.CDLL:
     L.orbfe_debug_reduced_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     L.orbfe_sim3_optimize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
     L.orbfe_debug_sim3_edges.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
+    L.orbfe_pose_graph_optimize.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.orbfe_debug_pose_graph_edges.argtypes = [vp, vp, vp, vp, vp]
+    L.orbfe_debug_pose_graph_phases.argtypes = [vp]
     _lib = L
     return L
 
@@ -1430,6 +1438,43 @@ class Context:
         err, chi2, jac = np.zeros((max(n, 1), 4)), np.zeros((max(n, 1), 2)), np.zeros((max(n, 1), 2, 2, 6))
         self._check(self.lib.orbfe_debug_sim3_edges(self.h, n, *(ptr(a) for a in arrs), *(float(v) for v in cam), ptr(est), ptr(err),
                                                     ptr(chi2), ptr(jac)))
+        return err[:n], chi2[:n], jac[:n]
+
+    @staticmethod
+    def _pose_graph(estimates, fixed, edges, meas):
+        est = np.ascontiguousarray(estimates, np.float64).reshape(-1, 8)
+        fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+        edges = np.asarray(edges, np.int32).reshape(-1, 2)
+        v0, v1 = np.ascontiguousarray(edges[:, 0]), np.ascontiguousarray(edges[:, 1])
+        meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 8)
+        if fixed.shape[0] != est.shape[0] or meas.shape[0] != edges.shape[0]:
+            raise ValueError("the graph's arrays disagree in length")
+        g = PoseGraph(est.shape[0], edges.shape[0], ptr(est), ptr(fixed), ptr(v0), ptr(v1), ptr(meas))
+        return g, (est, fixed, v0, v1, meas)  # (the arrays must outlive the call)
+
+    def pose_graph_optimize(self, estimates, fixed, edges, meas, iterations=20):
+        """Optimizer::optimizeEssentialGraph from the point where the graph is built (orbfe_pose_graph_optimize): estimates (nv, 8) =
+        qx qy qz qw tx ty tz s with s == 1, fixed (nv,), edges (ne, 2) = (vertex 0, vertex 1), meas (ne, 8)
+        -> (estimates (nv, 8), chi2 (ne,) at them, (iterations run, trials run))."""
+        g, keep = self._pose_graph(estimates, fixed, edges, meas)
+        out = keep[0].copy()
+        chi2 = np.zeros(max(g.n_edges, 1))
+        stats = np.zeros(2, np.int32)
+        self._check(self.lib.orbfe_pose_graph_optimize(self.h, C.byref(g), int(iterations), ptr(out), ptr(chi2), ptr(stats)))
+        return out, chi2[:g.n_edges], (int(stats[0]), int(stats[1]))
+
+    def debug_pose_graph_phases(self):
+        """(build, assemble, solve, evaluate) milliseconds of the last pose_graph_optimize made with ORBFE_PG_PHASES set"""
+        ms = np.zeros(4)
+        self._check(self.lib.orbfe_debug_pose_graph_phases(ptr(ms)))
+        return tuple(float(v) for v in ms)
+
+    def debug_pose_graph_edges(self, estimates, fixed, edges, meas):
+        """the edges of pose_graph_optimize at the given estimates -> (err (ne, 6), chi2 (ne,), jac (ne, 2, 6, 6) = [vertex][row][d])"""
+        g, keep = self._pose_graph(estimates, fixed, edges, meas)
+        n = g.n_edges
+        err, chi2, jac = np.zeros((max(n, 1), 6)), np.zeros(max(n, 1)), np.zeros((max(n, 1), 2, 6, 6))
+        self._check(self.lib.orbfe_debug_pose_graph_edges(self.h, C.byref(g), ptr(err), ptr(chi2), ptr(jac)))
         return err[:n], chi2[:n], jac[:n]
 
     # ---- frame glue ------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 //   orbfe_guided.hip   brute-force and grid-guided matching, map-point projection, the fused tracking chains
 //   orbfe_ba.hip       g2o edge evaluation, normal equations, local BA, pose-only optimisation
 //   orbfe_sim3opt.hip  OptimizeSim3 and its edge probe
+//   orbfe_posegraph.hip  optimizeEssentialGraph (the pose graph of correctLoop) and its edge probe
 //   orbfe_map.hip      map.pb / text maps
 #pragma once
 #include <hip/hip_runtime.h>
@@ -137,6 +138,17 @@ void launch_sim3_optimize(hipStream_t s, int n, const float* pc, const float* pm
 int sim3_optimize_register_capacity();
 void launch_debug_sim3_edges(hipStream_t s, int n, const float* pc, const float* pm, const float* uvc, const float* uvm, const double* wc,
                              const double* wm, BaParamsDev prm, const double* est, double* err, double* chi2, double* jac);
+// k_posegraph.hip
+int pg_max_waves();
+void launch_pg_build(hipStream_t s, int n_edges, int waves, const double* est, const uint8_t* fixed, const int32_t* ev0, const int32_t* ev1,
+                     const double* meas, double* Hee, double* be, double* err, double* chi2, double* jac);
+void launch_pg_maxdiag(hipStream_t s, int nf, const int32_t* blk_off, const int32_t* ent, const double* Hee, double* out);
+void launch_pg_assemble(hipStream_t s, int nf, int n_blocks, const int2* blk, const int32_t* blk_off, const int32_t* ent, const double* Hee,
+                        const double* be, const double* lambda_p, double* S, double* rhs);
+void launch_pg_update(hipStream_t s, int n_vertices, const int32_t* slot, const double* x, const double* est, double* trial);
+void launch_pg_chi2(hipStream_t s, int n_edges, const double* est, const int32_t* ev0, const int32_t* ev1, const double* meas, double* chi2);
+void launch_pg_reduce(hipStream_t s, int n_edges, const double* chi2, int n, const double* x, const double* rhs, const double* lambda_p,
+                      double* out);
 void launch_track_queries(hipStream_t s, int n, const uint8_t* d_flags, const uint8_t* d_visible, const float* d_cos, const int8_t* d_level, float th,
                           const float* d_sigma2, int n_levels, float* d_radius, int8_t* d_min_level, int8_t* d_max_level);
 void launch_track_claim(hipStream_t s, int n, const int32_t* d_n_cand, const int32_t* d_best_idx, const int32_t* d_best_dist, const int32_t* d_second,

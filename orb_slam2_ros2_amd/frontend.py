@@ -372,6 +372,12 @@ class Optimizer:
         return ctx.sim3_optimize(pc, pm, uv_c, uv_m, info_c, info_m, cam, model)
 
     @staticmethod
+    def optimizeEssentialGraph(ctx: Context, estimates, fixed, edges, meas, iterations=20):
+        """Optimizer::optimizeEssentialGraph (Optimizer.cc:746-920) from the point where the graph is built, scale fixed: returns
+        (estimates (nv, 8) in double, chi2 of every edge at them, (iterations, trials)); see Context.pose_graph_optimize."""
+        return ctx.pose_graph_optimize(estimates, fixed, edges, meas, iterations)
+
+    @staticmethod
     def OptimizeLocalMap(ctx: Context, problem, pose_fixed=None, iters_first=5, iters_second=10):
         """The g2o part of Optimizer::OptimizeLocalMap (Optimizer.cc:336-391) on the graph `problem` describes (the arrays of
         orbfe_ba_problem): optimize(5) with Huber, level-1 / kernel-off re-classification, optimize(10), final chi2 test.

@@ -899,6 +899,25 @@ class Optimizer {
     keep.resize(n);
     return nInliers;
   }
+  // Optimizer::optimizeEssentialGraph (src/Optimizer.cc:746-920) from the point where the graph is built, scale fixed: estimates
+  // ([nv][8] = qx qy qz qw tx ty tz s, s == 1) in / out, fixed [nv], edge e from vertex v0[e] to vertex v1[e] with the measurement
+  // meas[e] ([8]).  Returns (iterations run, trials run); chi2 (nullable) gets err . err of every edge at the final estimates.
+  static std::pair<int, int> optimizeEssentialGraph(orbfe_ctx* ctx, std::vector<double>& estimates, const std::vector<uint8_t>& fixed,
+                                                    const std::vector<int32_t>& v0, const std::vector<int32_t>& v1,
+                                                    const std::vector<double>& meas, int iterations = 20, std::vector<double>* chi2 = nullptr) {
+    const size_t nv = fixed.size(), ne = v0.size();
+    if (estimates.size() != 8 * nv || v1.size() != ne || meas.size() != 8 * ne)
+      throw std::invalid_argument("optimizeEssentialGraph: the graph's arrays disagree in length");
+    const orbfe_pose_graph g = {(int32_t)nv, (int32_t)ne, estimates.data(), fixed.data(), v0.data(), v1.data(), meas.data()};
+    std::vector<double> out(std::max<size_t>(8 * nv, 1));
+    if (chi2) chi2->assign(std::max<size_t>(ne, 1), 0.0);
+    int32_t stats[2] = {0, 0};
+    check(ctx, orbfe_pose_graph_optimize(ctx, &g, iterations, out.data(), chi2 ? chi2->data() : nullptr, stats));
+    out.resize(8 * nv);
+    estimates.swap(out);
+    if (chi2) chi2->resize(ne);
+    return {stats[0], stats[1]};
+  }
 };
 
 }  // namespace orbfe
