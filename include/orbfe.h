@@ -324,6 +324,33 @@ orbfe_status orbfe_ba_local_optimize(orbfe_ctx* ctx, const orbfe_ba_problem* pro
                                      int32_t iters_first, int32_t iters_second, const volatile uint8_t* stop_flag,
                                      const orbfe_ba_optimize_out* out);
 
+/* ---- global bundle adjustment: Optimizer::globalOptimization from the point where the graph is built (src/Optimizer.cc:934-1043) ----
+ * ONE SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg on the graph type of orbfe_ba_local_optimize: no
+ * classification round, no second round, then one computeError() on every edge at the final estimates.  A global BA runs on every
+ * keyframe of the map, so its reduced camera system is large and block-sparse (consecutive keyframes share points, a loop adds a few
+ * far blocks): solver 2 builds it as 6x6 block-CSR and solves it by a block-Jacobi preconditioned conjugate gradient in fp64 (x0 = 0,
+ * stop at r.M^-1 r <= pcg_tol^2 b.M^-1 b; no convergence within pcg_max_iter, or p.Sp not positive and finite, rejects the Levenberg trial
+ * as a bad pivot of the dense solvers does).  solver 1 is orbfe_ba_local_optimize(iterations, 0), its poses, points and chi2.  solver 0
+ * chooses by the number of non-fixed keyframes alone: 1 up to ORBFE_GBA_DENSE_MAX_FREE, 2 past it (the measured crossover: up to there
+ * the local BA's device-side solvers are faster, past it they give way to the panel solver).  Every sum has a fixed order: a
+ * repeated call is bit-identical.  stop_flag as in orbfe_ba_local_optimize.  n_edges == 0 returns the inputs.                         */
+#define ORBFE_GBA_DENSE_MAX_FREE 1000
+typedef struct orbfe_ba_global_options {
+  int32_t solver;        /* 0 auto, 1 dense (the local BA's solvers), 2 block-sparse PCG                          */
+  double pcg_tol;        /* <= 0: 1e-10                                                                         */
+  int32_t pcg_max_iter;  /* <= 0: 4 * 6 * (non-fixed keyframes)                                                 */
+} orbfe_ba_global_options;
+typedef struct orbfe_ba_global_out {
+  double* poses;         /* [n_poses][7]  optimised estimates (fixed poses unchanged)                            */
+  double* points;        /* [n_points][3]                                                                       */
+  double* chi2;          /* [n_edges] chi2 at the final estimates, nullable                                      */
+  int32_t* iterations;   /* [1] Levenberg iterations run, nullable                                               */
+  int64_t* cg_stats;     /* [3] trials, CG iterations in all, trials the solver rejected (zeros for solver 1); nullable */
+} orbfe_ba_global_out;
+orbfe_status orbfe_ba_global_optimize(orbfe_ctx* ctx, const orbfe_ba_problem* prob, const uint8_t* pose_fixed /*[n_poses], nullable*/,
+                                      int32_t iterations, const volatile uint8_t* stop_flag, const orbfe_ba_global_options* opt /*nullable*/,
+                                      const orbfe_ba_global_out* out);
+
 /* ---- grid-guided matching against the features of one slot ---------------------------------------------------------
  * Replaces VirtualFrame::initGrid + findFeaturesInArea (src/Frame.cc:53-69, 286-311) + ORBMatcher::getBestMatch
  * (src/ORBMatcher.cc:967-990), the core of the guided searches (ORBMatcher::searchByProjection, src/ORBMatcher.cc:265-347 and
@@ -1113,6 +1140,25 @@ orbfe_status orbfe_debug_pose_graph_edges(orbfe_ctx* ctx, const orbfe_pose_graph
  * (launch_lba_chol), ms[3] evaluate (update, chi2, the sums and the scalars' download).  Only calls made with ORBFE_PG_PHASES set in the
  * environment are measured (and slowed down by the synchronisations); all zero otherwise.  For tools/essential_graph_bench.py.          */
 orbfe_status orbfe_debug_pose_graph_phases(double* ms /*[4]*/);
+
+/* The reduced camera system of orbfe_ba_global_optimize's solver 2 at ONE linearisation, the given estimates and lambda, as block-CSR
+ * over the non-fixed keyframes in index order: *nnzb stored 6x6 blocks, row_off[nf + 1], col[nnzb] (ascending in a row, both triangles,
+ * the diagonal always present), blocks[nnzb][36] row-major, rhs[6 nf].  *nnzb and row_off are always written; col, blocks and rhs only
+ * if cap_blocks >= *nnzb (call with cap_blocks = 0 to size the arrays, which may then be NULL).                                       */
+orbfe_status orbfe_debug_ba_reduced_bsr(orbfe_ctx* ctx, const orbfe_ba_problem* prob, const uint8_t* pose_fixed /*nullable*/, double lambda,
+                                        int32_t cap_blocks, int32_t* nnzb, int32_t* row_off, int32_t* col, double* blocks, double* rhs);
+/* One block-CSR system S x = rhs of nb 6x6 block rows through the conjugate-gradient solver of orbfe_ba_global_optimize (the layout
+ * above; S symmetric, both triangles stored).  tol <= 0: 1e-10, max_iter <= 0: 4 * 6 * nb.  *ok = 1: converged, *iters iterations.
+ * *ok = 0 is ORBFE_OK too: a diagonal block that is missing or not positive definite (x = 0), p.Sp not positive and finite, or no
+ * convergence within max_iter (x = the last iterate).  A zero right-hand side gives x = 0, *ok = 1, 0 iterations.  A column out of
+ * range, a row whose columns do not ascend, nb < 1 or a NULL argument is ORBFE_EBADARG.                                              */
+orbfe_status orbfe_debug_bsr_pcg(orbfe_ctx* ctx, int32_t nb, const int32_t* row_off, const int32_t* col, const double* blocks,
+                                 const double* rhs, double tol, int32_t max_iter, double* x, int32_t* iters, int32_t* ok);
+/* Where the last orbfe_ba_global_optimize (solver 2) of this process spent its time: ms[0] build (evaluation and normal equations),
+ * ms[1] Schur (point inverses, W, the block-CSR system), ms[2] PCG, ms[3] evaluate (update, chi2, the scalars' download), in
+ * milliseconds of wall time with the stream synchronised after every phase, and ms[4] = kernel launches and copies enqueued (the solver's counted, the few around it per trial a constant).  Only calls
+ * made with ORBFE_GBA_PHASES set in the environment are measured; all zero otherwise.  For tools/global_ba_bench.py.                  */
+orbfe_status orbfe_debug_ba_global_phases(double* ms /*[5]*/);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,14 @@ class BaOptimizeOut(C.Structure):
                 ("iterations", C.c_void_p)]
 
 
+class BaGlobalOptions(C.Structure):
+    _fields_ = [("solver", C.c_int32), ("pcg_tol", C.c_double), ("pcg_max_iter", C.c_int32)]
+
+
+class BaGlobalOut(C.Structure):
+    _fields_ = [("poses", C.c_void_p), ("points", C.c_void_p), ("chi2", C.c_void_p), ("iterations", C.c_void_p), ("cg_stats", C.c_void_p)]
+
+
 class FramePose(C.Structure):
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("min_u", C.c_float), ("max_u", C.c_float), ("min_v", C.c_float),
                 ("max_v", C.c_float)]
@@ -191,7 +199,7 @@ EXPORTS = [
     "orbfe_get_capacity",
     "orbfe_extract", "orbfe_extract_batch", "orbfe_extract_slot", "orbfe_extract_slot_begin", "orbfe_extract_slot_end", "orbfe_extract_slots", "orbfe_frame_stereo", "orbfe_frame_stereo_slots", "orbfe_frame_rgbd_image", "orbfe_track_motion_model", "orbfe_fetch_batch", "orbfe_fetch_stereo_batch", "orbfe_get_pyramid", "orbfe_stereo_match", "orbfe_stereo_batch_device", "orbfe_sync",
     "orbfe_host_alloc", "orbfe_host_alloc_on", "orbfe_host_free", "orbfe_recommended_hw_queues", "orbfe_stream_submit", "orbfe_stream_wait", "orbfe_stream_device_results", "orbfe_record_bytes", "orbfe_stream_pack_records",
-    "orbfe_fetch_features", "orbfe_fetch_stereo", "orbfe_device_results", "orbfe_match_bruteforce", "orbfe_ba_eval_edges", "orbfe_ba_build_system", "orbfe_ba_local_optimize", "orbfe_pose_only_optimize", "orbfe_search_in_area", "orbfe_search_in_area_features", "orbfe_search_in_area_features_ex", "orbfe_extract_color", "orbfe_frame_rgbd", "orbfe_project_map_points", "orbfe_track_local_map",
+    "orbfe_fetch_features", "orbfe_fetch_stereo", "orbfe_device_results", "orbfe_match_bruteforce", "orbfe_ba_eval_edges", "orbfe_ba_build_system", "orbfe_ba_local_optimize", "orbfe_ba_global_optimize", "orbfe_pose_only_optimize", "orbfe_search_in_area", "orbfe_search_in_area_features", "orbfe_search_in_area_features_ex", "orbfe_extract_color", "orbfe_frame_rgbd", "orbfe_project_map_points", "orbfe_track_local_map",
     "orbfe_map_pb_summary", "orbfe_map_pb_reencode", "orbfe_map_pb_to_txt", "orbfe_map_txt_to_pb", "orbfe_map_local_graph", "orbfe_map_local_ba",
     "orbfe_vocab_load_txt", "orbfe_vocab_info_get", "orbfe_vocab_export", "orbfe_vocab_destroy", "orbfe_bow_transform", "orbfe_bow_slots",
     "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_set_bad", "orbfe_kfdb_erase", "orbfe_kfdb_size", "orbfe_kfdb_query",
@@ -205,8 +213,10 @@ EXPORTS = [
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
+    "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
 ]
 BOW_MAX_FEATURES = 65535
+GBA_DENSE_MAX_FREE = 1000   # ORBFE_GBA_DENSE_MAX_FREE: solver 0 of ba_global_optimize is dense up to this many non-fixed keyframes
 
 _lib = None
 
@@ -349,6 +359,10 @@ def load() -> C.CDLL:
     L.orbfe_debug_candidates.argtypes = [vp, i32, i32, vp, i32, vp]
     L.orbfe_debug_se3_oplus.argtypes = [vp, i32, vp, vp, vp]
     L.orbfe_debug_reduced_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.orbfe_ba_global_optimize.argtypes = [vp, C.POINTER(BaProblem), vp, i32, vp, C.POINTER(BaGlobalOptions), C.POINTER(BaGlobalOut)]
+    L.orbfe_debug_ba_reduced_bsr.argtypes = [vp, C.POINTER(BaProblem), vp, C.c_double, i32, vp, vp, vp, vp, vp]
+    L.orbfe_debug_bsr_pcg.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]
+    L.orbfe_debug_ba_global_phases.argtypes = [vp]
     L.orbfe_sim3_optimize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
     L.orbfe_debug_sim3_edges.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
     L.orbfe_pose_graph_optimize.argtypes = [vp, vp, i32, vp, vp, vp]
@@ -1299,6 +1313,68 @@ class Context:
         for k in ("level", "chi2", "bad"):
             out[k] = out[k][:E]
         return out
+
+    def _ba_problem(self, prob):
+        """the orbfe_ba_problem of a problem dict and the arrays it points into (keep them alive for the call)"""
+        f64 = lambda a, shape: np.ascontiguousarray(a, np.float64).reshape(shape)
+        keep = [f64(prob["poses"], (-1, 7)), f64(prob["points"], (-1, 3)), np.ascontiguousarray(prob["edge_pose"], np.int32),
+                np.ascontiguousarray(prob["edge_point"], np.int32), f64(prob["meas"], (-1, 3)), np.ascontiguousarray(prob["is_stereo"], np.uint8),
+                f64(prob["info"], -1), f64(prob["huber_delta"], -1)]
+        nk, npt, E = keep[0].shape[0], keep[1].shape[0], keep[2].size
+        bp = BaProblem(nk, npt, E, *[ptr(a).value for a in keep], prob["fx"], prob["fy"], prob["cx"], prob["cy"], prob["bf"])
+        return bp, keep, (nk, npt, E)
+
+    def ba_global_optimize(self, prob, pose_fixed=None, iterations=10, solver=0, pcg_tol=None, pcg_max_iter=0, stop=None):
+        """Optimizer::globalOptimization from the point where the graph is built (orbfe_ba_global_optimize): ONE optimize(iterations) on
+        the graph `prob` describes (see ba_synth.make_trajectory_problem), then chi2 of every edge at the final estimates.  solver 0 auto
+        (dense up to GBA_DENSE_MAX_FREE non-fixed keyframes), 1 dense, 2 block-sparse PCG -> dict(poses, points, chi2, iters,
+        cg_stats = (trials, CG iterations in all, trials the solver rejected))."""
+        bp, keep, (nk, npt, E) = self._ba_problem(prob)
+        fixed = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8)
+        out = dict(poses=np.zeros((nk, 7)), points=np.zeros((npt, 3)), chi2=np.zeros(max(E, 1)), iters=np.zeros(1, np.int32),
+                   cg_stats=np.zeros(3, np.int64))
+        opt = BaGlobalOptions(int(solver), 0.0 if pcg_tol is None else float(pcg_tol), int(pcg_max_iter))
+        o = BaGlobalOut(ptr(out["poses"]).value, ptr(out["points"]).value, ptr(out["chi2"]).value, ptr(out["iters"]).value,
+                        ptr(out["cg_stats"]).value)
+        if stop is not None:
+            assert isinstance(stop, np.ndarray) and stop.dtype == np.uint8 and stop.size >= 1
+        self._check(self.lib.orbfe_ba_global_optimize(self.h, C.byref(bp), ptr(fixed), int(iterations), ptr(stop), C.byref(opt), C.byref(o)))
+        out["chi2"] = out["chi2"][:E]
+        out["iters"] = int(out["iters"][0])
+        return out
+
+    @staticmethod
+    def ba_global_phases():
+        """(build, Schur, PCG, evaluate) milliseconds and the launches of the last ba_global_optimize made with ORBFE_GBA_PHASES set"""
+        ms = np.zeros(5)
+        load().orbfe_debug_ba_global_phases(ptr(ms))
+        return ms
+
+    def debug_ba_reduced_bsr(self, prob, pose_fixed=None, lam=0.0):
+        """the block-CSR reduced camera system of ONE linearisation of `prob` at its estimates and lambda `lam` ->
+        dict(row_off (nf + 1,), col (nnzb,), blocks (nnzb, 6, 6), rhs (6 nf,))"""
+        bp, keep, (nk, npt, E) = self._ba_problem(prob)
+        fixed = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8)
+        nf = nk if fixed is None else int((fixed == 0).sum())
+        nnzb = C.c_int32(0)
+        row_off = np.zeros(nf + 1, np.int32)
+        self._check(self.lib.orbfe_debug_ba_reduced_bsr(self.h, C.byref(bp), ptr(fixed), float(lam), 0, C.byref(nnzb), ptr(row_off), None, None, None))
+        nz = nnzb.value
+        col, blocks, rhs = np.zeros(max(nz, 1), np.int32), np.zeros((max(nz, 1), 6, 6)), np.zeros(max(6 * nf, 1))
+        self._check(self.lib.orbfe_debug_ba_reduced_bsr(self.h, C.byref(bp), ptr(fixed), float(lam), nz, C.byref(nnzb), ptr(row_off), ptr(col),
+                                                        ptr(blocks), ptr(rhs)))
+        return dict(row_off=row_off, col=col[:nz], blocks=blocks[:nz], rhs=rhs[:6 * nf])
+
+    def debug_bsr_pcg(self, row_off, col, blocks, rhs, tol=0.0, max_iter=0):
+        """one block-CSR system through the conjugate-gradient solver of ba_global_optimize -> (x, iterations, ok)"""
+        row_off, col = np.ascontiguousarray(row_off, np.int32), np.ascontiguousarray(col, np.int32)
+        blocks, rhs = np.ascontiguousarray(blocks, np.float64).reshape(-1, 36), np.ascontiguousarray(rhs, np.float64)
+        nb = row_off.size - 1
+        assert rhs.size == 6 * nb and blocks.shape[0] == col.size == row_off[-1]
+        x, it, ok = np.zeros(6 * nb), C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.orbfe_debug_bsr_pcg(self.h, nb, ptr(row_off), ptr(col), ptr(blocks), ptr(rhs), float(tol), int(max_iter), ptr(x),
+                                                 C.byref(it), C.byref(ok)))
+        return x, it.value, ok.value
 
     def project_map_points(self, pos, view_dir, max_dist, min_dist, Rcw, tcw, cam, bounds):
         """MapPoint::isInVision + predictLevel for n map points (MapPoint.cc:141-201); cam = (fx, fy, cx, cy), bounds = (minU, maxU,

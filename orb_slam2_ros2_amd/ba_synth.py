@@ -177,3 +177,69 @@ def make_sim3_problem(seed=11, n=200, n_outliers=20, noise_px=0.5, scale_factor=
     return dict(pc=Pc.astype(np.float32), pm=Pm.astype(np.float32), uv_c=(proj(Pc) + nz_c).astype(np.float32),
                 uv_m=(proj(Pm) + nz_m).astype(np.float32), info_c=inv2(sig_c), info_m=inv2(sig_m), cam=tuple(float(v) for v in cam),
                 model=np.concatenate([R0.reshape(9), t0]).astype(np.float32), truth_R=R, truth_t=t, outlier=out)
+
+
+def make_trajectory_problem(seed, n_kf, per_kf, loop=3, huber=True, outliers=0.05, scale_factor=1.2, n_levels=8, with_truth=False):
+    """A map as Optimizer::globalOptimization sees it after a loop closure: n_kf identity-rotation cameras stepping 0.25 m along x, the
+    last `loop` of them placed back near the start (at x = 0.1 + 0.25 k); per_kf * n_kf points spread along the path at depth 3..7 m,
+    each observed by 2..8 keyframes that are consecutive among the ones that see it (in keyframe order, so a window over the first
+    keyframes may run into the loop keyframes); 80 % stereo edges; information 1 / sigma^2 of a random octave for both edge kinds
+    (Optimizer.cc:975, :990); Huber deltas of the reference if `huber`, none (-1) otherwise; a fraction `outliers` of gross measurement
+    errors; keyframe 0 at its true pose (the reference fixes it).  The reduced camera system is a band of half-width <= 7 blocks plus the
+    loop blocks.  Deterministic: every draw comes from the integer hash generators of this module.  Returns the arrays of
+    orbfe_ba_problem."""
+    assert n_kf >= 2 and 0 <= loop < n_kf - 1 and per_kf >= 1
+    step, n_main = 0.25, n_kf - loop
+    cx_kf = np.concatenate([step * np.arange(n_main), 0.1 + step * np.arange(loop)])
+    poses = np.zeros((n_kf, 7))
+    poses[:, 3] = 1.0
+    poses[:, 4] = -cx_kf                                                       # t_cw = -R centre, R = I
+    n_pt = per_kf * n_kf
+    pid = np.arange(n_pt)
+    z = 3.0 + 4.0 * _u(seed, 3, pid)
+    points = np.stack([_u(seed, 1, pid) * step * (n_main - 1), (_u(seed, 2, pid) - 0.5) * 2.0, z], 1)
+    # the keyframes that see a point, in keyframe order: a window of the main chain around it, then the loop keyframes
+    half = int(np.ceil(0.65 * 7.0 / step)) + 1
+    cand = np.rint(points[:, 0] / step).astype(np.int64)[:, None] + np.arange(-half, half + 1)[None, :]
+    cand = np.concatenate([cand, np.broadcast_to(n_main + np.arange(loop), (n_pt, loop))], 1)
+    valid = (cand >= 0) & (cand < n_kf) & ((cand < n_main) | (np.arange(cand.shape[1])[None, :] > 2 * half))
+    ck = np.clip(cand, 0, n_kf - 1)
+    u_all = FX * (points[:, 0:1] - cx_kf[ck]) / z[:, None] + CX
+    v_pt = FY * points[:, 1] / z + CY
+    vis = valid & (u_all >= 0) & (u_all < 640) & ((v_pt >= 0) & (v_pt < 480))[:, None]
+    cnt = vis.sum(1)
+    want = np.minimum(2 + (hash_u64(seed, 4, pid) % np.uint64(7)).astype(np.int64), cnt)
+    start = (hash_u64(seed, 5, pid) % np.maximum(cnt - want + 1, 1).astype(np.uint64)).astype(np.int64)
+    rank = np.cumsum(vis, 1) - 1
+    take = vis & (rank >= start[:, None]) & (rank < (start + want)[:, None])
+    e_pt, col = np.nonzero(take)                                              # point-major, keyframes ascending
+    e_pose = ck[e_pt, col]
+    E = e_pt.size
+    eid = np.arange(E)
+    sigma = np.float32(scale_factor) ** np.arange(n_levels, dtype=np.float32)
+    octave = (hash_u64(seed, 6, eid) % np.uint64(n_levels)).astype(np.int64)
+    s = sigma[octave].astype(np.float64)
+    nz = np.stack([_irwin_hall(seed, 10, 3 * eid), _irwin_hall(seed, 10, 3 * eid + 1), _irwin_hall(seed, 10, 3 * eid + 2)], 1) * s[:, None]
+    if outliers > 0:
+        gross = (hash_u64(seed, 7, eid) % np.uint64(10000)).astype(np.int64) < int(round(outliers * 10000))
+        nz[gross] += np.array([35.0, -28.0, 31.0])
+    is_st = (hash_u64(seed, 8, eid) % np.uint64(5)) != 0                       # 80 % stereo
+    ze = z[e_pt]
+    u = FX * (points[e_pt, 0] - cx_kf[e_pose]) / ze + CX
+    v = FY * points[e_pt, 1] / ze + CY
+    ur = u - BF / ze
+    # measurements are float32 in the reference (kp.pt.x, rightU stored from float math)
+    meas = np.stack([np.float32(u + nz[:, 0]), np.float32(v + nz[:, 1]), np.where(is_st, np.float32(ur + nz[:, 2]), -1.0)], 1).astype(np.float64)
+    inv_s = (np.float32(1.0) / sigma[octave]).astype(np.float32)
+    info = (inv_s ** 2).astype(np.float64)                                    # getScaledFactorInv2 for both edge kinds
+    d_mono, d_stereo = float(np.float32(np.sqrt(5.991))), float(np.float32(np.sqrt(7.815)))
+    delta = np.where(is_st, d_stereo, d_mono) if huber else np.full(E, -1.0)
+    kid = np.arange(n_kf)
+    poses_est = poses.copy()
+    poses_est[1:, 4:] += 0.02 * np.stack([_irwin_hall(seed, 30, kid), _irwin_hall(seed, 50, kid), _irwin_hall(seed, 70, kid)], 1)[1:]
+    points_est = points + 0.03 * np.stack([_irwin_hall(seed, 90, pid), _irwin_hall(seed, 110, pid), _irwin_hall(seed, 130, pid)], 1)
+    out = dict(poses=poses_est, points=points_est, edge_pose=e_pose.astype(np.int32), edge_point=e_pt.astype(np.int32), meas=meas,
+               is_stereo=is_st.astype(np.uint8), info=info, huber_delta=np.asarray(delta, np.float64), fx=FX, fy=FY, cx=CX, cy=CY, bf=BF)
+    if with_truth:
+        out.update(poses_true=poses, points_true=points)
+    return out

@@ -474,24 +474,36 @@ void launch_lba_chol(hipStream_t s, int nf, double* S, double* rhs, double* x, i
     hipLaunchKernelGGL(k_lba_chol_back, dim3(1), dim3(1024), 0, s, n, S, Ldg, yg, x, ok);
   }
 }
+// the two ends of a trial that do not depend on how the reduced system is solved: point inverses and W before it, the update of the
+// estimates and computeScale after it
+void launch_lba_pre(hipStream_t s, int n_points, int n_edges, const int32_t* edge_point, const double* Hll, const double* Hpl,
+                    const double* lambda_p, double* Dinv, double* W, int* ok) {
+  if (n_points > 0) hipLaunchKernelGGL(k_lba_point_inv, dim3((n_points + 255) / 256), dim3(256), 0, s, n_points, Hll, lambda_p, Dinv, ok);
+  if (n_edges > 0) hipLaunchKernelGGL(k_lba_edge_w, dim3((n_edges + 255) / 256), dim3(256), 0, s, n_edges, edge_point, Hpl, Dinv, W);
+}
+void launch_lba_post(hipStream_t s, int n_poses, int n_points, const int32_t* pose_slot, const int32_t* pt_off, const int32_t* pt_edges,
+                     const int32_t* edge_pose, const uint8_t* fixed, const double* bp, const double* bl, const double* Hpl, const double* lambda_p,
+                     const double* Dinv, const double* x, double* poses, double* points, double* dxp, double* dxl, double* scale_out) {
+  const int nt = n_points + n_poses;
+  if (nt > 0)
+    hipLaunchKernelGGL(k_lba_update, dim3((nt + 255) / 256), dim3(256), 0, s, n_poses, n_points, pose_slot, x, pt_off, pt_edges, edge_pose, Hpl,
+                       bl, Dinv, poses, points, dxp, dxl);
+  hipLaunchKernelGGL(k_lba_scale, dim3(1), dim3(1024), 0, s, n_poses, n_points, fixed, dxp, bp, dxl, bl, lambda_p, scale_out);
+}
 void launch_lba_solve(hipStream_t s, int n_poses, int n_points, int n_edges, int nf, const int32_t* free_pose, const int32_t* pose_slot,
                       const int32_t* pair_off, const int2* pairs, const int32_t* ps_off, const int32_t* ps_edges, const int32_t* pt_off,
                       const int32_t* pt_edges, const int32_t* edge_pose, const int32_t* edge_point, const uint8_t* fixed, const double* Hpp,
                       const double* bp, const double* Hll, const double* bl, const double* Hpl, const double* lambda_p, double* Dinv, double* W,
                       double* S, double* rhs, double* x, int* ok, double* poses, double* points, double* dxp, double* dxl, double* scale_out,
                       double* big_scratch) {
-  if (n_points > 0) hipLaunchKernelGGL(k_lba_point_inv, dim3((n_points + 255) / 256), dim3(256), 0, s, n_points, Hll, lambda_p, Dinv, ok);
-  if (n_edges > 0) hipLaunchKernelGGL(k_lba_edge_w, dim3((n_edges + 255) / 256), dim3(256), 0, s, n_edges, edge_point, Hpl, Dinv, W);
+  launch_lba_pre(s, n_points, n_edges, edge_point, Hll, Hpl, lambda_p, Dinv, W, ok);
   if (nf > 0) {
     hipLaunchKernelGGL(k_lba_schur, dim3(nf, nf), dim3(64), 0, s, nf, free_pose, pair_off, pairs, ps_off, ps_edges, edge_point, Hpp, bp, bl,
                        Hpl, W, lambda_p, S, rhs);
     launch_lba_chol(s, nf, S, rhs, x, ok, big_scratch);
   }
-  const int nt = n_points + n_poses;
-  if (nt > 0)
-    hipLaunchKernelGGL(k_lba_update, dim3((nt + 255) / 256), dim3(256), 0, s, n_poses, n_points, pose_slot, x, pt_off, pt_edges, edge_pose, Hpl,
-                       bl, Dinv, poses, points, dxp, dxl);
-  hipLaunchKernelGGL(k_lba_scale, dim3(1), dim3(1024), 0, s, n_poses, n_points, fixed, dxp, bp, dxl, bl, lambda_p, scale_out);
+  launch_lba_post(s, n_poses, n_points, pose_slot, pt_off, pt_edges, edge_pose, fixed, bp, bl, Hpl, lambda_p, Dinv, x, poses, points, dxp, dxl,
+                  scale_out);
 }
 void launch_lba_classify(hipStream_t s, int n_edges, const double* chi2_last, const uint8_t* depth_pos, const uint8_t* is_stereo,
                          uint8_t* level, double* info_eff, double* delta_eff) {

@@ -98,6 +98,19 @@ void launch_lba_solve(hipStream_t s, int n_poses, int n_points, int n_edges, int
                       double* S, double* rhs, double* x, int* ok, double* poses, double* points, double* dxp, double* dxl, double* scale_out,
                       double* big_scratch);
 void launch_lba_chol(hipStream_t s, int nf, double* S, double* rhs, double* x, int* ok, double* big_scratch);
+void launch_lba_pre(hipStream_t s, int n_points, int n_edges, const int32_t* edge_point, const double* Hll, const double* Hpl,
+                    const double* lambda_p, double* Dinv, double* W, int* ok);
+void launch_lba_post(hipStream_t s, int n_poses, int n_points, const int32_t* pose_slot, const int32_t* pt_off, const int32_t* pt_edges,
+                     const int32_t* edge_pose, const uint8_t* fixed, const double* bp, const double* bl, const double* Hpl, const double* lambda_p,
+                     const double* Dinv, const double* x, double* poses, double* points, double* dxp, double* dxl, double* scale_out);
+// k_bsr.hip
+void launch_bsr_schur(hipStream_t s, int n_low, const int32_t* low, const int32_t* low_row, const int32_t* col, const int32_t* twin,
+                      const int32_t* pair_off, const int2* pairs, const int32_t* free_pose, const int32_t* ps_off, const int32_t* ps_edges,
+                      const int32_t* edge_point, const double* Hpp, const double* bp, const double* bl, const double* Hpl, const double* W,
+                      const double* lambda_p, double* blocks, double* rhs, double* Minv, int* ok);
+void launch_bsr_diag_inv(hipStream_t s, const BsrPcgLaunch& L);
+void launch_pcg_begin(hipStream_t s, const BsrPcgLaunch& L, double tol);
+void launch_pcg_iterations(hipStream_t s, const BsrPcgLaunch& L, int k0, int n);
 // k_lmbig.hip
 size_t lm_big_bytes(int nf);
 size_t lm_big_inv_bytes(int nf);

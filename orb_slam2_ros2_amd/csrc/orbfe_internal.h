@@ -228,6 +228,29 @@ struct LmLaunch {
   BaParamsDev prm;
 };
 
+// ---- block-CSR reduced system and its conjugate-gradient solver (k_bsr.hip, orbfe_gba.hip) ------------------------------------------
+enum { PCG_RUNNING = 0, PCG_CONVERGED = 1, PCG_BREAKDOWN = 2 };
+// The solver's scalars (device memory; the host reads iters and state between chunks of iterations).  Iteration k reads entry k & 1 of
+// rz and state and writes the other one.
+struct PcgState {
+  double rz[2];       // r . M^-1 r
+  double rz0, tol2;   // b . M^-1 b | tol^2: converged when rz <= tol2 * rz0
+  int32_t state[2];   // PCG_*
+  int32_t iters;      // iterations completed
+  int32_t pq_bad;     // this iteration's p . S p was not positive and finite
+  int32_t done;       // the verdict for the host (PCG_*): written with the state, read by no kernel
+  int32_t pad;
+};
+struct BsrPcgLaunch {
+  int nb;
+  const int32_t *row_off, *col;
+  const double *blocks, *rhs;
+  double *Minv, *x, *r, *z, *p, *q;  // [nb][36] | five vectors of 6 nb
+  double *part_pq, *part_rz;         // [nb] each: one partial per block row
+  PcgState* state;
+  int* ok;                           // cleared by a diagonal block that is not positive definite
+};
+
 // ---- bag of words (k_bow.hip, orbfe_bow.hip) --------------------------------------------------------------------------------------
 // Device layout of a vocabulary: every node but the root has a POSITION; the children of a node occupy consecutive positions in file order,
 // so one node's children are one contiguous block of 32-byte descriptors (desc[2 p], desc[2 p + 1]) and of records.

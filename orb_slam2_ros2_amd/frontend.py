@@ -385,6 +385,14 @@ class Optimizer:
         return ctx.ba_local_optimize(problem, pose_fixed, iters_first, iters_second)
 
     @staticmethod
+    def globalOptimization(ctx: Context, problem, pose_fixed, iterations, solver=0, pcg_tol=None):
+        """Optimizer::globalOptimization (Optimizer.cc:934-1043) from the point where the graph is built: ONE optimize(iterations) on the
+        graph `problem` describes, the reduced camera system block-sparse and solved by a preconditioned conjugate gradient past
+        _lib.GBA_DENSE_MAX_FREE non-fixed keyframes (solver 0; 1 dense, 2 sparse).  Returns dict(poses, points, chi2, iters, cg_stats):
+        what the reference stores in mTcwGBA / mPGBA; see Context.ba_global_optimize."""
+        return ctx.ba_global_optimize(problem, pose_fixed, iterations, solver=solver, pcg_tol=pcg_tol)
+
+    @staticmethod
     def evalEdges(ctx: Context, poses, points, edge_pose, edge_point, meas, is_stereo, info, huber_delta, fx, fy, cx, cy, bf,
                   jacobians=True):
         return ctx.ba_eval_edges(poses, points, edge_pose, edge_point, meas, is_stereo, info, huber_delta, fx, fy, cx, cy, bf,

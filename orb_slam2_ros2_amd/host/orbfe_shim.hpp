@@ -899,6 +899,28 @@ class Optimizer {
     keep.resize(n);
     return nInliers;
   }
+  // Optimizer::globalOptimization (src/Optimizer.cc:934-1043) from the point where the graph is built: ONE optimize(iterations) on the
+  // graph `prob` describes, then chi2 of every edge at the final estimates.  solver 0: dense up to ORBFE_GBA_DENSE_MAX_FREE non-fixed
+  // keyframes, block-sparse PCG past it (1 / 2 name them); pcgTol <= 0: 1e-10.  cgStats = trials, CG iterations, trials the solver rejected.
+  struct GlobalResult {
+    std::vector<double> poses, points, chi2;  // [nPoses][7] qx qy qz qw tx ty tz, [nPoints][3], [nEdges]
+    int32_t iterations = 0;
+    int64_t cgStats[3] = {0, 0, 0};
+  };
+  static GlobalResult globalOptimization(orbfe_ctx* ctx, const orbfe_ba_problem& prob, const std::vector<uint8_t>& poseFixed, int iterations,
+                                         const volatile bool* bStopFlag = nullptr, int solver = 0, double pcgTol = 0.0) {
+    if (!poseFixed.empty() && poseFixed.size() != (size_t)prob.n_poses)
+      throw std::invalid_argument("globalOptimization: poseFixed does not have one entry per pose");
+    GlobalResult r;
+    r.poses.resize(std::max<size_t>((size_t)prob.n_poses * 7, 1)), r.points.resize(std::max<size_t>((size_t)prob.n_points * 3, 1));
+    r.chi2.resize((size_t)std::max(prob.n_edges, 1));
+    const orbfe_ba_global_options opt = {solver, pcgTol, 0};
+    const orbfe_ba_global_out o = {r.poses.data(), r.points.data(), r.chi2.data(), &r.iterations, r.cgStats};
+    check(ctx, orbfe_ba_global_optimize(ctx, &prob, poseFixed.empty() ? nullptr : poseFixed.data(), iterations, (const volatile uint8_t*)bStopFlag,
+                                        &opt, &o));
+    r.poses.resize((size_t)prob.n_poses * 7), r.points.resize((size_t)prob.n_points * 3), r.chi2.resize(prob.n_edges);
+    return r;
+  }
   // Optimizer::optimizeEssentialGraph (src/Optimizer.cc:746-920) from the point where the graph is built, scale fixed: estimates
   // ([nv][8] = qx qy qz qw tx ty tz s, s == 1) in / out, fixed [nv], edge e from vertex v0[e] to vertex v1[e] with the measurement
   // meas[e] ([8]).  Returns (iterations run, trials run); chi2 (nullable) gets err . err of every edge at the final estimates.
