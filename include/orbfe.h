@@ -407,6 +407,9 @@ orbfe_status orbfe_pose_only_optimize(orbfe_ctx* ctx, int32_t n, const double* x
  * (Frame.cc:108,148) -- and, when depth != NULL, the RGB-D tail of Frame::Frame (src/Frame.cc:136-158): depth read at the
  * DISTORTED keypoint with truncated indices, divided by depth_scale in float, depth_out = d and right_u_out = x_undist - bf / d
  * where d > 0, else -1.  depth_type 0: uint16 image, 1: float image; rows depth_stride_bytes apart (host memory).
+ * Strides: a colour image's stride_bytes is at least 3 * width; depth_stride_bytes is at least width elements AND a multiple of the
+ * element size (2 or 4 bytes) -- anything else is ORBFE_EBADARG.  Either image may be a column range of a larger one (a cv::Mat ROI,
+ * stride = Mat::step): nothing behind the last element of the LAST row is read, i.e. stride * (height - 1) + width * element bytes.
  * Outputs [n_features] (entries past the keypoint count are -1), any may be NULL.  Stereo rigs are taken as rectified (k1 == 0,
  * the reference's only stereo configuration): orbfe_stereo_match does not undistort.                                          */
 typedef struct orbfe_camera {

@@ -376,6 +376,19 @@ def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _row_strided(a, dtypes):
+    """a as the C ABI takes an image: rows `strides[0]` bytes apart, everything inside a row contiguous.  A view that already is one (a
+    column range of a larger image, rows with padding) is passed through WITHOUT a copy, so its stride reaches the library; anything
+    else is made contiguous."""
+    a = np.asarray(a)
+    inner = a.dtype.itemsize
+    ok = a.dtype in dtypes and a.ndim >= 2 and a.strides[0] >= inner * int(np.prod(a.shape[1:]))
+    for ax in range(a.ndim - 1, 0, -1):
+        ok = ok and a.strides[ax] == inner
+        inner *= a.shape[ax]
+    return a if ok else np.ascontiguousarray(a, dtypes[0] if len(dtypes) == 1 else None)
+
+
 class PinnedArray:
     """numpy view of page-locked host memory from orbfe_host_alloc (freed with the object)"""
 
@@ -1555,8 +1568,9 @@ class Context:
 
     # ---- frame glue ------------------------------------------------------------------------------
     def extract_color(self, img: np.ndarray, order: int):
-        """img: (h, w, 3) uint8, order 1 = RGB / 2 = BGR -> (keypoints, descriptors) of slot 0"""
-        img = np.ascontiguousarray(img, np.uint8)
+        """img: (h, w, 3) uint8, order 1 = RGB / 2 = BGR -> (keypoints, descriptors) of slot 0.  A view whose rows are further apart
+        than 3 w bytes (its last two axes contiguous) is passed as it is, with its row stride."""
+        img = _row_strided(img, (np.uint8,))
         assert img.shape == (self.height, self.width, 3)
         kps = np.zeros(max(self.n_features, 1), KP_DTYPE)
         desc = np.zeros((max(self.n_features, 1), 32), np.uint8)
@@ -1565,14 +1579,15 @@ class Context:
         return kps[:n.value].copy(), desc[:n.value].copy()
 
     def frame_rgbd(self, slot, cam: dict, depth=None, depth_scale=1.0):
-        """cam: dict(fx fy cx cy k1 k2 p1 p2 k3 bf) -> (undistorted keypoints, depth, right_u); depth None: undistortion only"""
+        """cam: dict(fx fy cx cy k1 k2 p1 p2 k3 bf) -> (undistorted keypoints, depth, right_u); depth None: undistortion only.
+        depth: (h, w) uint16 / float32; a column range of a larger image is passed as it is, with the larger image's row stride."""
         cm = Camera(*[float(cam[k]) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf")])
         nf = max(self.n_features, 1)
         kps = np.zeros(nf, KP_DTYPE)
         d, ru = np.zeros(nf), np.zeros(nf)
         dtype, stride = 0, 0
         if depth is not None:
-            depth = np.ascontiguousarray(depth)
+            depth = _row_strided(depth, (np.uint16, np.float32))
             assert depth.dtype in (np.uint16, np.float32) and depth.shape == (self.height, self.width)
             dtype, stride = (0 if depth.dtype == np.uint16 else 1), depth.strides[0]
         self._check(self.lib.orbfe_frame_rgbd(self.h, slot, C.byref(cm), ptr(depth), dtype, stride, depth_scale, ptr(kps), ptr(d), ptr(ru)))
@@ -1586,8 +1601,7 @@ class Context:
         want = (self.height, self.width, 3) if color_order else (self.height, self.width)
         if img.shape != want:
             raise ValueError(f"image shape {img.shape} != {want}")
-        if not (img.dtype == np.uint8 and img.flags.c_contiguous):
-            img = np.ascontiguousarray(img, np.uint8)
+        img = _row_strided(img, (np.uint8,))    # (row-strided views of the image and of the depth go through with their strides)
         cm = Camera(*[float(cam[k]) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf")])
         nf = max(self.n_features, 1)
         kps, desc = np.zeros(nf, KP_DTYPE), np.zeros((nf, 32), np.uint8)
@@ -1595,7 +1609,7 @@ class Context:
         n = C.c_int32(0)
         dtype, stride = 0, 0
         if depth is not None:
-            depth = np.ascontiguousarray(depth)
+            depth = _row_strided(depth, (np.uint16, np.float32))
             assert depth.dtype in (np.uint16, np.float32) and depth.shape == (self.height, self.width)
             dtype, stride = (0 if depth.dtype == np.uint16 else 1), depth.strides[0]
         self._check(self.lib.orbfe_frame_rgbd_image(self.h, slot, img.ctypes.data, img.strides[0], color_order, C.byref(cm), ptr(depth), dtype,

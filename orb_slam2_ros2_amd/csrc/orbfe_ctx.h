@@ -31,6 +31,7 @@
 
 #include "orbfe_internal.h"
 #include "scratch_layout.h"
+#include "staged_rows.h"
 #include "search_area_layout.h"
 
 namespace orbfe {

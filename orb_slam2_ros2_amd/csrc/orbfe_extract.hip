@@ -301,7 +301,9 @@ static orbfe_status extract_lane(orbfe_ctx* c, orbfe_ctx::Lane& ln, int slot0, i
   const size_t o_cnt = o_desc + align_up((size_t)n_img * NF * 32, 256), o_ru = o_cnt + align_up((size_t)n_img * 4, 256);
   const bool extra = fs || fr;
   const size_t o_dp = o_ru + (extra ? align_up(NF * 8, 256) : 0), o_dimg = o_dp + (extra ? align_up(NF * 8, 256) : 0);
-  const size_t d_bytes = (fr && fr->depth) ? fr->depth_stride * (size_t)c->cfg.height : 0;
+  // (to the last row's last element: the caller's image may be a column range of a larger one -- staged_rows.h)
+  const size_t d_row = (size_t)c->cfg.width * ((fr && fr->depth_type == 0) ? 2 : 4);
+  const size_t d_bytes = (fr && fr->depth) ? staged_rows_bytes(fr->depth_stride, (size_t)c->cfg.height, d_row) : 0;
   const size_t total = o_dimg + align_up(d_bytes, 256);
   TRY(ensure_stage(c, ln, total));
   for (int i = 0; i < n_img && phase != 2; ++i) {
@@ -312,7 +314,7 @@ static orbfe_status extract_lane(orbfe_ctx* c, orbfe_ctx::Lane& ln, int slot0, i
     else
       for (int y = 0; y < L0.h; ++y) std::memcpy(dst + (size_t)y * L0.stride, imgs[i] + (size_t)y * stride, (size_t)c->cfg.width);
   }
-  if (d_bytes) std::memcpy(ln.h_stage + o_dimg, fr->depth, d_bytes);
+  if (d_bytes) stage_rows(ln.h_stage + o_dimg, fr->depth, fr->depth_stride, (size_t)c->cfg.height, d_row);
   FrameRgbdKey rkey;
   static_assert(sizeof(FrameRgbdKey) <= sizeof(orbfe_ctx::GraphEntry::rkey), "GraphEntry::rkey");
   std::memset(&rkey, 0, sizeof rkey);
@@ -540,8 +542,10 @@ orbfe_status orbfe_frame_rgbd_image(orbfe_ctx* c, int32_t slot, const uint8_t* i
   if (!c || !img || !cam) return fail(c, ORBFE_EBADARG, "frame_rgbd_image: NULL argument");
   if (color_order < 0 || color_order > 2) return fail(c, ORBFE_EBADARG, "frame_rgbd_image: color_order %d (0 = gray, 1 = RGB, 2 = BGR)", color_order);
   const size_t px = depth_type == 0 ? 2 : 4;
-  if (depth && (depth_type < 0 || depth_type > 1 || depth_stride < (size_t)c->cfg.width * px || !(depth_scale > 0)))
-    return fail(c, ORBFE_EBADARG, "frame_rgbd_image: depth type %d stride %zu scale %g", depth_type, depth_stride, (double)depth_scale);
+  // (a stride that is no multiple of the element size: k_frame_rgbd reads the element through a cast of the row pointer)
+  if (depth && (depth_type < 0 || depth_type > 1 || depth_stride < (size_t)c->cfg.width * px || depth_stride % px != 0 || !(depth_scale > 0)))
+    return fail(c, ORBFE_EBADARG, "frame_rgbd_image: depth type %d stride %zu (>= the row, a multiple of the element's %zu bytes) scale %g", depth_type,
+                depth_stride, px, (double)depth_scale);
   const uint8_t* one[1] = {img};
   const FrameRgbdReq fr = {color_order, *cam, depth, depth_type, depth_stride, depth_scale, depth_out, right_u_out, false};
   return extract_slots_impl(c, slot, 1, one, stride, kps_undistorted, desc, n_out, nullptr, &fr);
@@ -587,13 +591,14 @@ orbfe_status orbfe_frame_rgbd(orbfe_ctx* c, int32_t slot, const orbfe_camera* ca
   ApiLock api_lk(c);
   if (!c || !cam || slot < 0 || slot >= c->cfg.max_images) return fail(c, ORBFE_EBADARG, "frame_rgbd: bad slot / NULL camera");
   const size_t px = depth_type == 0 ? 2 : 4;
-  if (depth && (depth_type < 0 || depth_type > 1 || depth_stride < (size_t)c->cfg.width * px || !(depth_scale > 0)))
-    return fail(c, ORBFE_EBADARG, "frame_rgbd: depth type %d stride %zu scale %g", depth_type, depth_stride, (double)depth_scale);
+  if (depth && (depth_type < 0 || depth_type > 1 || depth_stride < (size_t)c->cfg.width * px || depth_stride % px != 0 || !(depth_scale > 0)))
+    return fail(c, ORBFE_EBADARG, "frame_rgbd: depth type %d stride %zu (>= the row, a multiple of the element's %zu bytes) scale %g", depth_type,
+                depth_stride, px, (double)depth_scale);
   TRY(slots_idle(c, slot, 1, "frame_rgbd"));
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
   const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
-  const size_t d_bytes = depth ? depth_stride * (size_t)c->cfg.height : 0;
+  const size_t d_bytes = depth ? staged_rows_bytes(depth_stride, (size_t)c->cfg.height, (size_t)c->cfg.width * px) : 0;  // (staged_rows.h)
   // The depth image is staged in page-locked memory and READ FROM THERE by the kernel (one 2- or 4-byte value per keypoint: uploading
   // 614 KB of a 640 x 480 16-bit image for 1000 reads was a third of the call); depth, rightU and the undistorted keypoints are written
   // to the staging buffer by the kernel as well: one 4-byte copy (the count), one synchronisation.
@@ -601,7 +606,7 @@ orbfe_status orbfe_frame_rgbd(orbfe_ctx* c, int32_t slot, const orbfe_camera* ca
   const size_t h_img = L.take(d_bytes), h_res = L.take<double>(NF), h_ru = L.take<double>(NF), h_n = L.take<int32_t>(1), h_k = L.take<orbfe_keypoint>(NF);
   StagedIo io;
   TRY(io.reserve(c, 0, L.end()));
-  if (depth) io.put(h_img, depth, d_bytes);
+  if (depth) stage_rows(io.h + h_img, depth, depth_stride, (size_t)c->cfg.height, (size_t)c->cfg.width * px);
   grid_invalidate(c, slot);  // (the keypoints move: a grid kept for the slot is stale)
   launch_frame_rgbd(c->stream, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, *cam, depth ? io.h + h_img : nullptr, depth_type, depth_stride,
                     depth_scale, (double*)(io.h + h_res), (double*)(io.h + h_ru), kps_out ? (orbfe_keypoint*)(io.h + h_k) : nullptr);

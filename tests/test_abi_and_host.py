@@ -175,6 +175,30 @@ def test_scratch_layout_host_program(tmp_path):
     assert r.returncode == 0 and r.stdout.strip() == "SCRATCH_LAYOUT_OK", r.stdout + r.stderr
 
 
+def test_staged_rows_host_program_under_sanitizers(tmp_path):
+    """tests/cpp/test_staged_rows.cpp: csrc/staged_rows.h (how much of a caller's strided depth image orbfe_frame_rgbd / orbfe_frame_rgbd_image
+    stage) on column ranges whose heap block ends with the last element of the last row, with the host compiler's address and
+    undefined-behaviour sanitizers when this g++ has their runtimes (a stand-alone program; nothing of it is loaded into python)"""
+    import subprocess
+    src = os.path.join(ROOT, "tests", "cpp", "test_staged_rows.cpp")
+    exe = str(tmp_path / "test_staged_rows")
+    base = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-o", exe, src]
+    mode = "address + undefined-behaviour sanitizers"
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        # only a g++ WITHOUT the sanitizers' runtimes may run the program plain; anything else the sanitized build says is a failure
+        assert re.search(r"cannot find -l(asan|ubsan)|cannot find lib(asan|ubsan)|lib(asan|ubsan)\S* ?: No such file", r.stderr), r.stderr[-3000:]
+        mode = "no sanitizer runtime on this machine: plain build"
+        subprocess.check_call(base, timeout=300)
+    print("test_staged_rows.cpp:", mode)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == "STAGED_ROWS_OK", (r.stdout + r.stderr)[-3000:]
+    # both staging sites go through the helper: no `stride * height` byte count of a depth image is left in the entry points
+    text = open(os.path.join(ROOT, "orb_slam2_ros2_amd", "csrc", "orbfe_extract.hip")).read()
+    assert text.count("stage_rows(") == 2 and text.count("staged_rows_bytes(") == 2
+    assert not re.search(r"depth_stride \* \(size_t\)c->cfg\.height", text)
+
+
 def test_no_kernel_reads_the_dispatch_packet():
     """A kernel with a private array the compiler cannot scalarise (or with blockDim / gridDim) gets the dispatch pointer: its waves then begin
     with a scalar load from the queue's ring buffer in HOST memory (r6: 13.6 us per wave of a pair's descriptor launch).  tools/check_dispatch_ptr.py

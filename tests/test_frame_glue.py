@@ -75,6 +75,55 @@ def test_oracle_rgbd_lookup_truncates_indices_and_marks_missing_depth(orc):
     assert df.tolist() == [1.0, 2.0, -1.0]
 
 
+@pytest.mark.parametrize("name", ["tum", "k1_zero", "k1_-4", "k1_-8"])
+def test_oracle_undistort_equals_the_numpy_restatement_early_exit_included(orc, name):
+    """orc_undistort_points against tests/input_shapes.py's float64 numpy restatement of the five iterations, bit for bit, on the cameras of
+    tests/test_gpu_input_shapes.py.  With k1 = -4 and -8 the radial factor 1 + k1 r2 + .. turns negative inside the image and the point
+    leaves through `icdist < 0` with its normalised input: an exit the TUM coefficients never take."""
+    import input_shapes as ish
+    w, h = 333, ish.S_H
+    k, _ = orc.extractor(synth.mono_image(2, w, h, n_rect=ish.N_RECT), n_features=300, n_levels=4).extract()
+    assert np.bincount(k["octave"], minlength=4).tolist() == [97, 81, 68, 54]
+    rng = np.random.default_rng(17)
+    grid = np.stack([rng.uniform(0, w, 2000), rng.uniform(0, h, 2000)], 1).astype(np.float32)
+    cam = ish.cameras(w, h)[name]
+    K, D = ish.cam_arrays(cam)
+    for xy in (np.stack([k["x"], k["y"]], 1), grid):
+        und, n_exit = ish.undistort_numpy(xy, cam)
+        assert np.array_equal(orc.undistort_points(xy, K, D).view(np.int32), und.view(np.int32))
+        print(f"{name}: {n_exit} of {len(xy)} points leave through icdist < 0")
+        if name.startswith("k1_-"):
+            assert 10 <= n_exit < len(xy)                            # both ways out of the loop are taken
+            inside = np.hypot((xy[:, 0] - cam["cx"]) / cam["fx"], (xy[:, 1] - cam["cy"]) / cam["fy"]) < 0.2
+            assert inside.any() and not np.array_equal(und[inside], xy[inside])      # .. and near the centre the points do move
+        else:
+            assert n_exit == 0
+        if name == "k1_zero":
+            assert np.array_equal(und.view(np.int32), xy.view(np.int32))             # Camera.cc:31: k1 alone decides
+
+
+def test_binding_passes_row_strided_views_through_without_a_copy():
+    """Context.extract_color / frame_rgbd / frame_rgbd_image hand a view's own row stride to the library when only its rows are apart
+    (a column range of a larger image, padded rows); anything else is made contiguous first."""
+    import input_shapes as ish
+    from orb_slam2_ros2_amd._lib import _row_strided
+    img = ish.color_image(2, 37, 9)
+    v = ish.padded_rows(img, 5)
+    out = _row_strided(v, (np.uint8,))
+    assert out is v and out.strides == (3 * 37 + 5, 3, 1) and np.array_equal(out, img)
+    assert _row_strided(img, (np.uint8,)) is img
+    for dt in (np.uint16, np.float32):
+        big = np.arange(9 * 45, dtype=dt).reshape(9, 45)
+        roi = big[:, 3:40]
+        out = _row_strided(roi, (np.uint16, np.float32))
+        assert out is roi and out.strides[0] == 45 * big.itemsize and out.ctypes.data == big.ctypes.data + 3 * big.itemsize
+    for bad in (img[:, ::2], img[::-1], img[..., ::-1], np.asfortranarray(img), big[:, ::2], big.T):
+        dts = (np.uint8,) if bad.dtype == np.uint8 else (np.uint16, np.float32)
+        out = _row_strided(bad, dts)
+        assert out is not bad and out.flags.c_contiguous and np.array_equal(out, bad) and out.dtype == bad.dtype
+    assert _row_strided(img.astype(np.int32), (np.uint8,)).dtype == np.uint8      # (as np.ascontiguousarray(img, np.uint8) did)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("order,variant", [(1, 0), (2, 0), (1, 1), (2, 1)])
 def test_device_color_frame_matches_oracle(orc, order, variant):
@@ -178,4 +227,30 @@ def test_device_glue_error_paths():
         ctx.frame_rgbd(0, TUM, np.zeros((480, 640), np.uint16), depth_scale=0.0)
     ku, dd, ru = ctx.frame_rgbd(0, TUM, np.zeros((480, 640), np.uint16), depth_scale=5000.0)
     assert (dd == -1).all() and (ru == -1).all()                    # no keypoints: every entry is "no depth"
+    # a depth stride that is no multiple of the element size (the kernel casts the row pointer): refused by both entry points, for both
+    # element types; the next multiple is accepted
+    gray = np.zeros((480, 640), np.uint8)
+    for dt in (np.uint16, np.float32):
+        sz = np.dtype(dt).itemsize
+        for extra in range(1, sz + 1):
+            stride, ok = 640 * sz + extra, extra == sz
+            raw = np.zeros(stride * 480, np.uint8)
+            view = np.ndarray((480, 640), dt, raw, 0, (stride, sz))
+            for call in (lambda: ctx.frame_rgbd(0, TUM, view, 5000.0), lambda: ctx.frame_rgbd_image(gray, TUM, view, 5000.0)):
+                if ok:
+                    call()
+                else:
+                    with pytest.raises(OrbfeError) as ei:
+                        call()
+                    assert ei.value.status == 1
+    # a colour stride below 3 * width (the binding would make such a view contiguous: straight to the C entry points)
+    from orb_slam2_ros2_amd._lib import Camera, KP_DTYPE, ptr
+    import ctypes as C
+    kps, desc, n = np.zeros(500, KP_DTYPE), np.zeros((500, 32), np.uint8), C.c_int32(0)
+    d, ru = np.zeros(500), np.zeros(500)
+    cm = Camera(*[float(TUM[k]) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf")])
+    for stride, want in ((3 * 640 - 1, 1), (640, 1), (3 * 640, 0)):
+        assert ctx.lib.orbfe_extract_color(ctx.h, ptr(img), stride, 1, ptr(kps), ptr(desc), C.byref(n)) == want
+        assert ctx.lib.orbfe_frame_rgbd_image(ctx.h, 0, ptr(img), stride, 2, C.byref(cm), None, 0, 0, 1.0, ptr(kps), ptr(desc), C.byref(n),
+                                              ptr(d), ptr(ru)) == want
     ctx.close()
