@@ -810,7 +810,7 @@ orbfe_status orbfe_sim3_optimize(orbfe_ctx* ctx, int32_t n, const float* pc /*[n
  *   stats          NULL or [2]: iterations run, trials run.
  * One upload, a host-driven loop of a few scalars per trial, one download.  The system of the nf non-fixed vertices is dense, 6 nf
  * square in double: nf <= ORBFE_PG_MAX_FREE (288 nf^2 bytes: 302 MB at the bound, what the panel solver of the local bundle adjustment
- * factorises in place).
+ * factorises in place).  ORBFE_PG_MAX_FREE is this dense solver's bound; orbfe_pose_graph_optimize_ex below has a sparse solver without one.
  * ORBFE_OK with nothing launched and the estimates copied through (chi2_out is not written): n_edges == 0, iterations == 0, every
  * vertex fixed.  Errors, with nothing written: ORBFE_EBADARG (a NULL context, graph or estimates_out; a negative count or iterations
  * < 0; a NULL array with a non-zero count; an edge index out of range; edge_v0[e] == edge_v1[e]; an entry that is not finite; an s
@@ -827,6 +827,31 @@ typedef struct orbfe_pose_graph {
 orbfe_status orbfe_pose_graph_optimize(orbfe_ctx* ctx, const orbfe_pose_graph* graph, int32_t iterations,
                                        double* estimates_out /*[n_vertices][8]*/, double* chi2_out /*[n_edges], nullable*/,
                                        int32_t* stats /*[2] iterations run, trials run; nullable*/);
+/* The same optimisation with a choice of linear solver; ORBFE_PG_MAX_FREE is the DENSE solver's bound only.
+ *   solver 1  orbfe_pose_graph_optimize, byte for byte (and its ORBFE_EBADSIZE past ORBFE_PG_MAX_FREE non-fixed vertices).
+ *   solver 2  a block-sparse Cholesky over the graph's own structure: the non-fixed vertices in vertex order, no
+ *             reordering -- keyframe ids are nearly a time order, so spanning tree and covisibility links make a band and a loop
+ *             connection one long row.  A host symbolic phase (elimination tree, the factor's columns) per call, then per trial one
+ *             assembly into the factor's storage and ONE single-workgroup kernel that factorises and substitutes.  No bound on the
+ *             vertices but memory (288 bytes per block of the factor; ORBFE_ENOMEM).  Same Levenberg-Marquardt loop and kernels otherwise;
+ *             the estimates agree with solver 1 to the factorisations' rounding (3e-15 after one iteration at 257 vertices), not bit for
+ *             bit.  Every sum has a fixed order: a repeated call is bit-identical.
+ *   solver 0  (and opt == NULL) sparse past ORBFE_PG_MAX_FREE non-fixed vertices; below it from ORBFE_PG_SPARSE_MIN_FREE on, unless the
+ *             factor is dense-ish: more than ORBFE_PG_SPARSE_MAX_COL_BLOCKS blocks per column on average (l_blocks > that x nf); dense
+ *             otherwise.  Both numbers are measured crossovers: 24 non-fixed vertices is the smallest measured size at
+ *             which the sparse solver wins; a factor of 20 blocks a column is the densest measured at which it wins at 100, 500 and
+ *             1000 keyframes alike (an essential graph has 7 to 9).
+ *   stats     NULL or [4]: iterations run, trials run, the solver used (1 or 2; the value asked for where nothing was launched), the
+ *             blocks of the factor with the diagonal ones (0 for solver 1).
+ * Everything else -- arguments, early returns, errors -- as orbfe_pose_graph_optimize; a solver outside 0 .. 2 is ORBFE_EBADARG.        */
+#define ORBFE_PG_SPARSE_MIN_FREE 24
+#define ORBFE_PG_SPARSE_MAX_COL_BLOCKS 20
+typedef struct orbfe_pose_graph_options {
+  int32_t solver;            /* 0 auto, 1 dense (orbfe_pose_graph_optimize), 2 block-sparse Cholesky */
+} orbfe_pose_graph_options;
+orbfe_status orbfe_pose_graph_optimize_ex(orbfe_ctx* ctx, const orbfe_pose_graph* graph, int32_t iterations,
+                                          const orbfe_pose_graph_options* opt /*nullable*/, double* estimates_out /*[n_vertices][8]*/,
+                                          double* chi2_out /*[n_edges], nullable*/, int32_t* stats /*[4], nullable*/);
 
 /* ---- new map points of a keyframe (LocalMapping::createNewMapPoints, src/LocalMapping.cc:165-285) ---------------------------------
  * One call runs loop 1 and loop 2 of createNewMapPoints for the current keyframe `cur` against the neighbours nbs[0 .. n_nb) IN THE
@@ -1143,6 +1168,15 @@ orbfe_status orbfe_debug_pose_graph_edges(orbfe_ctx* ctx, const orbfe_pose_graph
  * (launch_lba_chol), ms[3] evaluate (update, chi2, the sums and the scalars' download).  Only calls made with ORBFE_PG_PHASES set in the
  * environment are measured (and slowed down by the synchronisations); all zero otherwise.  For tools/essential_graph_bench.py.          */
 orbfe_status orbfe_debug_pose_graph_phases(double* ms /*[4]*/);
+/* One block-sparse symmetric positive definite system through the symbolic phase and the factor-and-solve kernel of
+ * orbfe_pose_graph_optimize_ex's solver 2, in the layout the optimiser gives them.  nb block rows of 6; the n_low given blocks are (low_row[q],
+ * low_col[q]), low_row >= low_col, each at most once, 36 doubles row-major each (of a diagonal block only the lower triangle is read); every
+ * other block is zero.  x [6 nb]; *ok = 0 and x = 0 where a pivot is not positive and finite (the status is still ORBFE_OK); *l_blocks
+ * (nullable) = the blocks of the factor.  ORBFE_EBADARG: a NULL argument, nb < 1, a block above the diagonal, out of range or given
+ * twice.                                                                                                                              */
+orbfe_status orbfe_debug_pg_sparse_solve(orbfe_ctx* ctx, int32_t nb, int32_t n_low, const int32_t* low_row, const int32_t* low_col,
+                                         const double* blocks /*[n_low][36]*/, const double* rhs /*[6 nb]*/, double* x /*[6 nb]*/,
+                                         int32_t* ok, int64_t* l_blocks /*nullable*/);
 
 /* The reduced camera system of orbfe_ba_global_optimize's solver 2 at ONE linearisation, the given estimates and lambda, as block-CSR
  * over the non-fixed keyframes in index order: *nnzb stored 6x6 blocks, row_off[nf + 1], col[nnzb] (ascending in a row, both triangles,

@@ -58,6 +58,10 @@ class PoseGraph(C.Structure):
                 ("edge_v0", C.c_void_p), ("edge_v1", C.c_void_p), ("meas", C.c_void_p)]
 
 
+class PoseGraphOptions(C.Structure):
+    _fields_ = [("solver", C.c_int32)]
+
+
 class BaSystemOut(C.Structure):
     _fields_ = [("Hpp", C.c_void_p), ("bp", C.c_void_p), ("Hll", C.c_void_p), ("bl", C.c_void_p), ("Hpl", C.c_void_p)]
 
@@ -206,16 +210,17 @@ EXPORTS = [
     "orbfe_kfdb_score", "orbfe_kfdb_group_filter",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_iterate", "orbfe_pnp_engine", "orbfe_pnp_stats",
     "orbfe_sim3_create", "orbfe_sim3_destroy", "orbfe_sim3_iterate", "orbfe_sim3_engine", "orbfe_sim3_stats", "orbfe_sim3_profile",
-    "orbfe_sim3_optimize", "orbfe_pose_graph_optimize",
+    "orbfe_sim3_optimize", "orbfe_pose_graph_optimize", "orbfe_pose_graph_optimize_ex",
     "orbfe_create_new_map_points", "orbfe_fuse_into_keyframes",
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
-    "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
+    "orbfe_debug_pg_sparse_solve", "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
 ]
 BOW_MAX_FEATURES = 65535
+PG_MAX_FREE = 1024          # ORBFE_PG_MAX_FREE: the dense pose-graph solver's bound on the non-fixed vertices
 GBA_DENSE_MAX_FREE = 1000   # ORBFE_GBA_DENSE_MAX_FREE: solver 0 of ba_global_optimize is dense up to this many non-fixed keyframes
 
 _lib = None
@@ -366,6 +371,8 @@ def load() -> C.CDLL:
     L.orbfe_sim3_optimize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
     L.orbfe_debug_sim3_edges.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp] + [C.c_float] * 4 + [vp, vp, vp, vp]
     L.orbfe_pose_graph_optimize.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.orbfe_pose_graph_optimize_ex.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.orbfe_debug_pg_sparse_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_debug_pose_graph_edges.argtypes = [vp, vp, vp, vp, vp]
     L.orbfe_debug_pose_graph_phases.argtypes = [vp]
     _lib = L
@@ -1541,16 +1548,34 @@ class Context:
         g = PoseGraph(est.shape[0], edges.shape[0], ptr(est), ptr(fixed), ptr(v0), ptr(v1), ptr(meas))
         return g, (est, fixed, v0, v1, meas)  # (the arrays must outlive the call)
 
-    def pose_graph_optimize(self, estimates, fixed, edges, meas, iterations=20):
+    def pose_graph_optimize(self, estimates, fixed, edges, meas, iterations=20, solver=None):
         """Optimizer::optimizeEssentialGraph from the point where the graph is built (orbfe_pose_graph_optimize): estimates (nv, 8) =
         qx qy qz qw tx ty tz s with s == 1, fixed (nv,), edges (ne, 2) = (vertex 0, vertex 1), meas (ne, 8)
-        -> (estimates (nv, 8), chi2 (ne,) at them, (iterations run, trials run))."""
+        -> (estimates (nv, 8), chi2 (ne,) at them, (iterations run, trials run)).
+        solver 0 (auto), 1 (dense) or 2 (block-sparse Cholesky) goes through orbfe_pose_graph_optimize_ex and the third value becomes
+        (iterations run, trials run, solver used, blocks of the factor)."""
         g, keep = self._pose_graph(estimates, fixed, edges, meas)
         out = keep[0].copy()
         chi2 = np.zeros(max(g.n_edges, 1))
+        if solver is not None:
+            stats = np.zeros(4, np.int32)
+            opt = PoseGraphOptions(int(solver))
+            self._check(self.lib.orbfe_pose_graph_optimize_ex(self.h, C.byref(g), int(iterations), C.byref(opt), ptr(out), ptr(chi2), ptr(stats)))
+            return out, chi2[:g.n_edges], tuple(int(v) for v in stats)
         stats = np.zeros(2, np.int32)
         self._check(self.lib.orbfe_pose_graph_optimize(self.h, C.byref(g), int(iterations), ptr(out), ptr(chi2), ptr(stats)))
         return out, chi2[:g.n_edges], (int(stats[0]), int(stats[1]))
+
+    def debug_pg_sparse_solve(self, nb, low_row, low_col, blocks, rhs):
+        """one block-sparse SPD system (its lower 6x6 blocks, row-major) through the symbolic phase and the factor-and-solve kernel of
+        pose_graph_optimize's solver 2 -> (x (6 nb,), ok, blocks of the factor)"""
+        low_row, low_col = np.ascontiguousarray(low_row, np.int32), np.ascontiguousarray(low_col, np.int32)
+        blocks, rhs = np.ascontiguousarray(blocks, np.float64).reshape(-1, 36), np.ascontiguousarray(rhs, np.float64)
+        assert rhs.size == 6 * nb and blocks.shape[0] == low_row.size == low_col.size
+        x, ok, lb = np.zeros(6 * nb), C.c_int32(-1), C.c_int64(0)
+        self._check(self.lib.orbfe_debug_pg_sparse_solve(self.h, int(nb), low_row.size, ptr(low_row), ptr(low_col), ptr(blocks), ptr(rhs), ptr(x),
+                                                         C.byref(ok), C.byref(lb)))
+        return x, ok.value, lb.value
 
     def debug_pose_graph_phases(self):
         """(build, assemble, solve, evaluate) milliseconds of the last pose_graph_optimize made with ORBFE_PG_PHASES set"""

@@ -163,6 +163,11 @@ void launch_pg_update(hipStream_t s, int n_vertices, const int32_t* slot, const 
 void launch_pg_chi2(hipStream_t s, int n_edges, const double* est, const int32_t* ev0, const int32_t* ev1, const double* meas, double* chi2);
 void launch_pg_reduce(hipStream_t s, int n_edges, const double* chi2, int n, const double* x, const double* rhs, const double* lambda_p,
                       double* out);
+// k_pgsparse.hip
+void launch_pgs_assemble(hipStream_t s, int n_blocks, const int2* blk, const int32_t* blk_off, const int32_t* ent, const int32_t* pos,
+                         const double* Hee, const double* be, const double* lambda_p, double* Lv, double* rhs);
+void launch_pgs_solve(hipStream_t s, int nb, const int32_t* col_off, const int32_t* row, int search_steps, double* Lv, const double* rhs,
+                      double* x, int* ok);
 void launch_track_queries(hipStream_t s, int n, const uint8_t* d_flags, const uint8_t* d_visible, const float* d_cos, const int8_t* d_level, float th,
                           const float* d_sigma2, int n_levels, float* d_radius, int8_t* d_min_level, int8_t* d_max_level);
 void launch_track_claim(hipStream_t s, int n, const int32_t* d_n_cand, const int32_t* d_best_idx, const int32_t* d_best_dist, const int32_t* d_second,

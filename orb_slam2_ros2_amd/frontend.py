@@ -372,10 +372,11 @@ class Optimizer:
         return ctx.sim3_optimize(pc, pm, uv_c, uv_m, info_c, info_m, cam, model)
 
     @staticmethod
-    def optimizeEssentialGraph(ctx: Context, estimates, fixed, edges, meas, iterations=20):
+    def optimizeEssentialGraph(ctx: Context, estimates, fixed, edges, meas, iterations=20, solver=None):
         """Optimizer::optimizeEssentialGraph (Optimizer.cc:746-920) from the point where the graph is built, scale fixed: returns
-        (estimates (nv, 8) in double, chi2 of every edge at them, (iterations, trials)); see Context.pose_graph_optimize."""
-        return ctx.pose_graph_optimize(estimates, fixed, edges, meas, iterations)
+        (estimates (nv, 8) in double, chi2 of every edge at them, (iterations, trials)); solver 0 / 1 / 2 (auto, dense, block-sparse
+        Cholesky: no bound on the keyframes) adds (solver used, blocks of the factor) to the last; see Context.pose_graph_optimize."""
+        return ctx.pose_graph_optimize(estimates, fixed, edges, meas, iterations, solver)
 
     @staticmethod
     def OptimizeLocalMap(ctx: Context, problem, pose_fixed=None, iters_first=5, iters_second=10):

@@ -212,7 +212,8 @@ void optimizeEssentialGraph(const LoopConnectionT& mLoopConnections, MapPtr mpMa
   if (G.vertexOfId.empty() || G.vertexOfId[0] < 0)
     throw std::runtime_error("optimizeEssentialGraph: no good keyframe of id 0 (the reference normalises by vertex 0)");
   std::vector<double> estimates = G.estimates;
-  orbfe::Optimizer::optimizeEssentialGraph(solverContext(2), estimates, G.fixed, G.v0, G.v1, G.meas, 20);
+  // solver 0: dense on a small map, the block-sparse Cholesky otherwise -- no bound on the keyframes (orbfe_pose_graph_optimize_ex)
+  orbfe::Optimizer::optimizeEssentialGraph(solverContext(2), estimates, G.fixed, G.v0, G.v1, G.meas, 20, nullptr, 0);
   applyEssentialGraph<Sim3RetT>(G, estimates, mpMap, pCurrKf);
 }
 

@@ -924,17 +924,26 @@ class Optimizer {
   // Optimizer::optimizeEssentialGraph (src/Optimizer.cc:746-920) from the point where the graph is built, scale fixed: estimates
   // ([nv][8] = qx qy qz qw tx ty tz s, s == 1) in / out, fixed [nv], edge e from vertex v0[e] to vertex v1[e] with the measurement
   // meas[e] ([8]).  Returns (iterations run, trials run); chi2 (nullable) gets err . err of every edge at the final estimates.
+  // solver < 0: orbfe_pose_graph_optimize (dense, at most ORBFE_PG_MAX_FREE non-fixed vertices); 0 auto, 1 dense, 2 block-sparse Cholesky:
+  // orbfe_pose_graph_optimize_ex, solverStats (nullable) = (solver used, blocks of the factor).
   static std::pair<int, int> optimizeEssentialGraph(orbfe_ctx* ctx, std::vector<double>& estimates, const std::vector<uint8_t>& fixed,
                                                     const std::vector<int32_t>& v0, const std::vector<int32_t>& v1,
-                                                    const std::vector<double>& meas, int iterations = 20, std::vector<double>* chi2 = nullptr) {
+                                                    const std::vector<double>& meas, int iterations = 20, std::vector<double>* chi2 = nullptr,
+                                                    int solver = -1, std::pair<int, int>* solverStats = nullptr) {
     const size_t nv = fixed.size(), ne = v0.size();
     if (estimates.size() != 8 * nv || v1.size() != ne || meas.size() != 8 * ne)
       throw std::invalid_argument("optimizeEssentialGraph: the graph's arrays disagree in length");
     const orbfe_pose_graph g = {(int32_t)nv, (int32_t)ne, estimates.data(), fixed.data(), v0.data(), v1.data(), meas.data()};
     std::vector<double> out(std::max<size_t>(8 * nv, 1));
     if (chi2) chi2->assign(std::max<size_t>(ne, 1), 0.0);
-    int32_t stats[2] = {0, 0};
-    check(ctx, orbfe_pose_graph_optimize(ctx, &g, iterations, out.data(), chi2 ? chi2->data() : nullptr, stats));
+    int32_t stats[4] = {0, 0, 1, 0};
+    if (solver < 0) {
+      check(ctx, orbfe_pose_graph_optimize(ctx, &g, iterations, out.data(), chi2 ? chi2->data() : nullptr, stats));
+    } else {
+      const orbfe_pose_graph_options opt = {solver};
+      check(ctx, orbfe_pose_graph_optimize_ex(ctx, &g, iterations, &opt, out.data(), chi2 ? chi2->data() : nullptr, stats));
+    }
+    if (solverStats) *solverStats = {stats[2], stats[3]};
     out.resize(8 * nv);
     estimates.swap(out);
     if (chi2) chi2->resize(ne);
