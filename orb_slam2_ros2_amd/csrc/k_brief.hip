@@ -351,12 +351,14 @@ __global__ __launch_bounds__(256) void k_list_moments_orient(const LevelDev* __r
 
 // ---------------------------------------------------------------------------------------------
 // 3. rotated BRIEF, one wave per keypoint.  The 37x37 window of the BLURRED plane that the rotated template
-//    can reach (|offset| <= 18) is staged in LDS with coalesced word loads; the 512 data-dependent byte reads
-//    then hit LDS instead of issuing 8 global gathers with ~64 distinct cache lines each.
+//    can reach (|offset| <= 18) is staged in LDS by LDS-DMA (global_load_lds_dwordx4: no register, no ds_write on the
+//    way); the 512 data-dependent byte reads then hit LDS instead of issuing 8 global gathers with ~64 distinct cache
+//    lines each.
 // ---------------------------------------------------------------------------------------------
 #define BRIEF_R 18
 #define BRIEF_ROWS (2 * BRIEF_R + 1)
-#define BRIEF_WORDS 11  // (3 + 37 + 3) / 4 rounded up
+#define BRIEF_PITCH 48        // bytes of a window row in LDS: (3 + 37 + 3) rounded up to whole 16-byte units of the LDS-DMA
+#define BRIEF_WIN_BYTES 2048  // one window buffer: two wave-instructions of 64 lanes x 16 bytes (37 rows x 48 bytes = 111 units are the window)
 
 #ifndef BRIEF_WAVES
 #define BRIEF_WAVES 4
@@ -396,13 +398,18 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
   // read; 8-byte entries read by ds_read_b64 put 32 to a sweep -- the coordinates -13 ... 13 of the standard template never collide
   // (equal addresses broadcast).  The window lies BETWEEN the two arrays so that no ds_read2_b64 can reach from one to the other:
   // that instruction takes twice the cycles of two single reads and banks 16 entries to the sweep again.
+  // (r7) TWO window buffers per wave, filled by LDS-DMA: keypoint k + 1 lands in one while k is tested from the other.  One
+  // wave-instruction of the DMA writes base + lane * 16, so a buffer is two of them (2048 bytes): units 0 .. 110 are the window
+  // (37 unpadded rows of 48 bytes, unit = 3 row + part), the lanes of units 111 .. 127 fetch unit 110 again into the buffer's tail.
   struct __attribute__((aligned(16))) Lds {
     double rc[BRIEF_WAVES][40];
-    uint32_t win[BRIEF_WAVES][BRIEF_ROWS * BRIEF_WORDS + 1];
+    uint8_t win[BRIEF_WAVES][2][BRIEF_WIN_BYTES];
     double rs[BRIEF_WAVES][40];
   };
-  static_assert(sizeof(double) * 40 * BRIEF_WAVES + sizeof(uint32_t) * (BRIEF_ROWS * BRIEF_WORDS + 1) * BRIEF_WAVES > 255 * 8 &&
-                    (sizeof(double) * 40 * BRIEF_WAVES + sizeof(uint32_t) * (BRIEF_ROWS * BRIEF_WORDS + 1) * BRIEF_WAVES) % 512 != 0,
+  static_assert(BRIEF_ROWS * BRIEF_PITCH <= BRIEF_WIN_BYTES && BRIEF_WIN_BYTES == 2 * 64 * 16 && BRIEF_PITCH % 16 == 0, "a window is two 16-byte LDS-DMA instructions");
+  static_assert((sizeof(double) * 40 * BRIEF_WAVES) % 16 == 0, "the LDS-DMA destination is 16-byte aligned");
+  static_assert(sizeof(double) * 40 * BRIEF_WAVES + 2 * BRIEF_WIN_BYTES * BRIEF_WAVES > 255 * 8 &&
+                    (sizeof(double) * 40 * BRIEF_WAVES + 2 * BRIEF_WIN_BYTES * BRIEF_WAVES) % 512 != 0,
                 "rc[w] and rs[w] must not be reachable by one ds_read2(st64)_b64");
   __shared__ Lds lds;
   BS_DECL
@@ -436,9 +443,9 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
     return;
   }
   const int lane = threadIdx.x & 63;
-  uint32_t* win = lds.win[threadIdx.x >> 6];
-  double* rc = lds.rc[threadIdx.x >> 6];
-  double* rs = lds.rs[threadIdx.x >> 6];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // in a scalar register: what follows from it stays on the scalar unit
+  double* rc = lds.rc[wave];
+  double* rs = lds.rs[wave];
   // XCD-aware block order: workgroups go round-robin to the 8 XCDs (own L2 each) and consecutive keypoints are spatial neighbours
   // (candidate order) whose 37x37 windows overlap; block b of the grid takes keypoint block (b % 8) * (grid / 8) + b / 8, so one XCD
   // works through one contiguous eighth of the list (gridDim.x is a multiple of 8).  Fetched bytes 2.69 -> 0.85 GB per 1024 images.
@@ -448,64 +455,62 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
   //  whatever they asked for first (stamps build, tools/exp/brief_stamps.sh) -- and the launch took 18 - 31 us.)
   const int per_xcd = rt.n_brief_blocks >> 3;
   const int kb = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-  const int k0 = (kb * BRIEF_WAVES + (threadIdx.x >> 6)) * BRIEF_KPW;
+  const int k0 = (kb * BRIEF_WAVES + wave) * BRIEF_KPW;
   const int img = blockIdx.y;
   if (k0 >= n_features) return;
   // A wave with one keypoint spent two thirds of its life parked at s_waitcnt: list entry -> window -> tests are dependent round
   // trips, and eight waves per SIMD do not cover them.  A wave now works through BRIEF_KPW consecutive keypoints as a three-stage
-  // pipeline: while keypoint i is tested, the window and sin / cos of keypoint i + 1 are in flight (parked in registers) and so is
-  // the list entry of keypoint i + 2; the lane's template pairs are fetched once.
+  // pipeline: while keypoint i is tested, the window of keypoint i + 1 is in flight (LDS-DMA into the wave's other buffer), its sin / cos
+  // are on their way to scalar registers and so is the list entry of keypoint i + 2; the lane's template pairs are fetched once.
+  // (r7) A wave works on ONE keypoint at a time, so k, the list entry and the sin / cos pair are wave-uniform: k is built from scalar
+  // values only and the records come through the scalar cache (s_load_dwordx4; both arrays are written by earlier kernels of the stream,
+  // never by this one), not as 64 lanes loading one address into 16 vector registers a stage.  They count on lgkmcnt: vmcnt carries the
+  // window DMA (and the descriptor stores) alone.
   const uint4* list = kpl + (size_t)img * n_features;
   const double2* sc = sincos + (size_t)img * n_features;
   const uint8_t* W = blur + (size_t)img * img_pitch;  // wave-uniform base; the rest of the address is a 32-bit offset
   const int k_last = min(k0 + BRIEF_KPW, n_features) - 1;
-  const uint32_t tp0 = *(const uint32_t*)(pattern + (0 * 64 + lane) * 4), tp1 = *(const uint32_t*)(pattern + (1 * 64 + lane) * 4);
-  const uint32_t tp2 = *(const uint32_t*)(pattern + (2 * 64 + lane) * 4), tp3 = *(const uint32_t*)(pattern + (3 * 64 + lane) * 4);
+  uint32_t tp0 = *(const uint32_t*)(pattern + (0 * 64 + lane) * 4), tp1 = *(const uint32_t*)(pattern + (1 * 64 + lane) * 4);
+  uint32_t tp2 = *(const uint32_t*)(pattern + (2 * 64 + lane) * 4), tp3 = *(const uint32_t*)(pattern + (3 * 64 + lane) * 4);
 #ifdef BRIEF_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" :: "v"(tp0), "v"(tp1), "v"(tp2), "v"(tp3) : "memory");
   bs_t1 = __builtin_amdgcn_s_memrealtime();  // (pattern arrived; the "first window parked" stamp is not taken in this build)
 #endif
-  // window load: 5 rows x 11 words per pass over lanes 0..54 (lane = 11 r0 + c0), 8 passes; a pass adds a wave-uniform 5 * stride to
-  // one address and parks its words at lane + 55 * pass -- one v_add per load where the flat index -> (row, word) split cost five
-  constexpr int NIT = (BRIEF_ROWS + 4) / 5;
-  const int ll = min(lane, 54);
-  const int r0 = (ll * 373) >> 12, c0 = ll - r0 * BRIEF_WORDS;  // ll / 11 for ll < 64
-  const int r_last = min(r0 + 5 * (NIT - 1), BRIEF_ROWS - 1);    // last pass: rows 35, 36 exist, the lanes of rows 37..39 re-read row 36
-  // (r6: the eight window words as two VECTORS, named component by component.  As an array `uint32_t wv[NIT]` the stage records that
-  //  rotate through the keypoint loop were private arrays the compiler moved to LDS, 32 bytes per thread addressed by the FLAT thread
-  //  number -- for which it reads the workgroup's y and z sizes from the dispatch packet, and that packet lives in the queue's ring
-  //  buffer in HOST memory: every wave of every launch of this kernel began with a scalar load across PCIe that no cache holds.  A pair's
-  //  2000 waves queued for theirs: first data after 13.6 us on average, 26.5 at worst, whatever they had asked for (stamps build,
-  //  tools/exp/brief_stamps.sh), a launch of 18 - 31 us.  No kernel of this library may touch blockDim / gridDim or keep a private array.)
-  static_assert(NIT == 8, "Stage holds eight window words");
-  struct Stage {
-    uint4 wa, wb;
-    double2 scv;
-  };
-  // requests the window and sin / cos of the keypoint in entry e (an unused slot -- x = 0xFFFF -- reads row 0 of plane 0: harmless)
-  auto request = [&](const uint4 e, int k, Stage& st) __attribute__((always_inline)) {
+  // window load: two LDS-DMA instructions of 16 bytes a lane.  The destination of one is buffer + lane * 16 whatever the lane asks for,
+  // so unit u = lane (+ 64) IS row u / 3, bytes 16 (u % 3) ... + 15 of the 48-byte row; the source stays per lane:
+  // plane + (y - 18 + row) stride + xa + 16 part, a multiple of 4 as before (xa, the strides and the plane offsets are).
+  // A 48-byte row ends at most at column x - 18 + 47 = x + 29 <= w + 9 (keypoints keep 19 pixels from the border: x <= w - 20), and
+  // the window's last row is y + 18 <= h - 2: the spill-over stays inside the next row of the SAME plane (w + 9 < 2 stride), it never
+  // leaves the plane, let alone the image's block.  (The 44-byte rows before reached w + 5 the same way.)
+  const int u1 = min(lane + 64, BRIEF_ROWS * (BRIEF_PITCH / 16) - 1);  // units 111 .. 127: unit 110 again, into the buffer's tail
+  const uint32_t row_a = (uint32_t)lane / 3u, row_b = (uint32_t)u1 / 3u;
+  const uint32_t col_a = 16u * ((uint32_t)lane - 3u * row_a), col_b = 16u * ((uint32_t)u1 - 3u * row_b);
+  typedef __attribute__((address_space(3))) uint8_t* lds_dst_t;
+  typedef const __attribute__((address_space(1))) uint8_t* glb_src_t;
+  // requests the window of the keypoint in entry e into buffer b (an unused slot -- x = 0xFFFF -- reads row 0 of plane 0: harmless)
+  auto request = [&](const uint4 e, int b) __attribute__((always_inline)) {
     const bool used = (e.x & 0xFFFFu) != 0xFFFFu;
     const int x = used ? (int)(e.x & 0xFFFFu) : BRIEF_R, y = used ? (int)(e.x >> 16) : BRIEF_R;
     const uint32_t plane = used ? e.z : 0u;
-    const int stride = used ? (int)e.w : 0;
-    const int xa = (x - BRIEF_R) & ~3;
-    const uint32_t step = 5u * (uint32_t)__builtin_amdgcn_readfirstlane(stride);
-    const uint32_t a0 = plane + (uint32_t)mad24u(y - BRIEF_R + r0, stride, xa + 4 * c0);
-#define BRIEF_WLD(it) (*(const uint32_t*)(W + (a0 + (uint32_t)(it) * step)))
-    st.wa.x = BRIEF_WLD(0), st.wa.y = BRIEF_WLD(1), st.wa.z = BRIEF_WLD(2), st.wa.w = BRIEF_WLD(3);
-    st.wb.x = BRIEF_WLD(4), st.wb.y = BRIEF_WLD(5), st.wb.z = BRIEF_WLD(6);
-#undef BRIEF_WLD
-    st.wb.w = *(const uint32_t*)(W + (plane + (uint32_t)mad24u(y - BRIEF_R + r_last, stride, xa + 4 * c0)));
-    st.scv = sc[k];
+    const uint32_t stride = used ? e.w : 0u;
+    const uint32_t xa = (uint32_t)(x - BRIEF_R) & ~3u;
+    const uint32_t s0 = plane + (uint32_t)(y - BRIEF_R) * stride + xa;  // (scalar unit)
+    uint8_t* dst = lds.win[wave][b];
+    __builtin_amdgcn_global_load_lds((glb_src_t)(W + (s0 + col_a + __umul24(row_a, stride))), (lds_dst_t)dst, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_src_t)(W + (s0 + col_b + __umul24(row_b, stride))), (lds_dst_t)(dst + 1024), 16, 0, 0);
   };
   uint4 e_cur = list[k0];
   uint4 e_nxt = list[min(k0 + 1, k_last)];
+  double2 sc_cur = sc[k0];
 #ifdef BRIEF_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   bs_ta = __builtin_amdgcn_s_memrealtime();
 #endif
-  Stage st_cur;
-  request(e_cur, k0, st_cur);
+  // The template words must have ARRIVED before the first DMA is issued: the compiler waits for an ordinary load's result with
+  // vmcnt(0) once an LDS-DMA is behind it on the counter, and where that wait falls in front of the tests it drains the window of the
+  // next keypoint too.  (They were requested first and come from L2 like the list entry the DMA needs anyway.)
+  asm volatile("" : "+v"(tp0), "+v"(tp1), "+v"(tp2), "+v"(tp3));
+  request(e_cur, 0);
 #ifdef BRIEF_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   bs_tb = __builtin_amdgcn_s_memrealtime();
@@ -515,18 +520,25 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
     const int k = k0 + i;
     if (k > k_last) break;  // wave-uniform
     // stage 1 / 2 for the keypoints behind this one
-    const uint4 e_nn = list[min(k + 2, k_last)];
-    Stage st_nxt;
-    if (i + 1 < BRIEF_KPW) request(e_nxt, min(k + 1, k_last), st_nxt);
+    uint4 e_nn = e_nxt;
+    double2 sc_nxt = sc_cur;
+    if (i + 2 < BRIEF_KPW) e_nn = list[min(k + 2, k_last)];
+    // vmcnt retires in order: with the two DMA instructions of keypoint k + 1 behind them, "at most two outstanding" means those of k
+    // have landed (the descriptor store of k - 1 between them only makes the wait stricter).  The issuing wave's own counted wait is
+    // all that orders its ds_read behind its LDS-DMA; no wave ends with a DMA in flight (every request is waited for below).
+    if (i + 1 < BRIEF_KPW && k < k_last) {  // wave-uniform
+      request(e_nxt, (i + 1) & 1);
+      sc_nxt = sc[k + 1];
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_wave_barrier();
     if ((e_cur.x & 0xFFFFu) != 0xFFFFu) {  // wave-uniform
       const int x = (int)(e_cur.x & 0xFFFFu), y = (int)(e_cur.x >> 16);
       const int xa = (x - BRIEF_R) & ~3;
-      if (lane < 55) {
-        win[lane] = st_cur.wa.x, win[lane + 55] = st_cur.wa.y, win[lane + 110] = st_cur.wa.z, win[lane + 165] = st_cur.wa.w;
-        win[lane + 220] = st_cur.wb.x, win[lane + 275] = st_cur.wb.y, win[lane + 330] = st_cur.wb.z;
-        if (r0 + 5 * (NIT - 1) < BRIEF_ROWS) win[lane + 385] = st_cur.wb.w;
-      }
-      const double sn = st_cur.scv.x, cs = st_cur.scv.y;
+      const uint8_t* win = lds.win[wave][i & 1];
+      const double sn = sc_cur.x, cs = sc_cur.y;
       // The rotation needs x cos, x sin, y cos, y sin in fp64 for 512 template points, but the coordinates are small integers:
       // 37 lanes form the products once ((double)v * cs is exactly what the per-point expression computes), every point then
       // takes two LDS reads and one fp64 add per coordinate instead of two fp64 multiplies and a conversion.
@@ -535,8 +547,8 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
         rc[lane] = v * cs;
         rs[lane] = v * sn;
       }
-      // the LDS accesses of one wave execute in order, so the window and the table written above are visible to every lane of this
-      // wave; the fence only pins the compiler
+      // the LDS accesses of one wave execute in order, so the table written above is visible to every lane of this wave (the window
+      // landed before the counted wait above let the wave on); the fence only pins the compiler
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       BS_MID
@@ -547,12 +559,19 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
       // parity of the candidates is unchanged): the row constant carries minus the window's first row rounded down to even, the column
       // constant minus the window's first column (a multiple of 4) plus the LDS byte address of the wave's window, less one window row
       // where the first row is odd.  v_mad_u32_u24 then reads the row in the low 24 bits of its first operand (0x400000 + row) and adds
-      // the whole second float: 44 row + column + address + 0x56400000, whose low 16 bits are the address.  Exact for |sum| < 2^21;
-      // the float additions are neither contracted nor re-associated (fp contract off, no fast-math).
+      // the whole second float: pitch row + column + address + 0x4B400000 + pitch 0x400000, whose low 16 bits are the address (the
+      // pitch is a multiple of 4, so pitch 0x400000 has none).  Exact for |sum| < 2^21; the float additions are neither contracted
+      // nor re-associated (fp contract off, no fast-math).
+      // (r7) Both constants take the window pitch and the LDS address of the buffer this keypoint landed in.  Restated for pitch 48:
+      // the row constant folds in -(y0w & ~1), even; the row index it leaves is (Y - y0w) + (y0w & 1), one too many where the first
+      // row is odd, and the column constant takes that row back as one pitch.  The column constant folds in -xa (a multiple of 4),
+      // the buffer address (a multiple of 16) and 0 or -48: even in every case, so the ties of the column sum fall where they fell.
       typedef const __attribute__((address_space(3))) uint8_t* lds_bytes_t;
+      auto magic_row = [](int y0w) { return (float)(12582912 - (y0w & ~1)); };
+      auto magic_col = [](int xa, int y0w, int pitch, int lds_addr) { return (float)(12582912 - xa + lds_addr - (y0w & 1) * pitch); };
       const int y0w = y - BRIEF_R;
-      const float magic_y = (float)(12582912 - (y0w & ~1));
-      const float magic_x = (float)(12582912 - xa + (int)(uint32_t)(uintptr_t)(lds_bytes_t)(const uint8_t*)win - (y0w & 1) * (BRIEF_WORDS * 4));
+      const float magic_y = magic_row(y0w);
+      const float magic_x = magic_col(xa, y0w, BRIEF_PITCH, (int)(uint32_t)(uintptr_t)(lds_bytes_t)win);
       auto tests = [&](const uint32_t tpg) __attribute__((always_inline)) -> unsigned long long {
         const int x1 = (int)(int8_t)(tpg & 255u), y1 = (int)(int8_t)((tpg >> 8) & 255u);
         const int x2 = (int)(int8_t)((tpg >> 16) & 255u), y2 = (int)(int8_t)(tpg >> 24);
@@ -561,13 +580,16 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
         const float p1y = (float)(rs[x1 + BRIEF_R] + rc[y1 + BRIEF_R]);  // x1 sin + y1 cos
         const float p2x = (float)(rc[x2 + BRIEF_R] - rs[y2 + BRIEF_R]);
         const float p2y = (float)(rs[x2 + BRIEF_R] + rc[y2 + BRIEF_R]);
-        const uint32_t a1 = (uint32_t)mad24u(__float_as_int((py + p1y) + magic_y), BRIEF_WORDS * 4, __float_as_int((px + p1x) + magic_x)) & 0xFFFFu;
-        const uint32_t a2 = (uint32_t)mad24u(__float_as_int((py + p2y) + magic_y), BRIEF_WORDS * 4, __float_as_int((px + p2x) + magic_x)) & 0xFFFFu;
+        const uint32_t a1 = (uint32_t)mad24u(__float_as_int((py + p1y) + magic_y), BRIEF_PITCH, __float_as_int((px + p1x) + magic_x)) & 0xFFFFu;
+        const uint32_t a2 = (uint32_t)mad24u(__float_as_int((py + p2y) + magic_y), BRIEF_PITCH, __float_as_int((px + p2x) + magic_x)) & 0xFFFFu;
         const int v1 = *(lds_bytes_t)(uintptr_t)a1;
         const int v2 = *(lds_bytes_t)(uintptr_t)a2;
         return __ballot(v1 < v2);
       };
-      // (four named words, not an array: see Stage above)
+      // (four named words, not an array.  r6: a private array that rotates through the keypoint loop is moved to LDS by the compiler,
+      //  addressed by the FLAT thread number -- for which it reads the workgroup's y and z sizes from the dispatch packet, and that packet
+      //  lives in the queue's ring buffer in HOST memory: every wave of every launch began with a scalar load across PCIe that no cache
+      //  holds, a launch of 18 - 31 us.  No kernel of this library may touch blockDim / gridDim or keep a private array.)
       const unsigned long long bits0 = tests(tp0), bits1 = tests(tp1), bits2 = tests(tp2), bits3 = tests(tp3);
       if (lane < 4) {
         unsigned long long* d64 = (unsigned long long*)(desc + ((size_t)img * n_features + k) * 32);
@@ -578,14 +600,15 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
         d64[lane] = b;
         if (desc_host) ((unsigned long long*)(desc_host + ((size_t)img * n_features + k) * 32))[lane] = b;
       }
-      // every lane has read what it needs of this window and table before the next keypoint's are parked over them
+      // every lane has read what it needs of this table, and of this window, before the next keypoint's table is written over the one
+      // and the window of the keypoint after that is requested into the other
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
     if (i + 1 < BRIEF_KPW) {
       e_cur = e_nxt;
       e_nxt = e_nn;
-      st_cur = st_nxt;
+      sc_cur = sc_nxt;
     }
   }
   BS_END(1)
