@@ -187,8 +187,10 @@ bool schur_solve(const Lba& S, const double* Hpp, const double* bp, const double
   return true;
 }
 
-// SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg; returns the number of solve() calls made
-int optimize(Lba& S, int iterations, const volatile int* stop, double* lambda_out) {
+// SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg; returns the number of solve() calls made;
+// trials_out (nullable): the trial steps they took
+int optimize(Lba& S, int iterations, const volatile int* stop, double* lambda_out, int32_t* trials_out) {
+  if (trials_out) *trials_out = 0;
   bool any = false;
   for (int e = 0; e < S.E; ++e) any = any || S.level[e] == 0;
   if (!any) return 0;
@@ -217,6 +219,7 @@ int optimize(Lba& S, int iterations, const volatile int* stop, double* lambda_ou
     do {
       const std::vector<double> poses_backup = S.poses, points_backup = S.points;  // push()
       const bool ok2 = schur_solve(S, Hpp.data(), bp.data(), Hll.data(), bl.data(), Hpl.data(), lambda, dxp.data(), dxl.data());
+      if (trials_out) ++*trials_out;
       if (ok2) {
         for (int k = 0; k < S.NK; ++k) {
           if (S.fixed && S.fixed[k]) continue;
@@ -269,12 +272,12 @@ extern "C" {
 
 // Problem layout as orbfe_ba_problem.  Outputs (any may be NULL): poses_out [n_poses][7], points_out [n_points][3],
 // level_out [n_edges] (1: excluded from the second round), chi2_out [n_edges] / bad_out [n_edges] (final computeError() and the
-// chi2 / depth test of Optimizer.cc:364-391), iters_out[2] (solve() calls of the two rounds).
+// chi2 / depth test of Optimizer.cc:364-391), iters_out[2] (solve() calls of the two rounds), trials_out[2] (their trial steps).
 void orc_ba_local_optimize(int n_poses, int n_points, int n_edges, const double* poses, const double* points, const int32_t* edge_pose,
                            const int32_t* edge_point, const double* meas, const uint8_t* is_stereo, const double* info,
                            const double* huber_delta, double fx, double fy, double cx, double cy, double bf, const uint8_t* pose_fixed,
                            int iters1, int iters2, double* poses_out, double* points_out, uint8_t* level_out, double* chi2_out,
-                           uint8_t* bad_out, int32_t* iters_out) {
+                           uint8_t* bad_out, int32_t* iters_out, int32_t* trials_out) {
   Lba S;
   S.NK = n_poses, S.NP = n_points, S.E = n_edges;
   S.ek = edge_pose, S.ep = edge_point, S.meas = meas, S.st = is_stereo, S.info = info;
@@ -285,7 +288,7 @@ void orc_ba_local_optimize(int n_poses, int n_points, int n_edges, const double*
   S.delta.assign(huber_delta, huber_delta + n_edges);
   S.level.assign(n_edges, 0);
   S.chi2_last.assign(n_edges, 0.0);
-  int it1 = optimize(S, iters1, nullptr, nullptr);
+  int it1 = optimize(S, iters1, nullptr, nullptr, trials_out);
   {  // Optimizer.cc:338-359
     std::vector<uint8_t> dp(n_edges);
     orc_ba_eval_edges(n_edges, S.poses.data(), S.points.data(), edge_pose, edge_point, meas, is_stereo, info, S.delta.data(), fx, fy, cx, cy,
@@ -299,7 +302,7 @@ void orc_ba_local_optimize(int n_poses, int n_points, int n_edges, const double*
       S.delta[e] = -1.0;  // setRobustKernel(nullptr)
     }
   }
-  int it2 = optimize(S, iters2, nullptr, nullptr);
+  int it2 = optimize(S, iters2, nullptr, nullptr, trials_out ? trials_out + 1 : nullptr);
   if (poses_out) std::memcpy(poses_out, S.poses.data(), sizeof(double) * S.poses.size());
   if (points_out) std::memcpy(points_out, S.points.data(), sizeof(double) * S.points.size());
   if (level_out) std::memcpy(level_out, S.level.data(), n_edges);

@@ -247,13 +247,16 @@ bool solve6(const double A[6][6], const double* b, double* x) {
   return true;
 }
 
-// SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg on the single pose vertex
-void optimize(const Problem& P, Pose& T, EdgeState& S, int iterations) {
+// SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg on the single pose vertex; counts (nullable): [0] += the
+// iterations started, [1] += the trial steps taken, [2] += those of the call's very first iteration (more than one: a trial was
+// rejected before any was accepted)
+void optimize(const Problem& P, Pose& T, EdgeState& S, int iterations, int32_t* counts) {
   bool any = false;
   for (int i = 0; i < P.n; ++i) any = any || S.level[i] == 0;
   if (!any) return;  // g2o: "0 vertices to optimize"
   double lambda = 0, ni = 2;
   for (int it = 0; it < iterations; ++it) {
+    if (counts) ++counts[0];
     compute_active_errors(P, T, S);
     double current_chi = active_robust_chi2(P, S);
     double temp_chi = current_chi;
@@ -274,6 +277,7 @@ void optimize(const Problem& P, Pose& T, EdgeState& S, int iterations) {
       for (int j = 0; j < 6; ++j) Hl[j][j] += lambda;
       double x[6] = {0, 0, 0, 0, 0, 0};
       const bool ok2 = solve6(Hl, b, x);
+      if (counts) ++counts[1], counts[2] += counts[0] == 1;
       T = oplus(T, x);
       compute_active_errors(P, T, S);
       temp_chi = active_robust_chi2(P, S);
@@ -307,9 +311,11 @@ void optimize(const Problem& P, Pose& T, EdgeState& S, int iterations) {
 extern "C" {
 
 // Returns edges - nBad of the last round (the value OptimizePoseOnly would return before its projection check).
-// sigma2[i] = getScaledFactor2(octave) as float.  inlier_out[i] in {0,1}.
+// sigma2[i] = getScaledFactor2(octave) as float.  inlier_out[i] in {0,1}.  counts_out (nullable, 3 values): iterations started and trial
+// steps taken over the four rounds, and the trial steps of the first iteration of the first round.
 int orc_pose_only_optimize(int n, const double* Xw, const double* meas, const double* info, const float* sigma2, const double* pose_in,
-                           double fx, double fy, double cx, double cy, double bf, double* pose_out, uint8_t* inlier_out) {
+                           double fx, double fy, double cx, double cy, double bf, double* pose_out, uint8_t* inlier_out,
+                           int32_t* counts_out) {
   Problem P{n, Xw, meas, info, fx, fy, cx, cy, bf, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815)};
   EdgeState S;
   S.err.assign((size_t)n * 3, 0.0);
@@ -322,10 +328,11 @@ int orc_pose_only_optimize(int n, const double* Xw, const double* meas, const do
   for (int i = 0; i < n; ++i) edge_error(P, T, i, &S.err[3 * i]);  // edge->computeError() at construction (Optimizer.cc:90,111)
   std::vector<uint8_t> inlier(n, 1);
   int n_bad = 0;
+  if (counts_out) counts_out[0] = counts_out[1] = counts_out[2] = 0;
   for (int round = 0; round < 4; ++round) {
     n_bad = 0;
     T = T0;  // poseVertex->setEstimate(se3): every round restarts from the initial pose (Optimizer.cc:127)
-    optimize(P, T, S, 10);
+    optimize(P, T, S, 10, counts_out);
     for (int pass = 0; pass < 2; ++pass) {  // mono edges first, then stereo (two std::map loops, Optimizer.cc:132-177)
       for (int i = 0; i < n; ++i) {
         const bool st = !(meas[3 * i + 2] < 0);

@@ -7,8 +7,8 @@
 //
 // One TRIAL (= one step of the enqueued stream), every kernel gated by state.run_step (six launches; every launch of a dependent
 // stream costs 4.6 us before it does anything, so the pose side of the system rides in k_lm_prep):
-//   k_lm_ctrl        (lm_ctrl_body) decide the outstanding trial (rho = (chi_cur - chi_trial) / (scale + 1e-3); accept: lambda *= max(1/3, 1 - (2 rho - 1)^3),
-//                    swap the estimate / system buffers; reject: lambda *= ni, ni *= 2), start the next iteration or trial, or finish
+//   k_lm_ctrl        (lm_ctrl_body) decide the outstanding trial (lm_ctrl.h: the gain ratio and the accept / reject rules; accept: swap the
+//                    estimate / system buffers), start the next iteration or trial, or finish
 //   k_lm_prep        per point: (Hll + lambda I)^-1, W(e) = Hpl(e) Dinv for its edges             (BlockSolver_6_3::solve, marginalised points)
 //                    + Hpp / bp per pose of the CURRENT system from its stored edge terms (blocks after the point blocks)
 //   k_lm_schur       one wave per block (i >= j) of free poses: S_ij = [i == j](Hpp_i + lambda I) - sum W(e1) Hpl(e2)^T, lanes over the pairs
@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_edge_dev.h"
+#include "lm_ctrl.h"
 #include "orbfe_internal.h"
 #include "wave_ops.h"
 
@@ -951,30 +952,14 @@ __device__ void lm_ctrl_body(LmState* __restrict__ st, const LmBuffers& B, int m
   // (a) a trial ran since the last control point: decide it
   if (s.phase == 1) {
     const double chi_trial = sum_trial;
-    const double scale = sum_scale;
-    const bool ok2 = s.ok != 0;
-    const double temp_chi = ok2 ? chi_trial : 1.7976931348623157e308;
-    double rho = (s.current_chi - temp_chi) / (scale + 1e-3);
-    if (!ok2) rho = -1.0;  // the linear solver failed: the trial is rejected whatever its step looked like
-    bool lambda_dead = false;
-    if (rho > 0 && isfinite(temp_chi)) {
-      double alpha = 1. - pow((2 * rho - 1), 3);
-      alpha = fmin(alpha, 2. / 3.);
-      s.lambda *= fmax(1. / 3., alpha);
-      s.ni = 2;
-      s.current_chi = temp_chi;
+    const LmDecision d = lm_decide(s.lambda, s.ni, s.current_chi, s.qmax, chi_trial, sum_scale, s.ok != 0, s.stopped != 0);
+    if (d.accepted) {
       if (s.cur) s.chi_of[0] = chi_trial; else s.chi_of[1] = chi_trial;
       s.cur ^= 1;  // accept: the trial's estimate AND its system become current (no pop)
-    } else {
-      s.lambda *= s.ni;
-      s.ni *= 2;
-      if (!isfinite(s.lambda)) lambda_dead = true;  // (g2o breaks out of the trial loop before ++qmax)
     }
-    if (!lambda_dead) ++s.qmax;
-    s.rho = rho;
-    if (!lambda_dead && rho < 0 && s.qmax < 10 && !s.stopped) {
+    if (d.next == LM_RETRY) {
       s.phase = 3;  // another trial of the same iteration: same system, new lambda
-    } else if (lambda_dead || s.qmax == 10 || rho == 0 || !isfinite(s.lambda)) {
+    } else if (d.next == LM_TERMINATE) {
       s.phase = 2;  // OptimizationAlgorithm::Terminate
     } else {
       ++s.it;
@@ -988,12 +973,7 @@ __device__ void lm_ctrl_body(LmState* __restrict__ st, const LmBuffers& B, int m
         s.phase = 2;
       } else {
         if (s.round) ++s.done[1]; else ++s.done[0];
-        s.current_chi = s.cur ? s.chi_of[1] : s.chi_of[0];
-        if (s.it == 0) {
-          s.lambda = 1e-5 * s.maxdiag;  // computeLambdaInit, tau = 1e-5
-          s.ni = 2;
-        }
-        s.qmax = 0;
+        lm_begin_iteration(s.lambda, s.ni, s.current_chi, s.qmax, s.cur ? s.chi_of[1] : s.chi_of[0], s.it, s.maxdiag);
         s.phase = 3;
       }
     }

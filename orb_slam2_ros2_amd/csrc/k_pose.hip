@@ -49,7 +49,7 @@ struct PoseShared {
   PoseDev T, T0, backup;
   double H[36], b[6], x[6];
   double red[28][POSE_THREADS / 64];
-  double lambda, ni, current_chi, temp_chi, rho;
+  double lambda, ni, current_chi;  // the damping state of lm_ctrl.h, with qmax
   int qmax, cont_inner, stop_outer, any_active, n_bad;
 };
 
@@ -178,15 +178,7 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_only(int n, const double*
         const double chi = eval_chi();
         build_system();
         if (tid == 0) {
-          S.current_chi = chi;
-          if (it == 0) {
-            double md = 0;
-            for (int j = 0; j < 6; ++j) md = fmax(fabs(S.H[7 * j]), md);
-            S.lambda = 1e-5 * md;
-            S.ni = 2;
-          }
-          S.rho = 0;
-          S.qmax = 0;
+          lm_begin_iteration(S.lambda, S.ni, S.current_chi, S.qmax, chi, it, lm6_maxdiag(S.H));
           S.stop_outer = 0;
         }
         __syncthreads();
@@ -205,29 +197,11 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_only(int n, const double*
           __syncthreads();
           const double tchi = eval_chi();
           if (tid == 0) {
-            double temp_chi = S.cont_inner ? tchi : 1.7976931348623157e308;
-            double rho = S.current_chi - temp_chi;
-            double scale = 0;
-            for (int j = 0; j < 6; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            bool finite_lambda = true;
-            if (rho > 0 && isfinite(temp_chi)) {
-              double alpha = 1. - pow((2 * rho - 1), 3);
-              alpha = fmin(alpha, 2. / 3.);
-              S.lambda *= fmax(1. / 3., alpha);
-              S.ni = 2;
-              S.current_chi = temp_chi;
-            } else {
-              S.lambda *= S.ni;
-              S.ni *= 2;
-              S.T = S.backup;
-              finite_lambda = isfinite(S.lambda);
-            }
-            S.rho = rho;
-            S.qmax += 1;
-            S.cont_inner = (finite_lambda && rho < 0 && S.qmax < 10) ? 1 : 0;
-            if (!S.cont_inner) S.stop_outer = (S.qmax == 10 || rho == 0 || !isfinite(S.lambda)) ? 1 : 0;
+            const double scale = lm6_scale(S.x, S.lambda, S.b);
+            const LmDecision d = lm_decide(S.lambda, S.ni, S.current_chi, S.qmax, tchi, scale, S.cont_inner != 0 /*ok2*/, false);
+            if (!d.accepted) S.T = S.backup;
+            S.cont_inner = d.next == LM_RETRY ? 1 : 0;
+            S.stop_outer = d.next == LM_TERMINATE ? 1 : 0;
           }
           __syncthreads();
           if (!S.cont_inner) break;
@@ -440,34 +414,13 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
           double xs[6], bs[6];
 #pragma unroll
           for (int j = 0; j < 6; ++j) xs[j] = S.trial_x[qmax][j], bs[j] = S.b[j];
-          const double temp_chi = trial_ok ? chi : 1.7976931348623157e308;
-          double rho = current_chi - temp_chi;
-          double scale = 0;
-#pragma unroll
-          for (int j = 0; j < 6; ++j) scale += xs[j] * (lambda * xs[j] + bs[j]);
-          scale += 1e-3;
-          rho /= scale;
-          bool finite_lambda = true, accepted = false;
-          if (rho > 0 && isfinite(temp_chi)) {
-            double alpha = 1. - pow((2 * rho - 1), 3);
-            alpha = fmin(alpha, 2. / 3.);
-            lambda *= fmax(1. / 3., alpha);
-            ni = 2;
-            current_chi = temp_chi;
-            accepted = true;
-            Tb = Te;
-          } else {
-            lambda *= ni;
-            ni *= 2;
-            finite_lambda = isfinite(lambda);  // (the estimate stays Tb: g2o restores its backup)
-          }
-          qmax += 1;
-          const bool cont_inner = finite_lambda && rho < 0 && qmax < 10;
-          if (cont_inner) continue;  // another trial of the same iteration (new lambda, the same system)
-          const bool stop_outer = qmax == 10 || rho == 0 || !isfinite(lambda);
-          if (stop_outer) break;
+          const double scale = lm6_scale(xs, lambda, bs);
+          const LmDecision d = lm_decide(lambda, ni, current_chi, qmax, chi, scale, trial_ok, false);
+          if (d.next == LM_RETRY) continue;  // another trial of the same iteration (new lambda, the same system)
+          if (d.accepted) Tb = Te;  // (rejected: the estimate stays Tb, where g2o restores its backup)
+          if (d.next == LM_TERMINATE) break;
           if (++it == 10) break;
-          if (!accepted) {  // (a trial neither accepted nor retried, e.g. a NaN gain ratio: the next iteration re-evaluates at the restored pose)
+          if (!d.accepted) {  // (a trial neither accepted nor retried, e.g. a NaN gain ratio: the next iteration re-evaluates at the restored pose)
             do_solve = false;
             Te = Tb;
             continue;
@@ -506,15 +459,7 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
           LM6_STAGE_REDUCE(NT, acc, S, tid)
         }
         PS(4)  // build
-        current_chi = chi_cur;
-        if (it == 0) {
-          double md = 0;
-#pragma unroll
-          for (int j = 0; j < 6; ++j) md = fmax(fabs(S.H[7 * j]), md);
-          lambda = 1e-5 * md;
-          ni = 2;
-        }
-        qmax = 0;
+        lm_begin_iteration(lambda, ni, current_chi, qmax, chi_cur, it, lm6_maxdiag(S.H));
         // The trial steps of this iteration, all at once: a rejected trial multiplies lambda by ni and doubles ni, the system and the pose
         // it starts from stay -- so trial q's damping is known now, and lane q solves (H + lambda_q I) x = b and applies x to the pose
         // beside the others (one instruction stream; a call of 28 iterations takes ~59 trials, most of the rejected ones in the runs of ten

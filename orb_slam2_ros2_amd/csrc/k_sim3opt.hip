@@ -173,34 +173,13 @@ __global__ __launch_bounds__(S3O_NT) void k_sim3_optimize(S3oArgs a) {
           double xs[6], bs[6];
 #pragma unroll
           for (int j = 0; j < 6; ++j) xs[j] = S.trial_x[qmax][j], bs[j] = S.b[j];
-          const double temp_chi = trial_ok ? chi : 1.7976931348623157e308;
-          double rho = current_chi - temp_chi;
-          double scale = 0;
-#pragma unroll
-          for (int j = 0; j < 6; ++j) scale += xs[j] * (lambda * xs[j] + bs[j]);
-          scale += 1e-3;
-          rho /= scale;
-          bool finite_lambda = true, accepted = false;
-          if (rho > 0 && isfinite(temp_chi)) {
-            double alpha = 1. - pow((2 * rho - 1), 3);
-            alpha = fmin(alpha, 2. / 3.);
-            lambda *= fmax(1. / 3., alpha);
-            ni = 2;
-            current_chi = temp_chi;
-            accepted = true;
-            Tb = Te;
-          } else {
-            lambda *= ni;
-            ni *= 2;
-            finite_lambda = isfinite(lambda);  // (the estimate stays Tb: g2o restores its backup)
-          }
-          qmax += 1;
-          const bool cont_inner = finite_lambda && rho < 0 && qmax < 10;
-          if (cont_inner) continue;  // another trial of the same iteration (new lambda, the same system)
-          const bool stop_outer = qmax == 10 || rho == 0 || !isfinite(lambda);
-          if (stop_outer) break;
+          const double scale = lm6_scale(xs, lambda, bs);
+          const LmDecision d = lm_decide(lambda, ni, current_chi, qmax, chi, scale, trial_ok, false);
+          if (d.next == LM_RETRY) continue;  // another trial of the same iteration (new lambda, the same system)
+          if (d.accepted) Tb = Te;  // (rejected: the estimate stays Tb, where g2o restores its backup)
+          if (d.next == LM_TERMINATE) break;
           if (++it == iterations) break;
-          if (!accepted) {  // (a trial neither accepted nor retried, e.g. a NaN gain ratio: the next iteration re-evaluates at the restored estimate)
+          if (!d.accepted) {  // (a trial neither accepted nor retried, e.g. a NaN gain ratio: the next iteration re-evaluates at the restored estimate)
             do_solve = false;
             continue;
           }
@@ -263,15 +242,8 @@ __global__ __launch_bounds__(S3O_NT) void k_sim3_optimize(S3oArgs a) {
           // (the previous system's b and trial table are rewritten only behind the barrier inside: every thread has read them by then)
           LM6_STAGE_REDUCE(NT, acc, S, tid)
         }
-        current_chi = chi_cur;
-        if (it == 0) {  // lambda is initialised at every optimize(): tau * max |diag| (the seventh diagonal entry is 0, O1)
-          double md = 0;
-#pragma unroll
-          for (int j = 0; j < 6; ++j) md = fmax(fabs(S.H[7 * j]), md);
-          lambda = 1e-5 * md;
-          ni = 2;
-        }
-        qmax = 0;
+        // (lambda is initialised at every optimize(): tau * max |diag|; the seventh diagonal entry is 0, O1)
+        lm_begin_iteration(lambda, ni, current_chi, qmax, chi_cur, it, lm6_maxdiag(S.H));
         // the trial steps of this iteration, all at once: lane q solves (H + lambda_q I) x = b and applies x to the estimate
         if (tid < LM6_TRIALS) {
           const double lam = lm6_trial_lambda(lambda, ni, tid);

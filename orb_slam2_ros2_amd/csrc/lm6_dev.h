@@ -1,14 +1,15 @@
 // lm6_dev.h -- what the one-vertex Levenberg-Marquardt kernels share (k_pose.hip's register-resident OptimizePoseOnly, k_sim3opt.hip's
-// OptimizeSim3): a 6-DoF vertex gives both the same 21 + 6 sums per linearisation, the same damped 6x6 solve and the same table of trial
-// dampings.  Device only.
+// OptimizeSim3): a 6-DoF vertex gives both the same 21 + 6 sums per linearisation, the same damped 6x6 solve, the same computeScale and
+// the same table of trial dampings (lm6_trial_lambda, next to the reject rule it unrolls: lm_ctrl.h).  Device only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lm_ctrl.h"
 #include "wave_ops.h"
 
 namespace orbfe {
 
-#define LM6_TRIALS 10  // g2o's Levenberg-Marquardt gives an iteration at most 10 trial steps (qmax)
+#define LM6_TRIALS LM_TRIALS
 #define LM6_STAGE_LD(NT) ((NT) + 8)  // doubles per row of the staged sums: rows 8 double-banks apart => the readers of a wave 2 per bank pair
 
 // (H + lambda I) x = b with H and b where they are (LDS), for the register-resident kernel, where this lane-0 solve and the pose update
@@ -54,12 +55,23 @@ __device__ __forceinline__ bool solve6_lambda(const double* H, double lambda, co
   return true;
 }
 
-// The damping of trial q of an iteration that starts with (lambda, ni): a rejected trial multiplies lambda by ni and doubles ni, the system
-// and the estimate it starts from stay -- so every trial's damping is known when the system is built.
-__device__ __forceinline__ double lm6_trial_lambda(double lambda, double ni, int q) {
-  double lam = lambda, nu = ni;
-  for (int k = 0; k < q; ++k) lam *= nu, nu *= 2;
-  return lam;
+// computeScale of a 6-vector step: sum of x_j (lambda x_j + b_j), j = 0 .. 5 (the 1e-3 is lm_decide's)
+__device__ __forceinline__ double lm6_scale(const double* x, double lambda, const double* b) {
+#pragma clang fp contract(off)
+  double scale = 0;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + b[j]);
+  return scale;
+}
+
+// max |H_jj| of the 6x6 system, j = 0 .. 5: what computeLambdaInit scales tau by
+// (the callers pass it to lm_begin_iteration at every iteration, which reads it at iteration 0: the compiler computed the scan
+//  unconditionally and selected on `it == 0` when it stood under that test too -- the same instructions either way)
+__device__ __forceinline__ double lm6_maxdiag(const double* H) {
+  double md = 0;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) md = fmax(fabs(H[7 * j]), md);
+  return md;
 }
 
 // The 27 sums of the normal equations over the NT threads of the workgroup (acc: the 21 entries of H's upper triangle row by row, then

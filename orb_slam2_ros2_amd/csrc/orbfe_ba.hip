@@ -1,6 +1,7 @@
 // orbfe_ba.hip -- the optimiser entry points: g2o edge evaluation and normal equations (diagnostic), the local BA
 // (Optimizer::OptimizeLocalMap, Optimizer.cc:336-391) and Optimizer::OptimizePoseOnly (:33-178).  (Split from orbfe_api.hip in r5.)
 #include "ba_host.h"
+#include "lm_host.h"
 namespace {
 
 // one orbfe_ba_local_optimize call: the arguments, what the entry point derived from them, and its ORBFE_LBA_TRACE marks
@@ -236,12 +237,7 @@ orbfe_status LbaCall::host_lm() {
   double* d_points = (double*)(b + o_pt);
   const int32_t* d_ek = (const int32_t*)(b + in[BA_EP]);
   const int32_t* d_ep = (const int32_t*)(b + in[BA_ET]);
-  double* d_sc = (double*)(b + o_sc);  // [0] robust chi2, [1] max diagonal, [2] lambda, [3] ok (int), [4] scale
-  struct HostScalars {
-    double chi, maxdiag, lambda;
-    int32_t ok, pad;
-    double scale;
-  };
+  double* d_sc = (double*)(b + o_sc);  // the loop's five scalars (lm_host.h)
   auto edges = [&](size_t o_inf) {  // computeError() on every edge, with the given information values
     launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, (const double*)(b + o_meas), b + o_st, (const double*)(b + o_inf),
                     (const double*)(b + o_delta), prm, (double*)(b + o_err), (double*)(b + o_chi2), (double*)(b + o_rho), nullptr, nullptr,
@@ -251,69 +247,38 @@ orbfe_status LbaCall::host_lm() {
     edges(o_info_eff);
     launch_lba_chi2_sum(st, E, (const double*)(b + o_chi2), (const double*)(b + o_rho), b + o_level, (double*)(b + o_last), d_sc);
   };
-  auto read_scalars = [&](HostScalars& h) -> hipError_t {
-    hipError_t e = hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-  };
   auto stopped = [&]() { return stop_flag && *stop_flag; };
   StageTimer tm(c, ORBFE_STAGE_BA, st);
-  auto optimize = [&](int iterations, int32_t& done) -> orbfe_status {  // SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve
+  auto optimize = [&](int iterations, int32_t& done) -> orbfe_status {  // SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve (lm_host.h)
     done = 0;
     if (E == 0) return ORBFE_OK;
-    double lambda = 0, ni = 2;
-    for (int it = 0; it < iterations; ++it) {
-      if (stopped()) break;
-      ++done;
+    auto linearize = [&](int it) -> orbfe_status {
       evaluate();
       launch_lm_build(st, K, 0, 0, 0, true);
       if (it == 0) launch_lba_maxdiag(st, NK, NP, (const double*)(b + o_hpp), (const double*)(b + o_hll), b + o_fix, d_sc + 1);
-      HostScalars h;
-      HIP_TRY(c, read_scalars(h));
-      double current_chi = h.chi;
-      if (it == 0) {
-        lambda = 1e-5 * h.maxdiag;  // computeLambdaInit, tau = 1e-5
-        ni = 2;
-      }
-      double rho = 0;
-      int qmax = 0;
-      do {
-        HIP_TRY(c, hipMemcpyAsync(b + o_pose_bk, d_poses, (size_t)NK * 56, hipMemcpyDeviceToDevice, st));  // push()
-        HIP_TRY(c, hipMemcpyAsync(b + o_pt_bk, d_points, (size_t)NP * 24, hipMemcpyDeviceToDevice, st));
-        struct {
-          double lambda;
-          int32_t ok, pad;
-        } upv = {lambda, 1, 0};
-        HIP_TRY(c, hipMemcpyAsync(d_sc + 2, &upv, sizeof upv, hipMemcpyHostToDevice, st));
-        launch_lba_solve(st, NK, NP, E, nf, (const int32_t*)(b + o_free), (const int32_t*)(b + o_slot), (const int32_t*)(b + o_pairoff),
-                         (const int2*)(b + o_pairs), (const int32_t*)(b + o_pso), (const int32_t*)(b + o_pse), (const int32_t*)(b + o_pto),
-                         (const int32_t*)(b + o_pte), d_ek, d_ep, b + o_fix, (const double*)(b + o_hpp), (const double*)(b + o_bp),
-                         (const double*)(b + o_hll), (const double*)(b + o_bl), (const double*)(b + o_hpl), d_sc + 2, (double*)(b + o_dinv),
-                         (double*)(b + o_w), (double*)(b + o_s), (double*)(b + o_rhs), (double*)(b + o_x), (int*)(d_sc + 3), d_poses, d_points,
-                         (double*)(b + o_dxp), (double*)(b + o_dxl), d_sc + 4, (double*)(b + o_big));
-        evaluate();
-        HIP_TRY(c, read_scalars(h));
-        const bool ok2 = h.ok != 0;
-        const double temp_chi = ok2 ? h.chi : std::numeric_limits<double>::max();
-        rho = (current_chi - temp_chi) / (h.scale + 1e-3);
-        if (!ok2) rho = -1.0;  // the linear solver failed: the trial is rejected whatever its step looked like
-        if (rho > 0 && std::isfinite(temp_chi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          lambda *= std::max(1. / 3., alpha);
-          ni = 2;
-          current_chi = temp_chi;
-        } else {
-          lambda *= ni;
-          ni *= 2;
-          HIP_TRY(c, hipMemcpyAsync(d_poses, b + o_pose_bk, (size_t)NK * 56, hipMemcpyDeviceToDevice, st));  // pop()
-          HIP_TRY(c, hipMemcpyAsync(d_points, b + o_pt_bk, (size_t)NP * 24, hipMemcpyDeviceToDevice, st));
-          if (!std::isfinite(lambda)) break;
-        }
-        ++qmax;
-      } while (rho < 0 && qmax < 10 && !stopped());
-      if (qmax == 10 || rho == 0 || !std::isfinite(lambda)) break;  // OptimizationAlgorithm::Terminate
-    }
-    return ORBFE_OK;
+      return ORBFE_OK;
+    };
+    auto trial = [&](double lambda, bool&) -> orbfe_status {
+      HIP_TRY(c, hipMemcpyAsync(b + o_pose_bk, d_poses, (size_t)NK * 56, hipMemcpyDeviceToDevice, st));  // push()
+      HIP_TRY(c, hipMemcpyAsync(b + o_pt_bk, d_points, (size_t)NP * 24, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(c, lm_host_upload(st, d_sc, lambda));
+      launch_lba_solve(st, NK, NP, E, nf, (const int32_t*)(b + o_free), (const int32_t*)(b + o_slot), (const int32_t*)(b + o_pairoff),
+                       (const int2*)(b + o_pairs), (const int32_t*)(b + o_pso), (const int32_t*)(b + o_pse), (const int32_t*)(b + o_pto),
+                       (const int32_t*)(b + o_pte), d_ek, d_ep, b + o_fix, (const double*)(b + o_hpp), (const double*)(b + o_bp),
+                       (const double*)(b + o_hll), (const double*)(b + o_bl), (const double*)(b + o_hpl), d_sc + 2, (double*)(b + o_dinv),
+                       (double*)(b + o_w), (double*)(b + o_s), (double*)(b + o_rhs), (double*)(b + o_x), (int*)(d_sc + 3), d_poses, d_points,
+                       (double*)(b + o_dxp), (double*)(b + o_dxl), d_sc + 4, (double*)(b + o_big));
+      evaluate();
+      return ORBFE_OK;
+    };
+    auto on_accept = [&]() -> orbfe_status { return ORBFE_OK; };
+    auto on_reject = [&](bool) -> orbfe_status {
+      HIP_TRY(c, hipMemcpyAsync(d_poses, b + o_pose_bk, (size_t)NK * 56, hipMemcpyDeviceToDevice, st));  // pop()
+      HIP_TRY(c, hipMemcpyAsync(d_points, b + o_pt_bk, (size_t)NP * 24, hipMemcpyDeviceToDevice, st));
+      return ORBFE_OK;
+    };
+    int32_t trials;
+    return lm_host_optimize(c, st, d_sc, iterations, stop_flag, done, trials, linearize, trial, on_accept, on_reject, [](int) {});
   };
   int32_t it1 = 0, it2 = 0;
   TRY(optimize(iters_first, it1));

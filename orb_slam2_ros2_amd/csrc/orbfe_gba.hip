@@ -3,6 +3,7 @@
 // conjugate gradient in place of the dense Cholesky (k_bsr.hip).  The Levenberg control is the host-driven loop of the local BA
 // (orbfe_ba.hip, host_lm) with its builders, update and sums; only the solver step differs.
 #include "ba_host.h"
+#include "lm_host.h"
 #include "bsr_symbolic.h"
 namespace {
 
@@ -178,97 +179,62 @@ orbfe_status gba_sparse(orbfe_ctx* c, const orbfe_ba_problem* p, const uint8_t* 
   double* d_points = io.dev<double>(in[BA_PT]);
   const int32_t* d_ek = io.dev<int32_t>(in[BA_EP]);
   const int32_t* d_ep = io.dev<int32_t>(in[BA_ET]);
-  double* d_sc = io.dev<double>(o_sc);  // [0] robust chi2, [1] max diagonal, [2] lambda, [3] ok (int), [4] scale
+  double* d_sc = io.dev<double>(o_sc);  // the loop's five scalars (lm_host.h)
   P.ok = (int*)(d_sc + 3);
   const SchurAt sa = {&sym, &so, o_free, o_hpp, o_bp, o_bl, o_hpl, o_w, o_sc + 16, o_blocks, o_rhs, po.minv, o_sc + 24};
-  struct HostScalars {
-    double chi, maxdiag, lambda;
-    int32_t ok, pad;
-    double scale;
-  };
   auto evaluate = [&]() {  // computeActiveErrors + activeRobustChi2 (no edge is ever excluded here: the information is the problem's)
     launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, io.dev<double>(in[BA_MEAS]), io.dev<uint8_t>(in[BA_ST]), io.dev<double>(in[BA_INFO]),
                     io.dev<double>(in[BA_DELTA]), prm, io.dev<double>(o_err), io.dev<double>(o_chi2), io.dev<double>(o_rho), nullptr, nullptr,
                     io.dev<uint8_t>(o_depth));
     launch_lba_chi2_sum(st, E, io.dev<double>(o_chi2), io.dev<double>(o_rho), io.dev<uint8_t>(o_level), io.dev<double>(o_last), d_sc);
   };
-  auto read_scalars = [&](HostScalars& h) -> hipError_t {
-    hipError_t e = hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-  };
-  auto stopped = [&]() { return stop_flag && *stop_flag; };
   StageTimer tm(c, ORBFE_STAGE_BA, st);
   GbaClock clk(st);
-  int64_t trials = 0, cg_iters = 0, rejected = 0;
-  int32_t done = 0;
-  // SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve: host_lm's control flow (orbfe_ba.hip), restated here with the solver
-  // step exchanged and no classification round, so that the local BA's own loop stays exactly as it was
-  double lambda = 0, ni = 2;
-  for (int it = 0; it < iterations; ++it) {
-    if (stopped()) break;
-    ++done;
+  int64_t cg_iters = 0, rejected = 0;
+  int32_t done = 0, trials = 0;
+  // SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve (lm_host.h): the local BA's host loop with the solver step
+  // exchanged and no classification round
+  auto linearize = [&](int it) -> orbfe_status {
     evaluate();
     launch_lm_build(st, K, 0, 0, 0, true);
     if (it == 0) launch_lba_maxdiag(st, NK, NP, io.dev<double>(o_hpp), io.dev<double>(o_hll), io.dev<uint8_t>(in[BA_FIX]), d_sc + 1);
-    HostScalars h;
-    HIP_TRY(c, read_scalars(h));
-    clk.lap(0, 6);
-    double current_chi = h.chi;
-    if (it == 0) {
-      lambda = 1e-5 * h.maxdiag;  // computeLambdaInit, tau = 1e-5
-      ni = 2;
-    }
-    double rho = 0;
-    int qmax = 0;
-    do {
-      HIP_TRY(c, hipMemcpyAsync(b + o_pose_bk, d_poses, NKs * 56, hipMemcpyDeviceToDevice, st));  // push()
-      HIP_TRY(c, hipMemcpyAsync(b + o_pt_bk, d_points, NPs * 24, hipMemcpyDeviceToDevice, st));
-      struct {
-        double lambda;
-        int32_t ok, pad;
-      } upv = {lambda, 1, 0};
-      HIP_TRY(c, hipMemcpyAsync(d_sc + 2, &upv, sizeof upv, hipMemcpyHostToDevice, st));
-      launch_lba_pre(st, NP, E, d_ep, io.dev<double>(o_hll), io.dev<double>(o_hpl), d_sc + 2, io.dev<double>(o_dinv), io.dev<double>(o_w),
-                     (int*)(d_sc + 3));
-      gba_schur(st, io, in, sa);
-      clk.lap(1, 6);
-      PcgResult pr;
-      pr.state = PCG_CONVERGED;  // (no free keyframe: nothing to solve)
-      int launches = 0;
-      if (nf > 0) TRY(run_pcg(c, st, P, tol, max_iter, &pr, &launches));
-      clk.lap(2, launches);
-      ++trials, cg_iters += pr.iters;
-      launch_lba_post(st, NK, NP, io.dev<int32_t>(o_slot), io.dev<int32_t>(in[BA_PTO]), io.dev<int32_t>(in[BA_PTE]), d_ek, io.dev<uint8_t>(in[BA_FIX]),
-                      io.dev<double>(o_bp), io.dev<double>(o_bl), io.dev<double>(o_hpl), d_sc + 2, io.dev<double>(o_dinv), P.x, d_poses, d_points,
-                      io.dev<double>(o_dxp), io.dev<double>(o_dxl), d_sc + 4);
-      evaluate();
-      HIP_TRY(c, read_scalars(h));
-      const bool ok2 = h.ok != 0 && pr.ok();
-      if (!ok2) ++rejected;
-      const double temp_chi = ok2 ? h.chi : std::numeric_limits<double>::max();
-      rho = (current_chi - temp_chi) / (h.scale + 1e-3);
-      if (!ok2) rho = -1.0;  // the linear solver failed: the trial is rejected whatever its step looked like
-      if (rho > 0 && std::isfinite(temp_chi)) {
-        double alpha = 1. - std::pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        lambda *= std::max(1. / 3., alpha);
-        ni = 2;
-        current_chi = temp_chi;
-      } else {
-        lambda *= ni;
-        ni *= 2;
-        HIP_TRY(c, hipMemcpyAsync(d_poses, b + o_pose_bk, NKs * 56, hipMemcpyDeviceToDevice, st));  // pop()
-        HIP_TRY(c, hipMemcpyAsync(d_points, b + o_pt_bk, NPs * 24, hipMemcpyDeviceToDevice, st));
-        if (!std::isfinite(lambda)) {
-          clk.lap(3, 7);
-          break;
-        }
-      }
-      clk.lap(3, 7);
-      ++qmax;
-    } while (rho < 0 && qmax < 10 && !stopped());
-    if (qmax == 10 || rho == 0 || !std::isfinite(lambda)) break;  // OptimizationAlgorithm::Terminate
-  }
+    return ORBFE_OK;
+  };
+  auto trial = [&](double lambda, bool& solver_ok) -> orbfe_status {
+    HIP_TRY(c, hipMemcpyAsync(b + o_pose_bk, d_poses, NKs * 56, hipMemcpyDeviceToDevice, st));  // push()
+    HIP_TRY(c, hipMemcpyAsync(b + o_pt_bk, d_points, NPs * 24, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, lm_host_upload(st, d_sc, lambda));
+    launch_lba_pre(st, NP, E, d_ep, io.dev<double>(o_hll), io.dev<double>(o_hpl), d_sc + 2, io.dev<double>(o_dinv), io.dev<double>(o_w),
+                   (int*)(d_sc + 3));
+    gba_schur(st, io, in, sa);
+    clk.lap(1, 6);
+    PcgResult pr;
+    pr.state = PCG_CONVERGED;  // (no free keyframe: nothing to solve)
+    int launches = 0;
+    if (nf > 0) TRY(run_pcg(c, st, P, tol, max_iter, &pr, &launches));
+    clk.lap(2, launches);
+    cg_iters += pr.iters;
+    solver_ok = pr.ok();
+    launch_lba_post(st, NK, NP, io.dev<int32_t>(o_slot), io.dev<int32_t>(in[BA_PTO]), io.dev<int32_t>(in[BA_PTE]), d_ek, io.dev<uint8_t>(in[BA_FIX]),
+                    io.dev<double>(o_bp), io.dev<double>(o_bl), io.dev<double>(o_hpl), d_sc + 2, io.dev<double>(o_dinv), P.x, d_poses, d_points,
+                    io.dev<double>(o_dxp), io.dev<double>(o_dxl), d_sc + 4);
+    evaluate();
+    return ORBFE_OK;
+  };
+  auto on_accept = [&]() -> orbfe_status {
+    clk.lap(3, 7);
+    return ORBFE_OK;
+  };
+  auto on_reject = [&](bool ok) -> orbfe_status {
+    if (!ok) ++rejected;
+    HIP_TRY(c, hipMemcpyAsync(d_poses, b + o_pose_bk, NKs * 56, hipMemcpyDeviceToDevice, st));  // pop()
+    HIP_TRY(c, hipMemcpyAsync(d_points, b + o_pt_bk, NPs * 24, hipMemcpyDeviceToDevice, st));
+    clk.lap(3, 7);
+    return ORBFE_OK;
+  };
+  TRY(lm_host_optimize(c, st, d_sc, iterations, stop_flag, done, trials, linearize, trial, on_accept, on_reject, [&](int phase) {
+    if (phase == 0) clk.lap(0, 6);  // (a trial's clock stops behind its pop copies: on_accept / on_reject)
+  }));
   // computeError() on every edge with the final estimates (Optimizer.cc:1000-1043 reads the vertices only; chi2 is this call's extra)
   launch_ba_edges(st, E, d_poses, d_points, d_ek, d_ep, io.dev<double>(in[BA_MEAS]), io.dev<uint8_t>(in[BA_ST]), io.dev<double>(in[BA_INFO]),
                   io.dev<double>(in[BA_DELTA]), prm, io.dev<double>(o_err), io.dev<double>(o_chi2), io.dev<double>(o_rho), nullptr, nullptr,

@@ -173,7 +173,7 @@ struct StereoRowsBuf {
 
 // The state record one control lane advances between the trials (device memory; the host reads it once per call).
 struct LmState {
-  double lambda, ni, current_chi, rho, maxdiag;
+  double lambda, ni, current_chi, maxdiag;  // (lambda, ni, current_chi and qmax: the damping state of lm_ctrl.h)
   double chi_of[2];     // robust chi2 of the estimate in buffer 0 / 1
   int32_t iters[2];     // iteration budgets of the two optimize() calls (Optimizer.cc:336, :361)
   int32_t done[2];      // iterations started (what optimize() returns)

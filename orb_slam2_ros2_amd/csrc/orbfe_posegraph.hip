@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <new>
 
+#include "lm_host.h"
 #include "orbfe_ctx.h"
 #include "pg_symbolic.h"
 #include "posegraph_edge_dev.h"
@@ -219,84 +220,46 @@ orbfe_status pg_optimize(orbfe_ctx* c, const char* who, const orbfe_pose_graph* 
   const double* d_meas = io.dev<double>(A.o_meas);
   double *d_hee = io.dev<double>(o_hee), *d_be = io.dev<double>(o_be), *d_s = io.dev<double>(o_s), *d_rhs = io.dev<double>(o_rhs),
          *d_x = io.dev<double>(o_x), *d_chi_t = io.dev<double>(o_chi_t);
-  double* d_sc = io.dev<double>(o_sc);  // [0] chi2, [1] max diagonal, [2] lambda, [3] ok (int), [4] scale
-  struct HostScalars {
-    double chi, maxdiag, lambda;
-    int32_t ok, pad;
-    double scale;
-  };
-  auto read_scalars = [&](HostScalars& h) -> hipError_t {
-    hipError_t e = hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-  };
+  double* d_sc = io.dev<double>(o_sc);  // the loop's five scalars (lm_host.h)
   int32_t done = 0, trials = 0;
   {
     StageTimer tm(c, ORBFE_STAGE_BA, st);
-    // SparseOptimizer::optimize(iterations) + OptimizationAlgorithmLevenberg::solve (G7)
-    double lambda = 0, ni = 2;
+    // SparseOptimizer::optimize(iterations) + OptimizationAlgorithmLevenberg::solve (G7): lm_host.h
     PhaseClock clk(st);
-    for (int it = 0; it < iterations; ++it) {
-      ++done;
+    auto linearize = [&](int it) -> orbfe_status {
       // computeActiveErrors + linearizeOplus + constructQuadraticForm of every edge at the current estimates
       launch_pg_build(st, NE, waves, d_est[cur], d_fix, d_v0, d_v1, d_meas, d_hee, d_be, io.dev<double>(o_err), d_chi_t, nullptr);
       launch_pg_reduce(st, NE, d_chi_t, 0, d_x, d_rhs, d_sc + 2, d_sc);
       if (it == 0) launch_pg_maxdiag(st, nf, d_boff, d_ent, d_hee, d_sc + 1);
-      HostScalars h;
       HIP_TRY(c, hipGetLastError());
-      HIP_TRY(c, read_scalars(h));
-      clk.lap(0);
-      double current_chi = h.chi;
-      if (it == 0) {
-        lambda = 1e-5 * h.maxdiag;  // computeLambdaInit, tau = 1e-5
-        ni = 2;
+      return ORBFE_OK;
+    };
+    auto trial = [&](double lambda, bool&) -> orbfe_status {
+      HIP_TRY(c, lm_host_upload(st, d_sc, lambda));
+      // (the factorisation works in place: the system is assembled for every trial)
+      HIP_TRY(c, hipMemsetAsync(d_s, 0, (sparse ? l_doubles : n * n) * 8, st));
+      if (sparse) {
+        launch_pgs_assemble(st, n_blocks, io.dev<int2>(o_blk), d_boff, d_ent, io.dev<int32_t>(o_pos), d_hee, d_be, d_sc + 2, d_s, d_rhs);
+        clk.lap(1);
+        launch_pgs_solve(st, nf, io.dev<int32_t>(o_coff), io.dev<int32_t>(o_row), sym.search_steps, d_s, d_rhs, d_x, (int*)(d_sc + 3));
+      } else {
+        launch_pg_assemble(st, nf, n_blocks, io.dev<int2>(o_blk), d_boff, d_ent, d_hee, d_be, d_sc + 2, d_s, d_rhs);
+        clk.lap(1);
+        launch_lba_chol(st, nf, d_s, d_rhs, d_x, (int*)(d_sc + 3), io.dev<double>(o_big));
       }
-      double rho = 0;
-      int qmax = 0;
-      do {
-        struct {
-          double lambda;
-          int32_t ok, pad;
-        } upv = {lambda, 1, 0};
-        HIP_TRY(c, hipMemcpyAsync(d_sc + 2, &upv, sizeof upv, hipMemcpyHostToDevice, st));
-        // (the factorisation works in place: the system is assembled for every trial)
-        HIP_TRY(c, hipMemsetAsync(d_s, 0, (sparse ? l_doubles : n * n) * 8, st));
-        if (sparse) {
-          launch_pgs_assemble(st, n_blocks, io.dev<int2>(o_blk), d_boff, d_ent, io.dev<int32_t>(o_pos), d_hee, d_be, d_sc + 2, d_s, d_rhs);
-          clk.lap(1);
-          launch_pgs_solve(st, nf, io.dev<int32_t>(o_coff), io.dev<int32_t>(o_row), sym.search_steps, d_s, d_rhs, d_x, (int*)(d_sc + 3));
-        } else {
-          launch_pg_assemble(st, nf, n_blocks, io.dev<int2>(o_blk), d_boff, d_ent, d_hee, d_be, d_sc + 2, d_s, d_rhs);
-          clk.lap(1);
-          launch_lba_chol(st, nf, d_s, d_rhs, d_x, (int*)(d_sc + 3), io.dev<double>(o_big));
-        }
-        clk.lap(2);
-        launch_pg_update(st, NV, io.dev<int32_t>(o_slot), d_x, d_est[cur], d_est[cur ^ 1]);
-        launch_pg_chi2(st, NE, d_est[cur ^ 1], d_v0, d_v1, d_meas, d_chi_t);
-        launch_pg_reduce(st, NE, d_chi_t, (int)n, d_x, d_rhs, d_sc + 2, d_sc);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, read_scalars(h));
-        clk.lap(3);
-        ++trials;
-        const bool ok2 = h.ok != 0;
-        const double temp_chi = ok2 ? h.chi : std::numeric_limits<double>::max();
-        rho = (current_chi - temp_chi) / (h.scale + 1e-3);
-        if (!ok2) rho = -1.0;  // the linear solver failed: the trial is rejected whatever its step looked like
-        if (rho > 0 && std::isfinite(temp_chi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          lambda *= std::max(1. / 3., alpha);
-          ni = 2;
-          current_chi = temp_chi;
-          cur ^= 1;  // the trial estimates are the current ones
-        } else {
-          lambda *= ni;
-          ni *= 2;
-          if (!std::isfinite(lambda)) break;
-        }
-        ++qmax;
-      } while (rho < 0 && qmax < 10);
-      if (qmax == 10 || rho == 0 || !std::isfinite(lambda)) break;  // OptimizationAlgorithm::Terminate
-    }
+      clk.lap(2);
+      launch_pg_update(st, NV, io.dev<int32_t>(o_slot), d_x, d_est[cur], d_est[cur ^ 1]);
+      launch_pg_chi2(st, NE, d_est[cur ^ 1], d_v0, d_v1, d_meas, d_chi_t);
+      launch_pg_reduce(st, NE, d_chi_t, (int)n, d_x, d_rhs, d_sc + 2, d_sc);
+      HIP_TRY(c, hipGetLastError());
+      return ORBFE_OK;
+    };
+    auto on_accept = [&]() -> orbfe_status {
+      cur ^= 1;  // the trial estimates are the current ones
+      return ORBFE_OK;
+    };
+    auto on_reject = [&](bool) -> orbfe_status { return ORBFE_OK; };
+    TRY(lm_host_optimize(c, st, d_sc, iterations, nullptr, done, trials, linearize, trial, on_accept, on_reject, [&](int phase) { clk.lap(phase); }));
     // the results: the current estimates and the chi2 of every edge at them
     HIP_TRY(c, hipMemcpyAsync(io.dev<double>(o_out), d_est[cur], NVs * 64, hipMemcpyDeviceToDevice, st));
     launch_pg_chi2(st, NE, d_est[cur], d_v0, d_v1, d_meas, io.dev<double>(o_chi));

@@ -65,6 +65,34 @@ def test_debug_edges_against_the_restatement(ctx):
     assert seen_pure >= 300 and seen_trig >= 3
 
 
+REJECTING = dict(seed=6, drift=(0.05, 0.2), loop=(3.0, 6.0), noise=0.1, consistent=False)
+REJECTING_SPREAD = 1.93e-6
+
+
+def test_rejected_trials_on_eight_vertices(ctx):
+    """The reject rule of the host loop (lm_host.h) on the dense solver: 7 free vertices joined by measurements that disagree (noise
+    0.1, a loop correction of 3 rad), 3 iterations.  The premise comes from the restatement alone: 7 trials for 3 iterations, 4 of them
+    rejected, and no gain ratio within 1e-3 of 0 (the smallest is 0.0115), so no last bit decides a trial.  The restatement's own spread
+    between its two summation orders is 1.93e-6 here (recomputed below), past the 1e-8 under which the cases' rule gives 1e-6: the
+    bound is 100 x the spread, as tests/essential_graph_cases.py sets it for such a case.  Counts equal, chi2 as the neighbouring test,
+    the same bytes on a second call."""
+    g = K.make_graph(7, **REJECTING)
+    a, b = R.optimize(*K.args(g), iterations=3), R.optimize(*K.args(g), iterations=3, reverse=True)
+    assert (a["iterations"], a["trials"]) == (3, 7) and a["accepts"].count(False) == 4 and a["accepts"] == b["accepts"]
+    assert min(abs(r) for r in a["rhos"]) >= K.QUAL_RHO and a["chis"][-1] < a["chis"][0]
+    spread = float(np.abs(a["est"] - b["est"]).max())
+    assert K.QUAL_DIFF < spread <= 3 * REJECTING_SPREAD
+    est, chi2, stats = ctx.pose_graph_optimize(*K.args(g), iterations=3, solver=1)
+    diff = float(np.abs(est - a["est"]).max())
+    print(f"8 vertices, 4 of 7 trials rejected: max |estimate - restatement| {diff:.2e} (restatement's spread {spread:.2e}); stats {stats}")
+    assert stats[:3] == (3, 7, 1)
+    assert diff <= 100 * REJECTING_SPREAD
+    c_ref = _chi2_at(g, est)
+    assert np.abs(chi2 - c_ref).max() <= 1e-6 * max(1.0, c_ref.max()) + 1e-12
+    again = ctx.pose_graph_optimize(*K.args(g), iterations=3, solver=1)
+    assert again[0].tobytes() == est.tobytes() and again[1].tobytes() == chi2.tobytes() and again[2] == stats
+
+
 @pytest.mark.parametrize("n", K.SIZES)
 def test_optimiser_matches_the_restatement(ctx, n):
     g = K.graph(n)

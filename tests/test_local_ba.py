@@ -140,6 +140,34 @@ def test_device_local_ba_duplicate_edges_past_42_and_100(orc, seed, n_free, n_pt
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("path", ["device_control", "host_lm", "duplicate_edges"])
+def test_device_local_ba_rejects_trials(orc, monkeypatch, path):
+    """The reject rule of lm_ctrl.h in the control kernel (k_lm_ctrl) and in the host loop (lm_host.h; reached by ORBFE_LBA_HOST_LM=1
+    and, as production reaches it, by a pose that observes a point twice) on 4 keyframes and 40 points whose start is 3 m (sigma) from
+    the optimum: 8 iterations of the first round, none of the second.  The premise comes from the oracle's own count: 12 trials for the
+    8 iterations (10 with the doubled edges).  Chosen on the CPU so that no gain ratio of the oracle's run is within 0.4 of 0: no last
+    bit decides a trial.  Asserts of test_device_local_ba_matches_oracle, and the same bytes on a second call."""
+    from orb_slam2_ros2_amd._lib import Context
+    pr, fixed = _problem(2, 4, 40, 1)
+    pr["points"] = pr["points"] + np.random.default_rng(2).normal(size=pr["points"].shape) * 3.0
+    if path == "duplicate_edges":
+        pr, fixed = _mutate(pr, fixed, "duplicate_edges", np.random.default_rng(2))
+        obs = np.stack([pr["edge_pose"], pr["edge_point"]], 1)
+        assert len(np.unique(obs, axis=0)) < len(obs)
+    o = orc.ba_local_optimize(pr, fixed, 8, 0)
+    assert (tuple(o["iters"]), tuple(o["trials"])) == ((8, 0), (10 if path == "duplicate_edges" else 12, 0))
+    if path == "host_lm":
+        monkeypatch.setenv("ORBFE_LBA_HOST_LM", "1")
+    ctx = Context(640, 480, n_features=500, max_images=1)
+    g = ctx.ba_local_optimize(pr, fixed, 8, 0)
+    again = ctx.ba_local_optimize(pr, fixed, 8, 0)
+    ctx.close()
+    print(f"local BA {path}: poses {_pose_dist(g['poses'], o['poses']):.2e}, points {np.abs(g['points'] - o['points']).max():.2e}")
+    _assert_matches_oracle(g, o, pr, fixed)
+    assert all(np.array_equal(again[k], g[k]) for k in ("poses", "points", "level", "chi2", "bad"))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("seed,n_kf,n_pt,n_fixed", [(14, 48, 2000, 5), (15, 74, 3000, 10), (11, 155, 2500, 5), (12, 101, 1500, 0), (13, 310, 4000, 10)])
 def test_device_local_ba_beyond_100_free_keyframes(orc, seed, n_kf, n_pt, n_fixed):
     """Optimizer::OptimizeLocalMap takes every keyframe covisible with the current one (getConnectedKfs(0), Optimizer.cc:232): no bound.

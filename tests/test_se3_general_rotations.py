@@ -394,6 +394,47 @@ def test_device_pose_only_on_gauged_problems(orc, ctx, seed, n, kernel, gauge, v
     assert np.abs(pose - a["pose"]).max() > 1e-3                      # it moved
 
 
+def _far_start(pose, start_seed=6):
+    """the start pose turned by 0.3 rad about a random axis and moved by 4 m (sigma, per axis)"""
+    rng = np.random.default_rng(start_seed)
+    ax = rng.normal(size=3)
+    ax /= np.linalg.norm(ax)
+    q = S.quat_mul(np.concatenate([np.sin(0.15) * ax, [np.cos(0.15)]]), pose[:4])
+    return np.concatenate([q, pose[4:] + rng.normal(size=3) * 4.0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n,kernel,first", [(10, 40, "reg256", 3), (13, 1025, "reg512", 4), (15, 2100, "memory", 3)])
+def test_device_pose_only_rejects_trials(orc, ctx, seed, n, kernel, first):
+    """The reject rule of lm_ctrl.h and the table of trial dampings (lm6_trial_lambda, entries q >= 1) where they decide the result, in
+    k_pose_only_reg<256> (fewer than 64 edges), k_pose_only_reg<512> and k_pose_only (the kernel follows from n: asserted): the start
+    is metres from the optimum (_far_start), so every round -- each restarts from it -- opens with rejected trials and goes on from the
+    first accepted one.  The premise comes from the oracle's own counts: the very first iteration takes `first` trial steps, all but
+    the last rejected.  Chosen on the CPU, where the oracle's gain ratios of that iteration are -2.63, -1.78, 0.41 (40 edges), -4.32,
+    -3.11, -0.036, 1.34 (1025) and -3.32, -2.30, 0.29 (2100), and every later one up to convergence is at least 0.018 from 0: no last
+    bit decides one of these trials.  (At the minimum every round ends in rejected trials whose gain ratio is chi2 noise over scale +
+    1e-3, as in every pose-only run; neither side moves by them.)  The oracle reaches the pose and the inliers it reaches from the
+    near start (asserted), the device the oracle's within the bounds of test_device_pose_only_on_gauged_problems, with the same
+    bytes on a second call."""
+    assert kernel == ("reg256" if n <= 1024 else "reg512" if n <= 2048 else "memory") and (n < 64) == (seed == 10)
+    p = S.gauge(ba_synth.make_pose_problem(seed=seed, n=n), *S.GAUGES["skew"])
+    near = _args(p)
+    a = dict(near, pose=_far_start(near["pose"]))
+    assert np.linalg.norm(a["pose"][4:] - near["pose"][4:]) > 3.0
+    r_good, r_pose, r_inl, (iterations, trials, first_iteration) = orc.pose_only_optimize(**a, counts=True)
+    assert first_iteration == first and trials > iterations >= 20, (iterations, trials, first_iteration)
+    n_good0, pose0, inl0 = orc.pose_only_optimize(**near)
+    assert np.abs(r_pose - pose0).max() < 1e-8 and np.array_equal(r_inl, inl0) and r_good == n_good0     # it still converges
+    n_good, pose, inl = ctx.pose_only_optimize(**a)
+    print(f"pose-only n={n}: {first_iteration} trials in the first iteration, {trials} for {iterations} iterations in the oracle; "
+          f"device vs oracle {np.abs(pose - r_pose).max():.2e}")
+    assert np.abs(pose - r_pose).max() < 1e-6
+    assert (inl != r_inl).sum() <= 1 and abs(n_good - r_good) <= 1
+    assert not inl[p["outlier"]].any()
+    again = ctx.pose_only_optimize(**a)
+    assert again[0] == n_good and again[1].tobytes() == pose.tobytes() and np.array_equal(again[2], inl)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,n_kf,n_pt,n_fixed,gauge,path", [
     (3, 12, 400, 2, "skew", "registers"), (3, 12, 400, 2, "near_y", "registers"), (14, 48, 2000, 5, "skew", "lmbig"),
