@@ -1110,6 +1110,36 @@ orbfe_status orbfe_search_by_sim3_points_stored(orbfe_ctx* ctx, orbfe_kfstore* s
                                                 int32_t n_levels, float th, float ratio, int32_t dist_threshold, int32_t* best_idx /*[m]*/,
                                                 int32_t* best_dist /*[m]*/);
 
+/* ---- the forward fuse over stored keyframes ----------------------------------------------------------------------------
+ * ORBMatcher::fuse(pkf, mapPoints, map, bLoop, th) (src/ORBMatcher.cc:682-707) of ONE list of m map points into n_kf keyframes of a
+ * store in one call: what LoopClosing::correctLoop (src/LoopClosing.cc:515-517) runs once per neighbour of the current keyframe and
+ * LocalMapping::fuseMapPoints (src/LocalMapping.cc:399) once per new keyframe.  The keyframes are named by id and read where the store
+ * keeps them (features, descriptors, bounds, area grid); only map state goes up: the poses, the point arrays, the scale factors.
+ * best_idx[k][j] is the feature of keyframe k that searchByProjection(pkf_k, {point j}, th, matches, true) (:573-609) puts in its
+ * DMatch, or -1; best_dist[k][j] its distance, 0 with -1.
+ *   usable       usable[j] == 0: -1.  The caller clears it for null, bad and not-in-map points; the "already held by the keyframe"
+ *                filter (:687-701) is live map state and stays with the caller, as does processFuseMps (:623-663)
+ *   isInVision   MapPoint::isInVision (src/MapPoint.cc:141-171) on poses[k] and keyframe k's STORED bounds, in
+ *                orbfe_project_map_points' arithmetic: rejected in this order: z < 0, not (d < max_dist && d > min_dist), not (u < maxU
+ *                && v < maxV && u > minU && v > minV), cosTheta < 0.5
+ *   window       octave o = predictLevel(max_dist, d) clamped to [0, min(7, n_levels - 1)]; radius ((cosTheta > 0.998f ? 2.5f : 4.0f)
+ *                * th) * (sf[o] * sf[o]) in float, in that order; octaves max(0, o - 1) .. min(n_levels - 1, o + 1) (clamped, unlike
+ *                searchBySim3); findFeaturesInArea over the keyframe's grid: rows outer, columns inner, index order inside a cell; no
+ *                filter on the keyframe's features
+ *   best match   getBestMatch (:967-990): first minimum; the second best is never an earlier record, INT_MAX with one candidate
+ *   accepted     the list is not empty && best < dist_threshold && (float)best / (float)second < ratio (both strict, :591)
+ * n_kf in 0 .. ORBFE_FUSE_MAX_KF, m <= 2^20; n_kf * m above ORBFE_FUSE_POINTS_MAX_PAIRS: ORBFE_EBADSIZE.  n_kf == 0 or m == 0: ORBFE_OK,
+ * nothing written.  ORBFE_EBADARG, nothing written: an unknown id, n_levels below the store's, a NULL array with a non-zero count, a
+ * pose entry, th or ratio not finite, a context on another device.  An id may appear twice.  Locks: the context's, then the store's
+ * (shared) for the whole synchronous duration.  One upload, two launches (one thread per pair projects and lists the pairs in vision,
+ * one wave per listed pair searches), one download.  The result does not depend on the order of the list.                            */
+#define ORBFE_FUSE_POINTS_MAX_PAIRS (1 << 22)
+orbfe_status orbfe_fuse_points_into_keyframes_stored(orbfe_ctx* ctx, orbfe_kfstore* store, int32_t n_kf, const uint64_t* kf_ids,
+                                                     const orbfe_fuse_pose* poses /*[n_kf]*/, const orbfe_sim3_points* pts,
+                                                     const orbfe_camera* cam, const float* scale_factors, int32_t n_levels, float th,
+                                                     float ratio, int32_t dist_threshold, int32_t* best_idx /*[n_kf][m]*/,
+                                                     int32_t* best_dist /*[n_kf][m]*/);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */
@@ -1196,6 +1226,9 @@ orbfe_status orbfe_debug_bsr_pcg(orbfe_ctx* ctx, int32_t nb, const int32_t* row_
  * milliseconds of wall time with the stream synchronised after every phase, and ms[4] = kernel launches and copies enqueued (the solver's counted, the few around it per trial a constant).  Only calls
  * made with ORBFE_GBA_PHASES set in the environment are measured; all zero otherwise.  For tools/global_ba_bench.py.                  */
 orbfe_status orbfe_debug_ba_global_phases(double* ms /*[5]*/);
+/* Device milliseconds, between events, of the two kernels of the last orbfe_fuse_points_into_keyframes_stored of this process that ran
+ * with the MATCH stage timed (orbfe_profile_enable): ms[0] the projection, ms[1] the search; zero before.  For tools/fuse_points_bench.py. */
+orbfe_status orbfe_debug_fuse_points_kernels(double* ms /*[2]*/);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,7 @@ BOW_MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i
 BOW_SEARCH_MAX_KF = 64
 BOW_TRACK, BOW_LOOP, BOW_ADD = 0, 1, 2
 FUSE_MAX_KF = 64
+FUSE_POINTS_MAX_PAIRS = 1 << 22
 TRI_REC_DTYPE = np.dtype([("nb", "<i4"), ("q", "<i4"), ("t", "<i4"), ("kind", "<i4"), ("xyz", "<f4", (3,))])
 TRI_MAX_NB = 64
 
@@ -215,6 +216,7 @@ EXPORTS = [
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
+    "orbfe_fuse_points_into_keyframes_stored", "orbfe_debug_fuse_points_kernels",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
     "orbfe_debug_pg_sparse_solve", "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
@@ -357,6 +359,9 @@ def load() -> C.CDLL:
     L.orbfe_search_by_sim3_stored.argtypes = [vp, vp, C.POINTER(Sim3Side), C.POINTER(Sim3Side), vp, f32, i32, vp, C.POINTER(Camera), vp, i32, f32,
                                               f32, i32, vp, i32, C.POINTER(i32)]
     L.orbfe_search_by_sim3_points_stored.argtypes = [vp, vp, u64, C.POINTER(Sim3Points), vp, f32, C.POINTER(Camera), vp, i32, f32, f32, i32, vp, vp]
+    L.orbfe_fuse_points_into_keyframes_stored.argtypes = [vp, vp, i32, vp, vp, C.POINTER(Sim3Points), C.POINTER(Camera), vp, i32, f32, f32, i32, vp,
+                                                          vp]
+    L.orbfe_debug_fuse_points_kernels.argtypes = [vp]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -2013,6 +2018,51 @@ class Context:
         self._check(self.lib.orbfe_search_by_sim3_points_stored(self.h, store.h, int(kf_id), C.byref(p), ptr(mdl), s, C.byref(cm), ptr(sf), len(sf),
                                                                 float(th), float(ratio), int(dist_threshold), ptr(bi), ptr(bd)))
         return bi[:m], bd[:m]
+
+    def fuse_points_into_keyframes_stored(self, store, kf_ids, poses, pts, cam, scale_factors, th, ratio, dist_threshold, out=None):
+        """The forward fuse ORBMatcher::fuse(pkf, mapPoints, map, bLoop, th) of ONE list of map points into the stored keyframes kf_ids in
+        one call (orbfe_fuse_points_into_keyframes_stored).  poses: [(Rcw, tcw)] per keyframe (or dicts with those keys); pts: dict(usable
+        [m], pos [m, 3], view_dir [m, 3], max_dist [m], min_dist [m], desc [m, 32]).  Returns (best_idx [K, m] (-1: none), best_dist [K, m]);
+        out = (best_idx, best_dist) supplies the arrays (a call that fails or has nothing to do leaves them as they are)."""
+        us = np.ascontiguousarray(pts["usable"], np.uint8).reshape(-1)
+        pos = np.ascontiguousarray(pts["pos"], np.float32).reshape(-1, 3)
+        vd = np.ascontiguousarray(pts["view_dir"], np.float32).reshape(-1, 3)
+        mx, mn = np.ascontiguousarray(pts["max_dist"], np.float32), np.ascontiguousarray(pts["min_dist"], np.float32)
+        d = np.ascontiguousarray(pts["desc"], np.uint8).reshape(-1, 32)
+        m = len(us)
+        if not m == len(pos) == len(vd) == len(mx) == len(mn) == len(d):
+            raise ValueError("fuse_points_into_keyframes_stored: the point arrays differ in length")
+        ids = np.ascontiguousarray(kf_ids, np.uint64).reshape(-1)
+        K = len(ids)
+        if len(poses) != K:
+            raise ValueError("fuse_points_into_keyframes_stored: one pose per keyframe")
+        ps = (FusePose * max(K, 1))()
+        for k, pz in enumerate(poses):
+            R, t = (pz["Rcw"], pz["tcw"]) if isinstance(pz, dict) else pz
+            ps[k].Rcw[:] = np.asarray(R, np.float32).reshape(9).tolist()
+            ps[k].tcw[:] = np.asarray(t, np.float32).reshape(3).tolist()
+        p = Sim3Points(m, *[ptr(a).value if m else None for a in (us, pos, vd, mx, mn, d)])
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        cm = Camera(float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), 0.0)
+        if out is None:
+            out = (np.full((K, m), -1, np.int32), np.zeros((K, m), np.int32))
+        bi, bd = out
+        if any(x.size < K * m or not x.flags.c_contiguous or x.dtype != np.int32 for x in out):
+            raise ValueError("fuse_points_into_keyframes_stored: out must be C-contiguous int32 arrays of at least [K, m]")
+        # (kept with the arrays behind them: tools/fuse_points_bench.py times the bare C call with the same arguments)
+        self._fuse_points_args = (self.h, store.h, K, ptr(ids) if K else None, C.cast(ps, C.c_void_p), C.byref(p), C.byref(cm), ptr(sf), len(sf),
+                                  float(np.float32(th)), float(np.float32(ratio)), int(dist_threshold), ptr(bi) if bi.size else None,
+                                  ptr(bd) if bd.size else None)
+        self._fuse_points_keep = (us, pos, vd, mx, mn, d, ids, ps, p, sf, cm, bi, bd)
+        self._check(self.lib.orbfe_fuse_points_into_keyframes_stored(*self._fuse_points_args))
+        return bi, bd
+
+    def fuse_points_kernel_ms(self):
+        """(projection, search): device milliseconds of the two kernels of the last fuse_points_into_keyframes_stored made with the MATCH
+        stage timed (profile_enable)"""
+        ms = np.zeros(2, np.float64)
+        self._check(self.lib.orbfe_debug_fuse_points_kernels(ptr(ms)))
+        return float(ms[0]), float(ms[1])
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -1,7 +1,8 @@
 // area_search_body.h -- findFeaturesInArea (src/Frame.cc:286-311) + getBestMatch (src/ORBMatcher.cc:967-990) of ONE query as one wave
 // runs it over a finished area grid (area_grid_body.h): rows outer, columns inner, index order inside a cell; the candidates that pass
 // the caller's filter wait in LDS until 64 of them make a chunk of the order-dependent fold (match_fold.h).  The one area loop of every
-// guided matcher: k_guided.hip's k_search_area, k_fuse.hip's k_fuse_search and both kernels of k_sim3search.hip; they differ in their
+// guided matcher: k_guided.hip's k_search_area, k_fuse.hip's k_fuse_search, both kernels of k_sim3search.hip and k_fusepoints.hip's
+// k_fusepts_search; they differ in their
 // filter (where a candidate's octave comes from, and what else excludes it), their prologue and their acceptance test, which stay with
 // them.  Every loop is bounded by the grid size or a cell's feature count.
 #pragma once

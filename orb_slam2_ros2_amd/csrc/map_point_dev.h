@@ -3,7 +3,8 @@
 //   A * x            3x3 * 3x1 gemm: float products summed left to right
 //   alpha A x + t    (float)((double)alpha * sum + t) (cv::gemm's alpha / beta; alpha = 1 multiplies exactly)
 //   cv::norm, Mat::dot  double accumulation of float elements
-// The one copy: k_guided.hip's k_project_map_points, k_fuse.hip's k_fuse_visible, k_sim3search.hip.  Every translation unit is built
+// The one copy: k_guided.hip's k_project_map_points, k_fuse.hip's k_fuse_visible, k_sim3search.hip, k_fusepoints.hip's
+// k_fusepts_project.  Every translation unit is built
 // without floating-point contraction (Makefile), which these expressions need.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -9,6 +9,7 @@
 //   orbfe_ba.hip       g2o edge evaluation, normal equations, local BA, pose-only optimisation
 //   orbfe_sim3opt.hip  OptimizeSim3 and its edge probe
 //   orbfe_posegraph.hip  optimizeEssentialGraph (the pose graph of correctLoop) and its edge probe
+//   orbfe_fusepoints.hip  the forward fuse of a list of map points into stored keyframes (the loop fuse of correctLoop)
 //   orbfe_map.hip      map.pb / text maps
 #pragma once
 #include <hip/hip_runtime.h>

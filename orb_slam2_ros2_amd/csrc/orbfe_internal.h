@@ -472,3 +472,28 @@ struct Sim3Points {
   int32_t m;
   float s, R[9], t[3];
 };
+
+// ---- the forward fuse over stored keyframes (k_fusepoints.hip, orbfe_fusepoints.hip) ------------------------------------
+// One target keyframe as the device reads it: its arrays where the keyframe store keeps them, its stored bounds, the pose of the call.
+struct FusePtsKf {
+  const orbfe_keypoint* kps;
+  const uint8_t* desc;
+  const int32_t *cell_off, *cell_feat;
+  int32_t n, rows, cols, clip_w, clip_h, pad;
+  float bounds[4];
+  float R[9], t[3];
+};
+// A pair (k, j) that passed isInVision, with what the projection found: the search does not project again.
+struct FusePtsEntry {
+  int32_t k, j, o;  // keyframe, point, predicted level
+  float u, v, cos_theta;
+};
+// the map points and the scale factors in the call's upload; m points, n_kf keyframes
+struct FusePtsParams {
+  float fx, fy, cx, cy;
+  float th, ratio, log_sf;
+  int32_t dist_threshold, max_level, n_levels, n_kf, m;
+  const uint8_t *usable, *desc;
+  const float *pos, *vdir, *max_dist, *min_dist, *sf;
+};
+#define FUSEPTS_SEARCH_BLOCKS 2048  // k_fusepts_search's fixed grid: 8192 waves, 32 per compute unit of 256

@@ -1,5 +1,5 @@
 // orbfe_kfstore.h -- the keyframe store's record (include/orbfe.h) as its host side (orbfe_kfstore.hip) and the calls
-// that read it (orbfe_fuse.hip, orbfe_tri.hip, orbfe_bowsearch.hip, orbfe_sim3search.hip) see it.
+// that read it (orbfe_fuse.hip, orbfe_tri.hip, orbfe_bowsearch.hip, orbfe_sim3search.hip, orbfe_fusepoints.hip) see it.
 #pragma once
 #include <shared_mutex>
 

@@ -776,6 +776,24 @@ class ORBMatcher {
                                                   mnMinThreshold, bestIdx.data(), bestDist.data()));
     bestIdx.resize(m), bestDist.resize(m);
   }
+  // ORBMatcher::fuse(pkf, mapPoints, map, bLoop, th) (src/ORBMatcher.cc:682-707) of ONE list of map points into the stored keyframes `ids`
+  // in one call (orbfe_fuse_points_into_keyframes_stored): bestIdx[k * m + j] = the feature of keyframe k that
+  // searchByProjection(pkf_k, {point j}, th, matches, true) (:573-609) puts in its DMatch or -1, bestDist its distance.  usable[j] = non-null,
+  // not bad, in the map; the "held by the keyframe" filter (:687-701) and processFuseMps (:623-663) stay with the caller.  poses[k]: getPose.
+  void fusePointsStored(orbfe_ctx* ctx, orbfe_kfstore* store, const std::vector<uint64_t>& ids, const std::vector<orbfe_fuse_pose>& poses,
+                        const LoopPoints& pts, float th, const Intrinsics& K, const std::vector<float>& scaleFactors, std::vector<int32_t>& bestIdx,
+                        std::vector<int32_t>& bestDist) const {
+    const size_t m = pts.usable.size(), n = ids.size() * m;
+    bestIdx.assign(std::max<size_t>(n, 1), -1), bestDist.assign(std::max<size_t>(n, 1), 0);
+    orbfe_sim3_points p = orbfe_sim3_points();
+    p.m = (int32_t)m;
+    p.usable = pts.usable.data(), p.pos = pts.pos.data(), p.view_dir = pts.viewDir.data(), p.max_dist = pts.maxDist.data(), p.min_dist = pts.minDist.data();
+    p.desc = m ? pts.desc[0].data() : nullptr;
+    const orbfe_camera cam = {K.fx, K.fy, K.cx, K.cy, 0, 0, 0, 0, 0, 0};
+    check(ctx, orbfe_fuse_points_into_keyframes_stored(ctx, store, (int32_t)ids.size(), ids.data(), poses.data(), &p, &cam, scaleFactors.data(),
+                                                       (int32_t)scaleFactors.size(), th, mfRatio, mnMinThreshold, bestIdx.data(), bestDist.data()));
+    bestIdx.resize(n), bestDist.resize(n);
+  }
   static void sim3Model(const Sim3& S, float model[12]) {  // orbfe_sim3_iterate's layout: R row-major, then t
     for (int a = 0; a < 9; ++a) model[a] = S.R[a];
     for (int a = 0; a < 3; ++a) model[9 + a] = S.t[a];

@@ -282,6 +282,78 @@ class MatcherExt:
             n_fuse.append(nf)
         return n_fuse, stats
 
+    def fusePointsIntoKeyframes(self, ctx, model, target_kfs, point_ids, store, cam, scale_factors, th=4.0, bLoop=True, search_in=None,
+                                reevaluate=True, max_kf=64, max_pairs=1 << 22):
+        """The loop `for pkf in target_kfs: matcher.fuse(pkf, points, map, bLoop, th)` of LoopClosing::correctLoop (src/LoopClosing.cc:515-517;
+        ORBMatcher::fuse, src/ORBMatcher.cc:682-707) from ONE device call (Context.fuse_points_into_keyframes_stored over the keyframes
+        target_kfs of `store`; search_in(target_kfs, poses, pts, cam, scale_factors, th, ratio, dist_threshold) -> (best_idx, best_dist)
+        replaces it without a device) and a sequential replay on `model`, the small mutable map of fuseIntoKeyframes with, besides:
+            model.in_map(pid)      model.pose(kf) -> (Rcw, tcw)      model.held(kf) -> the good points in kf's slots
+            model.point_arrays(pids) -> the arrays of the call for the points as they are NOW (-1: a null pointer)
+        point_ids: the map points in the caller's order.  More than max_kf keyframes or max_pairs pairs go in several calls, all issued
+        before the replay starts.
+        Why one call is enough: entry (k, j) is a function of point j's position, view direction, distance range and descriptor and of
+        keyframe k's pose, bounds and features.  The poses are fixed before the loop, addObservation changes none of the point's fields,
+        and MapPoint::replace(keep, drop) recomputes only `keep`'s descriptor, normal and depth (src/MapPoint.cc:229-230): an entry is
+        valid exactly while point j has not been the `keep` of a replace since the call.  Per target, in order: vMapPoints = the points
+        the keyframe does not hold NOW (:687-701); those of them that are live-good, in the map and have survived a replace are searched
+        again (one further call with that keyframe alone and their live arrays); the match list in ascending position in vMapPoints;
+        processFuseMps (:623-663) on a snapshot of the keyframe's slots with isBad / getObsNum read live.
+        reevaluate = False uses the stale entries (for tests).
+        Returns (nFuse per target, dict(device_entries, reevaluated, extra_calls))."""
+        def search(kfs, pts):
+            poses = [model.pose(kf) for kf in kfs]
+            if search_in is not None:
+                return search_in(kfs, poses, pts, cam, scale_factors, th, self.mfRatio, self.mnMinThreshold)
+            return ctx.fuse_points_into_keyframes_stored(store, kfs, poses, pts, cam, scale_factors, th, self.mfRatio, self.mnMinThreshold)
+
+        m = len(point_ids)
+        at_call = model.point_arrays(point_ids)
+        per_call = max(1, min(max_kf, max_pairs // max(m, 1)))
+        bi, bd = [], []
+        for k0 in range(0, len(target_kfs), per_call):
+            a, b = search(list(target_kfs[k0:k0 + per_call]), at_call)
+            bi.extend(a)
+            bd.extend(b)
+        survived = set()
+        stats = dict(device_entries=0, reevaluated=0, extra_calls=0)
+        n_fuse = []
+        for k, kf in enumerate(target_kfs):
+            held = model.held(kf)
+            v = [j for j in range(m) if point_ids[j] not in held]                                  # vMapPoints (:695-701), as positions in the list
+            live = [j for j in v if point_ids[j] >= 0 and not model.is_bad(point_ids[j]) and model.in_map(point_ids[j])]
+            again = [j for j in live if point_ids[j] in survived] if reevaluate else []
+            fresh = {}
+            if again:
+                a, b = search([kf], model.point_arrays([point_ids[j] for j in again]))
+                fresh = {j: (int(a[0][q]), int(b[0][q])) for q, j in enumerate(again)}
+                stats["extra_calls"] += 1
+                stats["reevaluated"] += len(again)
+            stats["device_entries"] += len(live) - len(again)
+            where = {j: p for p, j in enumerate(v)}
+            matches = []
+            for j in live:
+                f, d = fresh[j] if j in fresh else (int(bi[k][j]), int(bd[k][j]))
+                if f >= 0:
+                    matches.append((f, where[j], d))
+            f_ids = {q: model.slot(kf, q) for q in set(mt[0] for mt in matches)}                    # fMapPoints (:703): the slots the loop reads
+            nf = 0
+            for q, p, _ in matches:
+                p1, p2 = f_ids[q], point_ids[v[p]]
+                if p2 < 0 or model.is_bad(p2):
+                    continue
+                if p1 < 0 or model.is_bad(p1):
+                    model.set_slot(kf, q, p2)
+                    model.add_observation(p2, kf, q)
+                    nf += 1
+                elif p1 != p2:
+                    keep, drop = (p2, p1) if bLoop or model.n_obs(p1) < model.n_obs(p2) else (p1, p2)
+                    model.replace(keep, drop)
+                    survived.add(keep)
+                    nf += 1
+            n_fuse.append(nf)
+        return n_fuse, stats
+
     def searchForTriangulation(self, ctx, bow_args, kps1, kps2, pose1, pose1_inv, pose2, pose2_inv, k_inv, scale_factors):
         """ORBMatcher::searchForTriangulation (src/ORBMatcher.cc:736-787): searchByBow(pkf1, pkf2, matches, true) -- bow_args are the
         keyword arguments of ORBMatcher.searchByBow for (frame = pkf1, keyframe = pkf2) -- then the mutual epipolar test."""
