@@ -104,6 +104,41 @@ __device__ __forceinline__ int fast_max16(int a, int b) {
 #define FAST_MAX16(a, b) max(a, b)
 #endif
 
+// The necessary test of one pixel per lane: lane masks of  min over the four opposite pairs of max(pair) - v > thr  (mb: every pair has a
+// pixel brighter than v + thr) and of  v - max of min(pair) > thr  (md: ... darker).  In two blocks, the first on the pairs that arrive
+// first, with three registers beside the pixels (the kernel sits at its register limit: r4 is read once and serves as the third);
+// written out as blocks because the compiler puts an s_nop between any two single-instruction asm statements that depend on each
+// other (four per trip: each an issue slot of the wave, like a vector instruction), and the compares write the masks straight into
+// scalar registers.  (The 14 minima / maxima as 16-BIT instructions: see the FAST_SLIDE = 0 form of the trip.  What the trip's time follows --
+// its whole instruction stream, not its vector part --: profiles/NOTES_r9.md §2.)
+#define FAST_VERDICTS_DEF(NAME, THR_CLASS)                                                                                                  \
+  __device__ __forceinline__ void NAME(int r0, int r8, int r4, int r12, int r2, int r10, int r6, int r14, int v, int thr,                 \
+                                       unsigned long long& mb, unsigned long long& md) {                                                  \
+    int lo1, hi1, t0;                                                                                                                      \
+    asm("v_max_u16 %0, %3, %4\n\tv_max_u16 %1, %2, %5\n\tv_min_u16 %0, %0, %1\n\tv_min_u16 %1, %3, %4\n\t"                                 \
+        "v_min_u16 %2, %2, %5\n\tv_max_u16 %1, %1, %2"                                                                                    \
+        : "=&v"(lo1), "=&v"(hi1), "+v"(r4)                                                                                                 \
+        : "v"(r0), "v"(r8), "v"(r12));                                                                                                     \
+    asm("v_max_u16 %4, %5, %6\n\tv_min_u16 %2, %2, %4\n\tv_max_u16 %4, %7, %8\n\tv_min_u16 %2, %2, %4\n\t"                                 \
+        "v_min_u16 %4, %5, %6\n\tv_max_u16 %3, %3, %4\n\tv_min_u16 %4, %7, %8\n\tv_max_u16 %3, %3, %4\n\t"                                 \
+        "v_sub_u32 %2, %2, %9\n\tv_sub_u32 %3, %9, %3\n\tv_cmp_lt_i32 %0, %10, %2\n\tv_cmp_lt_i32 %1, %10, %3"                               \
+        : "=&s"(mb), "=&s"(md), "+v"(lo1), "+v"(hi1), "=&v"(t0)                                                                            \
+        : "v"(r2), "v"(r10), "v"(r6), "v"(r14), "v"(v), THR_CLASS(thr));                                                                   \
+  }
+#if FAST_OPS16
+FAST_VERDICTS_DEF(fast_verdicts_s, "s")  // the wave's threshold
+FAST_VERDICTS_DEF(fast_verdicts_v, "v")  // a lane's: 0x7FFF where the lane holds no interior pixel
+#else
+__device__ __forceinline__ void fast_verdicts_v(int r0, int r8, int r4, int r12, int r2, int r10, int r6, int r14, int v, int thr,
+                                                unsigned long long& mb, unsigned long long& md) {
+  const int lo_of_hi = min(min(max(r0, r8), max(r4, r12)), min(max(r2, r10), max(r6, r14)));
+  const int hi_of_lo = max(max(min(r0, r8), min(r4, r12)), max(min(r2, r10), min(r6, r14)));
+  mb = __ballot(lo_of_hi - v > thr), md = __ballot(v - hi_of_lo > thr);
+}
+#define fast_verdicts_s fast_verdicts_v
+#endif
+#undef FAST_VERDICTS_DEF
+
 __device__ __forceinline__ int mbcnt64(unsigned long long m, int acc) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, (uint32_t)acc));
 }
@@ -320,6 +355,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       nq = 0;
       int nd = 0;
       bool d_overflow = false;
+      bool cell_dual = false;  // (scalar) some pixel of the cell passed the necessary test for both polarities
       {
         const int shift = iw <= 16 ? 4 : (iw <= 32 ? 5 : 6);
         const int lw = 1 << shift, rpi = 64 >> shift;
@@ -329,7 +365,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 #if !FAST_SLIDE
           const int thr_x = ix < iw ? t_pass : 0x7FFF;
           const uint8_t* a0 = P + ly * PP + xa + ix;  // top-left corner of the pixel's 7x7 window
-          const uint32_t e_lane = (uint32_t)ix | ((uint32_t)ly << 7);
+          const uint32_t e_lane = (uint32_t)ix | ((uint32_t)ly << 7), e_lane_b = e_lane | Q_BRIGHT;
           const uint8_t* a = a0;
 #endif
 #if FAST_SLIDE
@@ -341,20 +377,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
           // instructions per wave 1151 -> 927, LDS-array cycles 2680 -> 2438, k_fast alone -0.7 % (rect) / -2.2 % (camera-like) -- and the step
           // within +-0.2 %: the kernel's LDS was not what held the step either.
           {
-            // rows per row group (rpi = 64 >> shift groups).  (With the 30-px grid's patches -- 31 interior rows, pitch 40 -- the two groups sit
-            // 640 bytes apart, i.e. on the same LDS banks, and the scoring trips, which read the survivors of both groups together, take 70 % more
-            // bank-conflict cycles than with r5's row order: 483 against 288 of ~2600 LDS cycles per wave, tools/exp/lds_sq.sh.  One row more in
-            // the first group (17 + 14: 680 bytes apart) does not change that and costs a seventeenth trip per cell: measured slower, dropped.)
-            const int H2 = (ih + rpi - 1) >> (6 - shift);
-            const int row0 = mul24u(ly, H2);
+            // rows per row group (rpi = 64 >> shift groups): Hm = ih / rpi for EVERY group, so that no trip of the loop has a lane without a row;
+            // the ih mod rpi rows left over take one trip of their own below, without the rings.  (Until r9 the groups had ceil(ih / rpi) rows, the
+            // last one fewer, and every trip selected and applied a row mask on the scalar unit.  With the 30-px grid's patches -- 31 interior rows,
+            // pitch 40 -- those groups sat 640 bytes apart, i.e. on the same LDS banks; they now sit 600 apart.)
+            const int Hm = ih >> (6 - shift), rem = ih - Hm * rpi;
+            const int row0 = mul24u(ly, Hm);
             const uint8_t* aw = P + row0 * PP + xa + ix;      // window of the lane's first row
-            const uint32_t e_row0 = (uint32_t)ix | ((uint32_t)row0 << 7);
-            // which lanes hold an interior pixel in trip t -- as SCALAR masks: the columns right of the interior never do (col_mask), the last row
-            // group runs out of rows at t_full = ih - (rpi - 1) H2 (the other groups have all H2), so the verdict masks are cut on the scalar unit
-            // and the threshold stays the wave-uniform t_pass: no per-lane threshold, no vector instruction for the bounds
+            // the lane's entry for the first row of the current seven trips, scored dark / scored bright
+            uint32_t e_d = (uint32_t)ix | ((uint32_t)row0 << 7), e_b = e_d | Q_BRIGHT;
+            // the columns right of the interior hold no pixel: a SCALAR mask, applied once per trip to the union of the two verdicts
             const unsigned long long col_mask = __ballot(ix < iw);
-            const unsigned long long not_last = rpi > 1 ? ((1ull << (64 - lw)) - 1ull) : 0ull;
-            const int t_full = ih - (rpi - 1) * H2;
+            uint16_t* qp = Q + nq;  // where the next survivor goes (kept as an address: one scalar add per trip)
+            // a trip's survivors -> queue.  The common path writes position | (dark ? 0 : Q_BRIGHT) and nothing else: a pixel that passed for
+            // both polarities is listed as dark like any other, and only where a trip holds one (a wave-uniform branch, about one cell in a
+            // hundred takes it at all) do its lanes write their entry again with Q_DUAL set and raise the cell's flag.  md is the mask as the
+            // compare wrote it: for a lane of m it says what the cut mask would.
+            auto append = [&](const unsigned long long mb, const unsigned long long md, const unsigned long long m, const uint32_t ed, const uint32_t eb,
+                              const uint32_t row) __attribute__((always_inline)) {
+              const bool any = __builtin_amdgcn_inverse_ballot_w64(m), pd = __builtin_amdgcn_inverse_ballot_w64(md);
+              if (any) qp[mbcnt64(m, 0)] = (uint16_t)((pd ? ed : eb) + row);  // (position and flag bits never overlap: one select, one add for the row)
+              if (__builtin_expect((mb & md) != 0ull, 0)) {
+                const unsigned long long m2 = mb & md & m;
+                if (__builtin_amdgcn_inverse_ballot_w64(m2)) qp[mbcnt64(m, 0)] = (uint16_t)((ed + row) | Q_DUAL);
+                if (m2) cell_dual = true;
+              }
+              qp += __popcll(m);
+            };
             int w3[7], w1[7], w5[7];
 #pragma unroll
             for (int k = 0; k < 6; ++k) w3[k] = aw[k * PP + 3];
@@ -387,26 +436,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
               (void)w5;
               const int r2 = a[5 * PP + 5], r6 = a[PP + 5];
 #endif
-              const int lo_of_hi = FAST_MIN16(FAST_MIN16(FAST_MAX16(r0, r8), FAST_MAX16(r4, r12)), FAST_MIN16(FAST_MAX16(r2, r10), FAST_MAX16(r6, r14)));
-              const int hi_of_lo = FAST_MAX16(FAST_MAX16(FAST_MIN16(r0, r8), FAST_MIN16(r4, r12)), FAST_MAX16(FAST_MIN16(r2, r10), FAST_MIN16(r6, r14)));
-              const int sb = lo_of_hi - v, sd = v - hi_of_lo;
-              const unsigned long long valid = t < t_full ? col_mask : (col_mask & not_last);
-              const unsigned long long mb = __ballot(sb > t_pass) & valid, md = __ballot(sd > t_pass) & valid;
-              const unsigned long long m = mb | md, m2 = mb & md;
-              const bool any = __builtin_amdgcn_inverse_ballot_w64(m), dual = __builtin_amdgcn_inverse_ballot_w64(m2);
-              const bool pd = __builtin_amdgcn_inverse_ballot_w64(md);
-              const uint32_t eh = e_row0 + ((uint32_t)t << 7);
-              if (any) Q[nq + mbcnt64(m, 0)] = (uint16_t)(eh | (pd ? 0u : Q_BRIGHT) | (dual ? Q_DUAL : 0u));
-              nq += __popcll(m);
+              unsigned long long mb, md;
+              fast_verdicts_s(r0, r8, r4, r12, r2, r10, r6, r14, v, t_pass, mb, md);
+              append(mb, md, (mb | md) & col_mask, e_d, e_b, (uint32_t)k << 7);
             };
-            for (int t0 = 0; t0 < H2; t0 += 7) {
+            // whole turns of the rings run without a bound test per trip (three scalar instructions each), the last Hm mod 7 trips with one
+            int t0 = 0;
+            for (; t0 + 7 <= Hm; t0 += 7) {
 #pragma unroll
-              for (int k = 0; k < 7; ++k) {
-                const int t = t0 + k;
-                if (t >= H2) break;  // wave-uniform
-                trip_s(t, k);
-              }
+              for (int k = 0; k < 7; ++k) trip_s(t0 + k, k);
+              // (both entries step in registers, behind an opaque copy: as e_row0 + (t << 7) the row is a second add in every trip)
+              e_d += 7u << 7, e_b += 7u << 7;
+              asm volatile("" : "+v"(e_d), "+v"(e_b));
             }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+              if (t0 + k >= Hm) break;  // wave-uniform
+              trip_s(t0 + k, k);
+            }
+            if (rem > 0) {  // wave-uniform: rows rpi Hm ... ih - 1, one per row group ly < rem, all nine pixels read; the other lanes get a threshold no margin passes
+              const int iy = min(rpi * Hm + ly, ih - 1);
+              const int thr = (ly < rem && ix < iw) ? t_pass : 0x7FFF;
+              const uint8_t* a = P + iy * PP + xa + ix;
+              const int v = a[3 * PP + 3];
+              const int r0 = a[6 * PP + 3], r8 = a[3], r4 = a[3 * PP + 6], r12 = a[3 * PP];
+              const int r2 = a[5 * PP + 5], r10 = a[PP + 1], r6 = a[PP + 5], r14 = a[5 * PP + 1];
+              unsigned long long mb, md;
+              fast_verdicts_v(r0, r8, r4, r12, r2, r10, r6, r14, v, thr, mb, md);
+              const uint32_t e = (uint32_t)ix | ((uint32_t)iy << 7);
+              append(mb, md, mb | md, e, e | Q_BRIGHT, 0u);
+            }
+            nq = (int)(qp - Q);
           }
 #else
           // every predicate is ONE vector compare whose lane mask feeds the ballot and the branch directly (a predicate built from
@@ -427,9 +487,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             const bool pd = sd > thr;
             const unsigned long long mb = __ballot(sb > thr), md = __ballot(pd);
             const unsigned long long m = mb | md, m2 = mb & md;
-            const bool any = __builtin_amdgcn_inverse_ballot_w64(m), dual = __builtin_amdgcn_inverse_ballot_w64(m2);
-            const uint32_t eh = e_lane + ((uint32_t)y0 << 7);
-            if (any) Q[nq + mbcnt64(m, 0)] = (uint16_t)(eh | (pd ? 0u : Q_BRIGHT) | (dual ? Q_DUAL : 0u));
+            const bool any = __builtin_amdgcn_inverse_ballot_w64(m);
+            if (any) Q[nq + mbcnt64(m, 0)] = (uint16_t)((pd ? e_lane : e_lane_b) + ((uint32_t)y0 << 7));
+            if (__builtin_expect(m2 != 0ull, 0)) {  // wave-uniform: both polarities passed -- listed as dark above, tagged here (see the FAST_SLIDE form)
+              if (__builtin_amdgcn_inverse_ballot_w64(m2)) Q[nq + mbcnt64(m, 0)] = (uint16_t)((e_lane + ((uint32_t)y0 << 7)) | Q_DUAL);
+              cell_dual = true;
+            }
             nq += __popcll(m);
           };
           // lanes right of the interior can never pass (thr_x), so the column test costs nothing per trip; the row test is only needed in
@@ -451,16 +514,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       //         Q for the bright one -- here, in 3.4 trips per cell, not in the test's 15.
       int nc = 0;
       for (int j0 = 0; j0 < nq; j0 += 64) {
-        const bool act = j0 + lane < nq;
+        // (the lanes that hold an entry as a scalar mask, the verdict ONE compare cut by it on the scalar unit: `act && A > t_pass` is
+        //  expanded to 0 / 1 per lane and compared again before its ballot, as in the necessary test)
+        const unsigned long long act_m = ~0ull >> (64 - min(nq - j0, 64));  // (1 ... 64 entries left: a shift by 63 ... 0)
         const uint32_t q = Q[min(j0 + lane, nq - 1)];
         const int ix = Q_IX(q), iy = Q_IY(q);
         const int A = arc_score1<PP>(P + iy * PP + xa + ix, (q & Q_BRIGHT) ? -1 : 1);
-        const bool c = act && A > t_pass;
+        const unsigned long long mc = __ballot(A > t_pass) & act_m;
+        const bool c = __builtin_amdgcn_inverse_ballot_w64(mc);
+        if (!cell_dual) {  // scalar branch, 99 cells in 100: no entry of this cell carries the tag -- keep = c, one ballot
+          if (c) {
+            V[(iy + 1) * PV + ix + 1] = (uint8_t)min(255, A);
+            Q[nc + mbcnt64(mc, 0)] = (uint16_t)q;  // (in place: this trip's entries were all read above, later trips read further back)
+          }
+          nc += __popcll(mc);
+          continue;
+        }
         if (c) V[(iy + 1) * PV + ix + 1] = (uint8_t)min(255, A);
-        const bool dual = act && (q & Q_DUAL);
-        const bool keep = c || dual;
-        const unsigned long long m = __ballot(keep), m2 = __ballot(dual);
-        if (keep) Q[nc + mbcnt64(m, 0)] = (uint16_t)q;  // (in place: this trip's entries were all read above, later trips read further back)
+        const unsigned long long m2 = __ballot((q & Q_DUAL) != 0u) & act_m, m = mc | m2;
+        const bool dual = __builtin_amdgcn_inverse_ballot_w64(m2), keep = __builtin_amdgcn_inverse_ballot_w64(m);
+        if (keep) Q[nc + mbcnt64(m, 0)] = (uint16_t)q;
         nc += __popcll(m);
         if (m2) {
           const int k = __popcll(m2);
