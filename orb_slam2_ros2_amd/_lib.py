@@ -523,30 +523,25 @@ class Vocabulary:
             pass
 
 
-class PnpParams(C.Structure):
+class RansacParams(C.Structure):
+    """orbfe_pnp_params and orbfe_sim3_params: one layout under two names"""
     _fields_ = [("min_set", C.c_int32), ("max_iterations", C.c_int32), ("ratio", C.c_float), ("prob", C.c_float)]
 
 
-class PnPSet:
-    """The PnPSolvers of one relocalisation on one device (orbfe_pnp, include/orbfe.h): problem i has the points
-    [offsets[i], offsets[i + 1]) of xyz (world) / uv (keypoints) / octave.  cam = (fx, fy, cx, cy); params = (min_set, max_iterations,
-    ratio, prob) or None for setRansacParams()'s defaults."""
+PnpParams = Sim3Params = RansacParams
 
-    def __init__(self, offsets, xyz, uv, octave, level_sigma2, cam, params=None, device_id=0):
+
+class _RansacSet:
+    """What PnPSet and Sim3Set share: the handle of a set made by orbfe_<_name>_create, and iterate's marshalling.  A subclass's __init__
+    calls _create; it has _cap (the room for the returned inliers) and shapes what iterate returns."""
+    _name = None
+
+    def _create(self, sizes, *args):
         self.lib = load()
-        o = np.ascontiguousarray(offsets, np.int64)
-        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        u = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
-        oc = np.ascontiguousarray(octave, np.int32).reshape(-1)
-        s2 = np.ascontiguousarray(level_sigma2, np.float32)
-        if len(o) < 1 or o[-1] != len(x) or len(u) != len(x) or len(oc) != len(x):
-            raise ValueError("PnPSet: offsets must end at len(xyz) == len(uv) == len(octave)")
-        self.sizes = np.diff(o)
-        cm = Camera(*(float(v) for v in cam), 0, 0, 0, 0, 0, 0)
-        pp = None if params is None else C.byref(PnpParams(*params))
+        self.sizes = sizes
+        self._fn = {k: getattr(self.lib, f"orbfe_{self._name}_{k}") for k in ("create", "destroy", "iterate", "stats")}
         h = C.c_void_p(None)
-        st = self.lib.orbfe_pnp_create(int(device_id), len(o) - 1, ptr(o), ptr(x), ptr(u), ptr(oc), ptr(s2), len(s2), C.byref(cm), pp,
-                                       C.byref(h))
+        st = self._fn["create"](*args, C.byref(h))
         if st != ORBFE_OK:
             raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
         self.h = h
@@ -557,7 +552,7 @@ class PnPSet:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.orbfe_pnp_destroy(self.h)
+            self._fn["destroy"](self.h)
             self.h = None
 
     def __del__(self):
@@ -566,56 +561,83 @@ class PnPSet:
         except Exception:
             pass
 
-    def iterate(self, problem, n, pose=None, inliers=None):
-        """Ransac::iterate(n, modelRet, bNoMore, vnInlierIndices) of one problem: (ret, no_more, Rcw (3, 3) float32 or None,
-        tcw (3,) float32 or None, inliers int32).  pose: None (empty Mats) or (Rcw, tcw); inliers: the entry list (appended to)."""
-        ent = np.zeros(0, np.int32) if inliers is None else np.ascontiguousarray(inliers, np.int32).reshape(-1)
-        cap = len(ent) + (int(n) + 2) * int(self.sizes[problem]) + 1
-        buf = np.zeros(cap, np.int32)
-        buf[:len(ent)] = ent
-        pz = np.zeros(12, np.float32)
+    def _iterate(self, problem, n, model, inliers, cap):
+        """-> (ret, no_more, the 12 floats or None, inliers int32); model: 12 floats or None, inliers: the entry list or None"""
+        ent = () if inliers is None else np.ascontiguousarray(inliers, np.int32).reshape(-1)
+        cap = self._cap(len(ent), int(n), problem) if cap is None else int(cap)
+        buf = np.empty(max(cap, 1), np.int32)  # (the library writes [0, k), and only that is returned)
+        if len(ent):
+            buf[:len(ent)] = ent
+        mz = np.zeros(12, np.float32)
         has = C.c_int32(0)
-        if pose is not None:
-            pz[:9] = np.asarray(pose[0], np.float32).reshape(9)
-            pz[9:] = np.asarray(pose[1], np.float32).reshape(3)
+        if model is not None:
+            mz[:] = model
             has.value = 1
         k = C.c_int64(len(ent))
         ret, nm = C.c_int32(0), C.c_int32(0)
-        self._check(self.lib.orbfe_pnp_iterate(self.h, int(problem), int(n), ptr(pz), C.byref(has), ptr(buf), C.byref(k), cap, C.byref(ret),
-                                               C.byref(nm)))
-        R, t = (pz[:9].reshape(3, 3).copy(), pz[9:].copy()) if has.value else (None, None)
-        return bool(ret.value), bool(nm.value), R, t, buf[:k.value].copy()
+        self._check(self._fn["iterate"](self.h, int(problem), int(n), ptr(mz), C.byref(has), ptr(buf), C.byref(k), cap, C.byref(ret), C.byref(nm)))
+        return bool(ret.value), bool(nm.value), (mz if has.value else None), buf[:k.value].copy()
 
     def stats(self):
         """(launch sequences, hypotheses evaluated on the device)"""
         a, b = C.c_int64(0), C.c_int64(0)
-        self._check(self.lib.orbfe_pnp_stats(self.h, C.byref(a), C.byref(b)))
+        self._check(self._fn["stats"](self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
 
-def pnp_engine(state=None):
-    """the process-wide PnP sampling engine's state (minstd_rand0's x); with `state`, set it first and return the old one"""
+def _ransac_engine(name, state):
     L = load()
     g = C.c_uint32(0)
     s = None if state is None else C.c_uint32(int(state))
-    st = L.orbfe_pnp_engine(C.byref(g), None if s is None else C.byref(s))
+    st = getattr(L, f"orbfe_{name}_engine")(C.byref(g), None if s is None else C.byref(s))
     if st != ORBFE_OK:
         raise OrbfeError(st, L.orbfe_last_error(None).decode())
     return g.value
 
 
-class Sim3Params(C.Structure):
-    _fields_ = [("min_set", C.c_int32), ("max_iterations", C.c_int32), ("ratio", C.c_float), ("prob", C.c_float)]
+class PnPSet(_RansacSet):
+    """The PnPSolvers of one relocalisation on one device (orbfe_pnp, include/orbfe.h): problem i has the points
+    [offsets[i], offsets[i + 1]) of xyz (world) / uv (keypoints) / octave.  cam = (fx, fy, cx, cy); params = (min_set, max_iterations,
+    ratio, prob) or None for setRansacParams()'s defaults."""
+    _name = "pnp"
+
+    def __init__(self, offsets, xyz, uv, octave, level_sigma2, cam, params=None, device_id=0):
+        o = np.ascontiguousarray(offsets, np.int64)
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        oc = np.ascontiguousarray(octave, np.int32).reshape(-1)
+        s2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(o) < 1 or o[-1] != len(x) or len(u) != len(x) or len(oc) != len(x):
+            raise ValueError("PnPSet: offsets must end at len(xyz) == len(uv) == len(octave)")
+        cm = Camera(*(float(v) for v in cam), 0, 0, 0, 0, 0, 0)
+        pp = None if params is None else C.byref(PnpParams(*params))
+        self._create(np.diff(o), int(device_id), len(o) - 1, ptr(o), ptr(x), ptr(u), ptr(oc), ptr(s2), len(s2), C.byref(cm), pp)
+
+    def _cap(self, n_entry, n, problem):  # P1: the list piles up every hypothesis's inliers
+        return n_entry + (n + 2) * int(self.sizes[problem]) + 1
+
+    def iterate(self, problem, n, pose=None, inliers=None):
+        """Ransac::iterate(n, modelRet, bNoMore, vnInlierIndices) of one problem: (ret, no_more, Rcw (3, 3) float32 or None,
+        tcw (3,) float32 or None, inliers int32).  pose: None (empty Mats) or (Rcw, tcw); inliers: the entry list (appended to)."""
+        if pose is not None:
+            pose = np.concatenate([np.asarray(pose[0], np.float32).reshape(9), np.asarray(pose[1], np.float32).reshape(3)])
+        ret, nm, m, inl = self._iterate(problem, n, pose, inliers, None)
+        return ret, nm, (None if m is None else m[:9].reshape(3, 3).copy()), (None if m is None else m[9:].copy()), inl
 
 
-class Sim3Set:
+def pnp_engine(state=None):
+    """the process-wide PnP sampling engine's state (minstd_rand0's x); with `state`, set it first and return the old one"""
+    return _ransac_engine("pnp", state)
+
+
+class Sim3Set(_RansacSet):
     """The Sim3Solvers of one LoopClosing::computeSim3 call on one device (orbfe_sim3, include/orbfe.h): problem i has the
     correspondences [offsets[i], offsets[i + 1]) of pos_p / pos_q (world positions of the two map points) and octave_p / octave_q, and
     the keyframe poses pose_p[i] / pose_q[i] (12 floats: R row-major, then t).  cam = (fx, fy, cx, cy); params = (min_set,
     max_iterations, ratio, prob) or None for Sim3Solver::create's defaults (min_set must be 3)."""
+    _name = "sim3"
 
     def __init__(self, offsets, pos_p, pos_q, octave_p, octave_q, pose_p, pose_q, level_sigma2, cam, params=None, device_id=0):
-        self.lib = load()
         o = np.ascontiguousarray(offsets, np.int64)
         xp = np.ascontiguousarray(pos_p, np.float32).reshape(-1, 3)
         xq = np.ascontiguousarray(pos_q, np.float32).reshape(-1, 3)
@@ -628,55 +650,19 @@ class Sim3Set:
             raise ValueError("Sim3Set: offsets must end at len(pos_p) == len(pos_q) == len(octave_p) == len(octave_q)")
         if len(tp) != len(o) - 1 or len(tq) != len(o) - 1:
             raise ValueError("Sim3Set: one pose_p and one pose_q per problem")
-        self.sizes = np.diff(o)
         cm = Camera(*(float(v) for v in cam), 0, 0, 0, 0, 0, 0)
         pp = None if params is None else C.byref(Sim3Params(*params))
-        h = C.c_void_p(None)
-        st = self.lib.orbfe_sim3_create(int(device_id), len(o) - 1, ptr(o), ptr(xp), ptr(xq), ptr(op), ptr(oq), ptr(tp), ptr(tq), ptr(s2),
-                                        len(s2), C.byref(cm), pp, C.byref(h))
-        if st != ORBFE_OK:
-            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
-        self.h = h
+        self._create(np.diff(o), int(device_id), len(o) - 1, ptr(o), ptr(xp), ptr(xq), ptr(op), ptr(oq), ptr(tp), ptr(tq), ptr(s2), len(s2),
+                     C.byref(cm), pp)
 
-    def _check(self, st):
-        if st != ORBFE_OK:
-            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.orbfe_sim3_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _cap(self, n_entry, n, problem):  # S2: a list is one hypothesis's inliers
+        size = int(self.sizes[problem]) if 0 <= int(problem) < len(self.sizes) else 0  # out of range: the library refuses it
+        return max(n_entry, size) + 1
 
     def iterate(self, problem, n, model=None, inliers=None, cap=None):
         """Ransac::iterate(n, modelRet, bNoMore, vnInlierIndices) of one problem: (ret, no_more, model float32[12] (Rqp row-major, then
         tqp; the scale is 1) or None, inliers int32).  model / inliers: the entry state, returned untouched when no hypothesis ran."""
-        ent = np.zeros(0, np.int32) if inliers is None else np.ascontiguousarray(inliers, np.int32).reshape(-1)
-        size = int(self.sizes[problem]) if 0 <= int(problem) < len(self.sizes) else 0  # out of range: the library refuses it
-        cap = max(len(ent), size) + 1 if cap is None else int(cap)
-        buf = np.zeros(max(cap, 1), np.int32)
-        buf[:len(ent)] = ent
-        mz = np.zeros(12, np.float32)
-        has = C.c_int32(0)
-        if model is not None:
-            mz[:] = np.asarray(model, np.float32).reshape(12)
-            has.value = 1
-        k = C.c_int64(len(ent))
-        ret, nm = C.c_int32(0), C.c_int32(0)
-        self._check(self.lib.orbfe_sim3_iterate(self.h, int(problem), int(n), ptr(mz), C.byref(has), ptr(buf), C.byref(k), cap, C.byref(ret),
-                                                C.byref(nm)))
-        return bool(ret.value), bool(nm.value), (mz.copy() if has.value else None), buf[:k.value].copy()
-
-    def stats(self):
-        """(launch sequences, hypotheses evaluated on the device)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        self._check(self.lib.orbfe_sim3_stats(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._iterate(problem, n, None if model is None else np.asarray(model, np.float32).reshape(12), inliers, cap)
 
     def profile(self, enable=None):
         """(device microseconds between the events around the launches, bytes uploaded by create and the speculations) so far;
@@ -689,13 +675,7 @@ class Sim3Set:
 def sim3_engine(state=None):
     """the process-wide Sim3 sampling engine's state (Ransac<Sim3Ret>'s own minstd_rand0, apart from pnp_engine's); with `state`, set
     it first and return the old one"""
-    L = load()
-    g = C.c_uint32(0)
-    s = None if state is None else C.c_uint32(int(state))
-    st = L.orbfe_sim3_engine(C.byref(g), None if s is None else C.byref(s))
-    if st != ORBFE_OK:
-        raise OrbfeError(st, L.orbfe_last_error(None).decode())
-    return g.value
+    return _ransac_engine("sim3", state)
 
 
 class KeyFrameDB:

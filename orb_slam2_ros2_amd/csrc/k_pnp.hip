@@ -643,14 +643,14 @@ __device__ void append_mask(PnpLds& S, const uint64_t* mask, int words, int* lis
   __syncthreads();
 }
 
-__global__ __launch_bounds__(PNP_HYP_WG) void k_pnp_hyp(const PnpHyp* __restrict__ hyps, const PnpProb* __restrict__ probs,
+__global__ __launch_bounds__(PNP_HYP_WG) void k_pnp_hyp(const PnpHyp* __restrict__ hyps, const RansacProb* __restrict__ probs,
                                                         const float* __restrict__ xyz, const float* __restrict__ uv,
                                                         const float* __restrict__ thr, PnpCam cam, PnpOut* __restrict__ out,
                                                         uint64_t* __restrict__ masks) {
   __shared__ PnpLds S;
   const int tid = threadIdx.x, h = blockIdx.x;
   const PnpHyp& H = hyps[h];
-  const PnpProb pr = probs[H.prob];
+  const RansacProb pr = probs[H.prob];
   const float* X = xyz + 3 * (int64_t)pr.off;
   const float* Q = uv + 2 * (int64_t)pr.off;
   if (H.given) {
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(PNP_HYP_WG) void k_pnp_hyp(const PnpHyp* __restrict
 }
 
 __global__ __launch_bounds__(PNP_CALL_WG) void k_pnp_call(const PnpCall* __restrict__ calls, const PnpHyp* __restrict__ hyps,
-                                                          const PnpProb* __restrict__ probs, const float* __restrict__ xyz,
+                                                          const RansacProb* __restrict__ probs, const float* __restrict__ xyz,
                                                           const float* __restrict__ uv, const float* __restrict__ thr, PnpCam cam,
                                                           const int* __restrict__ entry, PnpOut* __restrict__ out,
                                                           const uint64_t* __restrict__ masks, uint64_t* __restrict__ ref_masks,
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(PNP_CALL_WG) void k_pnp_call(const PnpCall* __restr
   __shared__ PnpLds S;
   const int tid = threadIdx.x;
   const PnpCall C = calls[blockIdx.x];
-  const PnpProb pr = probs[C.prob];
+  const RansacProb pr = probs[C.prob];
   const float* X = xyz + 3 * (int64_t)pr.off;
   const float* Q = uv + 2 * (int64_t)pr.off;
   const float* T = thr + pr.off;
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(PNP_CALL_WG) void k_pnp_call(const PnpCall* __restr
 
 }  // namespace
 
-void launch_pnp(hipStream_t st, const PnpHyp* hyps, int n_hyp, const PnpCall* calls, int n_calls, const PnpProb* probs, const float* xyz,
+void launch_pnp(hipStream_t st, const PnpHyp* hyps, int n_hyp, const PnpCall* calls, int n_calls, const RansacProb* probs, const float* xyz,
                 const float* uv, const float* thr, const float cam[4], const int* entry, PnpOut* out, uint64_t* masks, uint64_t* ref_masks,
                 int* lists) {
   const PnpCam c{cam[0], cam[1], cam[2], cam[3]};

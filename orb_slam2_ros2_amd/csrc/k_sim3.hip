@@ -152,14 +152,14 @@ __device__ int stage_chunk(Sim3Lds& S, int w0, int words, const float* __restric
   return k;
 }
 
-__global__ __launch_bounds__(SIM3_WG) void k_sim3_hyp(const Sim3Hyp* __restrict__ hyps, const Sim3Prob* __restrict__ probs,
+__global__ __launch_bounds__(SIM3_WG) void k_sim3_hyp(const Sim3Hyp* __restrict__ hyps, const RansacProb* __restrict__ probs,
                                                       const float* __restrict__ pq, const float* __restrict__ px,
                                                       const float* __restrict__ thr, Sim3Cam cam, Sim3Out* __restrict__ out,
                                                       uint64_t* __restrict__ masks, uint64_t* __restrict__ ref_masks) {
   __shared__ Sim3Lds S;
   const int lane = threadIdx.x, h = blockIdx.x;
   const Sim3Hyp H = hyps[h];
-  const Sim3Prob pr = probs[H.prob];
+  const RansacProb pr = probs[H.prob];
   const float* PQ = pq + 6 * (int64_t)pr.off;
   const float* PX = px + 4 * (int64_t)pr.off;
   const float* T = thr + 2 * (int64_t)pr.off;
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(SIM3_WG) void k_sim3_hyp(const Sim3Hyp* __restrict_
 
 }  // namespace
 
-void launch_sim3(hipStream_t st, const Sim3Hyp* hyps, int n_hyp, const Sim3Prob* probs, const float* pq, const float* px, const float* thr,
+void launch_sim3(hipStream_t st, const Sim3Hyp* hyps, int n_hyp, const RansacProb* probs, const float* pq, const float* px, const float* thr,
                  const float cam[4], Sim3Out* out, uint64_t* masks, uint64_t* ref_masks) {
   const Sim3Cam c{cam[0], cam[1], cam[2], cam[3]};
   if (n_hyp > 0)

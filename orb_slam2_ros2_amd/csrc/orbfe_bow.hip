@@ -313,8 +313,7 @@ orbfe_status orbfe_vocab_export(const orbfe_vocab* v, int32_t* parent, uint8_t* 
 
 void orbfe_vocab_destroy(orbfe_vocab* v) {
   if (!v) return;
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+  DeviceScope restore;  // the caller's current device, as it was
   for (int d = 0; d < kMaxDevices; ++d) {
     orbfe_vocab::Dev& x = v->dev[d];
     if (!x.rec && !x.desc && !x.weight) continue;
@@ -323,7 +322,6 @@ void orbfe_vocab_destroy(orbfe_vocab* v) {
     (void)hipFree(x.desc);
     (void)hipFree(x.weight);
   }
-  if (have_cur) (void)hipSetDevice(cur);  // the caller's current device, as it was
   delete v;
 }
 

@@ -398,6 +398,22 @@ static orbfe_status dev_alloc(orbfe_ctx* c, T** p, size_t count) {
   HIP_TRY(c, hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
   return ORBFE_OK;
 }
+// A device made current for the duration of a call that has no context (the sets, the database, the store, the vocabulary): every exit
+// path leaves the caller's current device as it found it.  err: what hipSetDevice returned.  Without a device it only puts the caller's back.
+struct DeviceScope {
+  int prev = -1;
+  bool have = false;
+  hipError_t err = hipSuccess;
+  explicit DeviceScope(int dev = -1) {
+    have = hipGetDevice(&prev) == hipSuccess;
+    if (dev >= 0) err = hipSetDevice(dev);
+  }
+  ~DeviceScope() {
+    if (have) (void)hipSetDevice(prev);
+  }
+  DeviceScope(const DeviceScope&) = delete;
+  DeviceScope& operator=(const DeviceScope&) = delete;
+};
 #define TRY(expr)                          \
   do {                                     \
     orbfe_status st_ = (expr);             \

@@ -289,12 +289,14 @@ struct KfdbRec {
   double score;
 };
 
-// ---- EPnP RANSAC (k_pnp.hip, orbfe_pnp.hip) ---------------------------------------------------------------------------------------
-// One problem (PnPSolver) of a set: its points at [off, off + n) of the set's xyz / uv / threshold arrays, an inlier mask of `words`
-// uint64 words, mnMinInlier.
-struct PnpProb {
+// ---- RANSAC sets (k_pnp.hip, k_sim3.hip, ransac_host.h) ---------------------------------------------------------------------------
+// One problem (a PnPSolver or a Sim3Solver) of a set: its points or correspondences at [off, off + n) of the set's per-point arrays, an
+// inlier mask of `words` uint64 words, mnMinInlier.
+struct RansacProb {
   int32_t off, n, words, min_inlier;
 };
+
+// ---- EPnP RANSAC (k_pnp.hip, orbfe_pnp.hip) ---------------------------------------------------------------------------------------
 // One hypothesis of a speculated schedule: four problem-local sample indices or, with given = 1, a pose to count (the entry pose of the
 // first call).  Its inlier mask sits at mask_off (in words) of the hypothesis masks, its refine mask at the same place of the refine masks.
 struct PnpHyp {
@@ -318,11 +320,6 @@ struct PnpOut {
 };
 
 // ---- Sim3 RANSAC (k_sim3.hip, orbfe_sim3.hip) -------------------------------------------------------------------------------------
-// One problem (Sim3Solver) of a set: its correspondences at [off, off + n) of the set's arrays, an inlier mask of `words` uint64 words,
-// mnMinInlier.
-struct Sim3Prob {
-  int32_t off, n, words, min_inlier;
-};
 // One hypothesis of a speculated schedule: three problem-local sample indices.  Its inlier mask sits at mask_off (in words) of the
 // hypothesis masks, its refine mask at the same place of the refine masks.
 struct Sim3Hyp {

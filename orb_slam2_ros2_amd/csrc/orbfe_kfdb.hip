@@ -175,18 +175,16 @@ orbfe_status orbfe_kfdb_create(int32_t device_id, int32_t n_words, orbfe_kfdb** 
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, ORBFE_EDEVICE, "orbfe_kfdb_create: no HIP device (this library has no CPU fallback)");
   if (device_id < 0 || device_id >= ndev) return fail(nullptr, ORBFE_EBADARG, "orbfe_kfdb_create: device %d of %d", device_id, ndev);
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
   std::unique_ptr<orbfe_kfdb> db(new (std::nothrow) orbfe_kfdb());
   if (!db) return fail(nullptr, ORBFE_ENOMEM, "orbfe_kfdb_create: out of memory");
   db->device = device_id;
   db->n_words = n_words;
   orbfe_status st = ORBFE_OK;
-  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking) != hipSuccess)
+  DeviceScope dev(device_id);
+  if (dev.err != hipSuccess || hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking) != hipSuccess)
     st = fail(nullptr, ORBFE_EDEVICE, "orbfe_kfdb_create: cannot create a stream on device %d", device_id);
   if (st == ORBFE_OK) st = reserve_slots(db.get(), 1024);
   if (st == ORBFE_OK) st = reserve_pool(db.get(), 0);
-  if (have_cur) (void)hipSetDevice(cur);
   if (st != ORBFE_OK) {
     orbfe_kfdb_destroy(db.release());
     return st;
@@ -197,14 +195,11 @@ orbfe_status orbfe_kfdb_create(int32_t device_id, int32_t n_words, orbfe_kfdb** 
 
 void orbfe_kfdb_destroy(orbfe_kfdb* db) {
   if (!db) return;
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-  (void)hipSetDevice(db->device);
+  DeviceScope dev(db->device);
   for (void* p : {(void*)db->d_slots, (void*)db->d_counts, (void*)db->d_words, (void*)db->d_values, (void*)db->d_io})
     if (p) (void)hipFree(p);
   if (db->h_io) (void)hipHostFree(db->h_io);
   if (db->stream) (void)hipStreamDestroy(db->stream);
-  if (have_cur) (void)hipSetDevice(cur);
   delete db;
 }
 
@@ -237,16 +232,8 @@ orbfe_status orbfe_kfdb_add(orbfe_kfdb* db, int32_t n_kf, const uint64_t* ids, c
       extra += (uint64_t)(offsets[i + 1] - offsets[i]);
     }
   if (todo.empty()) return ORBFE_OK;
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-  HIP_TRY(nullptr, hipSetDevice(db->device));
-  struct Restore {
-    bool on;
-    int d;
-    ~Restore() {
-      if (on) (void)hipSetDevice(d);
-    }
-  } restore{have_cur, cur};
+  DeviceScope dev(db->device);
+  HIP_TRY(nullptr, dev.err);
   const size_t reuse = std::min(todo.size(), db->free_slots.size());
   TRY(reserve_slots(db, db->slots.size() + (todo.size() - reuse)));
   TRY(reserve_pool(db, extra));
@@ -305,12 +292,9 @@ orbfe_status orbfe_kfdb_set_bad(orbfe_kfdb* db, int32_t n, const uint64_t* ids, 
   if (changed.empty()) return ORBFE_OK;
   std::sort(changed.begin(), changed.end());
   changed.erase(std::unique(changed.begin(), changed.end()), changed.end());
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-  HIP_TRY(nullptr, hipSetDevice(db->device));
-  const orbfe_status st = push_slots(db, changed);
-  if (have_cur) (void)hipSetDevice(cur);
-  return st;
+  DeviceScope dev(db->device);
+  HIP_TRY(nullptr, dev.err);
+  return push_slots(db, changed);
 }
 
 orbfe_status orbfe_kfdb_erase(orbfe_kfdb* db, int32_t n, const uint64_t* ids) {
@@ -328,12 +312,9 @@ orbfe_status orbfe_kfdb_erase(orbfe_kfdb* db, int32_t n, const uint64_t* ids) {
     changed.push_back((uint32_t)s);
   }
   if (changed.empty()) return ORBFE_OK;
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-  HIP_TRY(nullptr, hipSetDevice(db->device));
-  const orbfe_status st = push_slots(db, changed);
-  if (have_cur) (void)hipSetDevice(cur);
-  return st;
+  DeviceScope dev(db->device);
+  HIP_TRY(nullptr, dev.err);
+  return push_slots(db, changed);
 }
 
 orbfe_status orbfe_kfdb_size(orbfe_kfdb* db, int64_t* out) {

@@ -11,19 +11,6 @@ namespace {
 
 const size_t kDefaultSlab = (size_t)32 << 20;
 
-struct DeviceScope {  // the store's device for the duration of a call that has no context
-  int prev = -1;
-  bool have = false;
-  hipError_t err;
-  explicit DeviceScope(int dev) {
-    have = hipGetDevice(&prev) == hipSuccess;
-    err = hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (have) (void)hipSetDevice(prev);
-  }
-};
-
 // a block of `bytes`, from a new slab if the existing ones have no room
 orbfe_status take_block(orbfe_kfstore* s, size_t bytes, KfBlock* b, uint8_t** base) {
   if (!s->alloc.take(bytes, b)) {
