@@ -1140,6 +1140,83 @@ orbfe_status orbfe_fuse_points_into_keyframes_stored(orbfe_ctx* ctx, orbfe_kfsto
                                                      float ratio, int32_t dist_threshold, int32_t* best_idx /*[n_kf][m]*/,
                                                      int32_t* best_dist /*[n_kf][m]*/);
 
+/* ---- the relocalisation refine over a stored keyframe -------------------------------------------------------------------
+ * What Tracking::trackReLocalize does with ONE PnP hypothesis (src/Tracking.cc:565-584, addMatchByProject :612-629) as one call:
+ * setCurrFrameAttrib's map points, Optimizer::OptimizePoseOnly with its projection post-check (src/Optimizer.cc:33-203), the 10 / 50
+ * decisions, ORBMatcher::searchByProjection(frame, keyframe, matches, th) (src/ORBMatcher.cc:265-347, bFuse == false) with th_first,
+ * OptimizePoseOnly again, the search with th_second.  The frame's features are the device-resident results of `slot`, the keyframe's
+ * features, descriptors and octaves are read where the store keeps them; only map state goes up.
+ *   seed        the edges are the features f with held[f] >= 0 and good[held[f]], in feature order; the initial estimate is
+ *               Converter::ConvertTcw2SE3 of (Rcw, tcw) in fp64 (Eigen's trace / largest-diagonal branches, normalised twice, w >= 0)
+ *   optimise    orbfe_pose_only_optimize's kernel on the device-built edge list
+ *   post-check  VirtualFrame::project2UV with the pose the frame still has -- setPose comes last (Optimizer.cc:201): the PnP pose in the
+ *               first optimisation, Tcw[0] in the second: p = Rcw * X + tcw as orbfe_project_map_points computes it, u = x / z * fx +
+ *               cx, v = y / z * fy + cy in float; an inlier edge is dropped when !(z > 0) || u > max_u || u < 0 || v > max_v || v < 0;
+ *               n_inliers = edges - nBad; every feature that is no inlier loses its point; Tcw = Converter::ConvertSE32Tcw of the
+ *               estimate is the frame's pose from here on
+ *   decide #1   n_inliers < min_inliers: REJECT_1; n_inliers >= enough: ACCEPT_1; else search #1
+ *   search      twc = -(Rcw^T tcw), tlc = kf_Rcw twc + kf_tcw in float, a row times a vector summed left to right (tlc_z = tlc[2]);
+ *               |tlc_z| > baseline: forward (tlc_z > 0, octaves [o, 7]) or backward ([0, o]), else [max(0, o - 1), min(o + 1, 7)];
+ *               queries = the keyframe's features i with good[i], in index order, radius th * level_sigma2[o]; candidates = the frame's
+ *               features of the window that hold no point (one excluded_hit per occurrence of one that does); getBestMatch; accepted when
+ *               the list is not empty && (float)best / (float)second < ratio && best < min_threshold; setMapPoints in query order, the
+ *               last query that picked a feature keeps it; n_added = the accepted queries
+ *   decide #2   n_added[0] + n_inliers[0] < enough: REJECT_2; else optimise #2 from ConvertTcw2SE3 of Tcw[0] on what the frame holds
+ *               now, and the post-check again
+ *   decide #3   n_inliers[1] >= enough: ACCEPT_2; else search #2 with th_second and Tcw[1]; n_added[1] + n_inliers[1] < enough:
+ *               REJECT_3, else ACCEPT_3
+ * Outputs per stage s (0: first optimisation and search, 1: second): n_edges[s], n_inliers[s], inlier[s][f] (after the post-check),
+ * pose_se3[s] (the estimate, qx qy qz qw tx ty tz), Tcw[s] (Rcw row-major, then tcw), tlc_z[s], n_added[s], assigned[s][f] (the keyframe
+ * feature whose point frame feature f holds after search s, -1 none), excluded_hits[s][f], query_accepted[s][i]; final_assigned[f] is
+ * what the frame holds when the verdict falls.  A stage that did not run leaves zeros, -1 in assigned.  Every output array is required.
+ * ORBFE_EBADARG, nothing written: an unknown id, n unequal to the stored count, held[f] outside [-1, n), a pose, bounds or camera entry
+ * not finite, the context's n_levels below the store's, a NULL array, a context on another device.  ORBFE_EBADSIZE: a context of more
+ * than 2048 features.  Locks: the context's, then the store's (shared) for the whole synchronous duration.  One upload, one launch
+ * sequence whose kernels leave at once after the verdict has fallen, one download; no synchronisation in between.                      */
+typedef enum orbfe_reloc_verdict {
+  ORBFE_RELOC_REJECT_1 = 1, /* fewer than min_inliers after the first optimisation (Tracking.cc:567)            */
+  ORBFE_RELOC_ACCEPT_1 = 2, /* at least `enough` after the first optimisation (:579-584)                       */
+  ORBFE_RELOC_REJECT_2 = 3, /* the first search added too few (:619)                                           */
+  ORBFE_RELOC_ACCEPT_2 = 4, /* at least `enough` after the second optimisation (:622)                          */
+  ORBFE_RELOC_REJECT_3 = 5, /* the second search added too few (:625)                                          */
+  ORBFE_RELOC_ACCEPT_3 = 6
+} orbfe_reloc_verdict;
+typedef struct orbfe_reloc_input {
+  uint64_t kf_id;                /* the candidate keyframe in the store                                                   */
+  int32_t n;                     /* must equal the stored count                                                           */
+  const uint8_t* good;           /* [n] the keyframe feature's map point is non-null and not bad                          */
+  const float* pos;              /* [n][3] MapPoint::getPos() (read where good)                                           */
+  float kf_Rcw[9], kf_tcw[3];    /* the keyframe's pose                                                                   */
+  const int32_t* held;           /* [n_features] keyframe feature whose point setCurrFrameAttrib gives frame feature f, -1 */
+  const double* right_u;         /* [n_features], nullable (every edge mono)                                              */
+  float Rcw[9], tcw[3];          /* the PnP pose                                                                          */
+  float bounds[4];               /* the frame's mfMinU mfMaxU mfMinV mfMaxV                                               */
+  const float* level_sigma2;     /* [n_levels of the context]                                                             */
+  const float* level_inv_sigma2; /* [n_levels of the context]                                                             */
+  const orbfe_camera* cam;       /* fx fy cx cy bf (an undistorting camera: the features of the slot are the undistorted ones) */
+  float baseline;                /* Camera::mfBl                                                                          */
+  float th_first, th_second;     /* 10, 3 (Tracking.cc:618, 624)                                                          */
+  float ratio;                   /* ORBMatcher::mfRatio (0.9)                                                             */
+  int32_t min_threshold;         /* ORBMatcher::mnMinThreshold                                                            */
+  int32_t min_inliers, enough;   /* 10, 50                                                                                */
+} orbfe_reloc_input;
+typedef struct orbfe_reloc_output {
+  int32_t* verdict;          /* [1] orbfe_reloc_verdict     */
+  int32_t* n_edges;          /* [2]                         */
+  int32_t* n_inliers;        /* [2]                         */
+  int32_t* n_added;          /* [2]                         */
+  float* tlc_z;              /* [2]                         */
+  double* pose_se3;          /* [2][7]                      */
+  float* Tcw;                /* [2][12]                     */
+  uint8_t* inlier;           /* [2][n_features]             */
+  int32_t* assigned;         /* [2][n_features]             */
+  int32_t* final_assigned;   /* [n_features]                */
+  int32_t* excluded_hits;    /* [2][n_features]             */
+  uint8_t* query_accepted;   /* [2][n]                      */
+} orbfe_reloc_output;
+orbfe_status orbfe_reloc_refine_stored(orbfe_ctx* ctx, int32_t slot, orbfe_kfstore* store, const orbfe_reloc_input* in,
+                                       const orbfe_reloc_output* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

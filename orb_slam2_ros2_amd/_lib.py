@@ -108,6 +108,22 @@ class TrackOutput(C.Structure):
                 ("n_good", C.c_void_p), ("pose_out", C.c_void_p)]
 
 
+class RelocInput(C.Structure):
+    _fields_ = [("kf_id", C.c_uint64), ("n", C.c_int32), ("good", C.c_void_p), ("pos", C.c_void_p), ("kf_Rcw", C.c_float * 9),
+                ("kf_tcw", C.c_float * 3), ("held", C.c_void_p), ("right_u", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
+                ("bounds", C.c_float * 4), ("level_sigma2", C.c_void_p), ("level_inv_sigma2", C.c_void_p), ("cam", C.POINTER(Camera)),
+                ("baseline", C.c_float), ("th_first", C.c_float), ("th_second", C.c_float), ("ratio", C.c_float),
+                ("min_threshold", C.c_int32), ("min_inliers", C.c_int32), ("enough", C.c_int32)]
+
+
+class RelocOutput(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("verdict", "n_edges", "n_inliers", "n_added", "tlc_z", "pose_se3", "Tcw", "inlier", "assigned",
+                                          "final_assigned", "excluded_hits", "query_accepted")]
+
+
+RELOC_VERDICTS = {1: "REJECT_1", 2: "ACCEPT_1", 3: "REJECT_2", 4: "ACCEPT_2", 5: "REJECT_3", 6: "ACCEPT_3"}
+
+
 class MapSummary(C.Structure):
     _fields_ = [("next_id", C.c_uint64), ("n_scale_factors", C.c_int32), ("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32),
                 ("n_keypoints", C.c_int64), ("n_observations", C.c_int64)]
@@ -216,7 +232,7 @@ EXPORTS = [
     "orbfe_kfstore_create", "orbfe_kfstore_destroy", "orbfe_kfstore_add", "orbfe_kfstore_add_from_slot", "orbfe_kfstore_set_bow",
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
-    "orbfe_fuse_points_into_keyframes_stored", "orbfe_debug_fuse_points_kernels",
+    "orbfe_fuse_points_into_keyframes_stored", "orbfe_debug_fuse_points_kernels", "orbfe_reloc_refine_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
     "orbfe_debug_pg_sparse_solve", "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
@@ -362,6 +378,7 @@ def load() -> C.CDLL:
     L.orbfe_fuse_points_into_keyframes_stored.argtypes = [vp, vp, i32, vp, vp, C.POINTER(Sim3Points), C.POINTER(Camera), vp, i32, f32, f32, i32, vp,
                                                           vp]
     L.orbfe_debug_fuse_points_kernels.argtypes = [vp]
+    L.orbfe_reloc_refine_stored.argtypes = [vp, i32, vp, C.POINTER(RelocInput), C.POINTER(RelocOutput)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -2043,6 +2060,59 @@ class Context:
         ms = np.zeros(2, np.float64)
         self._check(self.lib.orbfe_debug_fuse_points_kernels(ptr(ms)))
         return float(ms[0]), float(ms[1])
+
+    def reloc_refine_stored(self, slot, store, kf_id, good, pos, kf_Rcw, kf_tcw, held, Rcw, tcw, cam, bounds, level_sigma2, level_inv_sigma2,
+                            baseline, right_u=None, th_first=10.0, th_second=3.0, ratio=0.9, min_threshold=50, min_inliers=10, enough=50,
+                            out=None):
+        """What Tracking::trackReLocalize does with one PnP hypothesis (Rcw, tcw) against the stored keyframe kf_id, as one call
+        (orbfe_reloc_refine_stored): setCurrFrameAttrib's points (held), OptimizePoseOnly with its post-check, the 10 / 50 decisions, the
+        two searchByProjection(frame, keyframe) and the second optimisation.  The frame is the extraction in `slot`; good [n], pos [n, 3]:
+        the keyframe's map state; cam = (fx, fy, cx, cy, bf); bounds = (minU, maxU, minV, maxV).
+        -> dict(verdict, verdict_name, n_edges [2], n_inliers [2], n_added [2], tlc_z [2], pose_se3 [2, 7], Tcw [2, 12], inlier [2, NF],
+        assigned [2, NF], final_assigned [NF], excluded_hits [2, NF], query_accepted [2, n]); out: such a dict to fill (a call that fails
+        leaves it as it is)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        good = np.ascontiguousarray(good, np.uint8).reshape(-1)
+        pos = f32(pos).reshape(-1, 3)
+        n, NF = len(good), self.n_features
+        if len(pos) != n:
+            raise ValueError("reloc_refine_stored: good and pos differ in length")
+        held = np.ascontiguousarray(held, np.int32).reshape(-1)
+        right_u = None if right_u is None else np.ascontiguousarray(right_u, np.float64)
+        if held.size != NF or (right_u is not None and right_u.size != NF):
+            raise ValueError("reloc_refine_stored: held / right_u must have n_features entries")
+        s2, is2 = f32(level_sigma2), f32(level_inv_sigma2)
+        if s2.size < self.n_levels or is2.size < self.n_levels:
+            raise ValueError("reloc_refine_stored: one sigma2 / inv_sigma2 per level of the context")
+        cm = Camera(*[float(np.float32(v)) for v in cam[:4]], 0, 0, 0, 0, 0, float(np.float32(cam[4])))
+        ri = RelocInput()
+        ri.kf_id, ri.n = int(kf_id), n
+        ri.good, ri.pos = (ptr(good).value, ptr(pos).value) if n else (None, None)
+        ri.kf_Rcw[:] = f32(kf_Rcw).reshape(9).tolist()
+        ri.kf_tcw[:] = f32(kf_tcw).reshape(3).tolist()
+        ri.held = ptr(held).value
+        ri.right_u = None if right_u is None else ptr(right_u).value
+        ri.Rcw[:] = f32(Rcw).reshape(9).tolist()
+        ri.tcw[:] = f32(tcw).reshape(3).tolist()
+        ri.bounds[:] = f32(bounds).reshape(4).tolist()
+        ri.level_sigma2, ri.level_inv_sigma2, ri.cam = ptr(s2).value, ptr(is2).value, C.pointer(cm)
+        ri.baseline, ri.th_first, ri.th_second, ri.ratio = float(baseline), float(th_first), float(th_second), float(ratio)
+        ri.min_threshold, ri.min_inliers, ri.enough = int(min_threshold), int(min_inliers), int(enough)
+        if out is None:
+            out = dict(verdict=np.zeros(1, np.int32), n_edges=np.zeros(2, np.int32), n_inliers=np.zeros(2, np.int32), n_added=np.zeros(2, np.int32),
+                       tlc_z=np.zeros(2, np.float32), pose_se3=np.zeros((2, 7)), Tcw=np.zeros((2, 12), np.float32), inlier=np.zeros((2, NF), np.uint8),
+                       assigned=np.full((2, NF), -1, np.int32), final_assigned=np.full(NF, -1, np.int32),
+                       excluded_hits=np.zeros((2, NF), np.int32), query_accepted=np.zeros((2, max(n, 1)), np.uint8))
+        ro = RelocOutput(*[ptr(out[k]).value for k, _ in RelocOutput._fields_])
+        # (kept with the arrays behind them: tools/reloc_refine_bench.py times the bare C call with the same arguments)
+        self._reloc_args = (self.h, int(slot), store.h, C.byref(ri), C.byref(ro))
+        self._reloc_keep = (good, pos, held, right_u, s2, is2, cm, ri, ro, out)
+        self._check(self.lib.orbfe_reloc_refine_stored(*self._reloc_args))
+        res = dict(out)
+        res["query_accepted"] = out["query_accepted"].reshape(2, -1)[:, :n] if n else np.zeros((2, 0), np.uint8)
+        res["verdict"] = int(out["verdict"][0])
+        res["verdict_name"] = RELOC_VERDICTS.get(res["verdict"], "?")
+        return res
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -1,0 +1,277 @@
+// k_reloc.hip -- the glue of orbfe_reloc_refine_stored (include/orbfe.h): what Tracking::trackReLocalize does with one PnP
+// hypothesis between its two Optimizer::OptimizePoseOnly calls and its two ORBMatcher::searchByProjection calls (src/Tracking.cc:565-584,
+// :612-629), on the device.  The optimisations themselves are k_pose.hip's launch_pose_only on the edge lists built here.
+//
+// k_reloc_seed    one workgroup: setCurrFrameAttrib's map points (Tracking.cc:503-512) as cur[f], the edge list of the first
+//                 optimisation in feature order (Optimizer.cc:58-117), Converter::ConvertTcw2SE3 of the PnP pose (:119).
+// k_reloc_check   one workgroup: the projection post-check with the pose the frame still has (:179-190), the nulling (:191-199),
+//                 Converter::ConvertSE32Tcw of the estimate (:201), edges - nBad, the verdict of Tracking.cc:567-584 / :622, and for
+//                 a search that follows tlc.z (ORBMatcher.cc:274-276) and the next optimisation's initial estimate.
+// k_reloc_search  one wave per feature of the stored keyframe (ORBMatcher.cc:283-343, bFuse == false) over the slot's grid through
+//                 area_search_body.h; its filter: the octave window by the motion direction, then "holds no point", with one hit
+//                 counted per occurrence of a feature that does (:321-331); its acceptance (:339) claims the feature for the LAST
+//                 query that picked it (setMapPoints, :344-345: an atomicMax over claims that start at -1).
+// k_reloc_after   one workgroup: the claims become what the frame holds, the sum test of Tracking.cc:619 / :625, and after the first
+//                 search the edge list of the second optimisation.
+// Every kernel after the seed reads the verdict word first and leaves when it has fallen; no kernel waits on another; every loop is
+// bounded by the feature count, the grid size or a cell's feature count.  Float arithmetic: map_point_dev.h's rows and `A x + t`, no
+// contraction; the two pose conversions are host/map_pb.hpp's tcw_to_se3 / se3_to_tcw operation for operation, in fp64.
+#include <hip/hip_runtime.h>
+
+#include "area_search_body.h"
+#include "map_point_dev.h"
+#include "orbfe_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace orbfe {
+namespace {
+
+// the largest-diagonal branch of Eigen::Quaterniond(Matrix3d) with the largest element at I (constant indices: the arrays stay registers)
+template <int I>
+__device__ __forceinline__ void quat_diag(const double (&m)[3][3], double (&q)[4]) {
+  constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+  double tr = sqrt(m[I][I] - m[J][J] - m[K][K] + 1.0);
+  q[I] = 0.5 * tr;
+  tr = 0.5 / tr;
+  q[3] = (m[K][J] - m[J][K]) * tr;
+  q[J] = (m[J][I] + m[I][J]) * tr;
+  q[K] = (m[K][I] + m[I][K]) * tr;
+}
+
+// Converter::ConvertTcw2SE3 (src/Optimizer.cc:630-645): host/map_pb.hpp's tcw_to_se3
+__device__ __forceinline__ void tcw_to_se3_dev(const float* R, const float* t, double* out) {
+  double m[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) m[i][j] = (double)R[i * 3 + j];
+  double q[4];
+  double tr = m[0][0] + m[1][1] + m[2][2];
+  if (tr > 0.0) {
+    tr = sqrt(tr + 1.0);
+    q[3] = 0.5 * tr;
+    tr = 0.5 / tr;
+    q[0] = (m[2][1] - m[1][2]) * tr, q[1] = (m[0][2] - m[2][0]) * tr, q[2] = (m[1][0] - m[0][1]) * tr;
+  } else if (m[2][2] > (m[1][1] > m[0][0] ? m[1][1] : m[0][0]))
+    quat_diag<2>(m, q);
+  else if (m[1][1] > m[0][0])
+    quat_diag<1>(m, q);
+  else
+    quat_diag<0>(m, q);
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {  // Quaterniond::normalize(), then SE3Quat::normalizeRotation()
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (n > 0.0) q[0] /= n, q[1] /= n, q[2] /= n, q[3] /= n;
+  }
+  if (q[3] < 0.0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];
+  out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
+  out[4] = (double)t[0], out[5] = (double)t[1], out[6] = (double)t[2];
+}
+
+// Converter::ConvertSE32Tcw (src/Optimizer.cc:653-675): host/map_pb.hpp's se3_to_tcw
+__device__ __forceinline__ void se3_to_tcw_dev(const double* p, float* R, float* t) {
+  const double x = p[0], y = p[1], z = p[2], w = p[3];
+  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = (float)(1.0 - (tyy + tzz)), R[1] = (float)(txy - twz), R[2] = (float)(txz + twy);
+  R[3] = (float)(txy + twz), R[4] = (float)(1.0 - (txx + tzz)), R[5] = (float)(tyz - twx);
+  R[6] = (float)(txz - twy), R[7] = (float)(tyz + twx), R[8] = (float)(1.0 - (txx + tyy));
+  t[0] = (float)p[4], t[1] = (float)p[5], t[2] = (float)p[6];
+}
+
+// The pose-only edges of what the frame holds (cur), in feature order, by the 1024 threads of one workgroup: k_track_edges' list
+// (Optimizer.cc:58-117).  Returns the count to every thread.
+__device__ __forceinline__ int build_edges(const RelocDev& P, int* s_wave, int* s_base) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (t == 0) *s_base = 0;
+  __syncthreads();
+  for (int f0 = 0; f0 < P.nf; f0 += 1024) {
+    const int f = f0 + t;
+    const int mp = f < P.nf ? P.cur[f] : -1;
+    const bool edge = mp >= 0;
+    const unsigned long long me = __ballot(edge);
+    if (lane == 0) s_wave[wv] = __popcll(me);
+    __syncthreads();
+    int before = *s_base, chunk = 0;
+    for (int w = 0; w < 16; ++w) {
+      if (w < wv) before += s_wave[w];
+      chunk += s_wave[w];
+    }
+    const int e = before + __popcll(me & ((1ull << lane) - 1ull));
+    if (f < P.nf) P.edge_of[f] = edge ? e : -1;
+    if (edge) {
+      const orbfe_keypoint k = P.f_kps[f];
+      P.Xw[3 * e] = (double)P.pos[3 * mp], P.Xw[3 * e + 1] = (double)P.pos[3 * mp + 1], P.Xw[3 * e + 2] = (double)P.pos[3 * mp + 2];
+      const double ru = P.right_u[f];
+      P.meas[3 * e] = (double)k.x, P.meas[3 * e + 1] = (double)k.y, P.meas[3 * e + 2] = ru < 0 ? -1.0 : ru;
+      const int oc = min(max(k.octave, 0), P.n_levels - 1);
+      P.info[e] = (double)P.inv_sigma2[oc];
+      P.sig[e] = P.sigma2[oc];
+    }
+    __syncthreads();
+    if (t == 0) *s_base += chunk;
+    __syncthreads();
+  }
+  return *s_base;
+}
+
+__global__ __launch_bounds__(1024) void k_reloc_seed(RelocDev P) {
+  __shared__ int s_wave[16], s_base;
+  const int t = threadIdx.x;
+  const int n_kp = min(*P.f_n_kp, P.nf);
+  for (int f = t; f < P.nf; f += 1024) {
+    const int h = f < n_kp ? P.held[f] : -1;
+    P.cur[f] = (h >= 0 && P.good[h]) ? h : -1;  // `if (pMp && !pMp->isBad()) setMapPoint` (Tracking.cc:510-511)
+  }
+  const int edges = build_edges(P, s_wave, &s_base);  // (a thread reads the cur[f] it wrote)
+  if (t == 0) {
+    P.hdr[RELOC_H_EDGES] = edges;
+    P.cnt[0] = edges > 0 ? edges : -1;  // no edge: the estimate stays, nothing is an inlier
+    tcw_to_se3_dev(P.R0, P.t0, P.p_init);
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_reloc_check(RelocDev P, int s) {
+  __shared__ int s_wave[16];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int verdict = P.hdr[RELOC_H_VERDICT];
+  __syncthreads();  // (every thread has read the word before thread 0 may write it)
+  if (verdict != 0) return;
+  const double* est = P.p_opt + 7 * s;
+  float R[9], tc[3], Rb[9], tb[3];
+  se3_to_tcw_dev(est, R, tc);
+  // the check projects with the pose the frame still has: setPose comes last (Optimizer.cc:201) -- the PnP pose, then the first float pose
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Rb[k] = s == 0 ? P.R0[k] : P.tcw_out[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) tb[k] = s == 0 ? P.t0[k] : P.tcw_out[9 + k];
+  int mine = 0;
+  for (int f0 = 0; f0 < P.nf; f0 += 1024) {
+    const int f = f0 + t;
+    bool inl = false;
+    if (f < P.nf) {
+      const int e = P.edge_of[f], mp = P.cur[f];
+      inl = e >= 0 && P.e_inl[e] != 0;
+      if (inl) {  // VirtualFrame::project2UV (src/Frame.cc:320-333) and the test of Optimizer.cc:185: 0, not mfMinU / mfMinV
+        const float X[3] = {P.pos[3 * mp], P.pos[3 * mp + 1], P.pos[3 * mp + 2]};
+        float pc[3];
+        affine(1.0f, Rb, X, tb, pc);
+        const float z = pc[2];
+        const float u = pc[0] / z * P.fx + P.cx, v = pc[1] / z * P.fy + P.cy;
+        if (!(z > 0.f) || u > P.max_u || u < 0.f || v > P.max_v || v < 0.f) inl = false;
+      }
+      P.inlier[(size_t)s * P.nf + f] = inl ? 1 : 0;
+      if (!inl) P.cur[f] = -1;  // `if (!inLier[idx]) mvpMapPoints[idx] = nullptr` (:191-194)
+    }
+    mine += __popcll(__ballot(inl));
+  }
+  if (lane == 0) s_wave[wv] = mine;
+  __syncthreads();
+  if (t != 0) return;
+  int n_in = 0;
+  for (int w = 0; w < 16; ++w) n_in += s_wave[w];
+  P.hdr[RELOC_H_INLIERS + s] = n_in;
+  for (int k = 0; k < 7; ++k) P.pose_out[7 * s + k] = est[k];
+  for (int k = 0; k < 9; ++k) P.tcw_out[12 * s + k] = R[k];
+  for (int k = 0; k < 3; ++k) P.tcw_out[12 * s + 9 + k] = tc[k];
+  if (s == 0 && n_in < P.min_inliers) {
+    P.hdr[RELOC_H_VERDICT] = ORBFE_RELOC_REJECT_1;
+    return;
+  }
+  if (n_in >= P.enough) {
+    P.hdr[RELOC_H_VERDICT] = s == 0 ? ORBFE_RELOC_ACCEPT_1 : ORBFE_RELOC_ACCEPT_2;
+    return;
+  }
+  // a search follows: twc = -Rcw^T tcw, tlc = Rkf twc + tkf (ORBMatcher.cc:274-276)
+  float twc[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) twc[r] = -(R[r] * tc[0] + R[3 + r] * tc[1] + R[6 + r] * tc[2]);
+  float tlc[3];
+  affine(1.0f, P.kf_R, twc, P.kf_t, tlc);
+  P.hdr[RELOC_H_TLCZ + s] = __float_as_int(tlc[2]);
+  if (s == 0) tcw_to_se3_dev(R, tc, P.p_init + 7);  // the frame's pose is the float one now (setPose, Optimizer.cc:201)
+}
+
+__global__ __launch_bounds__(256) void k_reloc_search(RelocDev P, int s) {
+  __shared__ int32_t stage_all[4][128];
+  if (P.hdr[RELOC_H_VERDICT] != 0) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int q = blockIdx.x * 4 + wv;
+  if (q >= P.n || !P.good[q]) return;  // `if (!pMp2 || pMp2->isBad()) continue` (:286-287)
+  const orbfe_keypoint kp = P.k_kps[q];
+  const int o = min(max(kp.octave, 0), P.n_levels - 1);
+  const float z = __int_as_float(P.hdr[RELOC_H_TLCZ + s]);
+  int lo, hi;
+  if (fabsf(z) > P.baseline) {
+    if (z > 0.f) lo = o, hi = 7;
+    else lo = 0, hi = o;
+  } else
+    lo = max(0, o - 1), hi = min(o + 1, 7);
+  const float rad = P.th[s] * P.sigma2[o];  // findFeaturesInArea: radius * getScaledFactor2(octave) (Frame.cc:289)
+  const uint4 a0 = *(const uint4*)(P.k_desc + (size_t)q * 32);
+  const uint4 a1 = *(const uint4*)(P.k_desc + (size_t)q * 32 + 16);
+  Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
+  const AreaTarget T = {P.f_desc, P.cell_off, P.cell_feat, P.rows, P.cols, P.clip_w, P.clip_h};
+  const uint4* __restrict__ kpl = P.f_kpl;
+  const int32_t* __restrict__ cur = P.cur;
+  int32_t* hits = P.hits + (size_t)s * P.nf;
+  const int total = area_fold(T, kp.x, kp.y, rad, a0, a1, stage_all[wv], lane, b, [&](int id) {
+    const int oc = (int)(kpl[id].y & 0xFFu);
+    if (!(oc <= hi && oc >= lo)) return false;
+    if (cur[id] >= 0) {  // the feature holds a point: addMatchInTrack, no candidate (:321-331)
+      atomicAdd(&hits[id], 1);
+      return false;
+    }
+    return true;
+  });
+  if (lane != 0 || total <= 0) return;
+  const float fr = (float)b.min_d / (float)b.second;  // getBestMatch's ratio (:988)
+  if (fr < P.ratio && b.min_d < P.min_threshold) {
+    atomicMax(&P.claim[(size_t)s * P.nf + b.min_idx], q);
+    atomicAdd(&P.hdr[RELOC_H_ADDED + s], 1);
+    P.qa[(size_t)s * P.n + q] = 1;
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_reloc_after(RelocDev P, int s) {
+  __shared__ int s_wave[16], s_base;
+  const int t = threadIdx.x;
+  const int verdict = P.hdr[RELOC_H_VERDICT];
+  __syncthreads();
+  if (verdict != 0) {
+    if (s == 0 && t == 0) P.cnt[1] = -1;  // no second optimisation
+    return;
+  }
+  for (int f = t; f < P.nf; f += 1024) {
+    const int cl = P.claim[(size_t)s * P.nf + f];
+    int c = P.cur[f];
+    if (cl >= 0) c = cl, P.cur[f] = cl;
+    P.assigned[(size_t)s * P.nf + f] = c;
+  }
+  const bool too_few = P.hdr[RELOC_H_ADDED + s] + P.hdr[RELOC_H_INLIERS + s] < P.enough;  // Tracking.cc:619, :625
+  if (too_few || s == 1) {
+    if (t == 0) {
+      P.hdr[RELOC_H_VERDICT] = too_few ? (s == 0 ? ORBFE_RELOC_REJECT_2 : ORBFE_RELOC_REJECT_3) : ORBFE_RELOC_ACCEPT_3;
+      if (s == 0) P.cnt[1] = -1;
+    }
+    return;
+  }
+  const int edges = build_edges(P, s_wave, &s_base);
+  if (t == 0) {
+    P.hdr[RELOC_H_EDGES + 1] = edges;
+    P.cnt[1] = edges > 0 ? edges : -1;
+  }
+}
+
+}  // namespace
+
+void launch_reloc_seed(hipStream_t st, const RelocDev& P) { hipLaunchKernelGGL(k_reloc_seed, dim3(1), dim3(1024), 0, st, P); }
+void launch_reloc_check(hipStream_t st, const RelocDev& P, int s) { hipLaunchKernelGGL(k_reloc_check, dim3(1), dim3(1024), 0, st, P, s); }
+void launch_reloc_search(hipStream_t st, const RelocDev& P, int s) {
+  if (P.n <= 0) return;
+  hipLaunchKernelGGL(k_reloc_search, dim3((unsigned)((P.n + 3) / 4)), dim3(256), 0, st, P, s);
+}
+void launch_reloc_after(hipStream_t st, const RelocDev& P, int s) { hipLaunchKernelGGL(k_reloc_after, dim3(1), dim3(1024), 0, st, P, s); }
+
+}  // namespace orbfe

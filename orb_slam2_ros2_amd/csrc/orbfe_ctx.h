@@ -534,6 +534,8 @@ struct ExtLevel0 {
   hipEvent_t inputs_free;       // nullable: recorded once the resize (which also writes level 0 of the pyramid) is done with the caller's images
 };
 void grid_invalidate(orbfe_ctx* c, int slot);
+// orbfe_guided.hip: the area grid of `slot` for the geometry ag, built on stream st unless the one kept from the last search still holds
+orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const AreaGrid& ag, const int32_t** d_off, const int32_t** d_feat);
 void note_slots_written(orbfe_ctx* c, int s0, int n, bool small);
 orbfe_status run_extract(orbfe_ctx* c, hipStream_t st, int img0, int n_img, hipEvent_t before_lists = nullptr, bool timing = true,
                          const ExtLevel0* ext = nullptr, const HostMirror* mirror = nullptr);

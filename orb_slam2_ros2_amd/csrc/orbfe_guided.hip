@@ -2,6 +2,33 @@
 // getBestMatch, ORBMatcher.cc:265-347, 561-612), MapPoint::isInVision / predictLevel, and the fused tracking chains
 // (orbfe_track_local_map / orbfe_track_motion_model).  (Split from orbfe_api.hip in r5, no change of behaviour.)
 #include "orbfe_ctx.h"
+
+// the grid of `slot` for the geometry ag on stream st: the one kept from the last search if the slot's keypoints are still the same
+orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const AreaGrid& ag, const int32_t** d_off, const int32_t** d_feat) {
+  const size_t NF = (size_t)std::max(c->cfg.n_features, 1), M = (size_t)c->cfg.max_images, ncells = (size_t)ag.rows * ag.cols;
+  if (ncells + 1 > c->grid_cells) {  // first use, or a larger grid than any before: (re)allocate, nothing cached survives
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->d_grid_off) (void)hipFree(c->d_grid_off);
+    if (!c->d_grid_feat) HIP_TRY(c, hipMalloc((void**)&c->d_grid_feat, M * NF * sizeof(int32_t)));
+    c->d_grid_off = nullptr;
+    HIP_TRY(c, hipMalloc((void**)&c->d_grid_off, M * (ncells + 1) * sizeof(int32_t)));
+    c->grid_cells = ncells + 1;
+    for (size_t k = 0; k < M; ++k) grid_invalidate(c, (int)k);
+  }
+  int32_t* off = c->d_grid_off + (size_t)slot * c->grid_cells;
+  int32_t* feat = c->d_grid_feat + (size_t)slot * NF;
+  const uint32_t key = ((uint32_t)ag.rows << 16) | (uint32_t)ag.cols;
+  uint64_t seen = c->grid_key[(size_t)slot].load();
+  if ((uint32_t)seen != key) {
+    launch_grid_build(st, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, ag.rows, ag.cols, off, feat);
+    // kept for the next search only if no extraction touched the slot since `seen` (its generation is part of the compared value); on
+    // failure nothing is cached: this call still uses what it built, the next one builds again
+    (void)c->grid_key[(size_t)slot].compare_exchange_strong(seen, (seen & 0xFFFFFFFF00000000ull) | key);
+  }
+  *d_off = off, *d_feat = feat;
+  return ORBFE_OK;
+}
+
 extern "C" {
 
 orbfe_status orbfe_match_bruteforce(orbfe_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, const uint32_t* cand_offsets,
@@ -54,32 +81,6 @@ orbfe_status orbfe_match_bruteforce(orbfe_ctx* c, const uint8_t* q, int32_t nq, 
 // uploaded (orbfe_search_in_area_features: a KeyFrame's keypoints and descriptors -- keyframes are not resident in a slot).
 // (AreaGrid, area_grid and the search's scratch layout: search_area_layout.h)
 static bool area_grid(const orbfe_ctx* c, const float* bounds, AreaGrid* g) { return area_grid(c->cfg.width, c->cfg.height, bounds, g); }
-
-// the grid of `slot` for the geometry ag on stream st: the one kept from the last search if the slot's keypoints are still the same
-static orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const AreaGrid& ag, const int32_t** d_off, const int32_t** d_feat) {
-  const size_t NF = (size_t)std::max(c->cfg.n_features, 1), M = (size_t)c->cfg.max_images, ncells = (size_t)ag.rows * ag.cols;
-  if (ncells + 1 > c->grid_cells) {  // first use, or a larger grid than any before: (re)allocate, nothing cached survives
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->d_grid_off) (void)hipFree(c->d_grid_off);
-    if (!c->d_grid_feat) HIP_TRY(c, hipMalloc((void**)&c->d_grid_feat, M * NF * sizeof(int32_t)));
-    c->d_grid_off = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&c->d_grid_off, M * (ncells + 1) * sizeof(int32_t)));
-    c->grid_cells = ncells + 1;
-    for (size_t k = 0; k < M; ++k) grid_invalidate(c, (int)k);
-  }
-  int32_t* off = c->d_grid_off + (size_t)slot * c->grid_cells;
-  int32_t* feat = c->d_grid_feat + (size_t)slot * NF;
-  const uint32_t key = ((uint32_t)ag.rows << 16) | (uint32_t)ag.cols;
-  uint64_t seen = c->grid_key[(size_t)slot].load();
-  if ((uint32_t)seen != key) {
-    launch_grid_build(st, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, ag.rows, ag.cols, off, feat);
-    // kept for the next search only if no extraction touched the slot since `seen` (its generation is part of the compared value); on
-    // failure nothing is cached: this call still uses what it built, the next one builds again
-    (void)c->grid_key[(size_t)slot].compare_exchange_strong(seen, (seen & 0xFFFFFFFF00000000ull) | key);
-  }
-  *d_off = off, *d_feat = feat;
-  return ORBFE_OK;
-}
 
 // the grid and the scratch layout of a search behind `start` bytes of the caller's own: the callers size their reservation from l->end()
 static orbfe_status search_area_plan(orbfe_ctx* c, const char* who, const float* bounds, size_t start, size_t n_target, int32_t nq,

@@ -494,3 +494,48 @@ struct FusePtsParams {
   const float *pos, *vdir, *max_dist, *min_dist, *sf;
 };
 #define FUSEPTS_SEARCH_BLOCKS 2048  // k_fusepts_search's fixed grid: 8192 waves, 32 per compute unit of 256
+
+// ---- the relocalisation refine over a stored keyframe (k_reloc.hip, orbfe_reloc.hip) -------------------------------------
+// Everything the kernels of one call read and write: the frame where its slot keeps it, the keyframe where the store keeps it, the map
+// state of the call's upload, the state that stays on the device and the block that goes down.  hdr: [0] verdict (0: still running),
+// [1..2] n_edges, [3..4] n_inliers, [5..6] n_added, [7..8] tlc_z as float bits.
+#define RELOC_H_VERDICT 0
+#define RELOC_H_EDGES 1
+#define RELOC_H_INLIERS 3
+#define RELOC_H_ADDED 5
+#define RELOC_H_TLCZ 7
+struct RelocDev {
+  // the frame (slot arrays) and its grid
+  const orbfe_keypoint* f_kps;
+  const uint4* f_kpl;
+  const uint8_t* f_desc;
+  const int32_t* f_n_kp;
+  const int32_t *cell_off, *cell_feat;
+  int32_t rows, cols, clip_w, clip_h, nf, n_levels;
+  // the stored keyframe and its map state
+  const orbfe_keypoint* k_kps;
+  const uint8_t* k_desc;
+  const uint8_t* good;
+  const float* pos;
+  int32_t n;
+  float kf_R[9], kf_t[3];
+  // the call
+  const int32_t* held;
+  const double* right_u;
+  const float *sigma2, *inv_sigma2;
+  float R0[9], t0[3];
+  float fx, fy, cx, cy, max_u, max_v, baseline, th[2], ratio;
+  int32_t min_threshold, min_inliers, enough;
+  // device state: what the frame holds, the claims of a search, the edge list of an optimisation and its results
+  int32_t *cur, *claim /*[2][nf]*/, *edge_of, *cnt /*[2] edge counts, -1: no optimisation*/;
+  double *Xw, *meas, *info, *p_init /*[2][7]*/, *p_opt /*[2][7]*/;
+  float* sig;
+  const uint8_t* e_inl;  // the optimiser's inlier flag per edge
+  // the downloaded block
+  int32_t* hdr;
+  double* pose_out /*[2][7]*/;
+  float* tcw_out /*[2][12]*/;
+  uint8_t* inlier /*[2][nf]*/;
+  int32_t *assigned /*[2][nf]*/, *hits /*[2][nf]*/;
+  uint8_t* qa /*[2][n]*/;
+};

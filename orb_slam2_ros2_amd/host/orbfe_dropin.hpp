@@ -1193,6 +1193,135 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
     return nMatches;
   }
 
+  // What Tracking::trackReLocalize does with ONE PnP hypothesis (src/Tracking.cc:565-584): setCurrFrameAttrib (:500-517),
+  // OptimizePoseOnly, and between 10 and 50 inliers addMatchByProject (:612-629).  The reference's chain on the bodies above -- what
+  // relocRefine falls back to, and what its one device call stands for.
+  template <class CameraT, class FramePtr, class KeyFramePtr, class RelocBowParamT>
+  static void setCurrFrameAttrib(FramePtr pCurr, KeyFramePtr pkf, const RelocBowParamT& relocBowParam, std::size_t idx, const std::vector<std::size_t>& vInliers,
+                                 const cv::Mat& Rcw, const cv::Mat& tcw, std::vector<int32_t>* held = nullptr) {
+    pCurr->setMapPointsNull();
+    auto kfMps = pkf->getMapPoints();
+    for (const std::size_t& inlierIdx : vInliers) {
+      const std::size_t matchID = relocBowParam.mvPnPId2MatchID[idx].at(inlierIdx);
+      const int pMpId = relocBowParam.mvAllMatches[idx][matchID].trainIdx, kPId = relocBowParam.mvAllMatches[idx][matchID].queryIdx;
+      auto pMp = kfMps[(size_t)pMpId];
+      if (pMp && !pMp->isBad()) {
+        pCurr->setMapPoint(kPId, pMp);
+        if (held && (size_t)kPId < (*held).size()) (*held)[(size_t)kPId] = pMpId;
+      }
+    }
+    float R[9], t[3];
+    poseFloats(Rcw, tcw, R, t);
+    pCurr->setPose(poseMat(R, t));
+  }
+  static cv::Mat poseMat(const float* R, const float* t) {  // the 4x4 float Tcw of a rotation and a translation
+    cv::Mat T(4, 4, CV_32F);
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) T.at<float>(r, c) = r == c ? 1.f : 0.f;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) T.at<float>(r, c) = R[3 * r + c];
+      T.at<float>(r, 3) = t[r];
+    }
+    return T;
+  }
+  template <class CameraT, class FramePtr, class KeyFramePtr>
+  static bool relocRefineBodies(FramePtr pCurr, KeyFramePtr pkf) {  // Tracking.cc:566-584 after setCurrFrameAttrib
+    int nInliers = OptimizePoseOnly<CameraT>(pCurr);
+    if (nInliers < 10) return false;
+    if (nInliers >= 50) return true;
+    if (!pkf || pkf->isBad()) return false;  // addMatchByProject (:614-615)
+    std::vector<cv::DMatch> matches2;
+    int nAddition = searchByProjection<CameraT>(pCurr, pkf, matches2, 10.f, false, 0.9f);
+    if (nAddition + nInliers < 50) return false;
+    nInliers = OptimizePoseOnly<CameraT>(pCurr);
+    if (nInliers < 50) {
+      nAddition = searchByProjection<CameraT>(pCurr, pkf, matches2, 3.f, false, 0.9f);
+      if (nAddition + nInliers < 50) return false;
+    }
+    return true;
+  }
+  // The same as ONE device call (orbfe_reloc_refine_stored) over a keyframe store (orbfe_kfstore_dropin.hpp): held is built
+  // from vInliers as setCurrFrameAttrib sets the points, and the side effects are replayed on the reference's objects in the reference's
+  // order: setMapPointsNull / setMapPoint / setPose, then per optimisation the nulling and addInlierInTrack and the pose, per search
+  // addMatchInTrack for every visit of a feature that holds a point and for every accepted query, and the slots.  A frame whose slot is
+  // no longer resident, a context of more than 2048 features, a distorting camera or a bad keyframe takes the bodies above.
+  template <class CameraT, class Store, class FramePtr, class KeyFramePtr, class RelocBowParamT>
+  static bool relocRefine(Store& store, FramePtr pCurr, KeyFramePtr pkf, const RelocBowParamT& relocBowParam, std::size_t idx,
+                          const std::vector<std::size_t>& vInliers, const cv::Mat& Rcw, const cv::Mat& tcw) {
+    const auto& ext = pCurr->mpExtractorLeft->device();
+    const orbfe_camera cam = cameraOf<CameraT>();
+    const bool distorting = cam.k1 != 0.f || cam.k2 != 0.f || cam.p1 != 0.f || cam.p2 != 0.f || cam.k3 != 0.f;
+    if (!ext.resident() || (size_t)orbfe_get_capacity(ext.context()) > 2048 || distorting || pkf->isBad()) {
+      setCurrFrameAttrib<CameraT>(pCurr, pkf, relocBowParam, idx, vInliers, Rcw, tcw);
+      return relocRefineBodies<CameraT>(pCurr, pkf);
+    }
+    orbfe_ctx* ctx = ext.context();
+    const size_t NF = (size_t)orbfe_get_capacity(ctx), N = pCurr->mvFeatsLeft.size();
+    std::vector<int32_t> held(NF, -1);
+    setCurrFrameAttrib<CameraT>(pCurr, pkf, relocBowParam, idx, vInliers, Rcw, tcw, &held);
+    store.ensureFeatures(pkf);
+    orbfe_kfstore_info info;
+    store.info(pkf, &info);
+    const size_t n = (size_t)info.n;
+    auto kfMps = pkf->getMapPoints();
+    std::vector<uint8_t> good(std::max<size_t>(n, 1), 0);
+    std::vector<float> pos(3 * std::max<size_t>(n, 1), 0.f);
+    for (size_t i = 0; i < n && i < kfMps.size(); ++i) {
+      if (!kfMps[i] || kfMps[i]->isBad()) continue;
+      good[i] = 1;
+      const cv::Mat X = kfMps[i]->getPos();
+      for (int a = 0; a < 3; ++a) pos[3 * i + a] = X.template at<float>(a);
+    }
+    const int nLevels = 8;
+    std::vector<float> sig2((size_t)nLevels), invSig2((size_t)nLevels);
+    for (int l = 0; l < nLevels; ++l) sig2[(size_t)l] = pCurr->getScaledFactor2(l), invSig2[(size_t)l] = pCurr->getScaledFactorInv2(l);
+    std::vector<double> rightU(NF, -1.0);
+    for (size_t f = 0; f < N && f < NF; ++f) rightU[f] = pCurr->getRightU(f);
+    orbfe_reloc_input in{};
+    in.kf_id = store.id(pkf), in.n = (int32_t)n, in.good = good.data(), in.pos = pos.data();
+    cv::Mat Rk, tk;
+    pkf->getPose(Rk, tk);
+    poseFloats(Rk, tk, in.kf_Rcw, in.kf_tcw);
+    poseFloats(Rcw, tcw, in.Rcw, in.tcw);
+    in.held = held.data(), in.right_u = rightU.data(), in.level_sigma2 = sig2.data(), in.level_inv_sigma2 = invSig2.data(), in.cam = &cam;
+    in.bounds[0] = pCurr->mfMinU, in.bounds[1] = pCurr->mfMaxU, in.bounds[2] = pCurr->mfMinV, in.bounds[3] = pCurr->mfMaxV;
+    in.baseline = CameraT::mfBl, in.th_first = 10.f, in.th_second = 3.f, in.ratio = 0.9f;
+    in.min_threshold = orbfe::ORBMatcher::mnMinThreshold, in.min_inliers = 10, in.enough = 50;
+    int32_t verdict = 0, nEdges[2], nInl[2], nAdded[2];
+    float tlcZ[2], Tcw[24];
+    double est[14];
+    std::vector<uint8_t> inl(2 * NF, 0), qa(2 * std::max<size_t>(n, 1), 0);
+    std::vector<int32_t> assigned(2 * NF, -1), fin(NF, -1), hits(2 * NF, 0);
+    orbfe_reloc_output out{};
+    out.verdict = &verdict, out.n_edges = nEdges, out.n_inliers = nInl, out.n_added = nAdded, out.tlc_z = tlcZ, out.pose_se3 = est, out.Tcw = Tcw;
+    out.inlier = inl.data(), out.assigned = assigned.data(), out.final_assigned = fin.data(), out.excluded_hits = hits.data();
+    out.query_accepted = qa.data();
+    check(ctx, orbfe_reloc_refine_stored(ctx, ext.slot(), store.get(), &in, &out));
+    auto& slots = pCurr->mvpMapPoints;
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && verdict < ORBFE_RELOC_ACCEPT_2) break;  // no second optimisation
+      // OptimizePoseOnly's tail (src/Optimizer.cc:191-201)
+      for (size_t f = 0; f < N && f < slots.size(); ++f) {
+        if (f < NF && inl[(size_t)s * NF + f])
+          slots[f]->addInlierInTrack();
+        else
+          slots[f] = nullptr;
+      }
+      pCurr->setPose(poseMat(Tcw + 12 * s, Tcw + 12 * s + 9));
+      if (verdict < (s == 0 ? ORBFE_RELOC_REJECT_2 : ORBFE_RELOC_REJECT_3)) break;  // no search
+      // searchByProjection's side effects (src/ORBMatcher.cc:321-331, :815-830)
+      for (size_t f = 0; f < N && f < NF && f < slots.size(); ++f)
+        for (int32_t k = 0; k < hits[(size_t)s * NF + f]; ++k) slots[f]->addMatchInTrack();
+      for (size_t i = 0; i < n; ++i)
+        if (qa[(size_t)s * n + i]) kfMps[i]->addMatchInTrack();
+      for (size_t f = 0; f < N && f < NF && f < slots.size(); ++f) {
+        const int32_t a = assigned[(size_t)s * NF + f];
+        if (a >= 0) slots[f] = kfMps[(size_t)a];
+      }
+    }
+    return verdict == ORBFE_RELOC_ACCEPT_1 || verdict == ORBFE_RELOC_ACCEPT_2 || verdict == ORBFE_RELOC_ACCEPT_3;
+  }
+
   // The tail of Frame::Frame (RGB-D) after extract() (src/Frame.cc:130-131, :139-157): depthImg.convertTo(CV_32F) / dScale, the copy of the
   // distorted keypoints, Camera::undistortPoints(mvFeatsLeft), the depth / rightU lookup -- as one call on the extractor's slot.  depthImg
   // as read from the file: CV_16U (TUM) or CV_32F.  initGrid() stays with the caller (the grid is rebuilt on the device per search).

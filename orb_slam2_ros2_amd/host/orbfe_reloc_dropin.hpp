@@ -14,6 +14,9 @@
 // (orbfe_search_by_sim3_stored / orbfe_search_by_sim3_points_stored),
 //     orbfe::dropin::searchBySim3<Camera>(store, mpCurr, mpMatch, matches, g2oScm, th, mfRatio)
 //     orbfe::dropin::searchBySim3<Camera>(store, pCurr, vLoopGroupMps, vMatchedMps, g2oScw, th, mfRatio)
+// what follows a successful iterate in Tracking::trackReLocalize (src/Tracking.cc:565-584) as one device call
+// (orbfe_reloc_refine_stored),
+//     if (orbfe::dropin::relocRefine<Camera>(store, mpCurrFrame, vpCandidateKFs[idx], relocBowParam, idx, vInliers, modelReti.mRcw, modelReti.mtcw))
 #pragma once
 
 #include <algorithm>
@@ -300,6 +303,15 @@ int searchBySim3(KeyframeStore<Access>& store, KeyFramePtr pCurr, const std::vec
       ++nMatches;
     }
   return nMatches;
+}
+
+// setCurrFrameAttrib + OptimizePoseOnly + addMatchByProject of ONE PnP hypothesis (src/Tracking.cc:565-584, :500-517, :612-629): true where the
+// reference sets pRelocKf and leaves its loops, false where it goes on to the next hypothesis.  The frame ends with the points, the pose
+// and its map points with the counters the reference's chain leaves (Bodies::relocRefine, orbfe_dropin.hpp).
+template <class CameraT, class FramePtr, class KeyFramePtr, class RelocBowParamT, class Access>
+bool relocRefine(KeyframeStore<Access>& store, FramePtr mpCurrFrame, KeyFramePtr pKF, const RelocBowParamT& relocBowParam, std::size_t idx,
+                 const std::vector<std::size_t>& vInliers, const cv::Mat& Rcw, const cv::Mat& tcw) {
+  return Bodies::template relocRefine<CameraT>(store, mpCurrFrame, pKF, relocBowParam, idx, vInliers, Rcw, tcw);
 }
 
 }  // namespace dropin
