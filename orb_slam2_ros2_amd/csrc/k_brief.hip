@@ -353,7 +353,9 @@ __global__ __launch_bounds__(256) void k_list_moments_orient(const LevelDev* __r
 // 3. rotated BRIEF, one wave per keypoint.  The 37x37 window of the BLURRED plane that the rotated template
 //    can reach (|offset| <= 18) is staged in LDS by LDS-DMA (global_load_lds_dwordx4: no register, no ds_write on the
 //    way); the 512 data-dependent byte reads then hit LDS instead of issuing 8 global gathers with ~64 distinct cache
-//    lines each.
+//    lines each.  (r10) A wave works through N keypoints in a rolled loop (N a kernel argument: 2 for a frame or two, 3 for batches;
+//    ORBFE_BRIEF_KPW forces it): the lane's sixteen table addresses, the DMA lane geometry and the store's lane offset are built once
+//    in front of it.
 // ---------------------------------------------------------------------------------------------
 #define BRIEF_R 18
 #define BRIEF_ROWS (2 * BRIEF_R + 1)
@@ -364,8 +366,27 @@ __global__ __launch_bounds__(256) void k_list_moments_orient(const LevelDev* __r
 #define BRIEF_WAVES 4
 #endif
 #ifndef BRIEF_KPW
-#define BRIEF_KPW 2  // consecutive keypoints per wave (measured: 2 and 3 equal, 4 and 8 slower -- fewer, longer waves balance worse)
+#define BRIEF_KPW 2  // keypoints per wave of a frame or two (a kernel argument since r10; with 4 000 keypoints a longer loop leaves SIMDs empty)
 #endif
+#ifndef BRIEF_KPW_BATCH
+// keypoints per wave of a batch.  Measured with the rolled loop, wave w on keypoints base + w + 4 i (r10, stage orient + brief of 512
+// pairs, ms; the unrolled parent 1.104): 2 -> 1.058, 3 -> 1.034, 4 -> 1.042, 6 -> 1.065, 8 -> 1.095, 16 -> 1.136.  The set-up is paid
+// once per wave, but past 3 something costs more than that saves -- supposed, not measured: the keypoints an XCD has in flight span
+// 4 N images' eighths, whose windows no longer stay in its L2.
+// (N CONSECUTIVE keypoints per wave lose at every N: 2 -> 1.132, 3 -> 1.176, 4 -> 1.213, 8 -> 1.297 -- the block's waves then hold
+//  keypoints N apart.  A resident form -- the grid sized to the chip, each wave striding through its XCD's share -- 1.33: dropped.)
+#define BRIEF_KPW_BATCH 3
+#endif
+#define BRIEF_KPW_MAX 64
+// window byte address of a test point: pitch x row + column, both still in the low bits of their rounded float sums (see the kernel).
+// One asm block: between an asm v_mad_u32_u24 and a v_and of the compiler's that reads it, the compiler put an s_nop; its own form
+// of the multiply-add (__umul24 + add) came out as the 64-bit v_mad_u64_u32.
+__device__ __forceinline__ uint32_t brief_addr(int row_bits, int col_bits) {
+  static_assert(BRIEF_PITCH == 48, "the pitch is spelled out in the instruction");
+  uint32_t d;
+  asm("v_mad_u32_u24 %0, %1, 48, %2\n\tv_and_b32 %0, 0xffff, %0" : "=v"(d) : "v"(row_bits), "v"(col_bits));
+  return d;
+}
 #ifdef BRIEF_STAMPS  // diagnostic build only (tools/exp/brief_stamps.sh): start / end of every descriptor wave and of the row-table workgroups, 100 MHz ticks
 __device__ unsigned long long g_rt_t[4][8];
 __device__ unsigned long long g_bs_rec[8192][6];  // [wave]: start, first window parked, end, kind (1 descriptor wave, 2 row-table workgroup), list entry arrived, window arrived
@@ -390,7 +411,7 @@ struct BriefRowTable {  // rowoff == nullptr: descriptor blocks only
 __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_brief(const uint8_t* __restrict__ blur, size_t img_pitch,
                                               const uint4* __restrict__ kpl, int n_features, const int8_t* __restrict__ pattern,
                                               const double2* __restrict__ sincos, uint8_t* __restrict__ desc, uint8_t* __restrict__ desc_host,
-                                              BriefRowTable rt) {
+                                              BriefRowTable rt, int kpw) {
 #pragma clang fp contract(off)
   // per wave (the waves never synchronise): the window, and v cos / v sin for every template coordinate v in [-18, 18] as two
   // arrays of doubles.  The kernel is bound by LDS cycles, most of them the table look-ups: as 16-byte (cos, sin) entries read by
@@ -444,38 +465,58 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
   }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // in a scalar register: what follows from it stays on the scalar unit
-  double* rc = lds.rc[wave];
-  double* rs = lds.rs[wave];
   // XCD-aware block order: workgroups go round-robin to the 8 XCDs (own L2 each) and consecutive keypoints are spatial neighbours
   // (candidate order) whose 37x37 windows overlap; block b of the grid takes keypoint block (b % 8) * (grid / 8) + b / 8, so one XCD
-  // works through one contiguous eighth of the list (gridDim.x is a multiple of 8).  Fetched bytes 2.69 -> 0.85 GB per 1024 images.
+  // works through one contiguous eighth of the list (the number of blocks is a multiple of 8).  Fetched bytes 2.69 -> 0.85 GB per 1024 images.
   // (r6: the number of descriptor blocks is a kernel ARGUMENT in both forms.  It used to be gridDim.x for the batches -- and the compiler
   //  derived that from the dispatch packet, which lives in the queue's ring buffer in HOST memory: every wave of the launch began with a
   //  scalar load across PCIe that no cache holds.  A pair's 2000 waves queued for it -- first data after 13.6 us on average, 26.5 at worst,
   //  whatever they asked for first (stamps build, tools/exp/brief_stamps.sh) -- and the launch took 18 - 31 us.)
+  // (r10) A block owns BRIEF_WAVES * kpw consecutive keypoints and wave w takes base + w + BRIEF_WAVES i, i = 0 .. kpw - 1: at every step
+  // the four waves of a block hold four NEIGHBOURS, whatever kpw is (kpw consecutive keypoints per wave put them kpw apart).
+  // (r10) Which eighth an XCD takes ROTATES with the image: the unused slots of a list are its tail, the last eighth, and with block b
+  // on eighth b % 8 of every image XCD 7 got them all and idled while the other seven finished (stage 1.105 -> 1.056 ms at two keypoints a wave).
   const int per_xcd = rt.n_brief_blocks >> 3;
-  const int kb = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-  const int k0 = (kb * BRIEF_WAVES + wave) * BRIEF_KPW;
+  const int kb = (((int)blockIdx.x + (int)blockIdx.y) & 7) * per_xcd + ((int)blockIdx.x >> 3);
+  const int kbase = kb * (BRIEF_WAVES * kpw) + wave;
   const int img = blockIdx.y;
-  if (k0 >= n_features) return;
+  if (kbase >= n_features) return;
+  const int k_last = kbase + BRIEF_WAVES * (min(kpw, (n_features - kbase + BRIEF_WAVES - 1) / BRIEF_WAVES) - 1);  // the wave's last keypoint: < n_features
   // A wave with one keypoint spent two thirds of its life parked at s_waitcnt: list entry -> window -> tests are dependent round
-  // trips, and eight waves per SIMD do not cover them.  A wave now works through BRIEF_KPW consecutive keypoints as a three-stage
-  // pipeline: while keypoint i is tested, the window of keypoint i + 1 is in flight (LDS-DMA into the wave's other buffer), its sin / cos
-  // are on their way to scalar registers and so is the list entry of keypoint i + 2; the lane's template pairs are fetched once.
+  // trips, and eight waves per SIMD do not cover them.  A wave works through its keypoints as a three-stage pipeline: while keypoint i
+  // is tested, the window of keypoint i + 1 is in flight (LDS-DMA into the wave's other buffer), its sin / cos are on their way to scalar
+  // registers and so is the list entry of keypoint i + 2.
   // (r7) A wave works on ONE keypoint at a time, so k, the list entry and the sin / cos pair are wave-uniform: k is built from scalar
   // values only and the records come through the scalar cache (s_load_dwordx4; both arrays are written by earlier kernels of the stream,
   // never by this one), not as 64 lanes loading one address into 16 vector registers a stage.  They count on lgkmcnt: vmcnt carries the
   // window DMA (and the descriptor stores) alone.
+  // (r10) The keypoint loop is ROLLED and its length (kpw) a kernel argument.  Unrolled twice, a third of a keypoint's instructions were the
+  // wave's set-up: everything below down to the loop depends on the lane and the launch only and is now paid once per kpw keypoints.
   const uint4* list = kpl + (size_t)img * n_features;
   const double2* sc = sincos + (size_t)img * n_features;
   const uint8_t* W = blur + (size_t)img * img_pitch;  // wave-uniform base; the rest of the address is a 32-bit offset
-  const int k_last = min(k0 + BRIEF_KPW, n_features) - 1;
-  uint32_t tp0 = *(const uint32_t*)(pattern + (0 * 64 + lane) * 4), tp1 = *(const uint32_t*)(pattern + (1 * 64 + lane) * 4);
-  uint32_t tp2 = *(const uint32_t*)(pattern + (2 * 64 + lane) * 4), tp3 = *(const uint32_t*)(pattern + (3 * 64 + lane) * 4);
-#ifdef BRIEF_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" :: "v"(tp0), "v"(tp1), "v"(tp2), "v"(tp3) : "memory");
-  bs_t1 = __builtin_amdgcn_s_memrealtime();  // (pattern arrived; the "first window parked" stamp is not taken in this build)
-#endif
+  typedef __attribute__((address_space(3))) uint8_t* lds_dst_t;
+  typedef const __attribute__((address_space(1))) uint8_t* glb_src_t;
+  typedef const __attribute__((address_space(3))) uint8_t* lds_bytes_t;
+  typedef const __attribute__((address_space(3))) double* lds_f64_t;
+  typedef __attribute__((address_space(3))) double* lds_f64w_t;
+  // LDS byte addresses of the wave's tables and of its first window buffer (scalar); rs[v] lies RS_OFF behind rc[v]: one address
+  // register per template coordinate serves both tables, the distance rides in the instruction's offset field
+  const uint32_t rc_addr = (uint32_t)(uintptr_t)(lds_bytes_t)(const uint8_t*)lds.rc[wave];
+  const uint32_t win_addr = (uint32_t)(uintptr_t)(lds_bytes_t)lds.win[wave][0];
+  constexpr uint32_t RS_OFF = (uint32_t)(sizeof(double) * 40 * BRIEF_WAVES + 2 * BRIEF_WIN_BYTES * BRIEF_WAVES);
+  static_assert(RS_OFF < 65536, "the distance of the two tables is a ds_read offset");
+  // the lane's sixteen template coordinates (pairs l, l + 64, l + 128, l + 192: x1, y1, x2, y2 each) as table addresses
+  uint32_t ta0, ta1, ta2, ta3, ta4, ta5, ta6, ta7, ta8, ta9, ta10, ta11, ta12, ta13, ta14, ta15;
+  {
+    const uint32_t tp0 = *(const uint32_t*)(pattern + (0 * 64 + lane) * 4), tp1 = *(const uint32_t*)(pattern + (1 * 64 + lane) * 4);
+    const uint32_t tp2 = *(const uint32_t*)(pattern + (2 * 64 + lane) * 4), tp3 = *(const uint32_t*)(pattern + (3 * 64 + lane) * 4);
+    auto entry = [&](uint32_t tpg, int byte) { return rc_addr + (uint32_t)(((int)(int8_t)((tpg >> (8 * byte)) & 255u) + BRIEF_R) * 8); };
+    ta0 = entry(tp0, 0), ta1 = entry(tp0, 1), ta2 = entry(tp0, 2), ta3 = entry(tp0, 3);
+    ta4 = entry(tp1, 0), ta5 = entry(tp1, 1), ta6 = entry(tp1, 2), ta7 = entry(tp1, 3);
+    ta8 = entry(tp2, 0), ta9 = entry(tp2, 1), ta10 = entry(tp2, 2), ta11 = entry(tp2, 3);
+    ta12 = entry(tp3, 0), ta13 = entry(tp3, 1), ta14 = entry(tp3, 2), ta15 = entry(tp3, 3);
+  }
   // window load: two LDS-DMA instructions of 16 bytes a lane.  The destination of one is buffer + lane * 16 whatever the lane asks for,
   // so unit u = lane (+ 64) IS row u / 3, bytes 16 (u % 3) ... + 15 of the 48-byte row; the source stays per lane:
   // plane + (y - 18 + row) stride + xa + 16 part, a multiple of 4 as before (xa, the strides and the plane offsets are).
@@ -483,52 +524,56 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
   // the window's last row is y + 18 <= h - 2: the spill-over stays inside the next row of the SAME plane (w + 9 < 2 stride), it never
   // leaves the plane, let alone the image's block.  (The 44-byte rows before reached w + 5 the same way.)
   const int u1 = min(lane + 64, BRIEF_ROWS * (BRIEF_PITCH / 16) - 1);  // units 111 .. 127: unit 110 again, into the buffer's tail
-  const uint32_t row_a = (uint32_t)lane / 3u, row_b = (uint32_t)u1 / 3u;
-  const uint32_t col_a = 16u * ((uint32_t)lane - 3u * row_a), col_b = 16u * ((uint32_t)u1 - 3u * row_b);
-  typedef __attribute__((address_space(3))) uint8_t* lds_dst_t;
-  typedef const __attribute__((address_space(1))) uint8_t* glb_src_t;
-  // requests the window of the keypoint in entry e into buffer b (an unused slot -- x = 0xFFFF -- reads row 0 of plane 0: harmless)
-  auto request = [&](const uint4 e, int b) __attribute__((always_inline)) {
+  uint32_t row_a = (uint32_t)lane / 3u, row_b = (uint32_t)u1 / 3u;
+  uint32_t col_a = 16u * ((uint32_t)lane - 3u * row_a), col_b = 16u * ((uint32_t)u1 - 3u * row_b);
+  // the table's writers (lanes 0 .. 36: coordinate v = lane - 18) and the descriptor's (lanes 0 .. 7: a dword each)
+  double tv = (double)(float)(lane - BRIEF_R);
+  uint32_t tw_addr = rc_addr + 8u * (uint32_t)lane;
+  uint32_t st_off = 4u * (uint32_t)lane;
+  // requests the window of the keypoint in entry e into the buffer at LDS offset wo of the wave's first (an unused slot -- x = 0xFFFF --
+  // reads row 0 of plane 0: harmless)
+  auto request = [&](const uint4 e, uint32_t wo) __attribute__((always_inline)) {
     const bool used = (e.x & 0xFFFFu) != 0xFFFFu;
     const int x = used ? (int)(e.x & 0xFFFFu) : BRIEF_R, y = used ? (int)(e.x >> 16) : BRIEF_R;
     const uint32_t plane = used ? e.z : 0u;
     const uint32_t stride = used ? e.w : 0u;
     const uint32_t xa = (uint32_t)(x - BRIEF_R) & ~3u;
     const uint32_t s0 = plane + (uint32_t)(y - BRIEF_R) * stride + xa;  // (scalar unit)
-    uint8_t* dst = lds.win[wave][b];
-    __builtin_amdgcn_global_load_lds((glb_src_t)(W + (s0 + col_a + __umul24(row_a, stride))), (lds_dst_t)dst, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((glb_src_t)(W + (s0 + col_b + __umul24(row_b, stride))), (lds_dst_t)(dst + 1024), 16, 0, 0);
+    lds_dst_t dst = (lds_dst_t)(uintptr_t)(win_addr + wo);
+    __builtin_amdgcn_global_load_lds((glb_src_t)(W + (s0 + col_a + __umul24(row_a, stride))), dst, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_src_t)(W + (s0 + col_b + __umul24(row_b, stride))), dst + 1024, 16, 0, 0);
   };
-  uint4 e_cur = list[k0];
-  uint4 e_nxt = list[min(k0 + 1, k_last)];
-  double2 sc_cur = sc[k0];
+  int k = kbase;
+  uint4 e_cur = list[k];
+  uint4 e_nxt = list[min(k + BRIEF_WAVES, k_last)];
+  double2 sc_cur = sc[k];
 #ifdef BRIEF_STAMPS
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   bs_ta = __builtin_amdgcn_s_memrealtime();
 #endif
   // The template words must have ARRIVED before the first DMA is issued: the compiler waits for an ordinary load's result with
   // vmcnt(0) once an LDS-DMA is behind it on the counter, and where that wait falls in front of the tests it drains the window of the
-  // next keypoint too.  (They were requested first and come from L2 like the list entry the DMA needs anyway.)
-  asm volatile("" : "+v"(tp0), "+v"(tp1), "+v"(tp2), "+v"(tp3));
-  request(e_cur, 0);
+  // next keypoint too.  (They were requested first and come from L2 like the list entry the DMA needs anyway.)  The same statement
+  // pins every per-lane constant in its register: none of them is built again inside the loop.
+  asm volatile("" : "+v"(ta0), "+v"(ta1), "+v"(ta2), "+v"(ta3), "+v"(ta4), "+v"(ta5), "+v"(ta6), "+v"(ta7), "+v"(ta8), "+v"(ta9), "+v"(ta10),
+               "+v"(ta11), "+v"(ta12), "+v"(ta13), "+v"(ta14), "+v"(ta15), "+v"(row_a), "+v"(row_b), "+v"(col_a), "+v"(col_b), "+v"(tv),
+               "+v"(tw_addr), "+v"(st_off));
+  request(e_cur, 0u);
 #ifdef BRIEF_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   bs_tb = __builtin_amdgcn_s_memrealtime();
 #endif
-#pragma unroll
-  for (int i = 0; i < BRIEF_KPW; ++i) {
-    const int k = k0 + i;
-    if (k > k_last) break;  // wave-uniform
+  uint32_t wo = 0u;  // LDS offset of the buffer keypoint k landed in: 0 / BRIEF_WIN_BYTES in turn (scalar)
+#pragma clang loop unroll(disable)
+  for (;;) {
     // stage 1 / 2 for the keypoints behind this one
-    uint4 e_nn = e_nxt;
-    double2 sc_nxt = sc_cur;
-    if (i + 2 < BRIEF_KPW) e_nn = list[min(k + 2, k_last)];
-    // vmcnt retires in order: with the two DMA instructions of keypoint k + 1 behind them, "at most two outstanding" means those of k
-    // have landed (the descriptor store of k - 1 between them only makes the wait stricter).  The issuing wave's own counted wait is
-    // all that orders its ds_read behind its LDS-DMA; no wave ends with a DMA in flight (every request is waited for below).
-    if (i + 1 < BRIEF_KPW && k < k_last) {  // wave-uniform
-      request(e_nxt, (i + 1) & 1);
-      sc_nxt = sc[k + 1];
+    const uint4 e_nn = list[min(k + 2 * BRIEF_WAVES, k_last)];
+    const double2 sc_nxt = sc[min(k + BRIEF_WAVES, k_last)];  // (beside the list entry, in front of the request: behind it the compiler made a vector load of it)
+    // vmcnt retires in order: with the two DMA instructions of the next keypoint behind them, "at most two outstanding" means those of k
+    // have landed (the descriptor store of the one before between them only makes the wait stricter).  The issuing wave's own counted
+    // wait is all that orders its ds_read behind its LDS-DMA; no wave ends with a DMA in flight (every request is waited for below).
+    if (k < k_last) {  // wave-uniform
+      request(e_nxt, wo ^ BRIEF_WIN_BYTES);
       asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -537,15 +582,13 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
     if ((e_cur.x & 0xFFFFu) != 0xFFFFu) {  // wave-uniform
       const int x = (int)(e_cur.x & 0xFFFFu), y = (int)(e_cur.x >> 16);
       const int xa = (x - BRIEF_R) & ~3;
-      const uint8_t* win = lds.win[wave][i & 1];
       const double sn = sc_cur.x, cs = sc_cur.y;
       // The rotation needs x cos, x sin, y cos, y sin in fp64 for 512 template points, but the coordinates are small integers:
       // 37 lanes form the products once ((double)v * cs is exactly what the per-point expression computes), every point then
       // takes two LDS reads and one fp64 add per coordinate instead of two fp64 multiplies and a conversion.
       if (lane <= 2 * BRIEF_R) {
-        const double v = (double)(float)(lane - BRIEF_R);
-        rc[lane] = v * cs;
-        rs[lane] = v * sn;
+        *(lds_f64w_t)(uintptr_t)tw_addr = tv * cs;
+        *(lds_f64w_t)(uintptr_t)(tw_addr + RS_OFF) = tv * sn;
       }
       // the LDS accesses of one wave execute in order, so the table written above is visible to every lane of this wave (the window
       // landed before the counted wait above let the wave on); the fence only pins the compiler
@@ -566,50 +609,61 @@ __global__ __launch_bounds__(64 * BRIEF_WAVES) __attribute__((amdgpu_waves_per_e
       // the row constant folds in -(y0w & ~1), even; the row index it leaves is (Y - y0w) + (y0w & 1), one too many where the first
       // row is odd, and the column constant takes that row back as one pitch.  The column constant folds in -xa (a multiple of 4),
       // the buffer address (a multiple of 16) and 0 or -48: even in every case, so the ties of the column sum fall where they fell.
-      typedef const __attribute__((address_space(3))) uint8_t* lds_bytes_t;
       auto magic_row = [](int y0w) { return (float)(12582912 - (y0w & ~1)); };
       auto magic_col = [](int xa, int y0w, int pitch, int lds_addr) { return (float)(12582912 - xa + lds_addr - (y0w & 1) * pitch); };
       const int y0w = y - BRIEF_R;
       const float magic_y = magic_row(y0w);
-      const float magic_x = magic_col(xa, y0w, BRIEF_PITCH, (int)(uint32_t)(uintptr_t)(lds_bytes_t)win);
-      auto tests = [&](const uint32_t tpg) __attribute__((always_inline)) -> unsigned long long {
-        const int x1 = (int)(int8_t)(tpg & 255u), y1 = (int)(int8_t)((tpg >> 8) & 255u);
-        const int x2 = (int)(int8_t)((tpg >> 16) & 255u), y2 = (int)(int8_t)(tpg >> 24);
+      const float magic_x = magic_col(xa, y0w, BRIEF_PITCH, (int)(win_addr + wo));
+      // one group of 64 tests: the lane's pair (x1, y1), (x2, y2) by its four table addresses.  All eight table reads are issued before
+      // the first is waited for.
+      auto tests = [&](uint32_t ax1, uint32_t ay1, uint32_t ax2, uint32_t ay2) __attribute__((always_inline)) -> unsigned long long {
+        const double c_x1 = *(lds_f64_t)(uintptr_t)ax1, s_y1 = *(lds_f64_t)(uintptr_t)(ay1 + RS_OFF);
+        const double s_x1 = *(lds_f64_t)(uintptr_t)(ax1 + RS_OFF), c_y1 = *(lds_f64_t)(uintptr_t)ay1;
+        const double c_x2 = *(lds_f64_t)(uintptr_t)ax2, s_y2 = *(lds_f64_t)(uintptr_t)(ay2 + RS_OFF);
+        const double s_x2 = *(lds_f64_t)(uintptr_t)(ax2 + RS_OFF), c_y2 = *(lds_f64_t)(uintptr_t)ay2;
         // float * double -> double, one rounding to float (rotateTemplate, ORBExtractor.cc:537-538)
-        const float p1x = (float)(rc[x1 + BRIEF_R] - rs[y1 + BRIEF_R]);  // x1 cos - y1 sin
-        const float p1y = (float)(rs[x1 + BRIEF_R] + rc[y1 + BRIEF_R]);  // x1 sin + y1 cos
-        const float p2x = (float)(rc[x2 + BRIEF_R] - rs[y2 + BRIEF_R]);
-        const float p2y = (float)(rs[x2 + BRIEF_R] + rc[y2 + BRIEF_R]);
-        const uint32_t a1 = (uint32_t)mad24u(__float_as_int((py + p1y) + magic_y), BRIEF_PITCH, __float_as_int((px + p1x) + magic_x)) & 0xFFFFu;
-        const uint32_t a2 = (uint32_t)mad24u(__float_as_int((py + p2y) + magic_y), BRIEF_PITCH, __float_as_int((px + p2x) + magic_x)) & 0xFFFFu;
+        const float p1x = (float)(c_x1 - s_y1);  // x1 cos - y1 sin
+        const float p1y = (float)(s_x1 + c_y1);  // x1 sin + y1 cos
+        const float p2x = (float)(c_x2 - s_y2);
+        const float p2y = (float)(s_x2 + c_y2);
+        const uint32_t a1 = brief_addr(__float_as_int((py + p1y) + magic_y), __float_as_int((px + p1x) + magic_x));
+        const uint32_t a2 = brief_addr(__float_as_int((py + p2y) + magic_y), __float_as_int((px + p2x) + magic_x));
         const int v1 = *(lds_bytes_t)(uintptr_t)a1;
         const int v2 = *(lds_bytes_t)(uintptr_t)a2;
         return __ballot(v1 < v2);
       };
-      // (four named words, not an array.  r6: a private array that rotates through the keypoint loop is moved to LDS by the compiler,
+      // (named registers, not an array.  r6: a private array that rotates through the keypoint loop is moved to LDS by the compiler,
       //  addressed by the FLAT thread number -- for which it reads the workgroup's y and z sizes from the dispatch packet, and that packet
       //  lives in the queue's ring buffer in HOST memory: every wave of every launch began with a scalar load across PCIe that no cache
       //  holds, a launch of 18 - 31 us.  No kernel of this library may touch blockDim / gridDim or keep a private array.)
-      const unsigned long long bits0 = tests(tp0), bits1 = tests(tp1), bits2 = tests(tp2), bits3 = tests(tp3);
-      if (lane < 4) {
-        unsigned long long* d64 = (unsigned long long*)(desc + ((size_t)img * n_features + k) * 32);
-        unsigned long long b = bits0;
-        if (lane == 1) b = bits1;
-        if (lane == 2) b = bits2;
-        if (lane == 3) b = bits3;
-        d64[lane] = b;
-        if (desc_host) ((unsigned long long*)(desc_host + ((size_t)img * n_features + k) * 32))[lane] = b;
+      const unsigned long long bits0 = tests(ta0, ta1, ta2, ta3), bits1 = tests(ta4, ta5, ta6, ta7);
+      const unsigned long long bits2 = tests(ta8, ta9, ta10, ta11), bits3 = tests(ta12, ta13, ta14, ta15);
+      // the eight ballot dwords go to lanes 0 .. 7 of one register (a v_writelane each) and leave as one 32-byte store by eight lanes
+      // (before: 8 moves from scalar registers and 6 selects to put 64 bits into each of lanes 0 .. 3, and a 64-bit address per lane)
+      // (one asm block: the lanes above 7 of dv stay undefined and are not stored; a scalar register a v_cmp wrote may be read as DATA by the
+      //  next vector instruction -- only as a lane SELECT would it need wait states)
+      uint32_t dv;
+      asm("v_writelane_b32 %0, %1, 0\n\tv_writelane_b32 %0, %2, 1\n\tv_writelane_b32 %0, %3, 2\n\tv_writelane_b32 %0, %4, 3\n\t"
+          "v_writelane_b32 %0, %5, 4\n\tv_writelane_b32 %0, %6, 5\n\tv_writelane_b32 %0, %7, 6\n\tv_writelane_b32 %0, %8, 7"
+          : "=v"(dv)
+          : "s"((uint32_t)bits0), "s"((uint32_t)(bits0 >> 32)), "s"((uint32_t)bits1), "s"((uint32_t)(bits1 >> 32)), "s"((uint32_t)bits2),
+            "s"((uint32_t)(bits2 >> 32)), "s"((uint32_t)bits3), "s"((uint32_t)(bits3 >> 32)));
+      if (lane < 8) {
+        const size_t o = ((size_t)img * n_features + k) * 32;  // (scalar; the lane's share is the 32-bit st_off)
+        *(uint32_t*)(desc + o + st_off) = dv;
+        if (desc_host) *(uint32_t*)(desc_host + o + st_off) = dv;
       }
       // every lane has read what it needs of this table, and of this window, before the next keypoint's table is written over the one
       // and the window of the keypoint after that is requested into the other
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
-    if (i + 1 < BRIEF_KPW) {
-      e_cur = e_nxt;
-      e_nxt = e_nn;
-      sc_cur = sc_nxt;
-    }
+    if (k >= k_last) break;  // wave-uniform
+    k += BRIEF_WAVES;
+    wo ^= BRIEF_WIN_BYTES;
+    e_cur = e_nxt;
+    e_nxt = e_nn;
+    sc_cur = sc_nxt;
   }
   BS_END(1)
 }
@@ -658,7 +712,7 @@ void launch_orient_brief(hipStream_t s, const LevelDev* d_lv, int n_levels, cons
                          int32_t* d_n_kp, double* d_theta, int2* d_moments, double2* d_sincos, KpX* d_kx,
                          uint4* d_kpl, int rows0, int n_img, hipEvent_t before_brief, hipEvent_t before_lists, orbfe_keypoint* h_kps,
                          uint8_t* h_desc, int32_t* h_n_kp, bool fuse_small, uint32_t* d_rowoff_slot, uint16_t* d_rowlist_slot, int32_t* d_n_match,
-                         int rt_rows, int rt_list_cap, int rt_slot0, int32_t* d_rt_flags) {
+                         int rt_rows, int rt_list_cap, int rt_slot0, int32_t* d_rt_flags, int brief_kpw) {
   // d_rowoff_slot != nullptr (a frame or two): the launch of the descriptors also builds the row table of every image into the slot's table
   if (n_img <= 0 || n_features <= 0) return;
   UmaxPacked u = 0;
@@ -669,7 +723,8 @@ void launch_orient_brief(hipStream_t s, const LevelDev* d_lv, int n_levels, cons
                        d_pyr, img_pitch, u, d_kpl, d_moments, d_sincos, d_kps, d_aux, d_kx, d_theta, rows0, d_n_kp, h_kps, h_n_kp,
                        (d_rowoff_slot && d_rt_flags) ? d_rt_flags + (size_t)rt_slot0 * 8 : (int32_t*)nullptr);
     if (before_brief) (void)hipStreamWaitEvent(s, before_brief, 0);
-    const int nb = (((n_features + BRIEF_WAVES * BRIEF_KPW - 1) / (BRIEF_WAVES * BRIEF_KPW)) + 7) & ~7;
+    const int kpw = brief_kpw > 0 ? std::min(brief_kpw, BRIEF_KPW_MAX) : BRIEF_KPW;  // (4 000 keypoints: a longer loop leaves SIMDs empty)
+    const int nb = (((n_features + BRIEF_WAVES * kpw - 1) / (BRIEF_WAVES * kpw)) + 7) & ~7;
     BriefRowTable rt{};
     rt.n_brief_blocks = nb;
     if (d_rowoff_slot && (size_t)(rt_rows + 4) * 4 <= 9000)
@@ -679,10 +734,10 @@ void launch_orient_brief(hipStream_t s, const LevelDev* d_lv, int n_levels, cons
     // alignment allows 16-byte copies; two descriptor workgroups per CU still fit beside it
     if (rt.rowoff && (rt.flags || rt_list_cap % 8 == 0)) rt.stage_cap = rt.flags ? 4 * std::min(n_features, 4096) : std::min(rt_list_cap, 20480);  // (parts: a band record, 8 bytes, per keypoint)
     hipLaunchKernelGGL(k_brief, dim3(nb + (rt.rowoff ? 8 : 0), n_img), dim3(64 * BRIEF_WAVES), (size_t)rt.stage_cap * 2, s, d_blur, img_pitch, d_kpl, n_features,
-                       d_pattern, d_sincos, d_desc, h_desc, rt);
+                       d_pattern, d_sincos, d_desc, h_desc, rt, kpw);
 #ifdef EXP_BRIEF_TWICE
     hipLaunchKernelGGL(k_brief, dim3(nb + (rt.rowoff ? 8 : 0), n_img), dim3(64 * BRIEF_WAVES), 0, s, d_blur, img_pitch, d_kpl, n_features, d_pattern,
-                       d_sincos, d_desc, h_desc, rt);
+                       d_sincos, d_desc, h_desc, rt, kpw);
 #endif
     return;
   }
@@ -702,9 +757,10 @@ void launch_orient_brief(hipStream_t s, const LevelDev* d_lv, int n_levels, cons
                      d_kps, d_aux, d_kx, d_theta, rows0, d_sel_count, n_levels, d_n_kp, h_kps, h_n_kp);
   if (before_brief) (void)hipStreamWaitEvent(s, before_brief, 0);  // the blurred planes come from another stream
   BriefRowTable rt_none{};
-  rt_none.n_brief_blocks = (((n_features + BRIEF_WAVES * BRIEF_KPW - 1) / (BRIEF_WAVES * BRIEF_KPW)) + 7) & ~7;  // (= the grid: no row-table blocks)
+  const int kpw = brief_kpw > 0 ? std::min(brief_kpw, BRIEF_KPW_MAX) : BRIEF_KPW_BATCH;
+  rt_none.n_brief_blocks = (((n_features + BRIEF_WAVES * kpw - 1) / (BRIEF_WAVES * kpw)) + 7) & ~7;  // (= the grid: no row-table blocks)
   hipLaunchKernelGGL(k_brief, dim3(rt_none.n_brief_blocks, n_img), dim3(64 * BRIEF_WAVES), 0, s, d_blur, img_pitch, d_kpl, n_features, d_pattern, d_sincos, d_desc,
-                     h_desc, rt_none);
+                     h_desc, rt_none, kpw);
 }
 
 }  // namespace orbfe

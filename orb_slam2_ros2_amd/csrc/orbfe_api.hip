@@ -698,6 +698,7 @@ orbfe_status orbfe_create(const orbfe_config* cfg, orbfe_ctx** out) {
     }
     if (const char* hl = getenv("ORBFE_LBA_HOST_LM")) c->lm_on_device = atoi(hl) == 0;
     if (const char* fc = getenv("ORBFE_FAST_CPW")) c->fast_cpw = std::max(0, std::min(64, atoi(fc)));
+    if (const char* bk = getenv("ORBFE_BRIEF_KPW")) c->brief_kpw = std::max(0, std::min(64, atoi(bk)));
     if (const char* fm = getenv("ORBFE_FAST_SIDE_MASK")) c->fast_side_mask = (int64_t)(strtoul(fm, nullptr, 0) & 0xFFFFu);
     if (const char* fg = getenv("ORBFE_FAST_SIDE_MERGE")) c->fast_side_merge = atoi(fg) != 0;
     const char* ov = getenv("ORBFE_OVERLAP_BLUR");

@@ -73,7 +73,8 @@ void launch_orient_brief(hipStream_t s, const LevelDev* d_lv, int n_levels, cons
                          int32_t* d_n_kp, double* d_theta, int2* d_moments, double2* d_sincos, KpX* d_kx,
                          uint4* d_kpl, int rows0, int n_img, hipEvent_t before_brief, hipEvent_t before_lists, orbfe_keypoint* h_kps, uint8_t* h_desc, int32_t* h_n_kp,
                          bool fuse_small, uint32_t* d_rowoff_slot = nullptr, uint16_t* d_rowlist_slot = nullptr,
-                         int32_t* d_n_match = nullptr, int rt_rows = 0, int rt_list_cap = 0, int rt_slot0 = 0, int32_t* d_rt_flags = nullptr);
+                         int32_t* d_n_match = nullptr, int rt_rows = 0, int rt_list_cap = 0, int rt_slot0 = 0, int32_t* d_rt_flags = nullptr,
+                         int brief_kpw = 0);  // keypoints per k_brief wave (0: the launcher's rule)
 // k_match.hip
 void launch_match_bruteforce(hipStream_t s, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, const uint32_t* d_off,
                              const uint32_t* d_cand, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second);
@@ -253,6 +254,7 @@ struct orbfe_ctx {
   bool pipeline_stereo = true;
   hipStream_t blur_stream = nullptr;
   int fast_cpw = 0;  // ORBFE_FAST_CPW: cells per k_fast wave (0: one for small launches, four for large ones)
+  int brief_kpw = 0;  // ORBFE_BRIEF_KPW: keypoints per k_brief wave (0: two for a frame or two, eight for batches)
   hipEvent_t ev_blur_go = nullptr, ev_blur_done = nullptr;
   // r6: the k_fast launches of the SMALL levels (fewer than 131072 cell x images: they run one or four cells per wave and each is little more
   // than a ramp and a tail) go to fast_stream beside the launches of the large levels.  fast_side_mask: -1 = that rule (default), else the
