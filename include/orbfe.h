@@ -1217,6 +1217,85 @@ typedef struct orbfe_reloc_output {
 orbfe_status orbfe_reloc_refine_stored(orbfe_ctx* ctx, int32_t slot, orbfe_kfstore* store, const orbfe_reloc_input* in,
                                        const orbfe_reloc_output* out);
 
+/* ---- trackReference over a stored keyframe -------------------------------------------------------------------------------
+ * Tracking::trackReference (src/Tracking.cc:360-371) as one call: Frame::computeBow (include/ORB_SLAM2/Frame.h:224-229),
+ * ORBMatcher::searchByBow(frame, keyframe) with verifyAngle and setMapPoints (src/ORBMatcher.cc:170-253, 815-830, 1013-1051), the :365
+ * decision, Optimizer::OptimizePoseOnly with its projection post-check (src/Optimizer.cc:33-203), the :370 decision.  The frame's
+ * keypoints, descriptors, angles and count are the device-resident results of `slot`; the reference keyframe's features, angles and
+ * FeatureVector are read where the store keeps them; only map state goes up.
+ *   T1 bow        vocab != NULL: orbfe_bow_slots' transform of the slot at `levelsup`; vocab == NULL: the host FeatureVector of the input
+ *                 (a frame whose computeBow has run; it must be the vector of the frame in `slot`: a feature index at or past the
+ *                 slot's keypoint count is matched against nothing meaningful and never receives a point).  Exactly one of the two;
+ *                 they are bit-identical by construction
+ *   T2 matches    orbfe_search_by_bow_stored's list for this one candidate in mode ORBFE_BOW_TRACK: keyframe flags `good`, frame flags
+ *                 `frame_good` (NULL: setMapPointsNull()), the reference's order, verifyAngle when check_orientation is set
+ *   T3 assign     setMapPoints in match order: frame feature `query` takes keyframe feature `train`'s point; of several matches that
+ *                 name one frame feature the last keeps it.  addMatchInTrack is the caller's, once per MATCH
+ *   T4 decide #1  n_matches < min_matches: REJECT_MATCHES; matches and assigned are reported (the reference has written the frame by
+ *                 then, :251 before :365), final_assigned = assigned, everything of the optimisation is zero
+ *   T5 edges      the features that hold a point, their own (frame_good) or an assigned one, in feature order; Xw from frame_pos[f] or
+ *                 pos[assigned[f]]; mono when right_u[f] < 0; information and thresholds as orbfe_pose_only_optimize
+ *   T6 optimise   from Converter::ConvertTcw2SE3 of (Rcw, tcw) (the relocalisation refine's seed), orbfe_pose_only_optimize's kernel
+ *   T7 post-check the relocalisation refine's, with the pose the frame still has (the input pose); n_inliers = edges - nBad; every
+ *                 feature that is no inlier loses its point (final_assigned); Tcw = Converter::ConvertSE32Tcw of the estimate
+ *   T8 decide #2  n_inliers >= min_inliers: ACCEPT, else REJECT_INLIERS
+ * Outputs, every array required but bow: verdict, n_matches, matches [n] (one per keyframe feature at most), assigned [n_features] (the
+ * keyframe feature whose point frame feature f holds after setMapPoints, -1 none, ORBFE_TRACKREF_OWN the point it came with), n_edges,
+ * n_inliers, inlier [n_features] (after the post-check), final_assigned [n_features], pose_se3 (qx qy qz qw tx ty tz), Tcw (Rcw row-major,
+ * then tcw); bow (nullable, ignored with vocab == NULL) receives the frame's BowVector and FeatureVector in orbfe_bow_slots' layout for
+ * one slot -- Frame::mBowVec / mFeatVec, which KeyFrameDB needs later.
+ * ORBFE_EBADARG, nothing written: an unknown id, n unequal to the stored count, a keyframe without FeatureVector, both or neither of
+ * vocab and a host FeatureVector, a malformed host FeatureVector (orbfe_kfstore_set_bow's checks), a pose, bounds or camera entry not
+ * finite, a NULL required array, the context's n_levels below the store's, a context on another device.  ORBFE_EBADSIZE: a context of
+ * more than 2048 features.  Locks: the context's, then the store's (shared) for the whole synchronous duration.  One upload, one launch
+ * sequence (transform, match, select, seed, optimise, check) whose kernels after the seed leave at once when the verdict has fallen,
+ * one download; no synchronisation in between.                                                                                        */
+typedef enum orbfe_trackref_verdict {
+  ORBFE_TRACKREF_REJECT_MATCHES = 1, /* fewer than min_matches matches (Tracking.cc:365)   */
+  ORBFE_TRACKREF_REJECT_INLIERS = 2, /* fewer than min_inliers after the optimisation (:370) */
+  ORBFE_TRACKREF_ACCEPT = 3
+} orbfe_trackref_verdict;
+#define ORBFE_TRACKREF_OWN (-2)
+typedef struct orbfe_trackref_input {
+  uint64_t kf_id;                /* the reference keyframe in the store (it needs a FeatureVector)                        */
+  int32_t n;                     /* must equal the stored count                                                           */
+  const uint8_t* good;           /* [n] the keyframe feature's map point is non-null and not bad                          */
+  const float* pos;              /* [n][3] MapPoint::getPos() (read where good)                                           */
+  const uint8_t* frame_good;     /* [n_features], nullable: the frame feature came with a good point                      */
+  const float* frame_pos;        /* [n_features][3], read where frame_good is set (required with frame_good)              */
+  const double* right_u;         /* [n_features], nullable (every edge mono)                                              */
+  float Rcw[9], tcw[3];          /* the pose the frame has: the last frame's (Tracking.cc:121)                            */
+  float bounds[4];               /* the frame's mfMinU mfMaxU mfMinV mfMaxV                                               */
+  const float* level_sigma2;     /* [n_levels of the context]                                                             */
+  const float* level_inv_sigma2; /* [n_levels of the context]                                                             */
+  const orbfe_camera* cam;       /* fx fy cx cy bf                                                                        */
+  int32_t levelsup;              /* 4                                                                                     */
+  float ratio;                   /* 0.7                                                                                   */
+  int32_t dist_threshold;        /* ORBMatcher::mnMinThreshold                                                            */
+  int32_t check_orientation;     /* 1                                                                                     */
+  int32_t min_matches;           /* 10 (the comment at :355 says 15, the code at :365 says 10)                            */
+  int32_t min_inliers;           /* 10                                                                                    */
+  int32_t n_nodes;               /* the frame's FeatureVector in orbfe_bow_out's layout: used iff vocab == NULL           */
+  const uint32_t* nodes;
+  const int32_t* node_offsets;
+  const uint32_t* features;
+} orbfe_trackref_input;
+typedef struct orbfe_trackref_output {
+  int32_t* verdict;           /* [1] orbfe_trackref_verdict  */
+  int32_t* n_matches;         /* [1]                         */
+  orbfe_bow_match* matches;   /* [n]                         */
+  int32_t* assigned;          /* [n_features]                */
+  int32_t* n_edges;           /* [1]                         */
+  int32_t* n_inliers;         /* [1]                         */
+  uint8_t* inlier;            /* [n_features]                */
+  int32_t* final_assigned;    /* [n_features]                */
+  double* pose_se3;           /* [7]                         */
+  float* Tcw;                 /* [12]                        */
+  const orbfe_bow_out* bow;   /* nullable                    */
+} orbfe_trackref_output;
+orbfe_status orbfe_track_reference_stored(orbfe_ctx* ctx, int32_t slot, const orbfe_vocab* vocab, orbfe_kfstore* store,
+                                          const orbfe_trackref_input* in, const orbfe_trackref_output* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

@@ -124,6 +124,23 @@ class RelocOutput(C.Structure):
 RELOC_VERDICTS = {1: "REJECT_1", 2: "ACCEPT_1", 3: "REJECT_2", 4: "ACCEPT_2", 5: "REJECT_3", 6: "ACCEPT_3"}
 
 
+class TrackRefInput(C.Structure):
+    _fields_ = [("kf_id", C.c_uint64), ("n", C.c_int32), ("good", C.c_void_p), ("pos", C.c_void_p), ("frame_good", C.c_void_p),
+                ("frame_pos", C.c_void_p), ("right_u", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("bounds", C.c_float * 4),
+                ("level_sigma2", C.c_void_p), ("level_inv_sigma2", C.c_void_p), ("cam", C.POINTER(Camera)), ("levelsup", C.c_int32),
+                ("ratio", C.c_float), ("dist_threshold", C.c_int32), ("check_orientation", C.c_int32), ("min_matches", C.c_int32),
+                ("min_inliers", C.c_int32), ("n_nodes", C.c_int32), ("nodes", C.c_void_p), ("node_offsets", C.c_void_p), ("features", C.c_void_p)]
+
+
+class TrackRefOutput(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("verdict", "n_matches", "matches", "assigned", "n_edges", "n_inliers", "inlier", "final_assigned",
+                                          "pose_se3", "Tcw", "bow")]
+
+
+TRACKREF_VERDICTS = {1: "REJECT_MATCHES", 2: "REJECT_INLIERS", 3: "ACCEPT"}
+TRACKREF_OWN = -2
+
+
 class MapSummary(C.Structure):
     _fields_ = [("next_id", C.c_uint64), ("n_scale_factors", C.c_int32), ("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32),
                 ("n_keypoints", C.c_int64), ("n_observations", C.c_int64)]
@@ -233,6 +250,7 @@ EXPORTS = [
     "orbfe_kfstore_erase", "orbfe_kfstore_size", "orbfe_kfstore_info_get", "orbfe_kfstore_fetch", "orbfe_fuse_into_keyframes_stored",
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
     "orbfe_fuse_points_into_keyframes_stored", "orbfe_debug_fuse_points_kernels", "orbfe_reloc_refine_stored",
+    "orbfe_track_reference_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
     "orbfe_debug_pg_sparse_solve", "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
@@ -379,6 +397,7 @@ def load() -> C.CDLL:
                                                           vp]
     L.orbfe_debug_fuse_points_kernels.argtypes = [vp]
     L.orbfe_reloc_refine_stored.argtypes = [vp, i32, vp, C.POINTER(RelocInput), C.POINTER(RelocOutput)]
+    L.orbfe_track_reference_stored.argtypes = [vp, i32, vp, vp, C.POINTER(TrackRefInput), C.POINTER(TrackRefOutput)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -2113,6 +2132,86 @@ class Context:
         res["verdict"] = int(out["verdict"][0])
         res["verdict_name"] = RELOC_VERDICTS.get(res["verdict"], "?")
         return res
+
+    def track_reference_stored(self, slot, vocab, store, kf_id, good, pos, Rcw, tcw, cam, bounds, level_sigma2, level_inv_sigma2,
+                               frame_good=None, frame_pos=None, right_u=None, feature_vector=None, want_bow=False, levelsup=4, ratio=0.7,
+                               dist_threshold=50, check_orientation=True, min_matches=10, min_inliers=10, out=None):
+        """Tracking::trackReference against the stored keyframe kf_id as one call (orbfe_track_reference_stored); the parameters and the
+        returned dict are described at track_reference_call, which builds the C arguments."""
+        args, keep = self.track_reference_call(slot, vocab, store, kf_id, good, pos, Rcw, tcw, cam, bounds, level_sigma2, level_inv_sigma2,
+                                               frame_good=frame_good, frame_pos=frame_pos, right_u=right_u, feature_vector=feature_vector,
+                                               want_bow=want_bow, levelsup=levelsup, ratio=ratio, dist_threshold=dist_threshold,
+                                               check_orientation=check_orientation, min_matches=min_matches, min_inliers=min_inliers, out=out)
+        self._check(self.lib.orbfe_track_reference_stored(*args))
+        out, bow_arrays = keep[-1], keep[-2]
+        res = {k: out[k] for k in ("assigned", "inlier", "final_assigned", "pose_se3", "Tcw")}
+        for k in ("verdict", "n_matches", "n_edges", "n_inliers"):
+            res[k] = int(out[k][0])
+        res["matches"] = out["matches"][:res["n_matches"]].copy()
+        res["verdict_name"] = TRACKREF_VERDICTS.get(res["verdict"], "?")
+        if want_bow and vocab is not None:
+            res["bow"] = _bow_split(bow_arrays, 0)
+        return res
+
+    def track_reference_call(self, slot, vocab, store, kf_id, good, pos, Rcw, tcw, cam, bounds, level_sigma2, level_inv_sigma2,
+                             frame_good=None, frame_pos=None, right_u=None, feature_vector=None, want_bow=False, levelsup=4, ratio=0.7,
+                             dist_threshold=50, check_orientation=True, min_matches=10, min_inliers=10, out=None):
+        """The ctypes arguments of orbfe_track_reference_stored for track_reference_stored's parameters -> (args, keep): the bare C call
+        is self.lib.orbfe_track_reference_stored(*args); keep holds the arrays behind the pointers (its last entry the output arrays)
+        and must live as long as args is used.  Nothing is kept on the context.
+        Tracking::trackReference against the stored keyframe kf_id as one call (orbfe_track_reference_stored): computeBow of the
+        extraction in `slot` (vocab: a Vocabulary) or the frame's FeatureVector given as feature_vector = (nodes, offsets, features) with
+        vocab None, searchByBow with setMapPoints, the 10-match decision, OptimizePoseOnly with its post-check, the 10-inlier decision.
+        good [n], pos [n, 3]: the keyframe's map state; frame_good [NF], frame_pos [NF, 3]: the points the frame came with (None: none);
+        (Rcw, tcw): the pose the frame has; cam = (fx, fy, cx, cy, bf); bounds = (minU, maxU, minV, maxV).
+        -> dict(verdict, verdict_name, n_matches, matches [n_matches] BOW_MATCH_DTYPE, assigned [NF] (TRACKREF_OWN: the point the feature
+        came with), n_edges, n_inliers, inlier [NF], final_assigned [NF], pose_se3 [7], Tcw [12]; with want_bow: bow = (words, values, nodes,
+        offsets, features) as bow_slots returns them); out: a dict of the raw output arrays to fill (a call that fails leaves it as it is)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        good = np.ascontiguousarray(good, np.uint8).reshape(-1)
+        pos = f32(pos).reshape(-1, 3)
+        n, NF = len(good), self.n_features
+        if len(pos) != n:
+            raise ValueError("track_reference_stored: good and pos differ in length")
+        right_u = None if right_u is None else np.ascontiguousarray(right_u, np.float64)
+        frame_good = None if frame_good is None else np.ascontiguousarray(frame_good, np.uint8).reshape(-1)
+        frame_pos = None if frame_pos is None else f32(frame_pos).reshape(-1, 3)
+        if (right_u is not None and right_u.size != NF) or (frame_good is not None and (frame_good.size != NF or frame_pos is None or len(frame_pos) != NF)):
+            raise ValueError("track_reference_stored: frame_good / frame_pos / right_u must have n_features entries")
+        s2, is2 = f32(level_sigma2), f32(level_inv_sigma2)
+        if s2.size < self.n_levels or is2.size < self.n_levels:
+            raise ValueError("track_reference_stored: one sigma2 / inv_sigma2 per level of the context")
+        cm = Camera(*[float(np.float32(v)) for v in cam[:4]], 0, 0, 0, 0, 0, float(np.float32(cam[4])))
+        ti = TrackRefInput()
+        ti.kf_id, ti.n = int(kf_id), n
+        ti.good, ti.pos = (ptr(good).value, ptr(pos).value) if n else (None, None)
+        if frame_good is not None:
+            ti.frame_good, ti.frame_pos = ptr(frame_good).value, ptr(frame_pos).value
+        ti.right_u = None if right_u is None else ptr(right_u).value
+        ti.Rcw[:] = f32(Rcw).reshape(9).tolist()
+        ti.tcw[:] = f32(tcw).reshape(3).tolist()
+        ti.bounds[:] = f32(bounds).reshape(4).tolist()
+        ti.level_sigma2, ti.level_inv_sigma2, ti.cam = ptr(s2).value, ptr(is2).value, C.pointer(cm)
+        ti.levelsup, ti.ratio, ti.dist_threshold = int(levelsup), float(ratio), int(dist_threshold)
+        ti.check_orientation, ti.min_matches, ti.min_inliers = int(bool(check_orientation)), int(min_matches), int(min_inliers)
+        fv = None
+        if feature_vector is not None:
+            nodes, offs, feats = feature_vector
+            fv = (np.ascontiguousarray(nodes, np.uint32), np.ascontiguousarray(offs, np.int32), np.ascontiguousarray(feats, np.uint32))
+            if len(fv[1]) != len(fv[0]) + 1 or (0 <= fv[1][-1] and fv[1][-1] > len(fv[2])):
+                raise ValueError("track_reference_stored: node_offsets must have len(nodes) + 1 entries ending inside features")
+            ti.n_nodes, ti.nodes, ti.node_offsets, ti.features = len(fv[0]), ptr(fv[0]).value, ptr(fv[1]).value, ptr(fv[2]).value
+        if out is None:
+            out = dict(verdict=np.zeros(1, np.int32), n_matches=np.zeros(1, np.int32), matches=np.zeros(max(n, 1), BOW_MATCH_DTYPE),
+                       assigned=np.full(NF, -1, np.int32), n_edges=np.zeros(1, np.int32), n_inliers=np.zeros(1, np.int32),
+                       inlier=np.zeros(NF, np.uint8), final_assigned=np.full(NF, -1, np.int32), pose_se3=np.zeros(7), Tcw=np.zeros(12, np.float32))
+        bow_arrays = bo = None
+        if want_bow:
+            bow_arrays = out.get("bow_arrays") or _bow_arrays(1, NF)
+            bo = BowOut(*[ptr(bow_arrays[k]).value for k, _ in BowOut._fields_])
+        to = TrackRefOutput(*[ptr(out[k]).value for k, _ in TrackRefOutput._fields_[:-1]], C.addressof(bo) if bo is not None else None)
+        args = (self.h, int(slot), None if vocab is None else vocab.h, store.h, C.byref(ti), C.byref(to))
+        return args, (good, pos, frame_good, frame_pos, right_u, s2, is2, cm, fv, ti, to, bo, bow_arrays, out)
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -12,6 +12,7 @@
 // k_bow_gather   one workgroup per candidate: the <= 64 lengths summed by one wave (every workgroup for itself: the lengths come from the
 //                previous launch, nobody waits), workgroup 0 writes match_offsets, and each list moves to its place -- unless the total
 //                exceeds the room, in which case only the offsets are written.
+// For one candidate and a frame in its extraction slot (orbfe_track_reference_stored) the first two run alone: launch_bow_search_one.
 //
 // Every loop is bounded by a feature count, a node count or BOW_ANGLE_BINS.
 #include <hip/hip_runtime.h>
@@ -27,7 +28,8 @@ namespace {
 
 using namespace orbfe;
 
-// Where the query's arrays are: behind the call's upload (BowQuery) or where the keyframe store keeps them (BowQueryStored).
+// Where the query's arrays are: behind the call's upload (BowQuery), where the keyframe store keeps them (BowQueryStored), or in an
+// extraction slot with a FeatureVector in device memory whose node count the host does not know (BowQuerySlot).
 __device__ __forceinline__ const uint8_t* q_desc(const uint8_t* up, const BowQuery& Q) { return up + Q.o_desc; }
 __device__ __forceinline__ const uint8_t* q_desc(const uint8_t*, const BowQueryStored& Q) { return Q.desc; }
 __device__ __forceinline__ const uint32_t* q_nodes(const uint8_t* up, const BowQuery& Q) { return (const uint32_t*)(up + Q.o_nodes); }
@@ -38,6 +40,14 @@ __device__ __forceinline__ const uint32_t* q_feat(const uint8_t* up, const BowQu
 __device__ __forceinline__ const uint32_t* q_feat(const uint8_t*, const BowQueryStored& Q) { return Q.feat; }
 __device__ __forceinline__ float q_angle(const uint8_t* up, const BowQuery& Q, int i) { return ((const float*)(up + Q.o_angle))[i]; }
 __device__ __forceinline__ float q_angle(const uint8_t*, const BowQueryStored& Q, int i) { return Q.kps[i].angle; }
+__device__ __forceinline__ const uint8_t* q_desc(const uint8_t*, const BowQuerySlot& Q) { return Q.desc; }
+__device__ __forceinline__ const uint32_t* q_nodes(const uint8_t*, const BowQuerySlot& Q) { return Q.nodes; }
+__device__ __forceinline__ const int32_t* q_offs(const uint8_t*, const BowQuerySlot& Q) { return Q.offs; }
+__device__ __forceinline__ const uint32_t* q_feat(const uint8_t*, const BowQuerySlot& Q) { return Q.feat; }
+__device__ __forceinline__ float q_angle(const uint8_t*, const BowQuerySlot& Q, int i) { return Q.kps[i].angle; }
+__device__ __forceinline__ int q_n_nodes(const BowQuery& Q) { return Q.n_nodes; }
+__device__ __forceinline__ int q_n_nodes(const BowQueryStored& Q) { return Q.n_nodes; }
+__device__ __forceinline__ int q_n_nodes(const BowQuerySlot& Q) { return *Q.n_nodes; }  // (written by the launch before)
 
 // ORBMatcher.cc:212-231: which query features are no candidates
 struct SkipQueryByMode {
@@ -60,9 +70,10 @@ __global__ __launch_bounds__(256) void k_bow_match(const uint8_t* __restrict__ u
   // ORBMatcher.cc:193-209: which keyframe features do not search
   const bool skip = P.mode == ORBFE_BOW_TRACK ? !(fb & ORBFE_TRI_GOOD) : P.mode == ORBFE_BOW_ADD ? (fb & 3) == 3 : false;
   int k = -1;
-  if (!skip && qr.n_nodes > 0) {
+  const int qn_nodes = q_n_nodes(qr);
+  if (!skip && qn_nodes > 0) {
     const uint32_t node = B.nodes[bow_entry_node(B.offs, B.n_nodes, j)];
-    k = bow_find_node(q_nodes(up, qr), qr.n_nodes, node);
+    k = bow_find_node(q_nodes(up, qr), qn_nodes, node);
   }
   if (k >= 0) {
     const int32_t* oq = q_offs(up, qr);
@@ -181,6 +192,12 @@ void launch_bow_search_t(hipStream_t st, const uint8_t* up, const BowKf* kfs, co
 void launch_bow_search(hipStream_t st, const uint8_t* up, const BowKf* kfs, const BowQuery& q, const BowParams& P, int max_feat, BowSlot* slots,
                        BowMatch* lists, int32_t* counts, int32_t* offsets, BowMatch* matches) {
   launch_bow_search_t(st, up, kfs, q, P, max_feat, slots, lists, counts, offsets, matches);
+}
+// one candidate, a frame in its slot: its list stays in `lists`, its length in counts[0] (no gather)
+void launch_bow_search_one(hipStream_t st, const uint8_t* up, const BowKf* kf, const BowQuerySlot& q, const BowParams& P, int n_feat,
+                           BowSlot* slots, BowMatch* lists, int32_t* counts) {
+  if (n_feat > 0) k_bow_match<BowQuerySlot><<<dim3((n_feat + 3) / 4, 1), 256, 0, st>>>(up, kf, q, P, slots);
+  k_bow_select<<<1, BOW_SEL_WG, 0, st>>>(kf, slots, lists, counts);
 }
 void launch_bow_search(hipStream_t st, const uint8_t* up, const BowKf* kfs, const BowQueryStored& q, const BowParams& P, int max_feat,
                        BowSlot* slots, BowMatch* lists, int32_t* counts, int32_t* offsets, BowMatch* matches) {

@@ -21,64 +21,14 @@
 #include "area_search_body.h"
 #include "map_point_dev.h"
 #include "orbfe_internal.h"
+#include "pose_check_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace orbfe {
 namespace {
 
-// the largest-diagonal branch of Eigen::Quaterniond(Matrix3d) with the largest element at I (constant indices: the arrays stay registers)
-template <int I>
-__device__ __forceinline__ void quat_diag(const double (&m)[3][3], double (&q)[4]) {
-  constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-  double tr = sqrt(m[I][I] - m[J][J] - m[K][K] + 1.0);
-  q[I] = 0.5 * tr;
-  tr = 0.5 / tr;
-  q[3] = (m[K][J] - m[J][K]) * tr;
-  q[J] = (m[J][I] + m[I][J]) * tr;
-  q[K] = (m[K][I] + m[I][K]) * tr;
-}
-
-// Converter::ConvertTcw2SE3 (src/Optimizer.cc:630-645): host/map_pb.hpp's tcw_to_se3
-__device__ __forceinline__ void tcw_to_se3_dev(const float* R, const float* t, double* out) {
-  double m[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) m[i][j] = (double)R[i * 3 + j];
-  double q[4];
-  double tr = m[0][0] + m[1][1] + m[2][2];
-  if (tr > 0.0) {
-    tr = sqrt(tr + 1.0);
-    q[3] = 0.5 * tr;
-    tr = 0.5 / tr;
-    q[0] = (m[2][1] - m[1][2]) * tr, q[1] = (m[0][2] - m[2][0]) * tr, q[2] = (m[1][0] - m[0][1]) * tr;
-  } else if (m[2][2] > (m[1][1] > m[0][0] ? m[1][1] : m[0][0]))
-    quat_diag<2>(m, q);
-  else if (m[1][1] > m[0][0])
-    quat_diag<1>(m, q);
-  else
-    quat_diag<0>(m, q);
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {  // Quaterniond::normalize(), then SE3Quat::normalizeRotation()
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (n > 0.0) q[0] /= n, q[1] /= n, q[2] /= n, q[3] /= n;
-  }
-  if (q[3] < 0.0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];
-  out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
-  out[4] = (double)t[0], out[5] = (double)t[1], out[6] = (double)t[2];
-}
-
-// Converter::ConvertSE32Tcw (src/Optimizer.cc:653-675): host/map_pb.hpp's se3_to_tcw
-__device__ __forceinline__ void se3_to_tcw_dev(const double* p, float* R, float* t) {
-  const double x = p[0], y = p[1], z = p[2], w = p[3];
-  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = (float)(1.0 - (tyy + tzz)), R[1] = (float)(txy - twz), R[2] = (float)(txz + twy);
-  R[3] = (float)(txy + twz), R[4] = (float)(1.0 - (txx + tzz)), R[5] = (float)(tyz - twx);
-  R[6] = (float)(txz - twy), R[7] = (float)(tyz + twx), R[8] = (float)(1.0 - (txx + tyy));
-  t[0] = (float)p[4], t[1] = (float)p[5], t[2] = (float)p[6];
-}
+// (the two pose conversions and the post-check: pose_check_dev.h, shared with k_trackref.hip)
 
 // The pose-only edges of what the frame holds (cur), in feature order, by the 1024 threads of one workgroup: k_track_edges' list
 // (Optimizer.cc:58-117).  Returns the count to every thread.
@@ -134,7 +84,7 @@ __global__ __launch_bounds__(1024) void k_reloc_seed(RelocDev P) {
 
 __global__ __launch_bounds__(1024) void k_reloc_check(RelocDev P, int s) {
   __shared__ int s_wave[16];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int t = threadIdx.x;
   const int verdict = P.hdr[RELOC_H_VERDICT];
   __syncthreads();  // (every thread has read the word before thread 0 may write it)
   if (verdict != 0) return;
@@ -146,31 +96,15 @@ __global__ __launch_bounds__(1024) void k_reloc_check(RelocDev P, int s) {
   for (int k = 0; k < 9; ++k) Rb[k] = s == 0 ? P.R0[k] : P.tcw_out[k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) tb[k] = s == 0 ? P.t0[k] : P.tcw_out[9 + k];
-  int mine = 0;
-  for (int f0 = 0; f0 < P.nf; f0 += 1024) {
-    const int f = f0 + t;
-    bool inl = false;
-    if (f < P.nf) {
-      const int e = P.edge_of[f], mp = P.cur[f];
-      inl = e >= 0 && P.e_inl[e] != 0;
-      if (inl) {  // VirtualFrame::project2UV (src/Frame.cc:320-333) and the test of Optimizer.cc:185: 0, not mfMinU / mfMinV
-        const float X[3] = {P.pos[3 * mp], P.pos[3 * mp + 1], P.pos[3 * mp + 2]};
-        float pc[3];
-        affine(1.0f, Rb, X, tb, pc);
-        const float z = pc[2];
-        const float u = pc[0] / z * P.fx + P.cx, v = pc[1] / z * P.fy + P.cy;
-        if (!(z > 0.f) || u > P.max_u || u < 0.f || v > P.max_v || v < 0.f) inl = false;
-      }
-      P.inlier[(size_t)s * P.nf + f] = inl ? 1 : 0;
-      if (!inl) P.cur[f] = -1;  // `if (!inLier[idx]) mvpMapPoints[idx] = nullptr` (:191-194)
-    }
-    mine += __popcll(__ballot(inl));
-  }
-  if (lane == 0) s_wave[wv] = mine;
-  __syncthreads();
+  const PostCheckCam K = {P.fx, P.fy, P.cx, P.cy, P.max_u, P.max_v};
+  const int n_in = post_check_1024(
+      P.nf, P.edge_of, P.e_inl, Rb, tb, K, P.inlier + (size_t)s * P.nf, s_wave,
+      [&](int f, float (&X)[3]) {
+        const int mp = P.cur[f];
+        X[0] = P.pos[3 * mp], X[1] = P.pos[3 * mp + 1], X[2] = P.pos[3 * mp + 2];
+      },
+      [&](int f) { P.cur[f] = -1; });
   if (t != 0) return;
-  int n_in = 0;
-  for (int w = 0; w < 16; ++w) n_in += s_wave[w];
   P.hdr[RELOC_H_INLIERS + s] = n_in;
   for (int k = 0; k < 7; ++k) P.pose_out[7 * s + k] = est[k];
   for (int k = 0; k < 9; ++k) P.tcw_out[12 * s + k] = R[k];

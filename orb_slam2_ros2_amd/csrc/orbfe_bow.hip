@@ -201,7 +201,9 @@ orbfe_status load_txt(const char* path, orbfe_vocab& v) {
   return ORBFE_OK;
 }
 
-// the vocabulary's copy on the context's device, made once per device
+}  // namespace
+
+// the vocabulary's copy on the context's device, made once per device (also asked for by orbfe_trackref.hip)
 orbfe_status vocab_on_device(orbfe_ctx* c, const orbfe_vocab* v, BowVocabDev& out) {
   if (c->device < 0 || c->device >= kMaxDevices) return fail(c, ORBFE_EBADARG, "bow: device %d beyond the vocabulary's table", c->device);
   orbfe_vocab::Dev& d = v->dev[c->device];
@@ -226,6 +228,8 @@ orbfe_status vocab_on_device(orbfe_ctx* c, const orbfe_vocab* v, BowVocabDev& ou
   out = BowVocabDev{d.rec, d.desc, d.weight, 0, v->root_nc, v->L};
   return ORBFE_OK;
 }
+
+namespace {
 
 struct BowLayout {
   ScratchRegion up, out;  // the descriptors a caller uploads (empty for slots) | the result block

@@ -429,6 +429,18 @@ struct BowQueryStored {
   uint32_t o_flags;
   int32_t n_nodes;
 };
+// The third form (orbfe_track_reference_stored): a frame in its extraction slot.  Descriptors and angles are the slot's
+// arrays; the FeatureVector is device memory too -- what k_bow_group has just written, or a host FeatureVector behind the call's upload
+// -- and its node count is read from device memory, because the host never sees the one k_bow_group wrote.
+struct BowQuerySlot {
+  const orbfe_keypoint* kps;
+  const uint8_t* desc;
+  const uint32_t* nodes;
+  const int32_t* offs;
+  const uint32_t* feat;
+  const int32_t* n_nodes;
+  uint32_t o_flags;
+};
 struct BowParams {
   int32_t mode, dist_threshold, check_orientation, n_kf;
   float ratio;
@@ -538,4 +550,41 @@ struct RelocDev {
   uint8_t* inlier /*[2][nf]*/;
   int32_t *assigned /*[2][nf]*/, *hits /*[2][nf]*/;
   uint8_t* qa /*[2][n]*/;
+};
+
+// ---- trackReference over a stored keyframe (k_trackref.hip, orbfe_trackref.hip) ------------------------------------------
+// Everything the glue kernels of one call read and write.  hdr: [0] verdict (0: still running), [1] n_matches, [2] n_edges, [3] n_inliers.
+#define TRACKREF_H_VERDICT 0
+#define TRACKREF_H_MATCHES 1
+#define TRACKREF_H_EDGES 2
+#define TRACKREF_H_INLIERS 3
+struct TrackRefDev {
+  // the frame (slot arrays)
+  const orbfe_keypoint* f_kps;
+  const int32_t* f_n_kp;
+  int32_t nf, n_levels;
+  // the map state of the call's upload: the keyframe's, then what the frame came with
+  const float* pos;         // [n][3]
+  const uint8_t* f_good;    // [nf]
+  const float* f_pos;       // [nf][3]
+  const double* right_u;    // [nf]
+  const float *sigma2, *inv_sigma2;
+  float R0[9], t0[3];
+  float fx, fy, cx, cy, max_u, max_v;
+  int32_t n, min_matches, min_inliers;
+  // searchByBow's list (k_bow_select, one candidate) and its length
+  const BowMatch* list;
+  const int32_t* n_list;
+  // device state: the edge list of the optimisation and its results
+  int32_t *edge_of, *cnt /*[1] edge count, -1: no optimisation*/;
+  double *Xw, *meas, *info, *p_init /*[7]*/, *p_opt /*[7]*/;
+  float* sig;
+  const uint8_t* e_inl;
+  // the downloaded block
+  int32_t* hdr;
+  BowMatch* matches /*[n]*/;
+  int32_t *assigned /*[nf]*/, *cur /*[nf]: final_assigned*/;
+  double* pose_out /*[7]*/;
+  float* tcw_out /*[12]*/;
+  uint8_t* inlier /*[nf]*/;
 };

@@ -1,0 +1,107 @@
+// pose_check_dev.h -- what surrounds a pose-only optimisation inside a fused Tracking step, shared by k_reloc.hip and
+// k_trackref.hip: the two pose conversions of Optimizer::OptimizePoseOnly (src/Optimizer.cc:119, :201) in fp64 and its
+// projection post-check (:179-199), as the 1024 threads of one workgroup run it.  The kernels differ only in where a held point's
+// position comes from and in what a feature that is no inlier loses; both are parameters here, so the post-check has one text.
+// Float arithmetic: map_point_dev.h's rows and `A x + t`; the includer switches contraction off.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "map_point_dev.h"
+
+namespace orbfe {
+
+// the largest-diagonal branch of Eigen::Quaterniond(Matrix3d) with the largest element at I (constant indices: the arrays stay registers)
+template <int I>
+__device__ __forceinline__ void quat_diag(const double (&m)[3][3], double (&q)[4]) {
+  constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+  double tr = sqrt(m[I][I] - m[J][J] - m[K][K] + 1.0);
+  q[I] = 0.5 * tr;
+  tr = 0.5 / tr;
+  q[3] = (m[K][J] - m[J][K]) * tr;
+  q[J] = (m[J][I] + m[I][J]) * tr;
+  q[K] = (m[K][I] + m[I][K]) * tr;
+}
+
+// Converter::ConvertTcw2SE3 (src/Optimizer.cc:630-645): host/map_pb.hpp's tcw_to_se3
+__device__ __forceinline__ void tcw_to_se3_dev(const float* R, const float* t, double* out) {
+  double m[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) m[i][j] = (double)R[i * 3 + j];
+  double q[4];
+  double tr = m[0][0] + m[1][1] + m[2][2];
+  if (tr > 0.0) {
+    tr = sqrt(tr + 1.0);
+    q[3] = 0.5 * tr;
+    tr = 0.5 / tr;
+    q[0] = (m[2][1] - m[1][2]) * tr, q[1] = (m[0][2] - m[2][0]) * tr, q[2] = (m[1][0] - m[0][1]) * tr;
+  } else if (m[2][2] > (m[1][1] > m[0][0] ? m[1][1] : m[0][0]))
+    quat_diag<2>(m, q);
+  else if (m[1][1] > m[0][0])
+    quat_diag<1>(m, q);
+  else
+    quat_diag<0>(m, q);
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {  // Quaterniond::normalize(), then SE3Quat::normalizeRotation()
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (n > 0.0) q[0] /= n, q[1] /= n, q[2] /= n, q[3] /= n;
+  }
+  if (q[3] < 0.0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];
+  out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
+  out[4] = (double)t[0], out[5] = (double)t[1], out[6] = (double)t[2];
+}
+
+// Converter::ConvertSE32Tcw (src/Optimizer.cc:653-675): host/map_pb.hpp's se3_to_tcw
+__device__ __forceinline__ void se3_to_tcw_dev(const double* p, float* R, float* t) {
+  const double x = p[0], y = p[1], z = p[2], w = p[3];
+  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = (float)(1.0 - (tyy + tzz)), R[1] = (float)(txy - twz), R[2] = (float)(txz + twy);
+  R[3] = (float)(txy + twz), R[4] = (float)(1.0 - (txx + tzz)), R[5] = (float)(tyz - twx);
+  R[6] = (float)(txz - twy), R[7] = (float)(tyz + twx), R[8] = (float)(1.0 - (txx + tyy));
+  t[0] = (float)p[4], t[1] = (float)p[5], t[2] = (float)p[6];
+}
+
+struct PostCheckCam {
+  float fx, fy, cx, cy, max_u, max_v;
+};
+
+// The post-check over the nf features of a frame by the 1024 threads of one workgroup (all of them call it): feature f is an inlier when
+// its edge is one of the optimiser's and its point projects into the image under (Rb, tb), the pose the frame still has.  pos_of(f, X)
+// gives the position of the point feature f holds (called for the optimiser's inliers only), drop(f) takes the point from a feature
+// that is no inlier (`if (!inLier[idx]) mvpMapPoints[idx] = nullptr`, :191-194).  Writes inlier[f]; returns edges - nBad to every thread.
+template <class PosOf, class Drop>
+__device__ __forceinline__ int post_check_1024(int nf, const int32_t* __restrict__ edge_of, const uint8_t* __restrict__ e_inl, const float (&Rb)[9],
+                                               const float (&tb)[3], const PostCheckCam& K, uint8_t* __restrict__ inlier, int* s_wave, PosOf pos_of,
+                                               Drop drop) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  int mine = 0;
+  for (int f0 = 0; f0 < nf; f0 += 1024) {
+    const int f = f0 + t;
+    bool inl = false;
+    if (f < nf) {
+      const int e = edge_of[f];
+      inl = e >= 0 && e_inl[e] != 0;
+      if (inl) {  // VirtualFrame::project2UV (src/Frame.cc:320-333) and the test of Optimizer.cc:185: 0, not mfMinU / mfMinV
+        float X[3];
+        pos_of(f, X);
+        float pc[3];
+        affine(1.0f, Rb, X, tb, pc);
+        const float z = pc[2];
+        const float u = pc[0] / z * K.fx + K.cx, v = pc[1] / z * K.fy + K.cy;
+        if (!(z > 0.f) || u > K.max_u || u < 0.f || v > K.max_v || v < 0.f) inl = false;
+      }
+      inlier[f] = inl ? 1 : 0;
+      if (!inl) drop(f);
+    }
+    mine += __popcll(__ballot(inl));
+  }
+  if (lane == 0) s_wave[wv] = mine;
+  __syncthreads();
+  int n_in = 0;
+  for (int w = 0; w < 16; ++w) n_in += s_wave[w];
+  return n_in;
+}
+
+}  // namespace orbfe

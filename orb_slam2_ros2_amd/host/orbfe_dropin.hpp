@@ -1322,6 +1322,114 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
     return verdict == ORBFE_RELOC_ACCEPT_1 || verdict == ORBFE_RELOC_ACCEPT_2 || verdict == ORBFE_RELOC_ACCEPT_3;
   }
 
+  // bool Tracking::trackReference() (src/Tracking.cc:360-371), the whole body, as ONE device call (orbfe_track_reference_stored, DESIGN
+  // 4.29) over a keyframe store (orbfe_kfstore_dropin.hpp): Frame::computeBow of the frame in its extraction slot (or the FeatureVector
+  // it already has), searchByBow(frame, reference keyframe) with setMapPoints, the 10-match test, OptimizePoseOnly with its tail, the
+  // 10-inlier test.  What goes up is map state: the keyframe's flags and positions, and what the frame still holds (the last frame's
+  // points after a failed trackMotionModel).  The side effects are replayed on the reference's objects in the reference's order:
+  // mBowVec / mFeatVec / mbBowComputed, addMatchInTrack and the slot per match, then the nulling, addInlierInTrack and setPose.  A
+  // keyframe that is not in the store or has no FeatureVector there, a frame whose slot is no longer resident, a context of more than
+  // 2048 features or a distorting camera takes the bodies of searchByBow and OptimizePoseOnly above.  vocab: the DBoW3::Vocabulary of
+  // host/compat (anything whose handle() is the orbfe_vocab).
+  template <class CameraT, class Store, class VocabPtr, class FramePtr, class KeyFramePtr>
+  static bool trackReference(Store& store, const VocabPtr& vocab, FramePtr pCurr, KeyFramePtr pkf, float mfRatio = 0.7f, bool mbCheckOri = true) {
+    const auto& ext = pCurr->mpExtractorLeft->device();
+    const orbfe_camera cam = cameraOf<CameraT>();
+    const bool distorting = cam.k1 != 0.f || cam.k2 != 0.f || cam.p1 != 0.f || cam.p2 != 0.f || cam.k3 != 0.f;
+    orbfe_kfstore_info info;
+    const bool stored = store.info(pkf, &info) && info.has_bow;
+    if (!stored || !ext.resident() || (size_t)orbfe_get_capacity(ext.context()) > 2048 || distorting) {
+      std::vector<cv::DMatch> matches;
+      if (searchByBow(pCurr, pkf, matches, false, false, mfRatio, mbCheckOri) < 10) return false;
+      return OptimizePoseOnly<CameraT>(pCurr) >= 10;
+    }
+    orbfe_ctx* ctx = ext.context();
+    const size_t NF = (size_t)orbfe_get_capacity(ctx), N = pCurr->mvFeatsLeft.size(), n = (size_t)info.n;
+    auto kfMps = pkf->getMapPoints();
+    std::vector<uint8_t> good(std::max<size_t>(n, 1), 0), frameGood(NF, 0);
+    std::vector<float> pos(3 * std::max<size_t>(n, 1), 0.f), framePos(3 * NF, 0.f);
+    for (size_t i = 0; i < n && i < kfMps.size(); ++i) {
+      if (!kfMps[i] || kfMps[i]->isBad()) continue;
+      good[i] = 1;
+      const cv::Mat X = kfMps[i]->getPos();
+      for (int a = 0; a < 3; ++a) pos[3 * i + a] = X.template at<float>(a);
+    }
+    auto& slots = pCurr->mvpMapPoints;
+    bool any = false;
+    for (size_t f = 0; f < N && f < NF && f < slots.size(); ++f) {
+      if (!slots[f] || slots[f]->isBad()) continue;
+      frameGood[f] = 1, any = true;
+      const cv::Mat X = slots[f]->getPos();
+      for (int a = 0; a < 3; ++a) framePos[3 * f + a] = X.template at<float>(a);
+    }
+    const int nLevels = std::max(store.levels(), (int)ORB_SLAM2_ROS2::ORBExtractor::mnLevels);  // the level count of the extractor's context
+    std::vector<float> sig2((size_t)nLevels), invSig2((size_t)nLevels);
+    for (int l = 0; l < nLevels; ++l) sig2[(size_t)l] = pCurr->getScaledFactor2(l), invSig2[(size_t)l] = pCurr->getScaledFactorInv2(l);
+    std::vector<double> rightU(NF, -1.0);
+    for (size_t f = 0; f < N && f < NF; ++f) rightU[f] = pCurr->getRightU(f);
+    orbfe_trackref_input in{};
+    in.kf_id = store.id(pkf), in.n = (int32_t)n, in.good = good.data(), in.pos = pos.data();
+    if (any) in.frame_good = frameGood.data(), in.frame_pos = framePos.data();
+    in.right_u = rightU.data(), in.level_sigma2 = sig2.data(), in.level_inv_sigma2 = invSig2.data(), in.cam = &cam;
+    poseFloats(pCurr->mRcw, pCurr->mtcw, in.Rcw, in.tcw);
+    in.bounds[0] = pCurr->mfMinU, in.bounds[1] = pCurr->mfMaxU, in.bounds[2] = pCurr->mfMinV, in.bounds[3] = pCurr->mfMaxV;
+    in.levelsup = 4, in.ratio = mfRatio, in.dist_threshold = orbfe::ORBMatcher::mnMinThreshold, in.check_orientation = mbCheckOri ? 1 : 0;
+    in.min_matches = 10, in.min_inliers = 10;
+    // Frame::computeBow (Frame.h:224-231): a frame that has its BoW sends the FeatureVector, another one gets both vectors from the call
+    std::vector<uint32_t> nodes, features;
+    std::vector<int32_t> offsets(1, 0);
+    const bool hadBow = pCurr->mbBowComputed;
+    if (hadBow) {
+      for (const auto& node : pCurr->mFeatVec) {
+        nodes.push_back((uint32_t)node.first);
+        for (const auto f : node.second) features.push_back((uint32_t)f);
+        offsets.push_back((int32_t)features.size());
+      }
+      in.n_nodes = (int32_t)nodes.size(), in.nodes = nodes.data(), in.node_offsets = offsets.data(), in.features = features.data();
+    }
+    std::vector<uint32_t> bWords(NF), bNodes(NF), bFeats(NF);
+    std::vector<double> bValues(NF);
+    std::vector<int32_t> bOffsets(NF + 1);
+    int32_t nWords = 0, nNodes = 0;
+    const orbfe_bow_out bow{bWords.data(), bValues.data(), &nWords, bNodes.data(), bOffsets.data(), bFeats.data(), &nNodes};
+    int32_t verdict = 0, nMatches = 0, nEdges = 0, nInliers = 0;
+    float Tcw[12];
+    double est[7];
+    std::vector<orbfe_bow_match> matches(std::max<size_t>(n, 1));
+    std::vector<int32_t> assigned(NF, -1), fin(NF, -1);
+    std::vector<uint8_t> inl(NF, 0);
+    orbfe_trackref_output out{};
+    out.verdict = &verdict, out.n_matches = &nMatches, out.matches = matches.data(), out.assigned = assigned.data(), out.n_edges = &nEdges;
+    out.n_inliers = &nInliers, out.inlier = inl.data(), out.final_assigned = fin.data(), out.pose_se3 = est, out.Tcw = Tcw;
+    out.bow = hadBow ? nullptr : &bow;
+    check(ctx, orbfe_track_reference_stored(ctx, ext.slot(), hadBow ? nullptr : (*vocab).handle(), store.get(), &in, &out));
+    if (!hadBow) {
+      pCurr->mBowVec.clear(), pCurr->mFeatVec.clear();
+      for (int32_t i = 0; i < nWords; ++i) pCurr->mBowVec.emplace_hint(pCurr->mBowVec.end(), bWords[(size_t)i], bValues[(size_t)i]);
+      for (int32_t i = 0; i < nNodes; ++i) {
+        auto& v = pCurr->mFeatVec[bNodes[(size_t)i]];
+        v.assign(bFeats.begin() + bOffsets[(size_t)i], bFeats.begin() + bOffsets[(size_t)i + 1]);
+      }
+      pCurr->mbBowComputed = true;
+    }
+    // setMapPoints (src/ORBMatcher.cc:815-830) in match order: in tracking mode every train is a good point
+    for (int32_t k = 0; k < nMatches; ++k) {
+      auto& p = kfMps[(size_t)matches[(size_t)k].train];
+      p->addMatchInTrack();
+      slots[(size_t)matches[(size_t)k].query] = p;
+    }
+    if (verdict == ORBFE_TRACKREF_REJECT_MATCHES) return false;
+    // OptimizePoseOnly's tail (src/Optimizer.cc:191-201)
+    for (size_t f = 0; f < N && f < slots.size(); ++f) {
+      if (f < NF && inl[f])
+        slots[f]->addInlierInTrack();
+      else
+        slots[f] = nullptr;
+    }
+    pCurr->setPose(poseMat(Tcw, Tcw + 9));
+    return verdict == ORBFE_TRACKREF_ACCEPT;
+  }
+
   // The tail of Frame::Frame (RGB-D) after extract() (src/Frame.cc:130-131, :139-157): depthImg.convertTo(CV_32F) / dScale, the copy of the
   // distorted keypoints, Camera::undistortPoints(mvFeatsLeft), the depth / rightU lookup -- as one call on the extractor's slot.  depthImg
   // as read from the file: CV_16U (TUM) or CV_32F.  initGrid() stays with the caller (the grid is rebuilt on the device per search).

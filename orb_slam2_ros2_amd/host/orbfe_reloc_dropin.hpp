@@ -17,6 +17,9 @@
 // what follows a successful iterate in Tracking::trackReLocalize (src/Tracking.cc:565-584) as one device call
 // (orbfe_reloc_refine_stored),
 //     if (orbfe::dropin::relocRefine<Camera>(store, mpCurrFrame, vpCandidateKFs[idx], relocBowParam, idx, vInliers, modelReti.mRcw, modelReti.mtcw))
+// the whole body of Tracking::trackReference (src/Tracking.cc:360-371) as one device call
+// (orbfe_track_reference_stored),
+//     return orbfe::dropin::trackReference<Camera>(store, mpVoc, mpCurrFrame, mpRefKf);
 #pragma once
 
 #include <algorithm>
@@ -312,6 +315,14 @@ template <class CameraT, class FramePtr, class KeyFramePtr, class RelocBowParamT
 bool relocRefine(KeyframeStore<Access>& store, FramePtr mpCurrFrame, KeyFramePtr pKF, const RelocBowParamT& relocBowParam, std::size_t idx,
                  const std::vector<std::size_t>& vInliers, const cv::Mat& Rcw, const cv::Mat& tcw) {
   return Bodies::template relocRefine<CameraT>(store, mpCurrFrame, pKF, relocBowParam, idx, vInliers, Rcw, tcw);
+}
+
+// bool Tracking::trackReference() (src/Tracking.cc:360-371): computeBow, searchByBow(mpCurrFrame, mpRefKf), the 10-match test,
+// OptimizePoseOnly, the 10-inlier test.  The frame ends with the points, the pose, the BoW vectors and its map points with the counters
+// the reference's body leaves (Bodies::trackReference, orbfe_dropin.hpp).  vocab: host/compat's DBoW3::Vocabulary (a pointer to it).
+template <class CameraT, class VocabPtr, class FramePtr, class KeyFramePtr, class Access>
+bool trackReference(KeyframeStore<Access>& store, const VocabPtr& vocab, FramePtr mpCurrFrame, KeyFramePtr mpRefKf) {
+  return Bodies::template trackReference<CameraT>(store, vocab, mpCurrFrame, mpRefKf, 0.7f, true);
 }
 
 }  // namespace dropin

@@ -794,6 +794,71 @@ class ORBMatcher {
                                                        (int32_t)scaleFactors.size(), th, mfRatio, mnMinThreshold, bestIdx.data(), bestDist.data()));
     bestIdx.resize(n), bestDist.resize(n);
   }
+  // Tracking::trackReference (src/Tracking.cc:360-371) of the frame in extraction slot `slot` against the stored keyframe `id`, as one
+  // call (orbfe_track_reference_stored), with this matcher's mfRatio and mbCheckOri.  good / pos: the keyframe's map state
+  // (KeyFrameView); frameGood / framePos ([capacity], [capacity][3]; empty: the frame holds nothing) and rightU ([capacity]; empty: mono)
+  // the frame's; (Rcw, tcw) the pose it has; bounds its mfMinU mfMaxU mfMinV mfMaxV.  vocab == nullptr: featVec is the frame's
+  // FeatureVector (node -> features); else the transform runs in the call and bowVec / featVec receive Frame::mBowVec / mFeatVec.
+  struct TrackReference {
+    int32_t verdict = 0, nMatches = 0, nEdges = 0, nInliers = 0;
+    std::vector<DMatch> matches;
+    std::vector<int32_t> assigned, finalAssigned;  // [capacity]: keyframe feature, -1, ORBFE_TRACKREF_OWN
+    std::vector<uint8_t> inlier;
+    double poseSE3[7] = {0, 0, 0, 0, 0, 0, 0};
+    float Tcw[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool accepted() const { return verdict == ORBFE_TRACKREF_ACCEPT; }
+  };
+  TrackReference trackReferenceStored(orbfe_ctx* ctx, int slot, const orbfe_vocab* vocab, orbfe_kfstore* store, uint64_t id, const KeyFrameView& kf,
+                                      const std::vector<uint8_t>& frameGood, const std::vector<float>& framePos, const std::vector<double>& rightU,
+                                      const float Rcw[9], const float tcw[3], const float bounds[4], const Intrinsics& K, float bf,
+                                      const std::vector<float>& sigma2, const std::vector<float>& invSigma2,
+                                      std::map<unsigned, double>* bowVec, std::map<unsigned, std::vector<unsigned>>& featVec, int levelsup = 4,
+                                      int minMatches = 10, int minInliers = 10) const {
+    const size_t NF = (size_t)std::max((int)orbfe_get_capacity(ctx), 1), n = kf.good.size();
+    TrackReference r;
+    r.assigned.assign(NF, -1), r.finalAssigned.assign(NF, -1), r.inlier.assign(NF, 0);
+    const orbfe_camera cam = {K.fx, K.fy, K.cx, K.cy, 0, 0, 0, 0, 0, bf};
+    orbfe_trackref_input in = orbfe_trackref_input();
+    in.kf_id = id, in.n = (int32_t)n, in.good = kf.good.data(), in.pos = kf.pos.data();
+    if (!frameGood.empty()) in.frame_good = frameGood.data(), in.frame_pos = framePos.data();
+    in.right_u = rightU.empty() ? nullptr : rightU.data();
+    for (int a = 0; a < 9; ++a) in.Rcw[a] = Rcw[a];
+    for (int a = 0; a < 3; ++a) in.tcw[a] = tcw[a];
+    for (int a = 0; a < 4; ++a) in.bounds[a] = bounds[a];
+    in.level_sigma2 = sigma2.data(), in.level_inv_sigma2 = invSigma2.data(), in.cam = &cam;
+    in.levelsup = levelsup, in.ratio = mfRatio, in.dist_threshold = mnMinThreshold, in.check_orientation = mbCheckOri ? 1 : 0;
+    in.min_matches = minMatches, in.min_inliers = minInliers;
+    std::vector<uint32_t> nodes, features;
+    std::vector<int32_t> offsets(1, 0);
+    if (!vocab) {
+      for (const auto& node : featVec) {
+        nodes.push_back((uint32_t)node.first);
+        for (const auto f : node.second) features.push_back((uint32_t)f);
+        offsets.push_back((int32_t)features.size());
+      }
+      in.n_nodes = (int32_t)nodes.size(), in.nodes = nodes.data(), in.node_offsets = offsets.data(), in.features = features.data();
+    }
+    std::vector<uint32_t> bWords(NF), bNodes(NF), bFeats(NF);
+    std::vector<double> bValues(NF);
+    std::vector<int32_t> bOffsets(NF + 1);
+    int32_t nWords = 0, nNodes = 0;
+    const orbfe_bow_out bow{bWords.data(), bValues.data(), &nWords, bNodes.data(), bOffsets.data(), bFeats.data(), &nNodes};
+    std::vector<orbfe_bow_match> found(std::max<size_t>(n, 1));
+    orbfe_trackref_output out = orbfe_trackref_output();
+    out.verdict = &r.verdict, out.n_matches = &r.nMatches, out.matches = found.data(), out.assigned = r.assigned.data(), out.n_edges = &r.nEdges;
+    out.n_inliers = &r.nInliers, out.inlier = r.inlier.data(), out.final_assigned = r.finalAssigned.data(), out.pose_se3 = r.poseSE3, out.Tcw = r.Tcw;
+    out.bow = vocab ? &bow : nullptr;
+    check(ctx, orbfe_track_reference_stored(ctx, slot, vocab, store, &in, &out));
+    for (int32_t k = 0; k < r.nMatches; ++k) r.matches.push_back({found[(size_t)k].query, found[(size_t)k].train, found[(size_t)k].distance});
+    if (vocab) {
+      featVec.clear();
+      if (bowVec) bowVec->clear();
+      for (int32_t i = 0; bowVec && i < nWords; ++i) bowVec->emplace_hint(bowVec->end(), bWords[(size_t)i], bValues[(size_t)i]);
+      for (int32_t i = 0; i < nNodes; ++i)
+        featVec[bNodes[(size_t)i]].assign(bFeats.begin() + bOffsets[(size_t)i], bFeats.begin() + bOffsets[(size_t)i + 1]);
+    }
+    return r;
+  }
   static void sim3Model(const Sim3& S, float model[12]) {  // orbfe_sim3_iterate's layout: R row-major, then t
     for (int a = 0; a < 9; ++a) model[a] = S.R[a];
     for (int a = 0; a < 3; ++a) model[9 + a] = S.t[a];
