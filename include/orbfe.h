@@ -1296,6 +1296,66 @@ typedef struct orbfe_trackref_output {
 orbfe_status orbfe_track_reference_stored(orbfe_ctx* ctx, int32_t slot, const orbfe_vocab* vocab, orbfe_kfstore* store,
                                           const orbfe_trackref_input* in, const orbfe_trackref_output* out);
 
+/* ---- map points resident on the device ------------------------------------------------------------------------------
+ * The half the keyframe store leaves out: one orbfe_mpstore holds, on ONE device and keyed by MapPoint::getID() (uint64), what
+ * orbfe_track_local_map uploads per local map point on every frame -- a row of exactly 64 bytes: pos[3], view_dir[3], max_dist, min_dist
+ * (float) and desc[32].  The host objects stay the truth: the store holds what the last upsert brought, and the caller upserts a point
+ * when setPos / setDesc / updateNormalAndDepth changed it.  isBad / isInMap are not stored: they travel as flags
+ * with every call.
+ * A paged direct index, no hash (the ids are sequential): page id / rows_per_page, row id % rows_per_page.  A page (its rows, then one
+ * presence byte per row: no value inside a row marks absence) is allocated by the first upsert that names one of its rows and never
+ * moves; the page table is a device array of page pointers.  The store has its own lock and serves every context on its device: upsert
+ * and erase take it exclusively; fetch, size and orbfe_track_local_map_stored take it shared for their whole (synchronous) duration.
+ *   create   rows_per_page 0: 16384, at most ORBFE_MP_MAX_ROWS_PER_PAGE; max_pages 0: 4096, at most ORBFE_MP_MAX_PAGES (the defaults: 64 Mi
+ *            ids; 1 MB + 16 KB of device memory per page in use).  create allocates the page table, 8 bytes per possible page.
+ *   upsert   fields: which arrays of the call are written, ORBFE_MP_POS (pos) | ORBFE_MP_NORMAL_DEPTH (view_dir, max_dist, min_dist) |
+ *            ORBFE_MP_DESC (desc); an array the mask does not name may be NULL.  Refused with ORBFE_EBADARG, nothing changed: an empty
+ *            or unknown mask, an id the store does not hold without all three fields (no row is ever half-initialised), an id listed
+ *            twice in the call.  An id at or past rows_per_page * max_pages: ORBFE_ECAPACITY, nothing changed.  One staged copy and one
+ *            launch; the call returns after the rows are on the device: every later call on any context of the device sees them.
+ *   erase    unknown ids are ignored.
+ *   fetch    the rows of n ids (an id may repeat) into the arrays whose pointer is not NULL; an id the store does not hold:
+ *            ORBFE_EBADARG, nothing written.
+ *   size     n_points; bytes_used = 64 * n_points; bytes_reserved = pages in use * rows_per_page * 65.
+ * orbfe_track_local_map_stored is orbfe_track_local_map with the map points named by id: ids[n_mp] in place of pos, view_dir, max_dist,
+ * min_dist and desc, every other field with its meaning there.  An id may repeat.  One launch in front of the chain gathers the rows into
+ * the arrays the chain reads; every output byte is what orbfe_track_local_map writes given the arrays orbfe_mpstore_fetch returns for
+ * `ids`.  Still ONE synchronisation: an id the store does not hold is found on the device (its point takes no part in the chain) and
+ * reported after the download -- ORBFE_EBADARG naming the first such id, none of the outputs written.  A store on another device than the
+ * context, ids NULL with n_mp > 0: ORBFE_EBADARG.  More than 2048 features per frame: ORBFE_EBADSIZE.                              */
+#define ORBFE_MP_POS 1u
+#define ORBFE_MP_NORMAL_DEPTH 2u
+#define ORBFE_MP_DESC 4u
+#define ORBFE_MP_ALL 7u
+#define ORBFE_MP_MAX_ROWS_PER_PAGE (1 << 20)
+#define ORBFE_MP_MAX_PAGES (1 << 16)
+typedef struct orbfe_mpstore orbfe_mpstore;
+typedef struct orbfe_track_stored_input {
+  int32_t n_mp;
+  const uint64_t* ids;           /* [n_mp] MapPoint::getID()                                                       */
+  const uint8_t* flags;          /* [n_mp], as orbfe_track_input                                                   */
+  const int32_t* held;           /* [n_features], nullable: index into ids                                         */
+  const double* right_u;         /* [n_features], nullable                                                         */
+  const float* level_sigma2;     /* [n_levels]                                                                     */
+  const float* level_inv_sigma2; /* [n_levels]                                                                     */
+  const double* pose_se3;        /* [7]                                                                            */
+  float th;
+  float ratio;
+  int32_t min_threshold;
+  int32_t min_matches;
+} orbfe_track_stored_input;
+orbfe_status orbfe_mpstore_create(int32_t device_id, int32_t rows_per_page, int32_t max_pages, orbfe_mpstore** out);
+void orbfe_mpstore_destroy(orbfe_mpstore* store);  /* no call on the store may still run */
+orbfe_status orbfe_mpstore_upsert(orbfe_mpstore* store, int32_t n, const uint64_t* ids, uint32_t fields, const float* pos /*[n][3]*/,
+                                  const float* view_dir /*[n][3]*/, const float* max_dist /*[n]*/, const float* min_dist /*[n]*/,
+                                  const uint8_t* desc /*[n][32]*/);
+orbfe_status orbfe_mpstore_erase(orbfe_mpstore* store, int32_t n, const uint64_t* ids);
+orbfe_status orbfe_mpstore_fetch(orbfe_mpstore* store, int32_t n, const uint64_t* ids, float* pos, float* view_dir, float* max_dist,
+                                 float* min_dist, uint8_t* desc);
+orbfe_status orbfe_mpstore_size(orbfe_mpstore* store, int64_t* n_points, int64_t* bytes_used, int64_t* bytes_reserved);
+orbfe_status orbfe_track_local_map_stored(orbfe_ctx* ctx, int32_t slot, orbfe_mpstore* store, const orbfe_frame_pose* pose,
+                                          const orbfe_camera* cam, const orbfe_track_stored_input* in, const orbfe_track_output* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

@@ -96,6 +96,12 @@ class TrackInput(C.Structure):
                 ("min_threshold", C.c_int32), ("min_matches", C.c_int32)]
 
 
+class TrackStoredInput(C.Structure):
+    _fields_ = [("n_mp", C.c_int32), ("ids", C.c_void_p), ("flags", C.c_void_p), ("held", C.c_void_p), ("right_u", C.c_void_p),
+                ("level_sigma2", C.c_void_p), ("level_inv_sigma2", C.c_void_p), ("pose_se3", C.c_void_p), ("th", C.c_float), ("ratio", C.c_float),
+                ("min_threshold", C.c_int32), ("min_matches", C.c_int32)]
+
+
 class MotionInput(C.Structure):
     _fields_ = [("n", C.c_int32), ("qxy", C.c_void_p), ("q_octave", C.c_void_p), ("q_min_level", C.c_void_p), ("q_max_level", C.c_void_p), ("desc", C.c_void_p),
                 ("pos", C.c_void_p), ("held", C.c_void_p), ("right_u", C.c_void_p), ("level_sigma2", C.c_void_p), ("level_inv_sigma2", C.c_void_p),
@@ -251,6 +257,8 @@ EXPORTS = [
     "orbfe_create_new_map_points_stored", "orbfe_search_by_bow_stored", "orbfe_search_by_sim3_stored", "orbfe_search_by_sim3_points_stored",
     "orbfe_fuse_points_into_keyframes_stored", "orbfe_debug_fuse_points_kernels", "orbfe_reloc_refine_stored",
     "orbfe_track_reference_stored",
+    "orbfe_mpstore_create", "orbfe_mpstore_destroy", "orbfe_mpstore_upsert", "orbfe_mpstore_erase", "orbfe_mpstore_fetch", "orbfe_mpstore_size",
+    "orbfe_track_local_map_stored",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
     "orbfe_debug_pg_sparse_solve", "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
@@ -398,6 +406,15 @@ def load() -> C.CDLL:
     L.orbfe_debug_fuse_points_kernels.argtypes = [vp]
     L.orbfe_reloc_refine_stored.argtypes = [vp, i32, vp, C.POINTER(RelocInput), C.POINTER(RelocOutput)]
     L.orbfe_track_reference_stored.argtypes = [vp, i32, vp, vp, C.POINTER(TrackRefInput), C.POINTER(TrackRefOutput)]
+    L.orbfe_mpstore_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.orbfe_mpstore_destroy.argtypes = [vp]
+    L.orbfe_mpstore_destroy.restype = None
+    L.orbfe_mpstore_upsert.argtypes = [vp, i32, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.orbfe_mpstore_erase.argtypes = [vp, i32, vp]
+    L.orbfe_mpstore_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbfe_mpstore_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.orbfe_track_local_map_stored.argtypes = [vp, i32, vp, C.POINTER(FramePose), C.POINTER(Camera), C.POINTER(TrackStoredInput),
+                                               C.POINTER(TrackOutput)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -896,6 +913,73 @@ class KeyframeStore:
                                                  p(out["cell_feat"]), *([None] * 3 if fv is None else [p(a) for a in fv])))
         out["bounds"], out["fv"] = i["bounds"], fv
         return out
+
+
+MP_POS, MP_NORMAL_DEPTH, MP_DESC, MP_ALL = 1, 2, 4, 7
+
+
+class MapPointStore:
+    """Map points resident on one device, keyed by uint64 id (orbfe_mpstore, include/orbfe.h): a 64-byte row per point --
+    pos, view_dir, max_dist, min_dist, desc -- in pages of rows_per_page rows, allocated on first use.  The host objects stay the truth:
+    upsert a point when it changed.  Any Context on the same device reads it through Context.track_local_map_stored."""
+
+    def __init__(self, device_id=0, rows_per_page=0, max_pages=0):
+        self.lib = load()
+        h = C.c_void_p(None)
+        st = self.lib.orbfe_mpstore_create(int(device_id), int(rows_per_page), int(max_pages), C.byref(h))
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+        self.h = h
+
+    def _check(self, st):
+        if st != ORBFE_OK:
+            raise OrbfeError(st, self.lib.orbfe_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbfe_mpstore_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upsert(self, ids, pos=None, view_dir=None, max_dist=None, min_dist=None, desc=None, fields=None):
+        """the arrays that are given (fields None: POS if pos, NORMAL_DEPTH if view_dir, max_dist and min_dist, DESC if desc) into the rows
+        of `ids`; an id the store does not hold needs all of them"""
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        n = len(i)
+        f32 = lambda a, w: None if a is None else np.ascontiguousarray(a, np.float32).reshape((n, w) if w > 1 else (n,))  # noqa: E731
+        pos, view_dir, max_dist, min_dist = f32(pos, 3), f32(view_dir, 3), f32(max_dist, 1), f32(min_dist, 1)
+        desc = None if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(n, 32)
+        if fields is None:
+            fields = (MP_POS if pos is not None else 0) | (MP_NORMAL_DEPTH if all(a is not None for a in (view_dir, max_dist, min_dist)) else 0) | \
+                (MP_DESC if desc is not None else 0)
+        self._check(self.lib.orbfe_mpstore_upsert(self.h, n, ptr(i), int(fields), ptr(pos), ptr(view_dir), ptr(max_dist), ptr(min_dist), ptr(desc)))
+
+    def erase(self, ids):
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        self._check(self.lib.orbfe_mpstore_erase(self.h, len(i), ptr(i)))
+
+    def fetch(self, ids):
+        """the rows of `ids` (an id may repeat) as dict(pos, view_dir, max_dist, min_dist, desc)"""
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint64)
+        n = len(i)
+        out = dict(pos=np.zeros((n, 3), np.float32), view_dir=np.zeros((n, 3), np.float32), max_dist=np.zeros(n, np.float32),
+                   min_dist=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8))
+        self._check(self.lib.orbfe_mpstore_fetch(self.h, n, ptr(i), *[ptr(out[k]) for k in ("pos", "view_dir", "max_dist", "min_dist", "desc")]))
+        return out
+
+    def size(self):
+        """dict(n_points, bytes_used, bytes_reserved)"""
+        n, u, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.orbfe_mpstore_size(self.h, C.byref(n), C.byref(u), C.byref(r)))
+        return dict(n_points=n.value, bytes_used=u.value, bytes_reserved=r.value)
+
+    def __len__(self):
+        return self.size()["n_points"]
 
 
 def group_filter(ids, scores, connected):
@@ -1457,6 +1541,33 @@ class Context:
         to = TrackOutput(ptr(out["assigned"]), ptr(out["edge_of"]), ptr(out["inlier"]), C.cast(C.byref(nm), C.c_void_p),
                          C.cast(C.byref(ne), C.c_void_p), C.cast(C.byref(ng), C.c_void_p), ptr(out["pose"]))
         self._check(self.lib.orbfe_track_local_map(self.h, slot, C.byref(fp), C.byref(cm), C.byref(ti), C.byref(to)))
+        out.update(n_matches=nm.value, n_edges=ne.value, n_good=ng.value)
+        return out
+
+    def track_local_map_stored(self, slot, store, ids, flags, Rcw, tcw, cam, bounds, pose_se3, level_sigma2, level_inv_sigma2, held=None,
+                               right_u=None, th=3.0, ratio=0.8, min_threshold=50, min_matches=30):
+        """track_local_map with the map points named by id in a MapPointStore (orbfe_track_local_map_stored): `ids` in place of pos,
+        view_dir, max_dist, min_dist and desc; held indexes `ids`.  Returns what track_local_map returns for the arrays store.fetch(ids)
+        gives; an id the store does not hold: OrbfeError(ORBFE_EBADARG)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        ids = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        n, NF = len(ids), self.n_features
+        if flags.size != n:
+            raise ValueError("flags must have one entry per id")
+        held = None if held is None else np.ascontiguousarray(held, np.int32)
+        right_u = None if right_u is None else np.ascontiguousarray(right_u, np.float64)
+        if (held is not None and held.size != NF) or (right_u is not None and right_u.size != NF):
+            raise ValueError("held / right_u must have n_features entries")
+        s2, is2, p0 = f32(level_sigma2), f32(level_inv_sigma2), np.ascontiguousarray(pose_se3, np.float64)
+        fp = FramePose((C.c_float * 9)(*f32(Rcw).reshape(9)), (C.c_float * 3)(*f32(tcw).reshape(3)), *[float(np.float32(b)) for b in bounds])
+        cm = Camera(*[float(np.float32(v)) for v in cam[:4]], 0, 0, 0, 0, 0, float(np.float32(cam[4])))
+        out = dict(assigned=np.zeros(NF, np.int32), edge_of=np.zeros(NF, np.int32), inlier=np.zeros(NF, np.uint8), pose=np.zeros(7))
+        nm, ne, ng = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        ti = TrackStoredInput(n, *[ptr(a) for a in (ids, flags, held, right_u, s2, is2, p0)], th, ratio, min_threshold, min_matches)
+        to = TrackOutput(ptr(out["assigned"]), ptr(out["edge_of"]), ptr(out["inlier"]), C.cast(C.byref(nm), C.c_void_p),
+                         C.cast(C.byref(ne), C.c_void_p), C.cast(C.byref(ng), C.c_void_p), ptr(out["pose"]))
+        self._check(self.lib.orbfe_track_local_map_stored(self.h, slot, store.h, C.byref(fp), C.byref(cm), C.byref(ti), C.byref(to)))
         out.update(n_matches=nm.value, n_edges=ne.value, n_good=ng.value)
         return out
 

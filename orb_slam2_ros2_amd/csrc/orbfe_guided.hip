@@ -2,6 +2,7 @@
 // getBestMatch, ORBMatcher.cc:265-347, 561-612), MapPoint::isInVision / predictLevel, and the fused tracking chains
 // (orbfe_track_local_map / orbfe_track_motion_model).  (Split from orbfe_api.hip in r5, no change of behaviour.)
 #include "orbfe_ctx.h"
+#include "orbfe_mpstore.h"
 
 // the grid of `slot` for the geometry ag on stream st: the one kept from the last search if the slot's keypoints are still the same
 orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const AreaGrid& ag, const int32_t** d_off, const int32_t** d_feat) {
@@ -261,6 +262,121 @@ static void track_results(StagedIo& io, size_t o_cnt, size_t o_ng, size_t o_po, 
   io.get(out->edge_of, o_eo, NF * 4);
 }
 
+// ---- orbfe_track_local_map and orbfe_track_local_map_stored: their own first step (the point arrays onto the device), one shared rest ----
+// The scratch of either call.  Array call: [ upload: point arrays, flags, frame | claim (0x7F fill) | device-only | download ], as ever.
+// Stored call: [ download | bad | upload: ids, flags, frame | claim | device-only, the gathered point arrays among it ] -- `bad`, the word
+// the gather sets for an id without a row, is the LAST take of the download and the FIRST of the upload: it goes up as 0 with the
+// inputs and comes down with the results, so no fill of its own and no second synchronisation.
+struct TrackLayout {
+  size_t o_pos, o_vd, o_mx, o_mn, o_desc, o_ids = 0, o_bad = 0, o_fl, o_held, o_ru, o_s2, o_is2, o_p0, o_claim, o_uv, o_dist, o_cos, o_lvl, o_vis,
+      o_rad, o_lo, o_hi, o_bi, o_bd, o_sd, o_nc, o_xw, o_ms, o_info, o_sig, o_err, o_l, o_r, o_cnt, o_ng, o_po, o_asg, o_eo, o_in, end;
+  ScratchRegion up, claim, down;
+  TrackLayout(size_t N, size_t NF, size_t nl, bool stored) {
+    ScratchLayout L;
+    auto points = [&] { o_pos = L.take<float>(N * 3), o_vd = L.take<float>(N * 3), o_mx = L.take<float>(N), o_mn = L.take<float>(N), o_desc = L.take(N * 32); };
+    auto frame = [&] {
+      o_fl = L.take(N), o_held = L.take<int32_t>(NF), o_ru = L.take<double>(NF), o_s2 = L.take<float>(nl), o_is2 = L.take<float>(nl), o_p0 = L.take(56);
+    };
+    auto results = [&] {
+      o_cnt = L.take(16), o_ng = L.take(8), o_po = L.take(56), o_asg = L.take<int32_t>(NF), o_eo = L.take<int32_t>(NF), o_in = L.take(NF);
+    };
+    if (stored) {
+      L.open(down), results(), o_bad = L.open(up).take(8), L.close(down);
+      o_ids = L.take<uint64_t>(N), frame(), L.close(up);
+    } else {
+      L.open(up), points(), frame(), L.close(up);
+    }
+    o_claim = L.open(claim).take<int32_t>(NF), L.close(claim);
+    if (stored) points();
+    o_uv = L.take<float>(N * 2), o_dist = L.take<float>(N), o_cos = L.take<float>(N), o_lvl = L.take(N), o_vis = L.take(N), o_rad = L.take<float>(N),
+    o_lo = L.take(N), o_hi = L.take(N), o_bi = L.take<int32_t>(N), o_bd = L.take<int32_t>(N), o_sd = L.take<int32_t>(N), o_nc = L.take<int32_t>(N),
+    o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF), o_sig = L.take<float>(NF),
+    o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF);
+    if (!stored) L.open(down), results(), L.close(down);
+    end = L.end();
+  }
+};
+
+// what both calls check alike and do before they touch the device.  have_points: the caller's own point arrays (or ids) are there --
+// reported with the other NULL arrays, behind the NULL-argument / bad-slot check, as orbfe_track_local_map always did
+static orbfe_status track_begin(orbfe_ctx* c, const char* who, int32_t slot, const orbfe_frame_pose* pose, const orbfe_camera* cam,
+                                const orbfe_track_input* in, bool have_points, const orbfe_track_output* out, AreaGrid* ag) {
+  if (!c || !pose || !cam || !in || !out || slot < 0 || slot >= c->cfg.max_images) return fail(c, ORBFE_EBADARG, "%s: NULL argument / bad slot", who);
+  const int n = in->n_mp;
+  const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
+  if (n < 0 || !in->pose_se3 || !in->level_sigma2 || !in->level_inv_sigma2 || !out->assigned || !out->n_matches || !out->n_edges || !out->n_good ||
+      !out->pose_out || !out->inlier || (n && (!have_points || !in->flags)))
+    return fail(c, ORBFE_EBADARG, "%s: NULL array", who);
+  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "%s: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", who, NF);
+  if (in->held)
+    for (size_t f = 0; f < NF; ++f)
+      if (in->held[f] < -1 || in->held[f] >= n) return fail(c, ORBFE_EBADARG, "%s: held[%zu] = %d out of range", who, f, in->held[f]);
+  const float bounds[4] = {pose->min_u, pose->max_u, pose->min_v, pose->max_v};
+  if (!area_grid(c, bounds, ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", who);
+  const size_t ncells = (size_t)ag->rows * ag->cols;
+  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", who, ncells);
+  TRY(slots_idle(c, slot, 1, who));
+  HIP_TRY(c, hipSetDevice(c->device));
+  return join_stereo(c);
+}
+
+// the flags and the frame's side of the upload into the staging buffer
+static void track_put_frame(StagedIo& io, const TrackLayout& T, size_t N, size_t NF, size_t nl, const orbfe_track_input* in) {
+  io.put(T.o_fl, in->flags, N);
+  if (in->held) io.put(T.o_held, in->held, NF * 4);
+  else std::memset(io.host<uint8_t>(T.o_held), 0xFF, NF * 4);
+  if (in->right_u) io.put(T.o_ru, in->right_u, NF * 8);
+  else
+    for (size_t f = 0; f < NF; ++f) io.host<double>(T.o_ru)[f] = -1.0;
+  io.put(T.o_s2, in->level_sigma2, nl * 4);
+  io.put(T.o_is2, in->level_inv_sigma2, nl * 4);
+  io.put(T.o_p0, in->pose_se3, 56);
+}
+
+// The rest, with the point arrays, the flags and the frame's inputs on the device: the claim fill, the six launches from
+// launch_project_map_points to launch_pose_only, the one download.  The caller reads the results (track_results).
+static orbfe_status track_chain(orbfe_ctx* c, StagedIo& io, const TrackLayout& T, int32_t slot, const AreaGrid& ag, const orbfe_frame_pose* pose,
+                                const orbfe_camera* cam, const orbfe_track_input* in) {
+  const int n = in->n_mp, nl = c->cfg.n_levels;
+  const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
+  hipStream_t st = c->stream;
+  uint8_t* b = io.d;
+  HIP_TRY(c, hipMemsetAsync(b + T.claim.begin, 0x7F, T.claim.bytes(), st));
+  const float cam4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
+  const float bounds[4] = {pose->min_u, pose->max_u, pose->min_v, pose->max_v};
+  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
+  {
+    StageTimer tm(c, ORBFE_STAGE_MATCH, st);
+    launch_project_map_points(st, n, (const float*)(b + T.o_pos), (const float*)(b + T.o_vd), (const float*)(b + T.o_mx), (const float*)(b + T.o_mn),
+                              pose->Rcw, pose->tcw, cam4, bounds, std::log(c->cfg.scale_factor), 7, (float*)(b + T.o_uv), (float*)(b + T.o_dist),
+                              (float*)(b + T.o_cos), (int8_t*)(b + T.o_lvl), b + T.o_vis);
+    launch_track_queries(st, n, b + T.o_fl, b + T.o_vis, (const float*)(b + T.o_cos), (const int8_t*)(b + T.o_lvl), in->th, (const float*)(b + T.o_s2),
+                         nl, (float*)(b + T.o_rad), (int8_t*)(b + T.o_lo), (int8_t*)(b + T.o_hi));
+    const int32_t *g_off = nullptr, *g_feat = nullptr;
+    TRY(slot_grid(c, st, slot, ag, &g_off, &g_feat));
+    launch_search_area(st, c->d_kpl + (size_t)slot * NF, c->d_desc + (size_t)slot * NF * 32, ag.clip_w, ag.clip_h, ag.rows, ag.cols,
+                       g_off, g_feat, n, (const float*)(b + T.o_uv), (const float*)(b + T.o_rad),
+                       (const int8_t*)(b + T.o_lo), (const int8_t*)(b + T.o_hi), b + T.o_desc, nullptr, (int32_t*)(b + T.o_bi), (int32_t*)(b + T.o_bd),
+                       (int32_t*)(b + T.o_sd), (int32_t*)(b + T.o_nc), nullptr);
+    launch_track_claim(st, n, (const int32_t*)(b + T.o_nc), (const int32_t*)(b + T.o_bi), (const int32_t*)(b + T.o_bd), (const int32_t*)(b + T.o_sd),
+                       in->min_threshold, in->ratio, (int32_t*)(b + T.o_claim));
+    launch_track_edges(st, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, (const int32_t*)(b + T.o_held), (const int32_t*)(b + T.o_claim),
+                       b + T.o_fl, (const float*)(b + T.o_pos), (const double*)(b + T.o_ru), (const float*)(b + T.o_s2), (const float*)(b + T.o_is2),
+                       in->min_matches, (int32_t*)(b + T.o_asg), (int32_t*)(b + T.o_eo), (double*)(b + T.o_xw), (double*)(b + T.o_ms),
+                       (double*)(b + T.o_info), (float*)(b + T.o_sig), (int32_t*)(b + T.o_cnt));
+  }
+  {
+    StageTimer tm(c, ORBFE_STAGE_BA, st);
+    launch_pose_only(st, (int)NF, (const double*)(b + T.o_xw), (const double*)(b + T.o_ms), (const double*)(b + T.o_info), (const float*)(b + T.o_sig),
+                     (const double*)(b + T.o_p0), prm, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), (double*)(b + T.o_err),
+                     b + T.o_l, b + T.o_r, b + T.o_in, (double*)(b + T.o_po), (int32_t*)(b + T.o_ng), (const int32_t*)(b + T.o_cnt) + 1);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, io.fetch(T.down));
+  drain_timers(c);
+  return ORBFE_OK;
+}
+
 // Tracking::trackLocalMap's device work as ONE call (src/Tracking.cc:641-675): isInVision / predictLevel per map point
 // (MapPoint.cc:141-201), ORBMatcher::searchByProjection(frame, map points, th) (ORBMatcher.cc:561-612) against the features of `slot`,
 // and Optimizer::OptimizePoseOnly (Optimizer.cc:33-178) on what the frame holds afterwards -- one upload, seven launches, one download;
@@ -268,90 +384,64 @@ static void track_results(StagedIo& io, size_t o_cnt, size_t o_ng, size_t o_po, 
 orbfe_status orbfe_track_local_map(orbfe_ctx* c, int32_t slot, const orbfe_frame_pose* pose, const orbfe_camera* cam, const orbfe_track_input* in,
                                    const orbfe_track_output* out) {
   ApiLock api_lk(c);
-  if (!c || !pose || !cam || !in || !out || slot < 0 || slot >= c->cfg.max_images) return fail(c, ORBFE_EBADARG, "track_local_map: NULL argument / bad slot");
-  const int n = in->n_mp, nl = c->cfg.n_levels;
-  const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
-  if (n < 0 || !in->pose_se3 || !in->level_sigma2 || !in->level_inv_sigma2 || !out->assigned || !out->n_matches || !out->n_edges || !out->n_good ||
-      !out->pose_out || !out->inlier || (n && (!in->pos || !in->view_dir || !in->max_dist || !in->min_dist || !in->desc || !in->flags)))
-    return fail(c, ORBFE_EBADARG, "track_local_map: NULL array");
-  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "track_local_map: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", NF);
-  if (in->held)
-    for (size_t f = 0; f < NF; ++f)
-      if (in->held[f] < -1 || in->held[f] >= n) return fail(c, ORBFE_EBADARG, "track_local_map: held[%zu] = %d out of range", f, in->held[f]);
-  const float bounds[4] = {pose->min_u, pose->max_u, pose->min_v, pose->max_v};
   AreaGrid ag;
-  if (!area_grid(c, bounds, &ag)) return fail(c, ORBFE_EBADARG, "track_local_map: bad frame bounds");
-  const size_t ncells = (size_t)ag.rows * ag.cols;
-  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "track_local_map: %zu grid cells exceed the LDS counters", ncells);
-  TRY(slots_idle(c, slot, 1, "track_local_map"));
-  HIP_TRY(c, hipSetDevice(c->device));
-  TRY(join_stereo(c));
-  const size_t N = (size_t)n;
-  // [ upload | claim (0x7F fill) | device-only | download ]
-  ScratchLayout L;
-  ScratchRegion up, claim, down;
-  const size_t o_pos = L.open(up).take<float>(N * 3), o_vd = L.take<float>(N * 3), o_mx = L.take<float>(N), o_mn = L.take<float>(N),
-               o_desc = L.take(N * 32), o_fl = L.take(N), o_held = L.take<int32_t>(NF), o_ru = L.take<double>(NF), o_s2 = L.take<float>((size_t)nl),
-               o_is2 = L.take<float>((size_t)nl), o_p0 = L.take(56), o_claim = L.close(up).open(claim).take<int32_t>(NF),
-               o_uv = L.close(claim).take<float>(N * 2), o_dist = L.take<float>(N), o_cos = L.take<float>(N), o_lvl = L.take(N), o_vis = L.take(N),
-               o_rad = L.take<float>(N), o_lo = L.take(N), o_hi = L.take(N), o_bi = L.take<int32_t>(N), o_bd = L.take<int32_t>(N),
-               o_sd = L.take<int32_t>(N), o_nc = L.take<int32_t>(N), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3),
-               o_info = L.take<double>(NF), o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF),
-               o_cnt = L.open(down).take(16), o_ng = L.take(8), o_po = L.take(56), o_asg = L.take<int32_t>(NF), o_eo = L.take<int32_t>(NF),
-               o_in = L.take(NF);
-  L.close(down);
+  TRY(track_begin(c, "track_local_map", slot, pose, cam, in, in && in->pos && in->view_dir && in->max_dist && in->min_dist && in->desc, out, &ag));
+  const size_t N = (size_t)in->n_mp, NF = (size_t)std::max(c->cfg.n_features, 1), nl = (size_t)c->cfg.n_levels;
+  const TrackLayout T(N, NF, nl, false);
   StagedIo io;
-  TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
-  io.put(o_pos, in->pos, N * 12);
-  io.put(o_vd, in->view_dir, N * 12);
-  io.put(o_mx, in->max_dist, N * 4);
-  io.put(o_mn, in->min_dist, N * 4);
-  io.put(o_desc, in->desc, N * 32);
-  io.put(o_fl, in->flags, N);
-  if (in->held) io.put(o_held, in->held, NF * 4);
-  else std::memset(io.host<uint8_t>(o_held), 0xFF, NF * 4);
-  if (in->right_u) io.put(o_ru, in->right_u, NF * 8);
-  else
-    for (size_t f = 0; f < NF; ++f) io.host<double>(o_ru)[f] = -1.0;
-  io.put(o_s2, in->level_sigma2, (size_t)nl * 4);
-  io.put(o_is2, in->level_inv_sigma2, (size_t)nl * 4);
-  io.put(o_p0, in->pose_se3, 56);
-  hipStream_t st = c->stream;
+  TRY(io.reserve(c, T.end, std::max(T.up.end, T.down.bytes())));
+  io.put(T.o_pos, in->pos, N * 12);
+  io.put(T.o_vd, in->view_dir, N * 12);
+  io.put(T.o_mx, in->max_dist, N * 4);
+  io.put(T.o_mn, in->min_dist, N * 4);
+  io.put(T.o_desc, in->desc, N * 32);
+  track_put_frame(io, T, N, NF, nl, in);
+  HIP_TRY(c, io.upload(T.up));
+  TRY(track_chain(c, io, T, slot, ag, pose, cam, in));
+  track_results(io, T.o_cnt, T.o_ng, T.o_po, T.o_asg, T.o_eo, T.o_in, NF, out);
+  return ORBFE_OK;
+}
+
+// orbfe_track_local_map with the map points named by id in a map-point store (include/orbfe.h): 8 bytes of id and the flag
+// go up per point instead of 73; k_mpstore_gather fills the point arrays in front of the same chain.  The store's lock is held shared
+// until the results are down: no upsert or erase touches a row or a page under the running kernels.
+orbfe_status orbfe_track_local_map_stored(orbfe_ctx* c, int32_t slot, orbfe_mpstore* store, const orbfe_frame_pose* pose, const orbfe_camera* cam,
+                                          const orbfe_track_stored_input* sin, const orbfe_track_output* out) {
+  ApiLock api_lk(c);
+  const char* who = "track_local_map_stored";
+  if (!c || !store || !sin) return fail(c, ORBFE_EBADARG, "%s: NULL argument", who);
+  if (sin->n_mp > (1 << 24)) return fail(c, ORBFE_EBADARG, "%s: more than 2^24 ids", who);
+  TRY(mpstore_check_ctx(c, store, who));
+  const orbfe_track_input in_v = {sin->n_mp, nullptr, nullptr, nullptr, nullptr, nullptr, sin->flags, sin->held, sin->right_u, sin->level_sigma2,
+                                  sin->level_inv_sigma2, sin->pose_se3, sin->th, sin->ratio, sin->min_threshold, sin->min_matches};
+  const orbfe_track_input* in = &in_v;
+  AreaGrid ag;
+  TRY(track_begin(c, who, slot, pose, cam, in, sin->ids != nullptr, out, &ag));
+  const int n = in->n_mp;
+  const size_t N = (size_t)n, NF = (size_t)std::max(c->cfg.n_features, 1), nl = (size_t)c->cfg.n_levels;
+  const TrackLayout T(N, NF, nl, true);
+  StagedIo io;
+  TRY(io.reserve(c, T.end, std::max(T.up.end, T.down.bytes())));
+  io.put(T.o_ids, sin->ids, N * 8);
+  *io.host<uint32_t>(T.o_bad) = 0;
+  track_put_frame(io, T, N, NF, nl, in);
+  std::shared_lock<std::shared_timed_mutex> lk(store->mu);
+  HIP_TRY(c, io.upload(T.up));
   uint8_t* b = io.d;
-  HIP_TRY(c, io.upload(up));
-  HIP_TRY(c, hipMemsetAsync(b + claim.begin, 0x7F, claim.bytes(), st));
-  const float cam4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
-  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
   {
-    StageTimer tm(c, ORBFE_STAGE_MATCH, st);
-    launch_project_map_points(st, n, (const float*)(b + o_pos), (const float*)(b + o_vd), (const float*)(b + o_mx), (const float*)(b + o_mn),
-                              pose->Rcw, pose->tcw, cam4, bounds, std::log(c->cfg.scale_factor), 7, (float*)(b + o_uv), (float*)(b + o_dist),
-                              (float*)(b + o_cos), (int8_t*)(b + o_lvl), b + o_vis);
-    launch_track_queries(st, n, b + o_fl, b + o_vis, (const float*)(b + o_cos), (const int8_t*)(b + o_lvl), in->th, (const float*)(b + o_s2), nl,
-                         (float*)(b + o_rad), (int8_t*)(b + o_lo), (int8_t*)(b + o_hi));
-    const int32_t *g_off = nullptr, *g_feat = nullptr;
-    TRY(slot_grid(c, st, slot, ag, &g_off, &g_feat));
-    launch_search_area(st, c->d_kpl + (size_t)slot * NF, c->d_desc + (size_t)slot * NF * 32, ag.clip_w, ag.clip_h, ag.rows, ag.cols,
-                       g_off, g_feat, n, (const float*)(b + o_uv), (const float*)(b + o_rad),
-                       (const int8_t*)(b + o_lo), (const int8_t*)(b + o_hi), b + o_desc, nullptr, (int32_t*)(b + o_bi), (int32_t*)(b + o_bd),
-                       (int32_t*)(b + o_sd), (int32_t*)(b + o_nc), nullptr);
-    launch_track_claim(st, n, (const int32_t*)(b + o_nc), (const int32_t*)(b + o_bi), (const int32_t*)(b + o_bd), (const int32_t*)(b + o_sd),
-                       in->min_threshold, in->ratio, (int32_t*)(b + o_claim));
-    launch_track_edges(st, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, (const int32_t*)(b + o_held), (const int32_t*)(b + o_claim),
-                       b + o_fl, (const float*)(b + o_pos), (const double*)(b + o_ru), (const float*)(b + o_s2), (const float*)(b + o_is2),
-                       in->min_matches, (int32_t*)(b + o_asg), (int32_t*)(b + o_eo), (double*)(b + o_xw), (double*)(b + o_ms),
-                       (double*)(b + o_info), (float*)(b + o_sig), (int32_t*)(b + o_cnt));
+    StageTimer tm(c, ORBFE_STAGE_MATCH, c->stream);
+    launch_mpstore_gather(c->stream, store->table(), n, (const uint64_t*)(b + T.o_ids),
+                          MpArrays{(float*)(b + T.o_pos), (float*)(b + T.o_vd), (float*)(b + T.o_mx), (float*)(b + T.o_mn), b + T.o_desc}, b + T.o_fl,
+                          (uint32_t*)(b + T.o_bad));
   }
-  {
-    StageTimer tm(c, ORBFE_STAGE_BA, st);
-    launch_pose_only(st, (int)NF, (const double*)(b + o_xw), (const double*)(b + o_ms), (const double*)(b + o_info), (const float*)(b + o_sig),
-                     (const double*)(b + o_p0), prm, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), (double*)(b + o_err), b + o_l,
-                     b + o_r, b + o_in, (double*)(b + o_po), (int32_t*)(b + o_ng), (const int32_t*)(b + o_cnt) + 1);
+  TRY(track_chain(c, io, T, slot, ag, pose, cam, in));
+  if (*(const uint32_t*)io.got(T.o_bad)) {
+    for (int i = 0; i < n; ++i)
+      if (!store->idx.has(sin->ids[i]))
+        return fail(c, ORBFE_EBADARG, "%s: map point %llu (ids[%d]) is not in the store", who, (unsigned long long)sin->ids[i], i);
+    return fail(c, ORBFE_EDEVICE, "%s: the device holds no row for an id the store's index lists", who);
   }
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, io.fetch(down));
-  drain_timers(c);
-  track_results(io, o_cnt, o_ng, o_po, o_asg, o_eo, o_in, NF, out);
+  track_results(io, T.o_cnt, T.o_ng, T.o_po, T.o_asg, T.o_eo, T.o_in, NF, out);
   return ORBFE_OK;
 }
 

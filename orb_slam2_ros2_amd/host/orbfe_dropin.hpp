@@ -34,6 +34,7 @@
 #include <opencv2/core.hpp>
 
 #include <atomic>
+#include <chrono>
 #include <set>
 
 #include "orbfe_shim.hpp"
@@ -963,7 +964,7 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
   // evaluates MapPoint::isInVision and predictLevel (MapPoint.cc:141-201) in the reference's float / double mix.
   template <class CameraT, class FramePtr, class MapPointPtr>
   static int trackLocalMap(FramePtr pframe, const std::vector<MapPointPtr>& mapPoints, float th, float mfRatio, int nLevels, int& nGood,
-                           int minMatches = 30) {
+                           int minMatches = 30, std::chrono::steady_clock::time_point* deviceDone = nullptr) {
     const auto& ext = pframe->mpExtractorLeft->device();
     const size_t N = pframe->mvFeatsLeft.size();
     if (!ext.resident() || (size_t)orbfe_get_capacity(ext.context()) > 2048) {
@@ -1038,6 +1039,17 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
     orbfe_track_output out{};
     out.assigned = assigned.data(), out.inlier = inl.data(), out.n_matches = &nMatches, out.n_edges = &nEdges, out.n_good = &good, out.pose_out = poseOut;
     check(ctx, orbfe_track_local_map(ctx, ext.slot(), &fp, &cam, &in, &out));
+    if (deviceDone) *deviceDone = std::chrono::steady_clock::now();  // (for timing the marshalling and the call without the replay)
+    return trackLocalMapReplay(pframe, ptrOf, held, assigned, inl, nMatches, nEdges, good, poseOut, nGood);
+  }
+
+  // What the frame and the map points see of a tracking-chain call (orbfe_track_local_map, orbfe_track_local_map_stored): the side effects
+  // of searchByProjection and of OptimizePoseOnly's tail, replayed from the call's outputs.  ptrOf: array index -> map point; held /
+  // assigned / inl: [capacity], what the features held on entry, hold after the search, and which edges ended as inliers.
+  template <class FramePtr, class BasePtr>
+  static int trackLocalMapReplay(FramePtr pframe, const std::vector<BasePtr>& ptrOf, const std::vector<int32_t>& held, const std::vector<int32_t>& assigned,
+                                 const std::vector<uint8_t>& inl, int32_t nMatches, int32_t nEdges, int32_t good, const double* poseOut, int& nGood) {
+    const size_t N = pframe->mvFeatsLeft.size(), NF = held.size();
     // searchByProjection's side effects (:595-599): the new assignments, in map-point order for the counters' sake
     for (size_t f = 0; f < N && f < NF; ++f)
       if (assigned[f] != held[f] && assigned[f] >= 0) {
@@ -1066,6 +1078,77 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
     pframe->setPose(poseToMat(poseOut));
     nGood = nEdges - nBad;
     return nMatches;
+  }
+
+  // trackLocalMap over a map-point store (orbfe_mpstore_dropin.hpp: dropin::MapPointStore<>; orbfe_track_local_map_stored):
+  // the same call with the local map points named by id.  The store is brought up to date first -- flush() marks the points touched since
+  // the last call stale, ensure() reads the stale ones among this call's points again and inserts the ones the store has never seen, the
+  // frame's own holders that are not in the list among them -- and then only getID(), isBad() and isInMap() are read per point.  Same fall-back, same side effects (trackLocalMapReplay).
+  template <class CameraT, class Store, class FramePtr, class MapPointPtr>
+  static int trackLocalMapStored(Store& store, FramePtr pframe, const std::vector<MapPointPtr>& mapPoints, float th, float mfRatio, int nLevels,
+                                 int& nGood, int minMatches = 30, std::chrono::steady_clock::time_point* deviceDone = nullptr) {
+    const auto& ext = pframe->mpExtractorLeft->device();
+    const size_t N = pframe->mvFeatsLeft.size();
+    if (!ext.resident() || (size_t)orbfe_get_capacity(ext.context()) > 2048) return trackLocalMap<CameraT>(pframe, mapPoints, th, mfRatio, nLevels, nGood, minMatches, deviceDone);
+    orbfe_ctx* ctx = ext.context();
+    const size_t NF = (size_t)orbfe_get_capacity(ctx);
+    using BasePtr = typename std::decay<decltype(pframe->getMapPoint(0))>::type;
+    auto frameMps = pframe->getMapPoints();
+    store.flush();  // the ids touched since the last call become stale: ensure reads such a point again when a list names it
+    store.ensure(mapPoints);
+    store.ensure(frameMps);
+    // the ids: the list as given (null entries dropped, a point listed twice once), then the points the frame holds that are not in it
+    std::vector<uint64_t> ids;
+    std::vector<uint8_t> flags;
+    std::vector<BasePtr> ptrOf;  // array index -> the map point
+    std::map<const void*, int> indexOf;
+    auto push = [&](const BasePtr& p, uint8_t listed) {
+      const bool bad = p->isBad(), inMap = p->isInMap();
+      ids.push_back(store.id(p));
+      flags.push_back((uint8_t)(listed | (bad ? 0 : 2) | ((!bad && inMap) ? 1 : 0)));
+      indexOf[(const void*)p.get()] = (int)ptrOf.size();
+      ptrOf.push_back(p);
+    };
+    for (const auto& pMp : mapPoints)
+      if (pMp && !indexOf.count((const void*)pMp.get())) push(BasePtr(pMp), 4);
+    std::vector<int32_t> held(NF, -1);
+    for (size_t f = 0; f < N && f < NF; ++f) {
+      const auto& h = frameMps[f];
+      if (!h) continue;
+      auto it = indexOf.find((const void*)h.get());
+      if (it == indexOf.end()) {
+        push(h, 0);
+        it = indexOf.find((const void*)h.get());
+      }
+      held[f] = it->second;
+    }
+    std::vector<double> rightU(NF, -1.0);
+    for (size_t f = 0; f < N && f < NF; ++f) rightU[f] = pframe->getRightU(f);
+    std::vector<float> sig2((size_t)nLevels), invSig2((size_t)nLevels);
+    for (int l = 0; l < nLevels; ++l) sig2[(size_t)l] = pframe->getScaledFactor2(l), invSig2[(size_t)l] = pframe->getScaledFactorInv2(l);
+    orbfe_frame_pose fp{};
+    for (int r = 0; r < 3; ++r) {
+      for (int c2 = 0; c2 < 3; ++c2) fp.Rcw[3 * r + c2] = pframe->mRcw.template at<float>(r, c2);
+      fp.tcw[r] = pframe->mtcw.template at<float>(r, 0);
+    }
+    fp.min_u = pframe->mfMinU, fp.max_u = pframe->mfMaxU, fp.min_v = pframe->mfMinV, fp.max_v = pframe->mfMaxV;
+    orbfe_camera cam{};
+    cam.fx = CameraT::mfFx, cam.fy = CameraT::mfFy, cam.cx = CameraT::mfCx, cam.cy = CameraT::mfCy, cam.bf = CameraT::mfBf;
+    double pose0[7], poseOut[7];
+    matToPose(pframe->mRcw, pframe->mtcw, pose0);
+    orbfe_track_stored_input in{};
+    in.n_mp = (int32_t)ptrOf.size();
+    in.ids = ids.data(), in.flags = flags.data();
+    in.held = held.data(), in.right_u = rightU.data(), in.level_sigma2 = sig2.data(), in.level_inv_sigma2 = invSig2.data(), in.pose_se3 = pose0;
+    in.th = th, in.ratio = mfRatio, in.min_threshold = orbfe::ORBMatcher::mnMinThreshold, in.min_matches = minMatches;
+    std::vector<int32_t> assigned(NF, -1);
+    std::vector<uint8_t> inl(NF, 0);
+    int32_t nMatches = 0, nEdges = 0, good = 0;
+    orbfe_track_output out{};
+    out.assigned = assigned.data(), out.inlier = inl.data(), out.n_matches = &nMatches, out.n_edges = &nEdges, out.n_good = &good, out.pose_out = poseOut;
+    check(ctx, orbfe_track_local_map_stored(ctx, ext.slot(), store.get(), &fp, &cam, &in, &out));
+    if (deviceDone) *deviceDone = std::chrono::steady_clock::now();
+    return trackLocalMapReplay(pframe, ptrOf, held, assigned, inl, nMatches, nEdges, good, poseOut, nGood);
   }
 
   // The middle of Tracking::trackMotionModel (src/Tracking.cc:385-396) as ONE device call (orbfe_track_motion_model):

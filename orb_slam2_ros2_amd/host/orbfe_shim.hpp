@@ -391,6 +391,51 @@ class ORBExtractor {
   mutable std::exception_ptr mPending;                  // what extract() captured on a foreign thread
 };
 
+// Map points resident on one device (orbfe_mpstore, include/orbfe.h): owns the store, throws what the C calls refuse.  The
+// arrays are orbfe_track_input's: pos / viewDir [n][3], maxDist / minDist [n], desc [n].
+class MapPointStore {
+ public:
+  explicit MapPointStore(int deviceId = 0, int rowsPerPage = 0, int maxPages = 0) {
+    if (orbfe_mpstore_create(deviceId, rowsPerPage, maxPages, &mStore) != ORBFE_OK)
+      throw std::runtime_error(std::string("orbfe_mpstore_create: ") + orbfe_last_error(nullptr));
+  }
+  ~MapPointStore() { orbfe_mpstore_destroy(mStore); }
+  MapPointStore(const MapPointStore&) = delete;
+  MapPointStore& operator=(const MapPointStore&) = delete;
+  orbfe_mpstore* get() const { return mStore; }
+  // fields: ORBFE_MP_POS | ORBFE_MP_NORMAL_DEPTH | ORBFE_MP_DESC; a vector the mask does not name may be empty
+  void upsert(const std::vector<uint64_t>& ids, uint32_t fields, const std::vector<float>& pos, const std::vector<float>& viewDir,
+              const std::vector<float>& maxDist, const std::vector<float>& minDist, const std::vector<Descriptor>& desc) {
+    const size_t n = ids.size();
+    if (((fields & ORBFE_MP_POS) && pos.size() != 3 * n) || ((fields & ORBFE_MP_DESC) && desc.size() != n) ||
+        ((fields & ORBFE_MP_NORMAL_DEPTH) && (viewDir.size() != 3 * n || maxDist.size() != n || minDist.size() != n)))
+      throw std::invalid_argument("MapPointStore::upsert: an array the field mask names has the wrong size");
+    static_assert(sizeof(Descriptor) == 32, "a descriptor is 32 bytes");
+    check(orbfe_mpstore_upsert(mStore, (int32_t)n, ids.data(), fields, pos.data(), viewDir.data(), maxDist.data(), minDist.data(),
+                               desc.empty() ? nullptr : desc[0].data()), "orbfe_mpstore_upsert");
+  }
+  void erase(const std::vector<uint64_t>& ids) { check(orbfe_mpstore_erase(mStore, (int32_t)ids.size(), ids.data()), "orbfe_mpstore_erase"); }
+  // false: one of the ids is not in the store (nothing written)
+  bool fetch(const std::vector<uint64_t>& ids, std::vector<float>& pos, std::vector<float>& viewDir, std::vector<float>& maxDist,
+             std::vector<float>& minDist, std::vector<Descriptor>& desc) const {
+    const size_t n = ids.size();
+    pos.resize(3 * n), viewDir.resize(3 * n), maxDist.resize(n), minDist.resize(n), desc.resize(n);
+    return orbfe_mpstore_fetch(mStore, (int32_t)n, ids.data(), pos.data(), viewDir.data(), maxDist.data(), minDist.data(),
+                               n ? desc[0].data() : nullptr) == ORBFE_OK;
+  }
+  size_t size(int64_t* bytesUsed = nullptr, int64_t* bytesReserved = nullptr) const {
+    int64_t n = 0;
+    check(orbfe_mpstore_size(mStore, &n, bytesUsed, bytesReserved), "orbfe_mpstore_size");
+    return (size_t)n;
+  }
+
+ private:
+  static void check(orbfe_status st, const char* what) {
+    if (st != ORBFE_OK) throw std::runtime_error(std::string(what) + ": " + orbfe_last_error(nullptr));
+  }
+  orbfe_mpstore* mStore = nullptr;
+};
+
 class ORBMatcher {
  public:
   static constexpr int mnMaxThreshold = 100, mnMinThreshold = 50, mnMeanThreshold = 75, mnW = 5, mnL = 5;  // ORBMatcher.cc:1086-1090
@@ -857,6 +902,42 @@ class ORBMatcher {
       for (int32_t i = 0; i < nNodes; ++i)
         featVec[bNodes[(size_t)i]].assign(bFeats.begin() + bOffsets[(size_t)i], bFeats.begin() + bOffsets[(size_t)i + 1]);
     }
+    return r;
+  }
+  // Tracking::trackLocalMap's device work (src/Tracking.cc:650-658) on the frame in extraction slot `slot`, the local map points named by
+  // id in a MapPointStore (orbfe_track_local_map_stored), with this matcher's mfRatio.  flags[i]: bit 0 = !isBad && isInMap,
+  // bit 1 = !isBad, bit 2 = in the list searchByProjection walks; held ([capacity], index into ids; empty: the frame holds nothing) and
+  // rightU ([capacity]; empty: mono) the frame's; (Rcw, tcw) and poseSE3 the pose it has.  An id the store does not hold throws.
+  struct TrackLocalMap {
+    int32_t nMatches = 0, nEdges = -1, nGood = 0;
+    std::vector<int32_t> assigned, edgeOf;  // [capacity]
+    std::vector<uint8_t> inlier;
+    double poseSE3[7] = {0, 0, 0, 0, 0, 0, 0};
+    bool optimised() const { return nEdges >= 0; }
+  };
+  TrackLocalMap trackLocalMapStored(orbfe_ctx* ctx, int slot, const MapPointStore& store, const std::vector<uint64_t>& ids,
+                                    const std::vector<uint8_t>& flags, const std::vector<int32_t>& held, const std::vector<double>& rightU,
+                                    const float Rcw[9], const float tcw[3], const float bounds[4], const double poseSE3[7], const Intrinsics& K, float bf,
+                                    const std::vector<float>& sigma2, const std::vector<float>& invSigma2, float th = 3.f, int minMatches = 30) const {
+    const size_t NF = (size_t)std::max((int)orbfe_get_capacity(ctx), 1);
+    if (flags.size() != ids.size() || (!held.empty() && held.size() != NF) || (!rightU.empty() && rightU.size() != NF))
+      throw std::invalid_argument("trackLocalMapStored: flags per id, held / rightU per feature slot");
+    TrackLocalMap r;
+    r.assigned.assign(NF, -1), r.edgeOf.assign(NF, -1), r.inlier.assign(NF, 0);
+    orbfe_frame_pose fp = orbfe_frame_pose();
+    for (int a = 0; a < 9; ++a) fp.Rcw[a] = Rcw[a];
+    for (int a = 0; a < 3; ++a) fp.tcw[a] = tcw[a];
+    fp.min_u = bounds[0], fp.max_u = bounds[1], fp.min_v = bounds[2], fp.max_v = bounds[3];
+    const orbfe_camera cam = {K.fx, K.fy, K.cx, K.cy, 0, 0, 0, 0, 0, bf};
+    orbfe_track_stored_input in = orbfe_track_stored_input();
+    in.n_mp = (int32_t)ids.size(), in.ids = ids.data(), in.flags = flags.data();
+    in.held = held.empty() ? nullptr : held.data(), in.right_u = rightU.empty() ? nullptr : rightU.data();
+    in.level_sigma2 = sigma2.data(), in.level_inv_sigma2 = invSigma2.data(), in.pose_se3 = poseSE3;
+    in.th = th, in.ratio = mfRatio, in.min_threshold = mnMinThreshold, in.min_matches = minMatches;
+    orbfe_track_output out = orbfe_track_output();
+    out.assigned = r.assigned.data(), out.edge_of = r.edgeOf.data(), out.inlier = r.inlier.data();
+    out.n_matches = &r.nMatches, out.n_edges = &r.nEdges, out.n_good = &r.nGood, out.pose_out = r.poseSE3;
+    check(ctx, orbfe_track_local_map_stored(ctx, slot, store.get(), &fp, &cam, &in, &out));
     return r;
   }
   static void sim3Model(const Sim3& S, float model[12]) {  // orbfe_sim3_iterate's layout: R row-major, then t
