@@ -1356,6 +1356,92 @@ orbfe_status orbfe_mpstore_size(orbfe_mpstore* store, int64_t* n_points, int64_t
 orbfe_status orbfe_track_local_map_stored(orbfe_ctx* ctx, int32_t slot, orbfe_mpstore* store, const orbfe_frame_pose* pose,
                                           const orbfe_camera* cam, const orbfe_track_stored_input* in, const orbfe_track_output* out);
 
+/* ---- trackMotionModel over two frame slots -------------------------------------------------------------------------------
+ * Tracking::trackMotionModel (src/Tracking.cc:381-406) from processLastFrame's unProject (:384; src/Frame.cc:179-202, :262-275) to the
+ * return of :405 as one call: the two ORBMatcher::searchByProjection(frame, lastFrame, matches, th) (src/ORBMatcher.cc:265-347, 815-830),
+ * the :388 and :392 decisions, Optimizer::OptimizePoseOnly with its projection post-check (src/Optimizer.cc:33-203), the isInMap count of
+ * :397-404.  Both frames are read where their extraction left them: `slot` / `last_slot` are the extraction slots of the current and the
+ * last frame's left image on this context, `pair` / `last_pair` the stereo pairs whose device-resident results give the current frame's
+ * right_u and the last frame's depth (orbfe_kfstore_add_from_slot's convention; pair < 0: every edge mono; last_pair < 0: no depth, no
+ * temporary point).  Only map state goes up: one flag byte per last-frame feature and the id of its point in `store` (or, with store ==
+ * NULL, its position).  The current frame arrives holding no map point (the state after createStereo / createRGBD, the only call site).
+ *   M1 unProject  a last-frame feature below the last slot's count with flag bit 0 clear and depth >= 0 gets a temporary point:
+ *                 x = (pt.x - cx) / fx, y = (pt.y - cy) / fy in float; p3dC = (float)(depth x), (float)(depth y), (float)depth, depth a
+ *                 double; p3dW = Rwc p3dC + twc as cv::gemm does it.  A temporary point is good and not in the map (temp, temp_pos)
+ *   M2 direction  twc1 = -Rcw^T tcw, tlc = last_Rcw twc1 + last_tcw; |tlc.z| > baseline: up (z > 0) or down (:270-280)
+ *   M3 queries    the last frame's features that hold a good point, their own or a temporary one, in feature order: centre the
+ *                 feature's position, radius th * level_sigma2[octave], octaves [o, 7] (up), [0, o] (down) or [max(0, o - 1),
+ *                 min(o + 1, 7)] (:300-313), the descriptor the last slot's
+ *   M4 search 1   orbfe_track_motion_model's: findFeaturesInArea, candidates that hold a good point dropped and counted
+ *                 (excluded_hits; none in this search, the frame arrives empty), getBestMatch, accepted when ratio < mfRatio and
+ *                 distance < mnMinThreshold; setMapPoints in query order: the last query that names a feature keeps it
+ *   M5 search 2   decided on the device: n_matches < min_matches and th_second > 0.  Radius th_second * level_sigma2[octave]; the
+ *                 features search 1 assigned are dropped and counted; the matches of search 1 stay; n_matches is the sum; passes = 2
+ *   M6 decide #1  n_matches < min_matches: REJECT_MATCHES; assigned (= final_assigned), the hits, query_matches and the temporaries are
+ *                 reported (the reference has written both frames by then), everything of the optimisation is zero
+ *   M7 optimise   the edges are the features that hold a point, in feature order; mono when right_u[f] < 0; from
+ *                 Converter::ConvertTcw2SE3 of (Rcw, tcw); orbfe_pose_only_optimize's kernel
+ *   M8 post-check the relocalisation refine's, with the pose the frame still has (the predicted one); n_inliers = edges - nBad; a
+ *                 feature that is no inlier loses its point (final_assigned); Tcw = Converter::ConvertSE32Tcw of the estimate
+ *   M9 count      n_in_map = the features that still hold a point whose flags are 3 (bit 1 is read only where bit 0 is set: a
+ *                 temporary point never counts)
+ *   M10 decide #2 n_in_map >= min_inliers: ACCEPT, else REJECT_INLIERS
+ * Inputs: last_flags [n_last], n_last = the context's feature capacity: bit 0 the feature's point is non-null and not bad, bit 1 that
+ * point isInMap(); exactly one of last_ids [n_last] (read where bit 0 is set, looked up in `store`; an id may repeat) with a store and
+ * last_pos [n_last][3] without one; (Rcw, tcw) the predicted pose the frame has (:385); last_Rcw, last_tcw, last_Rwc, last_twc the last
+ * frame's pose after :689, the reference's float members.  Outputs, every array required: verdict, passes (1 or 2), n_matches, n_edges,
+ * n_inliers, n_in_map; per frame feature [n_features]: assigned (the LAST-FRAME FEATURE whose point frame feature f holds, -1 none),
+ * final_assigned, inlier, excluded_hits; per last-frame feature [n_last]: query_matches (in how many searches its query was accepted:
+ * one addMatchInTrack each), temp (M1 made a point), temp_pos [n_last][3]; pose_se3 (qx qy qz qw tx ty tz), Tcw (Rcw row-major, then tcw).
+ * ORBFE_EBADARG, nothing written: a NULL required array, both or neither of store + last_ids and last_pos, slot == last_slot, a slot or a
+ * pair out of range, a pose, bounds or camera entry not finite, a store on another device.  An id the store does not hold is found on
+ * the device and reported after the download: ORBFE_EBADARG naming the first such id, none of the outputs written.  ORBFE_EBADSIZE: more
+ * than 2048 features per frame, a grid past the LDS counters.  Locks: the context's, then the store's (shared) for the whole synchronous
+ * duration.  One upload, one launch sequence (prepare, search, claim, between, search, claim, edges, optimise, check) whose second
+ * search leaves at once when it is not needed, one download; no synchronisation in between.                                          */
+typedef enum orbfe_motion_verdict {
+  ORBFE_MOTION_REJECT_MATCHES = 1, /* fewer than min_matches matches after both searches (Tracking.cc:392) */
+  ORBFE_MOTION_REJECT_INLIERS = 2, /* fewer than min_inliers in-map points after the optimisation (:405)   */
+  ORBFE_MOTION_ACCEPT = 3
+} orbfe_motion_verdict;
+typedef struct orbfe_motion_slots_input {
+  const uint8_t* last_flags;     /* [n_last] bit 0: good point, bit 1: that point isInMap()                               */
+  const uint64_t* last_ids;      /* [n_last] MapPoint::getID(), read where bit 0 is set (with a store)                    */
+  const float* last_pos;         /* [n_last][3] MapPoint::getPos(), read where bit 0 is set (without a store)             */
+  float Rcw[9], tcw[3];          /* the predicted pose the frame has (Tracking.cc:385)                                    */
+  float last_Rcw[9], last_tcw[3], last_Rwc[9], last_twc[3]; /* the last frame's pose after :689                           */
+  float bounds[4];               /* the frame's mfMinU mfMaxU mfMinV mfMaxV                                               */
+  const orbfe_camera* cam;       /* fx fy cx cy bf                                                                        */
+  float baseline;                /* Camera::mfBl                                                                          */
+  const float* level_sigma2;     /* [n_levels of the context]                                                             */
+  const float* level_inv_sigma2; /* [n_levels of the context]                                                             */
+  float th, th_second;           /* 15, 30; th_second <= 0: no second search                                              */
+  float ratio;                   /* 0.9                                                                                   */
+  int32_t min_threshold;         /* ORBMatcher::mnMinThreshold                                                            */
+  int32_t min_matches;           /* 20                                                                                    */
+  int32_t min_inliers;           /* 10                                                                                    */
+} orbfe_motion_slots_input;
+typedef struct orbfe_motion_slots_output {
+  int32_t* verdict;           /* [1] orbfe_motion_verdict    */
+  int32_t* passes;            /* [1]                         */
+  int32_t* n_matches;         /* [1]                         */
+  int32_t* n_edges;           /* [1]                         */
+  int32_t* n_inliers;         /* [1]                         */
+  int32_t* n_in_map;          /* [1]                         */
+  int32_t* assigned;          /* [n_features]                */
+  int32_t* final_assigned;    /* [n_features]                */
+  uint8_t* inlier;            /* [n_features]                */
+  int32_t* excluded_hits;     /* [n_features]                */
+  int32_t* query_matches;     /* [n_last]                    */
+  uint8_t* temp;              /* [n_last]                    */
+  float* temp_pos;            /* [n_last][3]                 */
+  double* pose_se3;           /* [7]                         */
+  float* Tcw;                 /* [12]                        */
+} orbfe_motion_slots_output;
+orbfe_status orbfe_track_motion_model_slots(orbfe_ctx* ctx, int32_t slot, int32_t pair, int32_t last_slot, int32_t last_pair,
+                                            orbfe_mpstore* store /* nullable */, const orbfe_motion_slots_input* in,
+                                            const orbfe_motion_slots_output* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------------
  * Stage timing with HIP events on the context stream.  Enable, run, then read the accumulated
  * per-stage milliseconds and launch counts.  Stage ids: see orbfe_stage.                             */

@@ -147,6 +147,35 @@ TRACKREF_VERDICTS = {1: "REJECT_MATCHES", 2: "REJECT_INLIERS", 3: "ACCEPT"}
 TRACKREF_OWN = -2
 
 
+class MotionSlotsInput(C.Structure):
+    _fields_ = [("last_flags", C.c_void_p), ("last_ids", C.c_void_p), ("last_pos", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
+                ("last_Rcw", C.c_float * 9), ("last_tcw", C.c_float * 3), ("last_Rwc", C.c_float * 9), ("last_twc", C.c_float * 3),
+                ("bounds", C.c_float * 4), ("cam", C.POINTER(Camera)), ("baseline", C.c_float), ("level_sigma2", C.c_void_p),
+                ("level_inv_sigma2", C.c_void_p), ("th", C.c_float), ("th_second", C.c_float), ("ratio", C.c_float),
+                ("min_threshold", C.c_int32), ("min_matches", C.c_int32), ("min_inliers", C.c_int32)]
+
+
+class MotionSlotsOutput(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("verdict", "passes", "n_matches", "n_edges", "n_inliers", "n_in_map", "assigned", "final_assigned",
+                                          "inlier", "excluded_hits", "query_matches", "temp", "temp_pos", "pose_se3", "Tcw")]
+
+
+MOTION_VERDICTS = {1: "REJECT_MATCHES", 2: "REJECT_INLIERS", 3: "ACCEPT"}
+
+
+def motion_slots_outputs(nf, fill=None):
+    """the raw output arrays of orbfe_track_motion_model_slots for nf features; fill: a byte every array is filled with (a sentinel)"""
+    o = dict(verdict=np.zeros(1, np.int32), passes=np.zeros(1, np.int32), n_matches=np.zeros(1, np.int32), n_edges=np.zeros(1, np.int32),
+             n_inliers=np.zeros(1, np.int32), n_in_map=np.zeros(1, np.int32), assigned=np.full(nf, -1, np.int32),
+             final_assigned=np.full(nf, -1, np.int32), inlier=np.zeros(nf, np.uint8), excluded_hits=np.zeros(nf, np.int32),
+             query_matches=np.zeros(nf, np.int32), temp=np.zeros(nf, np.uint8), temp_pos=np.zeros((nf, 3), np.float32), pose_se3=np.zeros(7),
+             Tcw=np.zeros(12, np.float32))
+    if fill is not None:
+        for v in o.values():
+            v.view(np.uint8)[...] = fill
+    return o
+
+
 class MapSummary(C.Structure):
     _fields_ = [("next_id", C.c_uint64), ("n_scale_factors", C.c_int32), ("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32),
                 ("n_keypoints", C.c_int64), ("n_observations", C.c_int64)]
@@ -258,7 +287,7 @@ EXPORTS = [
     "orbfe_fuse_points_into_keyframes_stored", "orbfe_debug_fuse_points_kernels", "orbfe_reloc_refine_stored",
     "orbfe_track_reference_stored",
     "orbfe_mpstore_create", "orbfe_mpstore_destroy", "orbfe_mpstore_upsert", "orbfe_mpstore_erase", "orbfe_mpstore_fetch", "orbfe_mpstore_size",
-    "orbfe_track_local_map_stored",
+    "orbfe_track_local_map_stored", "orbfe_track_motion_model_slots",
     "orbfe_profile_enable", "orbfe_profile_read", "orbfe_stage_name", "orbfe_debug_candidates", "orbfe_debug_se3_oplus",
     "orbfe_debug_reduced_solve", "orbfe_debug_sim3_edges", "orbfe_debug_pose_graph_edges", "orbfe_debug_pose_graph_phases",
     "orbfe_debug_pg_sparse_solve", "orbfe_debug_ba_reduced_bsr", "orbfe_debug_bsr_pcg", "orbfe_debug_ba_global_phases",
@@ -415,6 +444,7 @@ def load() -> C.CDLL:
     L.orbfe_mpstore_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.orbfe_track_local_map_stored.argtypes = [vp, i32, vp, C.POINTER(FramePose), C.POINTER(Camera), C.POINTER(TrackStoredInput),
                                                C.POINTER(TrackOutput)]
+    L.orbfe_track_motion_model_slots.argtypes = [vp, i32, i32, i32, i32, vp, C.POINTER(MotionSlotsInput), C.POINTER(MotionSlotsOutput)]
     L.orbfe_profile_enable.argtypes = [vp, i32]
     L.orbfe_profile_read.argtypes = [vp, vp, vp, i32]
     L.orbfe_stage_name.argtypes = [i32]
@@ -2323,6 +2353,68 @@ class Context:
         to = TrackRefOutput(*[ptr(out[k]).value for k, _ in TrackRefOutput._fields_[:-1]], C.addressof(bo) if bo is not None else None)
         args = (self.h, int(slot), None if vocab is None else vocab.h, store.h, C.byref(ti), C.byref(to))
         return args, (good, pos, frame_good, frame_pos, right_u, s2, is2, cm, fv, ti, to, bo, bow_arrays, out)
+
+    def track_motion_model_slots(self, slot, pair, last_slot, last_pair, last_flags, pose, last_pose, cam, bounds, baseline, level_sigma2,
+                                 level_inv_sigma2, store=None, last_ids=None, last_pos=None, th=15.0, th_second=30.0, ratio=0.9,
+                                 min_threshold=50, min_matches=20, min_inliers=10, out=None):
+        """Tracking::trackMotionModel from processLastFrame's unProject to its return as one call (orbfe_track_motion_model_slots); the
+        parameters and the returned dict are described at track_motion_slots_call, which builds the C arguments."""
+        args, keep = self.track_motion_slots_call(slot, pair, last_slot, last_pair, last_flags, pose, last_pose, cam, bounds, baseline,
+                                                  level_sigma2, level_inv_sigma2, store=store, last_ids=last_ids, last_pos=last_pos, th=th,
+                                                  th_second=th_second, ratio=ratio, min_threshold=min_threshold, min_matches=min_matches,
+                                                  min_inliers=min_inliers, out=out)
+        self._check(self.lib.orbfe_track_motion_model_slots(*args))
+        out = keep[-1]
+        res = {k: out[k] for k in ("assigned", "final_assigned", "inlier", "excluded_hits", "query_matches", "temp", "temp_pos", "pose_se3", "Tcw")}
+        for k in ("verdict", "passes", "n_matches", "n_edges", "n_inliers", "n_in_map"):
+            res[k] = int(out[k][0])
+        res["verdict_name"] = MOTION_VERDICTS.get(res["verdict"], "?")
+        return res
+
+    def track_motion_slots_call(self, slot, pair, last_slot, last_pair, last_flags, pose, last_pose, cam, bounds, baseline, level_sigma2,
+                                level_inv_sigma2, store=None, last_ids=None, last_pos=None, th=15.0, th_second=30.0, ratio=0.9,
+                                min_threshold=50, min_matches=20, min_inliers=10, out=None):
+        """The ctypes arguments of orbfe_track_motion_model_slots -> (args, keep): the bare C call is
+        self.lib.orbfe_track_motion_model_slots(*args); keep holds the arrays behind the pointers (its last entry the output arrays).
+        slot / last_slot: the extraction slots of the current and the last frame's left image; pair / last_pair: the stereo pairs that hold
+        the current frame's right_u and the last frame's depth (-1: mono edges / no temporary points).  last_flags [NF]: bit 0 the
+        last-frame feature holds a good point, bit 1 that point is in the map; its points by id in a MapPointStore (store, last_ids [NF])
+        or by position (last_pos [NF, 3]).  pose = (Rcw, tcw): the predicted pose the frame has; last_pose = (Rcw, tcw, Rwc, twc) of the
+        last frame; cam = (fx, fy, cx, cy, bf); bounds = (minU, maxU, minV, maxV); baseline = Camera::mfBl.
+        -> dict(verdict, verdict_name, passes, n_matches, n_edges, n_inliers, n_in_map, assigned [NF] (the last-frame feature whose point
+        frame feature f holds), final_assigned [NF], inlier [NF], excluded_hits [NF], query_matches [NF], temp [NF], temp_pos [NF, 3],
+        pose_se3 [7], Tcw [12]); out: a dict of the raw output arrays to fill (a call that fails leaves it as it is)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        NF = self.n_features
+        last_flags = np.ascontiguousarray(last_flags, np.uint8).reshape(-1)
+        last_ids = None if last_ids is None else np.ascontiguousarray(last_ids, np.uint64).reshape(-1)
+        last_pos = None if last_pos is None else f32(last_pos).reshape(-1, 3)
+        if last_flags.size != NF or (last_ids is not None and last_ids.size != NF) or (last_pos is not None and len(last_pos) != NF):
+            raise ValueError("track_motion_model_slots: last_flags / last_ids / last_pos must have n_features entries")
+        s2, is2 = f32(level_sigma2), f32(level_inv_sigma2)
+        if s2.size < self.n_levels or is2.size < self.n_levels:
+            raise ValueError("track_motion_model_slots: one sigma2 / inv_sigma2 per level of the context")
+        cm = Camera(*[float(np.float32(v)) for v in cam[:4]], 0, 0, 0, 0, 0, float(np.float32(cam[4])))
+        mi = MotionSlotsInput()
+        mi.last_flags = ptr(last_flags).value
+        mi.last_ids = None if last_ids is None else ptr(last_ids).value
+        mi.last_pos = None if last_pos is None else ptr(last_pos).value
+        mi.Rcw[:] = f32(pose[0]).reshape(9).tolist()
+        mi.tcw[:] = f32(pose[1]).reshape(3).tolist()
+        mi.last_Rcw[:] = f32(last_pose[0]).reshape(9).tolist()
+        mi.last_tcw[:] = f32(last_pose[1]).reshape(3).tolist()
+        mi.last_Rwc[:] = f32(last_pose[2]).reshape(9).tolist()
+        mi.last_twc[:] = f32(last_pose[3]).reshape(3).tolist()
+        mi.bounds[:] = f32(bounds).reshape(4).tolist()
+        mi.cam, mi.baseline = C.pointer(cm), float(np.float32(baseline))
+        mi.level_sigma2, mi.level_inv_sigma2 = ptr(s2).value, ptr(is2).value
+        mi.th, mi.th_second, mi.ratio = float(th), float(th_second), float(ratio)
+        mi.min_threshold, mi.min_matches, mi.min_inliers = int(min_threshold), int(min_matches), int(min_inliers)
+        if out is None:
+            out = motion_slots_outputs(NF)
+        mo = MotionSlotsOutput(*[ptr(out[k]).value for k, _ in MotionSlotsOutput._fields_])
+        args = (self.h, int(slot), int(pair), int(last_slot), int(last_pair), None if store is None else store.h, C.byref(mi), C.byref(mo))
+        return args, (last_flags, last_ids, last_pos, s2, is2, cm, mi, mo, out)
 
     # ---- instrumentation ------------------------------------------------------------------------
     def profile_enable(self, on=True):

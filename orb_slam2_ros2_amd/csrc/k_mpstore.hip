@@ -18,20 +18,7 @@ namespace {
 
 const int MP_NT = 256;
 
-// the row of `id` and its presence byte; nullptr: the id is past the capacity or its page does not exist
-__device__ inline uint8_t* mp_row(const MpTable& t, uint64_t id, uint8_t** presence) {
-  if (id >= (uint64_t)t.rows_per_page * t.max_pages) return nullptr;
-  uint32_t page, row;
-  if ((id >> 32) == 0) {  // (the usual case: a 32-bit division)
-    page = (uint32_t)id / t.rows_per_page, row = (uint32_t)id % t.rows_per_page;
-  } else {
-    page = (uint32_t)(id / t.rows_per_page), row = (uint32_t)(id % t.rows_per_page);
-  }
-  uint8_t* base = t.table[page];
-  if (!base) return nullptr;
-  *presence = base + (size_t)t.rows_per_page * kMpRowBytes + row;
-  return base + (size_t)row * kMpRowBytes;
-}
+// (mp_row, the row of an id and its presence byte: orbfe_mpstore.h, shared with k_motion.hip)
 
 __global__ __launch_bounds__(MP_NT) void k_mpstore_gather(MpTable t, int n, const uint64_t* __restrict__ ids, MpArrays out,
                                                           uint8_t* __restrict__ flags, uint32_t* __restrict__ absent) {

@@ -118,12 +118,7 @@ __global__ __launch_bounds__(1024) void k_reloc_check(RelocDev P, int s) {
     return;
   }
   // a search follows: twc = -Rcw^T tcw, tlc = Rkf twc + tkf (ORBMatcher.cc:274-276)
-  float twc[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) twc[r] = -(R[r] * tc[0] + R[3 + r] * tc[1] + R[6 + r] * tc[2]);
-  float tlc[3];
-  affine(1.0f, P.kf_R, twc, P.kf_t, tlc);
-  P.hdr[RELOC_H_TLCZ + s] = __float_as_int(tlc[2]);
+  P.hdr[RELOC_H_TLCZ + s] = __float_as_int(tlc_z_dev(R, tc, P.kf_R, P.kf_t));
   if (s == 0) tcw_to_se3_dev(R, tc, P.p_init + 7);  // the frame's pose is the float one now (setPose, Optimizer.cc:201)
 }
 
@@ -137,11 +132,7 @@ __global__ __launch_bounds__(256) void k_reloc_search(RelocDev P, int s) {
   const int o = min(max(kp.octave, 0), P.n_levels - 1);
   const float z = __int_as_float(P.hdr[RELOC_H_TLCZ + s]);
   int lo, hi;
-  if (fabsf(z) > P.baseline) {
-    if (z > 0.f) lo = o, hi = 7;
-    else lo = 0, hi = o;
-  } else
-    lo = max(0, o - 1), hi = min(o + 1, 7);
+  motion_window(o, z, P.baseline, lo, hi);
   const float rad = P.th[s] * P.sigma2[o];  // findFeaturesInArea: radius * getScaledFactor2(octave) (Frame.cc:289)
   const uint4 a0 = *(const uint4*)(P.k_desc + (size_t)q * 32);
   const uint4 a1 = *(const uint4*)(P.k_desc + (size_t)q * 32 + 16);

@@ -588,3 +588,52 @@ struct TrackRefDev {
   float* tcw_out /*[12]*/;
   uint8_t* inlier /*[nf]*/;
 };
+
+// ---- trackMotionModel over two frame slots (k_motion.hip, orbfe_motion.hip) ----------------------------------------------
+// Everything the glue kernels of one call read and write.  Queries are indexed by LAST-FRAME FEATURE: a feature that is no query has
+// radius -1 in both passes (k_search_area leaves such a query at once), so the searches keep a host-side count (the feature capacity),
+// nothing is compacted and the query descriptors are the last slot's own array.  hdr: [0] verdict, [1] passes, [2] n_matches,
+// [3] n_edges, [4] n_inliers, [5] n_in_map.
+#define MOTION_H_VERDICT 0
+#define MOTION_H_PASSES 1
+#define MOTION_H_MATCHES 2
+#define MOTION_H_EDGES 3
+#define MOTION_H_INLIERS 4
+#define MOTION_H_INMAP 5
+struct MotionDev {
+  // the two frames (slot arrays); l_depth nullptr: no depth
+  const orbfe_keypoint *f_kps, *l_kps;
+  const int32_t *f_n_kp, *l_n_kp;
+  const double* l_depth;
+  int32_t nf, n_levels;
+  // the map state of the call's upload; table nullptr: positions from l_pos, else from the store's rows of l_ids (MpTable's fields)
+  const uint8_t* l_flags;
+  const uint64_t* l_ids;
+  const float* l_pos;
+  const uint8_t* const* table;
+  uint32_t rows_per_page, max_pages;
+  const float *sigma2, *inv_sigma2;
+  float R0[9], t0[3], lR[9], lt[3], lRwc[9], ltwc[3];
+  float fx, fy, cx, cy, max_u, max_v, baseline, th, th_second;
+  int32_t min_matches, min_inliers;
+  // device state: the query arrays of both passes, the claims and the accepted-query counter, what the second pass excludes, the edge
+  // list's results
+  float *qxy, *rad1, *rad2, *q_pos;
+  int8_t *lo, *hi;
+  uint8_t *q_flags, *ex2;
+  const int32_t *claim1, *n_accept;
+  const uint8_t *qa1, *qa2;
+  const int32_t *edge_of, *cnt /*[0] n_matches, [1] edge count, -1: no optimisation*/;
+  double *p_init /*[7]*/;
+  const double* p_opt /*[7]*/;
+  const uint8_t* e_inl;
+  // the downloaded block
+  int32_t* hdr;
+  uint32_t* bad;  // set by a flagged id without a row
+  const int32_t* assigned /*[nf]*/;
+  int32_t *cur /*[nf]: final_assigned*/, *qm /*[nf]: query_matches*/;
+  uint8_t *inlier /*[nf]*/, *temp /*[nf]*/;
+  float* temp_pos /*[nf][3]*/;
+  double* pose_out /*[7]*/;
+  float* tcw_out /*[12]*/;
+};

@@ -17,6 +17,22 @@ struct MpTable {
   uint8_t* const* table;
   uint32_t rows_per_page, max_pages;
 };
+// the row of `id` and its presence byte; nullptr: the id is past the capacity or its page does not exist (k_mpstore.hip's kernels, and
+// k_motion.hip's prepare kernel, which reads a position where it lies)
+__device__ inline uint8_t* mp_row(const MpTable& t, uint64_t id, uint8_t** presence) {
+  if (id >= (uint64_t)t.rows_per_page * t.max_pages) return nullptr;
+  uint32_t page, row;
+  if ((id >> 32) == 0) {  // (the usual case: a 32-bit division)
+    page = (uint32_t)id / t.rows_per_page, row = (uint32_t)id % t.rows_per_page;
+  } else {
+    page = (uint32_t)(id / t.rows_per_page), row = (uint32_t)(id % t.rows_per_page);
+  }
+  uint8_t* base = t.table[page];
+  if (!base) return nullptr;
+  *presence = base + (size_t)t.rows_per_page * kMpRowBytes + row;
+  return base + (size_t)row * kMpRowBytes;
+}
+
 // The arrays a gather fills / a scatter reads, one entry per listed id, in orbfe_track_input's layout.
 struct MpArrays {
   float *pos, *view_dir, *max_dist, *min_dist;

@@ -1,7 +1,9 @@
-// pose_check_dev.h -- what surrounds a pose-only optimisation inside a fused Tracking step, shared by k_reloc.hip and
-// k_trackref.hip: the two pose conversions of Optimizer::OptimizePoseOnly (src/Optimizer.cc:119, :201) in fp64 and its
-// projection post-check (:179-199), as the 1024 threads of one workgroup run it.  The kernels differ only in where a held point's
-// position comes from and in what a feature that is no inlier loses; both are parameters here, so the post-check has one text.
+// pose_check_dev.h -- what surrounds a pose-only optimisation inside a fused Tracking step, shared by k_reloc.hip,
+// k_trackref.hip and k_motion.hip: the two pose conversions of Optimizer::OptimizePoseOnly
+// (src/Optimizer.cc:119, :201) in fp64 and its projection post-check (:179-199), as the 1024 threads of one workgroup run it.  The kernels
+// differ only in where a held point's position comes from and in what a feature that is no inlier loses; both are parameters here, so
+// the post-check has one text.  Beside them the motion direction and the octave window of searchByProjection(frame, other frame), which
+// the relocalisation refine and the motion model share.
 // Float arithmetic: map_point_dev.h's rows and `A x + t`; the includer switches contraction off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,6 +63,26 @@ __device__ __forceinline__ void se3_to_tcw_dev(const double* p, float* R, float*
   R[3] = (float)(txy + twz), R[4] = (float)(1.0 - (txx + tzz)), R[5] = (float)(tyz - twx);
   R[6] = (float)(txz - twy), R[7] = (float)(tyz + twx), R[8] = (float)(1.0 - (txx + tyy));
   t[0] = (float)p[4], t[1] = (float)p[5], t[2] = (float)p[6];
+}
+
+// The motion direction of ORBMatcher::searchByProjection(frame, other frame) (src/ORBMatcher.cc:274-276): twc = -Rcw^T tcw of the searching
+// frame, tlc = R2 twc + t2 with the other frame's pose; returns tlc.z
+__device__ __forceinline__ float tlc_z_dev(const float* R, const float* tc, const float* R2, const float* t2) {
+  float twc[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) twc[r] = -(R[r] * tc[0] + R[3 + r] * tc[1] + R[6 + r] * tc[2]);
+  float tlc[3];
+  affine(1.0f, R2, twc, t2, tlc);
+  return tlc[2];
+}
+
+// the octave window of a query of octave o under that direction (:279-280, :300-313)
+__device__ __forceinline__ void motion_window(int o, float z, float baseline, int& lo, int& hi) {
+  if (fabsf(z) > baseline) {
+    if (z > 0.f) lo = o, hi = 7;
+    else lo = 0, hi = o;
+  } else
+    lo = max(0, o - 1), hi = min(o + 1, 7);
 }
 
 struct PostCheckCam {

@@ -1276,6 +1276,113 @@ static void OptimizeLocalMap(KeyFramePtr pkframe, bool& isStop) {
     return nMatches;
   }
 
+  // a stereo frame whose two extractions and stereo match still sit in one slot pair of its context (ORBExtractor::extractStereo): the
+  // left slot, or -1.  The pair of that slot, slot / 2, then holds the frame's right_u and depth.
+  template <class FramePtr>
+  static int residentPairSlot(const FramePtr& pFrame) {
+    if (!pFrame->mpExtractorLeft || !pFrame->mpExtractorRight) return -1;
+    const auto &l = pFrame->mpExtractorLeft->device(), &r = pFrame->mpExtractorRight->device();
+    if (!l.resident() || !r.resident() || l.context() != r.context() || (l.slot() & 1) || r.slot() != l.slot() + 1) return -1;
+    return l.slot();
+  }
+
+  // bool Tracking::trackMotionModel() after its two setPose calls (src/Tracking.cc:384-405 with processLastFrame's :691-693) as ONE device
+  // call (orbfe_track_motion_model_slots) over a map-point store (orbfe_mpstore_dropin.hpp): Frame::unProject of the last
+  // frame, both searchByProjection(frame, lastFrame), the 20-match tests, OptimizePoseOnly with its tail, the isInMap count.  Both frames
+  // are read in the slots their extraction left them in; what goes up is a flag byte and an id per last-frame feature.  The side effects
+  // are replayed on the reference's objects in the reference's order: the temporary points (MapPoint::create of the positions the device
+  // computed) into the last frame and tempPoints, setMapPoints with addMatchInTrack per match and per excluded candidate, then the
+  // nulling, addInlierInTrack and setPose.  Falls back to the bodies above (Frame::unProject, trackMotionModel, the count) when either
+  // frame is no longer resident as a stereo pair of one context, the current frame holds a point, the context has more than 2048
+  // features or the camera distorts.
+  template <class CameraT, class Store, class FramePtr1, class FramePtr2, class MapPointPtr>
+  static bool trackMotionModelSlots(Store& store, FramePtr1 pCurr, FramePtr2 pLast, std::vector<MapPointPtr>& tempPoints, float mfRatio = 0.9f) {
+    const int slot = residentPairSlot(pCurr), lastSlot = residentPairSlot(pLast);
+    const orbfe_camera cam = cameraOf<CameraT>();
+    const bool distorting = cam.k1 != 0.f || cam.k2 != 0.f || cam.p1 != 0.f || cam.p2 != 0.f || cam.k3 != 0.f;
+    bool holds = false;
+    for (const auto& p : pCurr->getMapPoints()) holds = holds || (p && !p->isBad());
+    if (slot < 0 || lastSlot < 0 || slot == lastSlot || pCurr->mpExtractorLeft->device().context() != pLast->mpExtractorLeft->device().context() ||
+        (size_t)orbfe_get_capacity(pCurr->mpExtractorLeft->device().context()) > 2048 || holds || distorting) {
+      std::vector<MapPointPtr> mapPoints;
+      pLast->unProject(mapPoints);
+      std::swap(mapPoints, tempPoints);
+      int nGood = 0;
+      if (trackMotionModel<CameraT>(pCurr, pLast, mfRatio, nGood) < 20) return false;
+      int inLiers = 0;
+      for (const auto& p : pCurr->getMapPoints()) inLiers += (p && p->isInMap()) ? 1 : 0;
+      return inLiers >= 10;
+    }
+    orbfe_ctx* ctx = pCurr->mpExtractorLeft->device().context();
+    const size_t NF = (size_t)orbfe_get_capacity(ctx), N = pCurr->mvFeatsLeft.size(), NL = pLast->mvFeatsLeft.size();
+    auto& lastSlots = pLast->mvpMapPoints;
+    std::vector<uint8_t> flags(NF, 0);
+    std::vector<uint64_t> ids(NF, 0);
+    std::vector<MapPointPtr> own;
+    for (size_t i = 0; i < NL && i < NF && i < lastSlots.size(); ++i) {
+      const auto& p = lastSlots[i];
+      if (!p || p->isBad()) continue;
+      flags[i] = (uint8_t)(1 | (p->isInMap() ? 2 : 0));
+      ids[i] = store.id(p);
+      own.push_back(p);
+    }
+    store.ensure(own);  // the points the store has never seen, or that changed since, go up once
+    const int nLevels = 8;
+    std::vector<float> sig2((size_t)nLevels), invSig2((size_t)nLevels);
+    for (int l = 0; l < nLevels; ++l) sig2[(size_t)l] = pCurr->getScaledFactor2(l), invSig2[(size_t)l] = pCurr->getScaledFactorInv2(l);
+    orbfe_motion_slots_input in{};
+    in.last_flags = flags.data(), in.last_ids = ids.data();
+    poseFloats(pCurr->mRcw, pCurr->mtcw, in.Rcw, in.tcw);
+    poseFloats(pLast->mRcw, pLast->mtcw, in.last_Rcw, in.last_tcw);
+    poseFloats(pLast->mRwc, pLast->mtwc, in.last_Rwc, in.last_twc);
+    in.bounds[0] = pCurr->mfMinU, in.bounds[1] = pCurr->mfMaxU, in.bounds[2] = pCurr->mfMinV, in.bounds[3] = pCurr->mfMaxV;
+    in.cam = &cam, in.baseline = CameraT::mfBl, in.level_sigma2 = sig2.data(), in.level_inv_sigma2 = invSig2.data();
+    in.th = 15.f, in.th_second = 30.f, in.ratio = mfRatio, in.min_threshold = orbfe::ORBMatcher::mnMinThreshold, in.min_matches = 20, in.min_inliers = 10;
+    int32_t verdict = 0, passes = 0, nMatches = 0, nEdges = 0, nInliers = 0, nInMap = 0;
+    std::vector<int32_t> assigned(NF, -1), fin(NF, -1), hits(NF, 0), qMatches(NF, 0);
+    std::vector<uint8_t> inl(NF, 0), temp(NF, 0);
+    std::vector<float> tempPos(3 * NF, 0.f);
+    double est[7];
+    float Tcw[12];
+    orbfe_motion_slots_output out{};
+    out.verdict = &verdict, out.passes = &passes, out.n_matches = &nMatches, out.n_edges = &nEdges, out.n_inliers = &nInliers, out.n_in_map = &nInMap;
+    out.assigned = assigned.data(), out.final_assigned = fin.data(), out.inlier = inl.data(), out.excluded_hits = hits.data();
+    out.query_matches = qMatches.data(), out.temp = temp.data(), out.temp_pos = tempPos.data(), out.pose_se3 = est, out.Tcw = Tcw;
+    check(ctx, orbfe_track_motion_model_slots(ctx, slot, slot / 2, lastSlot, lastSlot / 2, store.get(), &in, &out));
+    // Frame::unProject (src/Frame.cc:179-202): the temporary points, then what processLastFrame keeps of them (Tracking.cc:691-693)
+    using MapPointT = typename MapPointPtr::element_type;
+    std::vector<MapPointPtr> mapPoints(NL, nullptr);
+    for (size_t i = 0; i < NL && i < lastSlots.size(); ++i) {
+      if (i < NF && temp[i]) {
+        cv::Mat p3dW(3, 1, CV_32F);
+        for (int a = 0; a < 3; ++a) p3dW.template at<float>(a) = tempPos[3 * i + (size_t)a];
+        mapPoints[i] = MapPointT::create(p3dW);
+      } else if (lastSlots[i] && !lastSlots[i]->isBad())
+        mapPoints[i] = lastSlots[i];
+    }
+    lastSlots = mapPoints;
+    std::swap(mapPoints, tempPoints);
+    // the side effects of the searches: addMatchInTrack of the point a feature holds for every query that met it as a candidate
+    // (ORBMatcher.cc:321-331), then setMapPoints (:815-830): one addMatchInTrack per accepted query and search, the last one keeps the feature
+    auto& slots = pCurr->mvpMapPoints;
+    for (size_t f = 0; f < N && f < NF; ++f)
+      for (int32_t k = 0; assigned[f] >= 0 && k < hits[f]; ++k) lastSlots[(size_t)assigned[f]]->addMatchInTrack();
+    for (size_t i = 0; i < NL && i < NF; ++i)
+      for (int32_t k = 0; k < qMatches[i]; ++k) lastSlots[i]->addMatchInTrack();
+    for (size_t f = 0; f < N && f < NF && f < slots.size(); ++f)
+      if (assigned[f] >= 0) slots[f] = lastSlots[(size_t)assigned[f]];
+    if (verdict == ORBFE_MOTION_REJECT_MATCHES) return false;
+    // OptimizePoseOnly's tail (src/Optimizer.cc:191-201)
+    for (size_t f = 0; f < N && f < slots.size(); ++f) {
+      if (f < NF && inl[f])
+        slots[f]->addInlierInTrack();
+      else
+        slots[f] = nullptr;
+    }
+    pCurr->setPose(poseMat(Tcw, Tcw + 9));
+    return verdict == ORBFE_MOTION_ACCEPT;
+  }
+
   // What Tracking::trackReLocalize does with ONE PnP hypothesis (src/Tracking.cc:565-584): setCurrFrameAttrib (:500-517),
   // OptimizePoseOnly, and between 10 and 50 inliers addMatchByProject (:612-629).  The reference's chain on the bodies above -- what
   // relocRefine falls back to, and what its one device call stands for.
