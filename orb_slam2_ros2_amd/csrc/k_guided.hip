@@ -6,13 +6,18 @@
 // overlap its search box, rows outer / columns inner / index order inside a cell, filtered by octave range and an exclusion
 // mask, scanned with the reference's order-dependent best / second-best rule.  SURVEY 8f, row f1.
 // The kernels here are thin: the grid build is area_grid_body.h, the area loop and the fold area_search_body.h (this file's filter: the
-// octave of the packed record, then the exclusion mask and its hit counts), isInVision / predictLevel map_point_dev.h.
+// octave of the packed record, then the exclusion mask and its hit counts), isInVision / predictLevel map_point_dev.h, the pose-only
+// edge list of the tracking chain pose_check_dev.h (k_track_edges says what a feature holds and counts the matches).
 #include <hip/hip_runtime.h>
 
 #include "area_search_body.h"
 #include "map_point_dev.h"
 #include "orbfe_internal.h"
+#include "pose_check_dev.h"
 #include "search_area_layout.h"
+#include "wave_ops.h"
+
+#pragma clang fp contract(off)
 
 namespace orbfe {
 
@@ -146,13 +151,10 @@ __global__ __launch_bounds__(256) void k_track_claim(int n, const int32_t* __res
 // held[f]: map point the feature holds on entry (-1 none); mp_flags bit 0: !isBad && isInMap (the occupancy test, ORBMatcher.cc:595, and
 // the search loop's own filter, :575), bit 1: !isBad (the initial count, :566-571, and the edge test, Optimizer.cc:64), bit 2: member of
 // the list searchByProjection walks.
-__global__ __launch_bounds__(1024) void k_track_edges(const orbfe_keypoint* __restrict__ kps, const int32_t* __restrict__ n_kp_ptr, int n_features,
-                                                      const int32_t* __restrict__ held, const int32_t* __restrict__ claim,
-                                                      const uint8_t* __restrict__ mp_flags, const float* __restrict__ mp_pos,
-                                                      const double* __restrict__ right_u, const float* __restrict__ level_sigma2,
-                                                      const float* __restrict__ level_inv_sigma2, int min_matches,
-                                                      int32_t* __restrict__ assigned, int32_t* __restrict__ edge_of, double* __restrict__ Xw,
-                                                      double* __restrict__ meas, double* __restrict__ info, float* __restrict__ sigma2,
+// The edge list itself is pose_check_dev.h's pose_edges_1024 (of F only the frame view is read: no pose, no camera).
+__global__ __launch_bounds__(1024) void k_track_edges(PoseFrameDev F, PoseEdgesDev E, const int32_t* __restrict__ held,
+                                                      const int32_t* __restrict__ claim, const uint8_t* __restrict__ mp_flags,
+                                                      const float* __restrict__ mp_pos, int min_matches, int32_t* __restrict__ assigned,
                                                       int32_t* __restrict__ counts /*[0] n_matches, [1] n_edges (-1: below min_matches)*/,
                                                       int32_t unclaimed, const int32_t* __restrict__ n_accept, int base_matches) {
   // unclaimed: the value a claim starts with (0x7F7F7F7F under atomicMin, -1 under atomicMax).  n_accept (nullable, the frame <- frame
@@ -160,52 +162,29 @@ __global__ __launch_bounds__(1024) void k_track_edges(const orbfe_keypoint* __re
   __shared__ int s_wave[16], s_match[16];
   __shared__ int s_base;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int n_kp = min(*n_kp_ptr, n_features);
-  if (t == 0) s_base = 0;
-  int total_matches = 0;
-  __syncthreads();
-  for (int f0 = 0; f0 < n_features; f0 += 1024) {
-    const int f = f0 + t;
+  const int n_kp = min(*F.n_kp, F.nf);
+  int my_matches = 0;  // this thread's features: one for a good point held on entry, one for a claim taken
+  const int edges = pose_edges_1024(F, E, s_wave, &s_base, [&](int f) -> const float* {
     int mp = -1;
-    bool c_held = false, c_new = false, edge = false;
     if (f < n_kp) {
       const int h = held ? held[f] : -1;
-      c_held = h >= 0 && (mp_flags[h] & 2);  // `if (pMp && !pMp->isBad()) ++nMatches` (ORBMatcher.cc:566-571)
+      if (h >= 0 && (mp_flags[h] & 2)) ++my_matches;  // `if (pMp && !pMp->isBad()) ++nMatches` (ORBMatcher.cc:566-571)
       mp = h;
       const int cl = claim[f];
-      if (cl != unclaimed && !(h >= 0 && (mp_flags[h] & 1))) mp = cl, c_new = true;  // setMapPoint + ++nMatches (:595-599)
-      edge = mp >= 0 && (mp_flags[mp] & 2);
+      if (cl != unclaimed && !(h >= 0 && (mp_flags[h] & 1))) mp = cl, ++my_matches;  // setMapPoint + ++nMatches (:595-599)
     }
-    if (f < n_features) assigned[f] = mp;
-    const unsigned long long me = __ballot(edge);
-    const int wm = __popcll(__ballot(c_held)) + __popcll(__ballot(c_new));
-    if (lane == 0) s_wave[wv] = __popcll(me), s_match[wv] = wm;
-    __syncthreads();
-    int before = s_base, chunk_edges = 0, chunk_matches = 0;
-    for (int w = 0; w < 16; ++w) {
-      if (w < wv) before += s_wave[w];
-      chunk_edges += s_wave[w], chunk_matches += s_match[w];
-    }
-    total_matches += chunk_matches;
-    const int pos = before + __popcll(me & ((1ull << lane) - 1ull));
-    if (f < n_features) edge_of[f] = edge ? pos : -1;
-    if (edge) {
-      const orbfe_keypoint k = kps[f];
-      Xw[3 * pos] = (double)mp_pos[3 * mp], Xw[3 * pos + 1] = (double)mp_pos[3 * mp + 1], Xw[3 * pos + 2] = (double)mp_pos[3 * mp + 2];
-      const double ru = right_u ? right_u[f] : -1.0;
-      meas[3 * pos] = (double)k.x, meas[3 * pos + 1] = (double)k.y, meas[3 * pos + 2] = ru < 0 ? -1.0 : ru;
-      const int oc = k.octave;
-      info[pos] = (double)level_inv_sigma2[oc];
-      sigma2[pos] = level_sigma2[oc];
-    }
-    __syncthreads();
-    if (t == 0) s_base += chunk_edges;
-    __syncthreads();
-  }
+    assigned[f] = mp;
+    return mp >= 0 && (mp_flags[mp] & 2) ? mp_pos + 3 * mp : nullptr;
+  });
+  my_matches = wave_reduce_dpp<OpAddI>(my_matches);
+  if (lane == 0) s_match[wv] = my_matches;
+  __syncthreads();
   if (t == 0) {
+    int total_matches = 0;
+    for (int w = 0; w < 16; ++w) total_matches += s_match[w];
     if (n_accept) total_matches = base_matches + *n_accept;
     counts[0] = total_matches;
-    counts[1] = total_matches < min_matches ? -1 : s_base;  // Tracking::trackLocalMap returns before the optimisation (Tracking.cc:656-657)
+    counts[1] = total_matches < min_matches ? -1 : edges;  // Tracking::trackLocalMap returns before the optimisation (Tracking.cc:656-657)
   }
 }
 
@@ -221,12 +200,11 @@ void launch_track_claim(hipStream_t s, int n, const int32_t* d_n_cand, const int
   hipLaunchKernelGGL(k_track_claim, dim3((n + 255) / 256), dim3(256), 0, s, n, d_n_cand, d_best_idx, d_best_dist, d_second, min_threshold, ratio, d_claim,
                      last_wins, d_n_accept, d_accepted);
 }
-void launch_track_edges(hipStream_t s, const orbfe_keypoint* d_kps, const int32_t* d_n_kp, int n_features, const int32_t* d_held, const int32_t* d_claim,
-                        const uint8_t* d_mp_flags, const float* d_mp_pos, const double* d_right_u, const float* d_sigma2, const float* d_inv_sigma2,
-                        int min_matches, int32_t* d_assigned, int32_t* d_edge_of, double* d_Xw, double* d_meas, double* d_info, float* d_sig,
-                        int32_t* d_counts, int32_t unclaimed, const int32_t* d_n_accept, int base_matches) {
-  hipLaunchKernelGGL(k_track_edges, dim3(1), dim3(1024), 0, s, d_kps, d_n_kp, n_features, d_held, d_claim, d_mp_flags, d_mp_pos, d_right_u, d_sigma2,
-                     d_inv_sigma2, min_matches, d_assigned, d_edge_of, d_Xw, d_meas, d_info, d_sig, d_counts, unclaimed, d_n_accept, base_matches);
+void launch_track_edges(hipStream_t s, const PoseFrameDev& F, const PoseEdgesDev& E, const int32_t* d_held, const int32_t* d_claim,
+                        const uint8_t* d_mp_flags, const float* d_mp_pos, int min_matches, int32_t* d_assigned, int32_t* d_counts, int32_t unclaimed,
+                        const int32_t* d_n_accept, int base_matches) {
+  hipLaunchKernelGGL(k_track_edges, dim3(1), dim3(1024), 0, s, F, E, d_held, d_claim, d_mp_flags, d_mp_pos, min_matches, d_assigned, d_counts,
+                     unclaimed, d_n_accept, base_matches);
 }
 
 void launch_project_map_points(hipStream_t s, int n, const float* d_pos, const float* d_vdir, const float* d_max, const float* d_min,

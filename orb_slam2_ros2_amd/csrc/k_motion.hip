@@ -12,7 +12,8 @@
 //                  second search (-1 for every query when it is not wanted: its kernels then leave at once) and the features the first
 //                  search assigned, which the second drops as candidates and counts (ORBMatcher.cc:321-331).
 // k_motion_check   one workgroup: query_matches, the :392 decision as k_track_edges left it (edge count -1), pose_check_dev.h's
-//                  post-check with the pose the frame still has, Converter::ConvertSE32Tcw, the isInMap count of :397-404, the verdict.
+//                  post-check with the pose the frame still has, Converter::ConvertSE32Tcw and the write-back, the isInMap count of
+//                  :397-404, the verdict.
 // No kernel waits on another; every loop is bounded by the feature capacity.  Float arithmetic: map_point_dev.h's rows and `A x + t`, no
 // contraction; the conversions in fp64.
 #include <hip/hip_runtime.h>
@@ -28,9 +29,9 @@ namespace {
 
 __global__ __launch_bounds__(256) void k_motion_prep(MotionDev P) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) tcw_to_se3_dev(P.R0, P.t0, P.p_init);
-  if (i >= P.nf) return;
-  const int n_last = min(max(*P.l_n_kp, 0), P.nf);
+  if (i == 0) tcw_to_se3_dev(P.F.R0, P.F.t0, P.p_init);
+  if (i >= P.F.nf) return;
+  const int n_last = min(max(*P.l_n_kp, 0), P.F.nf);
   const bool valid = i < n_last;
   orbfe_keypoint kp = {};
   if (valid) kp = P.l_kps[i];
@@ -54,18 +55,18 @@ __global__ __launch_bounds__(256) void k_motion_prep(MotionDev P) {
   } else if (valid && P.l_depth) {
     const double depth = P.l_depth[i];
     if (depth >= 0) {  // VirtualFrame::unProject (Frame.cc:262-275), then mRwc * p3dC + mtwc (:195)
-      const float x = (kp.x - P.cx) / P.fx, y = (kp.y - P.cy) / P.fy;
+      const float x = (kp.x - P.F.cx) / P.F.fx, y = (kp.y - P.F.cy) / P.F.fy;
       const float pc[3] = {(float)(depth * (double)x), (float)(depth * (double)y), (float)depth};
       affine(1.0f, P.lRwc, pc, P.ltwc, X);
       temp = true;
     }
   }
   const bool query = good || temp;
-  const int o = min(max(kp.octave, 0), P.n_levels - 1);
+  const int o = min(max(kp.octave, 0), P.F.n_levels - 1);
   int lo, hi;
-  motion_window(o, tlc_z_dev(P.R0, P.t0, P.lR, P.lt), P.baseline, lo, hi);
+  motion_window(o, tlc_z_dev(P.F.R0, P.F.t0, P.lR, P.lt), P.baseline, lo, hi);
   P.qxy[2 * i] = kp.x, P.qxy[2 * i + 1] = kp.y;
-  P.rad1[i] = query ? P.th * P.sigma2[o] : -1.f;  // findFeaturesInArea: radius * getScaledFactor2(octave) (Frame.cc:289)
+  P.rad1[i] = query ? P.th * P.F.sigma2[o] : -1.f;  // findFeaturesInArea: radius * getScaledFactor2(octave) (Frame.cc:289)
   P.lo[i] = (int8_t)lo, P.hi[i] = (int8_t)hi;
   P.q_pos[3 * i] = X[0], P.q_pos[3 * i + 1] = X[1], P.q_pos[3 * i + 2] = X[2];
   P.q_flags[i] = query ? 3 : 0;  // k_track_edges' flags: every query is a good point
@@ -76,11 +77,11 @@ __global__ __launch_bounds__(256) void k_motion_prep(MotionDev P) {
 __global__ __launch_bounds__(1024) void k_motion_between(MotionDev P) {
   const int t = threadIdx.x;
   const bool second = *P.n_accept < P.min_matches && P.th_second > 0.f;  // Tracking.cc:388 (uniform over the workgroup)
-  for (int i = t; i < P.nf; i += 1024) {
+  for (int i = t; i < P.F.nf; i += 1024) {
     float r = -1.f;
     if (second && P.q_flags[i]) {
-      const int o = min(max(P.l_kps[i].octave, 0), P.n_levels - 1);
-      r = P.th_second * P.sigma2[o];
+      const int o = min(max(P.l_kps[i].octave, 0), P.F.n_levels - 1);
+      r = P.th_second * P.F.sigma2[o];
     }
     P.rad2[i] = r;
     P.ex2[i] = P.claim1[i] >= 0 ? 1 : 0;  // the feature holds a point of the first search: no candidate of the second (:321-331)
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(1024) void k_motion_check(MotionDev P) {
   __shared__ int s_wave[16], s_map[16];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int edges = P.cnt[1];
-  for (int f = t; f < P.nf; f += 1024) {
+  for (int f = t; f < P.F.nf; f += 1024) {
     P.qm[f] = (int)P.qa1[f] + (int)P.qa2[f];  // setMapPoints' addMatchInTrack: once per accepted query and search
     P.cur[f] = P.assigned[f];
   }
@@ -100,16 +101,10 @@ __global__ __launch_bounds__(1024) void k_motion_check(MotionDev P) {
     if (t == 0) P.hdr[MOTION_H_MATCHES] = P.cnt[0], P.hdr[MOTION_H_VERDICT] = ORBFE_MOTION_REJECT_MATCHES;
     return;
   }
-  float R[9], tc[3], Rb[9], tb[3];
+  float R[9], tc[3];
   se3_to_tcw_dev(P.p_opt, R, tc);
-  // the check projects with the pose the frame still has, the predicted one: setPose comes last (Optimizer.cc:201)
-#pragma unroll
-  for (int k = 0; k < 9; ++k) Rb[k] = P.R0[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) tb[k] = P.t0[k];
-  const PostCheckCam K = {P.fx, P.fy, P.cx, P.cy, P.max_u, P.max_v};
-  const int n_in = post_check_1024(
-      P.nf, P.edge_of, P.e_inl, Rb, tb, K, P.inlier, s_wave,
+  const int n_in = post_check_1024(  // (the pose the frame still has is the predicted one)
+      P.F, P.F.R0, P.F.t0, P.E, P.inlier, s_wave,
       [&](int f, float (&X)[3]) {
         const int a = P.assigned[f];
         X[0] = P.q_pos[3 * a], X[1] = P.q_pos[3 * a + 1], X[2] = P.q_pos[3 * a + 2];
@@ -117,10 +112,10 @@ __global__ __launch_bounds__(1024) void k_motion_check(MotionDev P) {
       [&](int f) { P.cur[f] = -1; });  // (a thread drops the cur[f] it wrote above)
   // `if (pMp && pMp->isInMap()) ++inLiers` over what the frame holds now (Tracking.cc:397-404); a temporary point is not in the map
   int mine = 0;
-  for (int f0 = 0; f0 < P.nf; f0 += 1024) {
+  for (int f0 = 0; f0 < P.F.nf; f0 += 1024) {
     const int f = f0 + t;
     bool in_map = false;
-    if (f < P.nf) {
+    if (f < P.F.nf) {
       const int a = P.cur[f];
       in_map = a >= 0 && (P.l_flags[a] & 3) == 3;
     }
@@ -135,16 +130,14 @@ __global__ __launch_bounds__(1024) void k_motion_check(MotionDev P) {
   P.hdr[MOTION_H_EDGES] = edges;
   P.hdr[MOTION_H_INLIERS] = n_in;
   P.hdr[MOTION_H_INMAP] = n_map;
-  for (int k = 0; k < 7; ++k) P.pose_out[k] = P.p_opt[k];
-  for (int k = 0; k < 9; ++k) P.tcw_out[k] = R[k];
-  for (int k = 0; k < 3; ++k) P.tcw_out[9 + k] = tc[k];
+  pose_write_back(P.p_opt, R, tc, P.pose_out, P.tcw_out);
   P.hdr[MOTION_H_VERDICT] = n_map >= P.min_inliers ? ORBFE_MOTION_ACCEPT : ORBFE_MOTION_REJECT_INLIERS;  // Tracking.cc:405
 }
 
 }  // namespace
 
 void launch_motion_prep(hipStream_t st, const MotionDev& P) {
-  hipLaunchKernelGGL(k_motion_prep, dim3((unsigned)((P.nf + 255) / 256)), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_motion_prep, dim3((unsigned)((P.F.nf + 255) / 256)), dim3(256), 0, st, P);
 }
 void launch_motion_between(hipStream_t st, const MotionDev& P) { hipLaunchKernelGGL(k_motion_between, dim3(1), dim3(1024), 0, st, P); }
 void launch_motion_check(hipStream_t st, const MotionDev& P) { hipLaunchKernelGGL(k_motion_check, dim3(1), dim3(1024), 0, st, P); }

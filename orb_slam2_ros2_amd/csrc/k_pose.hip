@@ -510,21 +510,31 @@ __global__ __launch_bounds__(NT) void k_pose_only_reg(int n, const double* __res
   }
 }
 
-void launch_pose_only(hipStream_t s, int n, const double* Xw, const double* meas, const double* info, const float* sigma2,
-                      const double* pose_in, BaParamsDev prm, double d_mono, double d_stereo, double* err, uint8_t* level,
-                      uint8_t* robust, uint8_t* inlier, double* pose_out, int32_t* n_good, const int32_t* n_dev) {
-  // n_dev (nullable, the tracking chain): the edge count in device memory, n its upper bound (register kernels only)
-  // (past POSE_RT * POSE_EPT edges: round 2's kernel, which re-reads the edges from memory every pass)
-  // 256 threads up to 1024 edges (one wave per SIMD: the 27 wave reductions of a build are issued once per SIMD, not twice), 512 up to 2048
-  if (n_dev && n > 256 * POSE_EPT && n <= POSE_RT * POSE_EPT)  // the count is on the device: the 256-thread kernel takes it if it fits (20 % faster there), else the next launch does
+static_assert(POSE_REG_EDGES == POSE_RT * POSE_EPT, "orbfe_internal.h states the register kernels' capacity");
+
+// The register kernels alone, for n <= POSE_REG_EDGES (the tracking calls refuse a larger frame before they get here).
+// n_dev (nullable, the tracking chain): the edge count in device memory, n its upper bound
+// 256 threads up to 1024 edges (one wave per SIMD: the 27 wave reductions of a build are issued once per SIMD, not twice), 512 up to 2048
+void launch_pose_only_reg(hipStream_t s, int n, const double* Xw, const double* meas, const double* info, const float* sigma2,
+                          const double* pose_in, BaParamsDev prm, double d_mono, double d_stereo, uint8_t* inlier, double* pose_out,
+                          int32_t* n_good, const int32_t* n_dev) {
+  if (n_dev && n > 256 * POSE_EPT)  // the count is on the device: the 256-thread kernel takes it if it fits (20 % faster there), else the next launch does
     hipLaunchKernelGGL(k_pose_only_reg<256>, dim3(1), dim3(256), 0, s, 256 * POSE_EPT, Xw, meas, info, sigma2, pose_in, prm, d_mono, d_stereo, inlier,
                        pose_out, n_good, n_dev);
   if (n <= 256 * POSE_EPT)
     hipLaunchKernelGGL(k_pose_only_reg<256>, dim3(1), dim3(256), 0, s, n, Xw, meas, info, sigma2, pose_in, prm, d_mono, d_stereo, inlier, pose_out,
                        n_good, n_dev);
-  else if (n <= POSE_RT * POSE_EPT)
+  else
     hipLaunchKernelGGL(k_pose_only_reg<POSE_RT>, dim3(1), dim3(POSE_RT), 0, s, n, Xw, meas, info, sigma2, pose_in, prm, d_mono, d_stereo, inlier, pose_out,
                        n_good, n_dev);
+}
+
+// any n: past POSE_REG_EDGES edges round 2's kernel, which re-reads the edges from memory every pass (err, level, robust are its scratch)
+void launch_pose_only(hipStream_t s, int n, const double* Xw, const double* meas, const double* info, const float* sigma2,
+                      const double* pose_in, BaParamsDev prm, double d_mono, double d_stereo, double* err, uint8_t* level,
+                      uint8_t* robust, uint8_t* inlier, double* pose_out, int32_t* n_good, const int32_t* n_dev) {
+  if (n <= POSE_REG_EDGES)
+    launch_pose_only_reg(s, n, Xw, meas, info, sigma2, pose_in, prm, d_mono, d_stereo, inlier, pose_out, n_good, n_dev);
   else
     hipLaunchKernelGGL(k_pose_only, dim3(1), dim3(POSE_THREADS), 0, s, n, Xw, meas, info, sigma2, pose_in, prm, d_mono, d_stereo, err,
                        level, robust, inlier, pose_out, n_good);

@@ -3,9 +3,10 @@
 // :612-629), on the device.  The optimisations themselves are k_pose.hip's launch_pose_only on the edge lists built here.
 //
 // k_reloc_seed    one workgroup: setCurrFrameAttrib's map points (Tracking.cc:503-512) as cur[f], the edge list of the first
-//                 optimisation in feature order (Optimizer.cc:58-117), Converter::ConvertTcw2SE3 of the PnP pose (:119).
+//                 optimisation in feature order (Optimizer.cc:58-117: pose_check_dev.h's pose_edges_1024), Converter::ConvertTcw2SE3 of
+//                 the PnP pose (:119).
 // k_reloc_check   one workgroup: the projection post-check with the pose the frame still has (:179-190), the nulling (:191-199),
-//                 Converter::ConvertSE32Tcw of the estimate (:201), edges - nBad, the verdict of Tracking.cc:567-584 / :622, and for
+//                 Converter::ConvertSE32Tcw of the estimate (:201) and its write-back, edges - nBad, the verdict of Tracking.cc:567-584 / :622, and for
 //                 a search that follows tlc.z (ORBMatcher.cc:274-276) and the next optimisation's initial estimate.
 // k_reloc_search  one wave per feature of the stored keyframe (ORBMatcher.cc:283-343, bFuse == false) over the slot's grid through
 //                 area_search_body.h; its filter: the octave window by the motion direction, then "holds no point", with one hit
@@ -28,49 +29,19 @@
 namespace orbfe {
 namespace {
 
-// (the two pose conversions and the post-check: pose_check_dev.h, shared with k_trackref.hip)
-
-// The pose-only edges of what the frame holds (cur), in feature order, by the 1024 threads of one workgroup: k_track_edges' list
-// (Optimizer.cc:58-117).  Returns the count to every thread.
+// The pose-only edges of what the frame holds (cur), in feature order: pose_check_dev.h's list.  Returns the count to every thread.
 __device__ __forceinline__ int build_edges(const RelocDev& P, int* s_wave, int* s_base) {
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (t == 0) *s_base = 0;
-  __syncthreads();
-  for (int f0 = 0; f0 < P.nf; f0 += 1024) {
-    const int f = f0 + t;
-    const int mp = f < P.nf ? P.cur[f] : -1;
-    const bool edge = mp >= 0;
-    const unsigned long long me = __ballot(edge);
-    if (lane == 0) s_wave[wv] = __popcll(me);
-    __syncthreads();
-    int before = *s_base, chunk = 0;
-    for (int w = 0; w < 16; ++w) {
-      if (w < wv) before += s_wave[w];
-      chunk += s_wave[w];
-    }
-    const int e = before + __popcll(me & ((1ull << lane) - 1ull));
-    if (f < P.nf) P.edge_of[f] = edge ? e : -1;
-    if (edge) {
-      const orbfe_keypoint k = P.f_kps[f];
-      P.Xw[3 * e] = (double)P.pos[3 * mp], P.Xw[3 * e + 1] = (double)P.pos[3 * mp + 1], P.Xw[3 * e + 2] = (double)P.pos[3 * mp + 2];
-      const double ru = P.right_u[f];
-      P.meas[3 * e] = (double)k.x, P.meas[3 * e + 1] = (double)k.y, P.meas[3 * e + 2] = ru < 0 ? -1.0 : ru;
-      const int oc = min(max(k.octave, 0), P.n_levels - 1);
-      P.info[e] = (double)P.inv_sigma2[oc];
-      P.sig[e] = P.sigma2[oc];
-    }
-    __syncthreads();
-    if (t == 0) *s_base += chunk;
-    __syncthreads();
-  }
-  return *s_base;
+  return pose_edges_1024(P.F, P.E, s_wave, s_base, [&](int f) -> const float* {
+    const int mp = P.cur[f];
+    return mp >= 0 ? P.pos + 3 * mp : nullptr;
+  });
 }
 
 __global__ __launch_bounds__(1024) void k_reloc_seed(RelocDev P) {
   __shared__ int s_wave[16], s_base;
   const int t = threadIdx.x;
-  const int n_kp = min(*P.f_n_kp, P.nf);
-  for (int f = t; f < P.nf; f += 1024) {
+  const int n_kp = min(*P.F.n_kp, P.F.nf);
+  for (int f = t; f < P.F.nf; f += 1024) {
     const int h = f < n_kp ? P.held[f] : -1;
     P.cur[f] = (h >= 0 && P.good[h]) ? h : -1;  // `if (pMp && !pMp->isBad()) setMapPoint` (Tracking.cc:510-511)
   }
@@ -78,7 +49,7 @@ __global__ __launch_bounds__(1024) void k_reloc_seed(RelocDev P) {
   if (t == 0) {
     P.hdr[RELOC_H_EDGES] = edges;
     P.cnt[0] = edges > 0 ? edges : -1;  // no edge: the estimate stays, nothing is an inlier
-    tcw_to_se3_dev(P.R0, P.t0, P.p_init);
+    tcw_to_se3_dev(P.F.R0, P.F.t0, P.p_init);
   }
 }
 
@@ -89,16 +60,15 @@ __global__ __launch_bounds__(1024) void k_reloc_check(RelocDev P, int s) {
   __syncthreads();  // (every thread has read the word before thread 0 may write it)
   if (verdict != 0) return;
   const double* est = P.p_opt + 7 * s;
-  float R[9], tc[3], Rb[9], tb[3];
+  float R[9], tc[3], Rf[9], tf[3];
   se3_to_tcw_dev(est, R, tc);
-  // the check projects with the pose the frame still has: setPose comes last (Optimizer.cc:201) -- the PnP pose, then the first float pose
+  // the pose the frame still has: the PnP pose, then the first float pose
 #pragma unroll
-  for (int k = 0; k < 9; ++k) Rb[k] = s == 0 ? P.R0[k] : P.tcw_out[k];
+  for (int k = 0; k < 9; ++k) Rf[k] = s == 0 ? P.F.R0[k] : P.tcw_out[k];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) tb[k] = s == 0 ? P.t0[k] : P.tcw_out[9 + k];
-  const PostCheckCam K = {P.fx, P.fy, P.cx, P.cy, P.max_u, P.max_v};
+  for (int k = 0; k < 3; ++k) tf[k] = s == 0 ? P.F.t0[k] : P.tcw_out[9 + k];
   const int n_in = post_check_1024(
-      P.nf, P.edge_of, P.e_inl, Rb, tb, K, P.inlier + (size_t)s * P.nf, s_wave,
+      P.F, Rf, tf, P.E, P.inlier + (size_t)s * P.F.nf, s_wave,
       [&](int f, float (&X)[3]) {
         const int mp = P.cur[f];
         X[0] = P.pos[3 * mp], X[1] = P.pos[3 * mp + 1], X[2] = P.pos[3 * mp + 2];
@@ -106,9 +76,7 @@ __global__ __launch_bounds__(1024) void k_reloc_check(RelocDev P, int s) {
       [&](int f) { P.cur[f] = -1; });
   if (t != 0) return;
   P.hdr[RELOC_H_INLIERS + s] = n_in;
-  for (int k = 0; k < 7; ++k) P.pose_out[7 * s + k] = est[k];
-  for (int k = 0; k < 9; ++k) P.tcw_out[12 * s + k] = R[k];
-  for (int k = 0; k < 3; ++k) P.tcw_out[12 * s + 9 + k] = tc[k];
+  pose_write_back(est, R, tc, P.pose_out + 7 * s, P.tcw_out + 12 * s);
   if (s == 0 && n_in < P.min_inliers) {
     P.hdr[RELOC_H_VERDICT] = ORBFE_RELOC_REJECT_1;
     return;
@@ -129,18 +97,18 @@ __global__ __launch_bounds__(256) void k_reloc_search(RelocDev P, int s) {
   const int q = blockIdx.x * 4 + wv;
   if (q >= P.n || !P.good[q]) return;  // `if (!pMp2 || pMp2->isBad()) continue` (:286-287)
   const orbfe_keypoint kp = P.k_kps[q];
-  const int o = min(max(kp.octave, 0), P.n_levels - 1);
+  const int o = min(max(kp.octave, 0), P.F.n_levels - 1);
   const float z = __int_as_float(P.hdr[RELOC_H_TLCZ + s]);
   int lo, hi;
   motion_window(o, z, P.baseline, lo, hi);
-  const float rad = P.th[s] * P.sigma2[o];  // findFeaturesInArea: radius * getScaledFactor2(octave) (Frame.cc:289)
+  const float rad = P.th[s] * P.F.sigma2[o];  // findFeaturesInArea: radius * getScaledFactor2(octave) (Frame.cc:289)
   const uint4 a0 = *(const uint4*)(P.k_desc + (size_t)q * 32);
   const uint4 a1 = *(const uint4*)(P.k_desc + (size_t)q * 32 + 16);
   Best2 b = {ORB_INT_MAX, ORB_INT_MAX, 0};
   const AreaTarget T = {P.f_desc, P.cell_off, P.cell_feat, P.rows, P.cols, P.clip_w, P.clip_h};
   const uint4* __restrict__ kpl = P.f_kpl;
   const int32_t* __restrict__ cur = P.cur;
-  int32_t* hits = P.hits + (size_t)s * P.nf;
+  int32_t* hits = P.hits + (size_t)s * P.F.nf;
   const int total = area_fold(T, kp.x, kp.y, rad, a0, a1, stage_all[wv], lane, b, [&](int id) {
     const int oc = (int)(kpl[id].y & 0xFFu);
     if (!(oc <= hi && oc >= lo)) return false;
@@ -153,7 +121,7 @@ __global__ __launch_bounds__(256) void k_reloc_search(RelocDev P, int s) {
   if (lane != 0 || total <= 0) return;
   const float fr = (float)b.min_d / (float)b.second;  // getBestMatch's ratio (:988)
   if (fr < P.ratio && b.min_d < P.min_threshold) {
-    atomicMax(&P.claim[(size_t)s * P.nf + b.min_idx], q);
+    atomicMax(&P.claim[(size_t)s * P.F.nf + b.min_idx], q);
     atomicAdd(&P.hdr[RELOC_H_ADDED + s], 1);
     P.qa[(size_t)s * P.n + q] = 1;
   }
@@ -168,11 +136,11 @@ __global__ __launch_bounds__(1024) void k_reloc_after(RelocDev P, int s) {
     if (s == 0 && t == 0) P.cnt[1] = -1;  // no second optimisation
     return;
   }
-  for (int f = t; f < P.nf; f += 1024) {
-    const int cl = P.claim[(size_t)s * P.nf + f];
+  for (int f = t; f < P.F.nf; f += 1024) {
+    const int cl = P.claim[(size_t)s * P.F.nf + f];
     int c = P.cur[f];
     if (cl >= 0) c = cl, P.cur[f] = cl;
-    P.assigned[(size_t)s * P.nf + f] = c;
+    P.assigned[(size_t)s * P.F.nf + f] = c;
   }
   const bool too_few = P.hdr[RELOC_H_ADDED + s] + P.hdr[RELOC_H_INLIERS + s] < P.enough;  // Tracking.cc:619, :625
   if (too_few || s == 1) {

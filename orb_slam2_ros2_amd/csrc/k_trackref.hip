@@ -6,9 +6,9 @@
 //                    so the nulling branch cannot fire) as a maximum of the match index per frame feature -- the last match that names a
 //                    feature keeps it --, the :365 decision, the edge list of Optimizer::OptimizePoseOnly in feature order
 //                    (Optimizer.cc:58-117) over the points the frame came with and the assigned ones, Converter::ConvertTcw2SE3 of the
-//                    frame's pose (:119).
+//                    frame's pose (:119).  The edge list is pose_check_dev.h's pose_edges_1024; this kernel says what a feature holds.
 // k_trackref_check   one workgroup: pose_check_dev.h's post-check with the pose the frame still has (:179-199),
-//                    Converter::ConvertSE32Tcw of the estimate (:201), edges - nBad, the :370 decision.
+//                    Converter::ConvertSE32Tcw of the estimate (:201) and its write-back, edges - nBad, the :370 decision.
 // The check reads the verdict word first and leaves when the seed has rejected; the pose kernel between them sees no edge list through its
 // device count.  No kernel waits on another; every loop is bounded by the feature count or the match count (at most one per keyframe
 // feature).  Float arithmetic: map_point_dev.h's rows and `A x + t`, no contraction; the conversions in fp64.
@@ -22,16 +22,13 @@
 namespace orbfe {
 namespace {
 
-#define TRACKREF_MAX_NF 2048  // the pose kernel's bound on a frame's features: the claims fit the LDS
-
 __global__ __launch_bounds__(1024) void k_trackref_seed(TrackRefDev P) {
-  __shared__ int s_claim[TRACKREF_MAX_NF];
+  __shared__ int s_claim[POSE_REG_EDGES];  // (the host refuses a frame of more features: the claims fit the LDS)
   __shared__ int s_wave[16], s_base;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int n_kp = min(*P.f_n_kp, P.nf);
+  const int t = threadIdx.x;
+  const int n_kp = min(*P.F.n_kp, P.F.nf);
   const int nm = min(max(*P.n_list, 0), P.n);
-  for (int f = t; f < P.nf; f += 1024) s_claim[f] = -1;
-  if (t == 0) s_base = 0;
+  for (int f = t; f < P.F.nf; f += 1024) s_claim[f] = -1;
   __syncthreads();
   for (int m = t; m < nm; m += 1024) {
     const BowMatch x = P.list[m];
@@ -41,71 +38,41 @@ __global__ __launch_bounds__(1024) void k_trackref_seed(TrackRefDev P) {
     if (x.q >= 0 && x.q < n_kp) atomicMax(&s_claim[x.q], m);
   }
   __syncthreads();
-  const bool reject = nm < P.min_matches;  // Tracking.cc:365, after the frame was written (ORBMatcher.cc:251)
-  for (int f0 = 0; f0 < P.nf; f0 += 1024) {
-    const int f = f0 + t;
+  for (int f = t; f < P.F.nf; f += 1024) {  // what the frame holds now: the claim's point, else the one it came with
     int a = -1;
-    if (f < P.nf) {
-      const int cl = s_claim[f];
-      if (cl >= 0) a = P.list[cl].t;
-      else if (f < n_kp && P.f_good[f]) a = ORBFE_TRACKREF_OWN;
-      P.assigned[f] = a;
-      P.cur[f] = a;
-    }
-    if (reject) continue;  // (uniform over the workgroup)
-    // the edges: every feature that holds a point, in feature order -- a ballot per wave, the waves' counts summed in wave order
-    const bool edge = a != -1;
-    const unsigned long long me = __ballot(edge);
-    if (lane == 0) s_wave[wv] = __popcll(me);
-    __syncthreads();
-    int before = s_base, chunk = 0;
-    for (int w = 0; w < 16; ++w) {
-      if (w < wv) before += s_wave[w];
-      chunk += s_wave[w];
-    }
-    const int e = before + __popcll(me & ((1ull << lane) - 1ull));
-    if (f < P.nf) P.edge_of[f] = edge ? e : -1;
-    if (edge) {
-      const orbfe_keypoint k = P.f_kps[f];
-      const float* X = a >= 0 ? P.pos + 3 * (size_t)a : P.f_pos + 3 * (size_t)f;
-      P.Xw[3 * e] = (double)X[0], P.Xw[3 * e + 1] = (double)X[1], P.Xw[3 * e + 2] = (double)X[2];
-      const double ru = P.right_u[f];
-      P.meas[3 * e] = (double)k.x, P.meas[3 * e + 1] = (double)k.y, P.meas[3 * e + 2] = ru < 0 ? -1.0 : ru;
-      const int oc = min(max(k.octave, 0), P.n_levels - 1);
-      P.info[e] = (double)P.inv_sigma2[oc];
-      P.sig[e] = P.sigma2[oc];
-    }
-    __syncthreads();
-    if (t == 0) s_base += chunk;
-    __syncthreads();
+    const int cl = s_claim[f];
+    if (cl >= 0) a = P.list[cl].t;
+    else if (f < n_kp && P.f_good[f]) a = ORBFE_TRACKREF_OWN;
+    P.assigned[f] = a;
+    P.cur[f] = a;
   }
-  if (t != 0) return;
-  P.hdr[TRACKREF_H_MATCHES] = nm;
-  if (reject) {
+  if (nm < P.min_matches) {  // Tracking.cc:365, after the frame was written (ORBMatcher.cc:251)
+    if (t != 0) return;
+    P.hdr[TRACKREF_H_MATCHES] = nm;
     P.hdr[TRACKREF_H_VERDICT] = ORBFE_TRACKREF_REJECT_MATCHES;
     P.cnt[0] = -1;  // no optimisation
     return;
   }
-  const int edges = s_base;
+  // the edges: every feature that holds a point (a thread reads the cur[f] it wrote)
+  const int edges = pose_edges_1024(P.F, P.E, s_wave, &s_base, [&](int f) -> const float* {
+    const int a = P.cur[f];
+    return a == -1 ? nullptr : a >= 0 ? P.pos + 3 * (size_t)a : P.f_pos + 3 * (size_t)f;
+  });
+  if (t != 0) return;
+  P.hdr[TRACKREF_H_MATCHES] = nm;
   P.hdr[TRACKREF_H_EDGES] = edges;
   P.cnt[0] = edges > 0 ? edges : -1;  // no edge: the estimate stays, nothing is an inlier
-  tcw_to_se3_dev(P.R0, P.t0, P.p_init);
+  tcw_to_se3_dev(P.F.R0, P.F.t0, P.p_init);
 }
 
 __global__ __launch_bounds__(1024) void k_trackref_check(TrackRefDev P) {
   __shared__ int s_wave[16];
   const int t = threadIdx.x;
   if (P.hdr[TRACKREF_H_VERDICT] != 0) return;  // (written by the seed only: every thread reads the same word)
-  float R[9], tc[3], Rb[9], tb[3];
+  float R[9], tc[3];
   se3_to_tcw_dev(P.p_opt, R, tc);
-  // the check projects with the pose the frame still has: setPose comes last (Optimizer.cc:201)
-#pragma unroll
-  for (int k = 0; k < 9; ++k) Rb[k] = P.R0[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) tb[k] = P.t0[k];
-  const PostCheckCam K = {P.fx, P.fy, P.cx, P.cy, P.max_u, P.max_v};
   const int n_in = post_check_1024(
-      P.nf, P.edge_of, P.e_inl, Rb, tb, K, P.inlier, s_wave,
+      P.F, P.F.R0, P.F.t0, P.E, P.inlier, s_wave,
       [&](int f, float (&X)[3]) {
         const int a = P.assigned[f];
         const float* src = a >= 0 ? P.pos + 3 * (size_t)a : P.f_pos + 3 * (size_t)f;
@@ -114,9 +81,7 @@ __global__ __launch_bounds__(1024) void k_trackref_check(TrackRefDev P) {
       [&](int f) { P.cur[f] = -1; });
   if (t != 0) return;
   P.hdr[TRACKREF_H_INLIERS] = n_in;
-  for (int k = 0; k < 7; ++k) P.pose_out[k] = P.p_opt[k];
-  for (int k = 0; k < 9; ++k) P.tcw_out[k] = R[k];
-  for (int k = 0; k < 3; ++k) P.tcw_out[9 + k] = tc[k];
+  pose_write_back(P.p_opt, R, tc, P.pose_out, P.tcw_out);
   P.hdr[TRACKREF_H_VERDICT] = n_in >= P.min_inliers ? ORBFE_TRACKREF_ACCEPT : ORBFE_TRACKREF_REJECT_INLIERS;  // Tracking.cc:370
 }
 

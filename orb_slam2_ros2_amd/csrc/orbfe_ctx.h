@@ -146,6 +146,9 @@ void launch_lm_final(hipStream_t s, const LmLaunch& L);
 void launch_pose_only(hipStream_t s, int n, const double* Xw, const double* meas, const double* info, const float* sigma2,
                       const double* pose_in, BaParamsDev prm, double d_mono, double d_stereo, double* err, uint8_t* level,
                       uint8_t* robust, uint8_t* inlier, double* pose_out, int32_t* n_good, const int32_t* n_dev = nullptr);
+void launch_pose_only_reg(hipStream_t s, int n, const double* Xw, const double* meas, const double* info, const float* sigma2,
+                          const double* pose_in, BaParamsDev prm, double d_mono, double d_stereo, uint8_t* inlier, double* pose_out,
+                          int32_t* n_good, const int32_t* n_dev);  // n <= POSE_REG_EDGES: no scratch of the memory kernel
 void launch_debug_se3_oplus(hipStream_t s, int n, const double* poses, const double* upd, double* out);
 // k_sim3opt.hip
 void launch_sim3_optimize(hipStream_t s, int n, const float* pc, const float* pm, const float* uvc, const float* uvm, const double* wc,
@@ -174,10 +177,9 @@ void launch_track_queries(hipStream_t s, int n, const uint8_t* d_flags, const ui
                           const float* d_sigma2, int n_levels, float* d_radius, int8_t* d_min_level, int8_t* d_max_level);
 void launch_track_claim(hipStream_t s, int n, const int32_t* d_n_cand, const int32_t* d_best_idx, const int32_t* d_best_dist, const int32_t* d_second,
                         int min_threshold, float ratio, int32_t* d_claim, int last_wins = 0, int32_t* d_n_accept = nullptr, uint8_t* d_accepted = nullptr);
-void launch_track_edges(hipStream_t s, const orbfe_keypoint* d_kps, const int32_t* d_n_kp, int n_features, const int32_t* d_held, const int32_t* d_claim,
-                        const uint8_t* d_mp_flags, const float* d_mp_pos, const double* d_right_u, const float* d_sigma2, const float* d_inv_sigma2,
-                        int min_matches, int32_t* d_assigned, int32_t* d_edge_of, double* d_Xw, double* d_meas, double* d_info, float* d_sig,
-                        int32_t* d_counts, int32_t unclaimed = 0x7F7F7F7F, const int32_t* d_n_accept = nullptr, int base_matches = 0);
+void launch_track_edges(hipStream_t s, const PoseFrameDev& F, const PoseEdgesDev& E, const int32_t* d_held, const int32_t* d_claim,
+                        const uint8_t* d_mp_flags, const float* d_mp_pos, int min_matches, int32_t* d_assigned, int32_t* d_counts,
+                        int32_t unclaimed = 0x7F7F7F7F, const int32_t* d_n_accept = nullptr, int base_matches = 0);
 }  // namespace orbfe
 
 using namespace orbfe;

@@ -3,6 +3,7 @@
 // (orbfe_track_local_map / orbfe_track_motion_model).  (Split from orbfe_api.hip in r5, no change of behaviour.)
 #include "orbfe_ctx.h"
 #include "orbfe_mpstore.h"
+#include "pose_call.h"
 
 // the grid of `slot` for the geometry ag on stream st: the one kept from the last search if the slot's keypoints are still the same
 orbfe_status slot_grid(orbfe_ctx* c, hipStream_t st, int slot, const AreaGrid& ag, const int32_t** d_off, const int32_t** d_feat) {
@@ -81,15 +82,11 @@ orbfe_status orbfe_match_bruteforce(orbfe_ctx* c, const uint8_t* q, int32_t nq, 
 // The grid-guided search against a feature set on the device: the features of an image slot (orbfe_search_in_area) or a set the caller
 // uploaded (orbfe_search_in_area_features: a KeyFrame's keypoints and descriptors -- keyframes are not resident in a slot).
 // (AreaGrid, area_grid and the search's scratch layout: search_area_layout.h)
-static bool area_grid(const orbfe_ctx* c, const float* bounds, AreaGrid* g) { return area_grid(c->cfg.width, c->cfg.height, bounds, g); }
-
 // the grid and the scratch layout of a search behind `start` bytes of the caller's own: the callers size their reservation from l->end()
 static orbfe_status search_area_plan(orbfe_ctx* c, const char* who, const float* bounds, size_t start, size_t n_target, int32_t nq,
                                      SearchAreaLayout* l) {
   AreaGrid ag;
-  if (!area_grid(c, bounds, &ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", who);
-  const size_t ncells = (size_t)ag.rows * ag.cols;
-  if (area_grid_lds(ncells, n_target).refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", who, ncells);
+  TRY(check_area_grid(c, who, bounds, n_target, &ag));
   *l = search_area_layout(start, ag, n_target, (size_t)nq);
   return ORBFE_OK;
 }
@@ -249,17 +246,16 @@ orbfe_status orbfe_project_map_points(orbfe_ctx* c, int32_t n, const float* pos,
   return ORBFE_OK;
 }
 // what both tracking chains hand back from their downloaded block: the counts, the pose, the assignment and the inlier flag of every feature
-static void track_results(StagedIo& io, size_t o_cnt, size_t o_ng, size_t o_po, size_t o_asg, size_t o_eo, size_t o_in, size_t NF,
-                          const orbfe_track_output* out) {
-  const int32_t *cnt = (const int32_t*)io.got(o_cnt), *eo = (const int32_t*)io.got(o_eo);
-  const uint8_t* ein = io.got(o_in);
+static void track_results(StagedIo& io, size_t o_cnt, const PoseWorkspace& W, size_t o_asg, const orbfe_track_output* out) {
+  const int32_t *cnt = (const int32_t*)io.got(o_cnt), *eo = (const int32_t*)io.got(W.o_eo);
+  const uint8_t* ein = io.got(W.o_ei);
   *out->n_matches = cnt[0];
   *out->n_edges = cnt[1];
-  io.get(out->n_good, o_ng, 4);
-  io.get(out->pose_out, o_po, 56);
-  io.get(out->assigned, o_asg, NF * 4);
-  for (size_t f = 0; f < NF; ++f) out->inlier[f] = (cnt[1] >= 0 && eo[f] >= 0) ? ein[eo[f]] : 0;
-  io.get(out->edge_of, o_eo, NF * 4);
+  io.get(out->n_good, W.o_ng, 4);
+  io.get(out->pose_out, W.o_p1, 56);
+  io.get(out->assigned, o_asg, W.NF * 4);
+  for (size_t f = 0; f < W.NF; ++f) out->inlier[f] = (cnt[1] >= 0 && eo[f] >= 0) ? ein[eo[f]] : 0;
+  io.get(out->edge_of, W.o_eo, W.NF * 4);
 }
 
 // ---- orbfe_track_local_map and orbfe_track_local_map_stored: their own first step (the point arrays onto the device), one shared rest ----
@@ -268,18 +264,16 @@ static void track_results(StagedIo& io, size_t o_cnt, size_t o_ng, size_t o_po, 
 // the gather sets for an id without a row, is the LAST take of the download and the FIRST of the upload: it goes up as 0 with the
 // inputs and comes down with the results, so no fill of its own and no second synchronisation.
 struct TrackLayout {
-  size_t o_pos, o_vd, o_mx, o_mn, o_desc, o_ids = 0, o_bad = 0, o_fl, o_held, o_ru, o_s2, o_is2, o_p0, o_claim, o_uv, o_dist, o_cos, o_lvl, o_vis,
-      o_rad, o_lo, o_hi, o_bi, o_bd, o_sd, o_nc, o_xw, o_ms, o_info, o_sig, o_err, o_l, o_r, o_cnt, o_ng, o_po, o_asg, o_eo, o_in, end;
+  size_t o_pos, o_vd, o_mx, o_mn, o_desc, o_ids = 0, o_bad = 0, o_fl, o_held, o_claim, o_uv, o_dist, o_cos, o_lvl, o_vis, o_rad, o_lo, o_hi, o_bi,
+      o_bd, o_sd, o_nc, o_cnt, o_asg, end;
+  PoseWorkspace W;  // the seed goes up with the frame, the results come down
+  FrameUpload U;
   ScratchRegion up, claim, down;
-  TrackLayout(size_t N, size_t NF, size_t nl, bool stored) {
+  TrackLayout(size_t N, size_t NF, size_t nl, bool stored) : W(NF) {
     ScratchLayout L;
     auto points = [&] { o_pos = L.take<float>(N * 3), o_vd = L.take<float>(N * 3), o_mx = L.take<float>(N), o_mn = L.take<float>(N), o_desc = L.take(N * 32); };
-    auto frame = [&] {
-      o_fl = L.take(N), o_held = L.take<int32_t>(NF), o_ru = L.take<double>(NF), o_s2 = L.take<float>(nl), o_is2 = L.take<float>(nl), o_p0 = L.take(56);
-    };
-    auto results = [&] {
-      o_cnt = L.take(16), o_ng = L.take(8), o_po = L.take(56), o_asg = L.take<int32_t>(NF), o_eo = L.take<int32_t>(NF), o_in = L.take(NF);
-    };
+    auto frame = [&] { o_fl = L.take(N), o_held = L.take<int32_t>(NF), U.take(L, NF, nl), W.take_seed(L); };
+    auto results = [&] { o_cnt = L.take(16), W.take_results(L), o_asg = L.take<int32_t>(NF); };
     if (stored) {
       L.open(down), results(), o_bad = L.open(up).take(8), L.close(down);
       o_ids = L.take<uint64_t>(N), frame(), L.close(up);
@@ -289,9 +283,8 @@ struct TrackLayout {
     o_claim = L.open(claim).take<int32_t>(NF), L.close(claim);
     if (stored) points();
     o_uv = L.take<float>(N * 2), o_dist = L.take<float>(N), o_cos = L.take<float>(N), o_lvl = L.take(N), o_vis = L.take(N), o_rad = L.take<float>(N),
-    o_lo = L.take(N), o_hi = L.take(N), o_bi = L.take<int32_t>(N), o_bd = L.take<int32_t>(N), o_sd = L.take<int32_t>(N), o_nc = L.take<int32_t>(N),
-    o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF), o_sig = L.take<float>(NF),
-    o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF);
+    o_lo = L.take(N), o_hi = L.take(N), o_bi = L.take<int32_t>(N), o_bd = L.take<int32_t>(N), o_sd = L.take<int32_t>(N), o_nc = L.take<int32_t>(N);
+    W.take_list(L);
     if (!stored) L.open(down), results(), L.close(down);
     end = L.end();
   }
@@ -307,14 +300,10 @@ static orbfe_status track_begin(orbfe_ctx* c, const char* who, int32_t slot, con
   if (n < 0 || !in->pose_se3 || !in->level_sigma2 || !in->level_inv_sigma2 || !out->assigned || !out->n_matches || !out->n_edges || !out->n_good ||
       !out->pose_out || !out->inlier || (n && (!have_points || !in->flags)))
     return fail(c, ORBFE_EBADARG, "%s: NULL array", who);
-  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "%s: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", who, NF);
-  if (in->held)
-    for (size_t f = 0; f < NF; ++f)
-      if (in->held[f] < -1 || in->held[f] >= n) return fail(c, ORBFE_EBADARG, "%s: held[%zu] = %d out of range", who, f, in->held[f]);
+  TRY(pose_check_features(c, who, NF));
+  if (in->held) TRY(check_held(c, who, in->held, NF, n));
   const float bounds[4] = {pose->min_u, pose->max_u, pose->min_v, pose->max_v};
-  if (!area_grid(c, bounds, ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", who);
-  const size_t ncells = (size_t)ag->rows * ag->cols;
-  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", who, ncells);
+  TRY(check_area_grid(c, who, bounds, NF, ag));
   TRY(slots_idle(c, slot, 1, who));
   HIP_TRY(c, hipSetDevice(c->device));
   return join_stereo(c);
@@ -325,12 +314,8 @@ static void track_put_frame(StagedIo& io, const TrackLayout& T, size_t N, size_t
   io.put(T.o_fl, in->flags, N);
   if (in->held) io.put(T.o_held, in->held, NF * 4);
   else std::memset(io.host<uint8_t>(T.o_held), 0xFF, NF * 4);
-  if (in->right_u) io.put(T.o_ru, in->right_u, NF * 8);
-  else
-    for (size_t f = 0; f < NF; ++f) io.host<double>(T.o_ru)[f] = -1.0;
-  io.put(T.o_s2, in->level_sigma2, nl * 4);
-  io.put(T.o_is2, in->level_inv_sigma2, nl * 4);
-  io.put(T.o_p0, in->pose_se3, 56);
+  put_frame(io, T.U, NF, nl, in->right_u, in->level_sigma2, in->level_inv_sigma2);
+  io.put(T.W.o_p0, in->pose_se3, 56);
 }
 
 // The rest, with the point arrays, the flags and the frame's inputs on the device: the claim fill, the six launches from
@@ -344,13 +329,13 @@ static orbfe_status track_chain(orbfe_ctx* c, StagedIo& io, const TrackLayout& T
   HIP_TRY(c, hipMemsetAsync(b + T.claim.begin, 0x7F, T.claim.bytes(), st));
   const float cam4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
   const float bounds[4] = {pose->min_u, pose->max_u, pose->min_v, pose->max_v};
-  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
+  const PoseFrameDev F = pose_frame(c, slot, b, T.U);
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, st);
     launch_project_map_points(st, n, (const float*)(b + T.o_pos), (const float*)(b + T.o_vd), (const float*)(b + T.o_mx), (const float*)(b + T.o_mn),
                               pose->Rcw, pose->tcw, cam4, bounds, std::log(c->cfg.scale_factor), 7, (float*)(b + T.o_uv), (float*)(b + T.o_dist),
                               (float*)(b + T.o_cos), (int8_t*)(b + T.o_lvl), b + T.o_vis);
-    launch_track_queries(st, n, b + T.o_fl, b + T.o_vis, (const float*)(b + T.o_cos), (const int8_t*)(b + T.o_lvl), in->th, (const float*)(b + T.o_s2),
+    launch_track_queries(st, n, b + T.o_fl, b + T.o_vis, (const float*)(b + T.o_cos), (const int8_t*)(b + T.o_lvl), in->th, F.sigma2,
                          nl, (float*)(b + T.o_rad), (int8_t*)(b + T.o_lo), (int8_t*)(b + T.o_hi));
     const int32_t *g_off = nullptr, *g_feat = nullptr;
     TRY(slot_grid(c, st, slot, ag, &g_off, &g_feat));
@@ -360,17 +345,10 @@ static orbfe_status track_chain(orbfe_ctx* c, StagedIo& io, const TrackLayout& T
                        (int32_t*)(b + T.o_sd), (int32_t*)(b + T.o_nc), nullptr);
     launch_track_claim(st, n, (const int32_t*)(b + T.o_nc), (const int32_t*)(b + T.o_bi), (const int32_t*)(b + T.o_bd), (const int32_t*)(b + T.o_sd),
                        in->min_threshold, in->ratio, (int32_t*)(b + T.o_claim));
-    launch_track_edges(st, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, (const int32_t*)(b + T.o_held), (const int32_t*)(b + T.o_claim),
-                       b + T.o_fl, (const float*)(b + T.o_pos), (const double*)(b + T.o_ru), (const float*)(b + T.o_s2), (const float*)(b + T.o_is2),
-                       in->min_matches, (int32_t*)(b + T.o_asg), (int32_t*)(b + T.o_eo), (double*)(b + T.o_xw), (double*)(b + T.o_ms),
-                       (double*)(b + T.o_info), (float*)(b + T.o_sig), (int32_t*)(b + T.o_cnt));
+    launch_track_edges(st, F, pose_edges(T.W, b), (const int32_t*)(b + T.o_held), (const int32_t*)(b + T.o_claim), b + T.o_fl,
+                       (const float*)(b + T.o_pos), in->min_matches, (int32_t*)(b + T.o_asg), (int32_t*)(b + T.o_cnt));
   }
-  {
-    StageTimer tm(c, ORBFE_STAGE_BA, st);
-    launch_pose_only(st, (int)NF, (const double*)(b + T.o_xw), (const double*)(b + T.o_ms), (const double*)(b + T.o_info), (const float*)(b + T.o_sig),
-                     (const double*)(b + T.o_p0), prm, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), (double*)(b + T.o_err),
-                     b + T.o_l, b + T.o_r, b + T.o_in, (double*)(b + T.o_po), (int32_t*)(b + T.o_ng), (const int32_t*)(b + T.o_cnt) + 1);
-  }
+  pose_optimise(c, st, T.W, b, cam, 0, (const int32_t*)(b + T.o_cnt) + 1);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, io.fetch(T.down));
   drain_timers(c);
@@ -398,7 +376,7 @@ orbfe_status orbfe_track_local_map(orbfe_ctx* c, int32_t slot, const orbfe_frame
   track_put_frame(io, T, N, NF, nl, in);
   HIP_TRY(c, io.upload(T.up));
   TRY(track_chain(c, io, T, slot, ag, pose, cam, in));
-  track_results(io, T.o_cnt, T.o_ng, T.o_po, T.o_asg, T.o_eo, T.o_in, NF, out);
+  track_results(io, T.o_cnt, T.W, T.o_asg, out);
   return ORBFE_OK;
 }
 
@@ -441,7 +419,7 @@ orbfe_status orbfe_track_local_map_stored(orbfe_ctx* c, int32_t slot, orbfe_mpst
         return fail(c, ORBFE_EBADARG, "%s: map point %llu (ids[%d]) is not in the store", who, (unsigned long long)sin->ids[i], i);
     return fail(c, ORBFE_EDEVICE, "%s: the device holds no row for an id the store's index lists", who);
   }
-  track_results(io, T.o_cnt, T.o_ng, T.o_po, T.o_asg, T.o_eo, T.o_in, NF, out);
+  track_results(io, T.o_cnt, T.W, T.o_asg, out);
   return ORBFE_OK;
 }
 
@@ -460,29 +438,26 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
     return fail(c, ORBFE_EBADARG, "track_motion_model: NULL array");
   for (int i = 0; i < n; ++i)
     if (in->q_octave[i] < 0 || in->q_octave[i] >= nl) return fail(c, ORBFE_EBADARG, "track_motion_model: q_octave[%d] = %d", i, (int)in->q_octave[i]);
-  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "track_motion_model: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", NF);
-  if (in->held)
-    for (size_t f = 0; f < NF; ++f)
-      if (in->held[f] < -1 || in->held[f] >= n) return fail(c, ORBFE_EBADARG, "track_motion_model: held[%zu] = %d out of range", f, in->held[f]);
+  const char* fn = "track_motion_model";
+  TRY(pose_check_features(c, fn, NF));
+  if (in->held) TRY(check_held(c, fn, in->held, NF, n));
   AreaGrid ag;
-  if (!area_grid(c, bounds4, &ag)) return fail(c, ORBFE_EBADARG, "track_motion_model: bad frame bounds");
-  const size_t ncells = (size_t)ag.rows * ag.cols;
-  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "track_motion_model: %zu grid cells exceed the LDS counters", ncells);
-  TRY(slots_idle(c, slot, 1, "track_motion_model"));
+  TRY(check_area_grid(c, fn, bounds4, NF, &ag));
+  TRY(slots_idle(c, slot, 1, fn));
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(join_stereo(c));
   const size_t N = (size_t)n;
   // [ upload once | upload per pass | claim (-1 fill) | hits and counter (0 fill) | device-only | download ]
   ScratchLayout L;
   ScratchRegion up, up_pass, claim, zero, down;
+  PoseWorkspace W(NF);
+  FrameUpload U;
   const size_t o_qxy = L.open(up).take<float>(N * 2), o_lo = L.take(N), o_hi = L.take(N), o_desc = L.take(N * 32), o_pos = L.take<float>(N * 3),
-               o_fl = L.take(N), o_ru = L.take<double>(NF), o_s2 = L.take<float>((size_t)nl), o_is2 = L.take<float>((size_t)nl), o_p0 = L.take(56),
-               o_rad = L.open(up_pass).take<float>(N), o_held = L.take<int32_t>(NF), o_ex = L.take(NF),
+               o_fl = L.take(N), o_rad = W.take_seed(U.take(L, NF, (size_t)nl)).open(up_pass).take<float>(N), o_held = L.take<int32_t>(NF),
+               o_ex = L.take(NF),
                o_claim = L.close(up_pass).close(up).open(claim).take<int32_t>(NF), o_eh = L.close(claim).open(zero).take<int32_t>(NF),
                o_acc = L.take(16), o_qa = L.take(N), o_bi = L.close(zero).take<int32_t>(N), o_bd = L.take<int32_t>(N), o_sd = L.take<int32_t>(N),
-               o_nc = L.take<int32_t>(N), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF),
-               o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF), o_cnt = L.open(down).take(16),
-               o_ng = L.take(8), o_po = L.take(56), o_asg = L.take<int32_t>(NF), o_eo = L.take<int32_t>(NF), o_in = L.take(NF),
+               o_nc = L.take<int32_t>(N), o_cnt = W.take_list(L).open(down).take(16), o_asg = W.take_results(L).take<int32_t>(NF),
                o_ehd = L.take<int32_t>(NF), o_qad = L.take(N);
   L.close(down);
   StagedIo io;
@@ -494,17 +469,13 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
   io.put(o_desc, in->desc, N * 32);
   io.put(o_pos, in->pos, N * 12);
   std::memset(io.host<uint8_t>(o_fl), 3, N);  // every query is a good map point in the map (the caller's filter, ORBMatcher.cc:286-289)
-  if (in->right_u) io.put(o_ru, in->right_u, NF * 8);
-  else
-    for (size_t f = 0; f < NF; ++f) io.host<double>(o_ru)[f] = -1.0;
-  io.put(o_s2, in->level_sigma2, (size_t)nl * 4);
-  io.put(o_is2, in->level_inv_sigma2, (size_t)nl * 4);
-  io.put(o_p0, in->pose_se3, 56);
+  put_frame(io, U, NF, (size_t)nl, in->right_u, in->level_sigma2, in->level_inv_sigma2);
+  io.put(W.o_p0, in->pose_se3, 56);
   std::vector<int32_t> held(NF, -1);
   if (in->held) std::memcpy(held.data(), in->held, NF * 4);
   std::vector<int32_t> hits_total(excluded_hits ? NF : 0, 0), qm_total(query_matches ? N : 0, 0);
   hipStream_t st = c->stream;
-  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
+  const PoseFrameDev F = pose_frame(c, slot, b, U);
   int base_matches = 0, n_pass = 0;
   const int32_t* cnt = nullptr;
   for (int pass = 0; pass < 2; ++pass) {
@@ -527,17 +498,10 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
                          (int32_t*)(b + o_sd), (int32_t*)(b + o_nc), (int32_t*)(b + o_eh));
       launch_track_claim(st, n, (const int32_t*)(b + o_nc), (const int32_t*)(b + o_bi), (const int32_t*)(b + o_bd), (const int32_t*)(b + o_sd),
                          in->min_threshold, in->ratio, (int32_t*)(b + o_claim), 1, (int32_t*)(b + o_acc), b + o_qa);
-      launch_track_edges(st, c->d_kps + (size_t)slot * NF, c->d_n_kp + slot, (int)NF, (const int32_t*)(b + o_held), (const int32_t*)(b + o_claim),
-                         b + o_fl, (const float*)(b + o_pos), (const double*)(b + o_ru), (const float*)(b + o_s2), (const float*)(b + o_is2),
-                         in->min_matches, (int32_t*)(b + o_asg), (int32_t*)(b + o_eo), (double*)(b + o_xw), (double*)(b + o_ms),
-                         (double*)(b + o_info), (float*)(b + o_sig), (int32_t*)(b + o_cnt), -1, (const int32_t*)(b + o_acc), base_matches);
+      launch_track_edges(st, F, pose_edges(W, b), (const int32_t*)(b + o_held), (const int32_t*)(b + o_claim), b + o_fl, (const float*)(b + o_pos),
+                         in->min_matches, (int32_t*)(b + o_asg), (int32_t*)(b + o_cnt), -1, (const int32_t*)(b + o_acc), base_matches);
     }
-    {
-      StageTimer tm(c, ORBFE_STAGE_BA, st);
-      launch_pose_only(st, (int)NF, (const double*)(b + o_xw), (const double*)(b + o_ms), (const double*)(b + o_info), (const float*)(b + o_sig),
-                       (const double*)(b + o_p0), prm, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), (double*)(b + o_err), b + o_l,
-                       b + o_r, b + o_in, (double*)(b + o_po), (int32_t*)(b + o_ng), (const int32_t*)(b + o_cnt) + 1);
-    }
+    pose_optimise(c, st, W, b, cam, 0, (const int32_t*)(b + o_cnt) + 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(b + o_ehd, b + o_eh, NF * 4, hipMemcpyDeviceToDevice, st));  // (the hits sit in front of the downloaded block)
     HIP_TRY(c, hipMemcpyAsync(b + o_qad, b + o_qa, N, hipMemcpyDeviceToDevice, st));
@@ -556,7 +520,7 @@ orbfe_status orbfe_track_motion_model(orbfe_ctx* c, int32_t slot, const float* b
     io.get(held.data(), o_asg, NF * 4);
   }
   drain_timers(c);
-  track_results(io, o_cnt, o_ng, o_po, o_asg, o_eo, o_in, NF, out);
+  track_results(io, o_cnt, W, o_asg, out);
   if (excluded_hits) std::memcpy(excluded_hits, hits_total.data(), NF * 4);
   if (query_matches && n) std::memcpy(query_matches, qm_total.data(), (size_t)n * 4);
   if (passes) *passes = n_pass;

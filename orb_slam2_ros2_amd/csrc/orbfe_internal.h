@@ -507,6 +507,28 @@ struct FusePtsParams {
 };
 #define FUSEPTS_SEARCH_BLOCKS 2048  // k_fusepts_search's fixed grid: 8192 waves, 32 per compute unit of 256
 
+// ---- the pose-only step of the six tracking calls (pose_check_dev.h on the device, pose_call.h on the host) ------------------------------
+// The register kernels of k_pose.hip take this many edges (POSE_RT * POSE_EPT there); a frame holds one edge per feature at most, so the
+// six calls refuse a context of more features, and k_trackref_seed keeps a claim per feature in LDS.
+#define POSE_REG_EDGES 2048
+// The frame of the step: its features where the slot keeps them, and for the fused calls the pose it has on entry and its camera.
+struct PoseFrameDev {
+  const orbfe_keypoint* kps;
+  const int32_t* n_kp;  // the slot's count, at most nf
+  int32_t nf, n_levels;
+  const double* right_u;             // [nf], negative: a mono edge
+  const float *sigma2, *inv_sigma2;  // [n_levels]
+  float R0[9], t0[3];                // the pose the frame has until setPose (Optimizer.cc:201)
+  float fx, fy, cx, cy, max_u, max_v;
+};
+// The edge list of Optimizer::OptimizePoseOnly in feature order (Optimizer.cc:58-117), as pose_edges_1024 writes it.
+struct PoseEdgesDev {
+  int32_t* edge_of;  // [nf] the edge of a feature, -1: none
+  double *Xw, *meas, *info;
+  float* sig;
+  const uint8_t* e_inl;  // the optimiser's inlier flag per edge
+};
+
 // ---- the relocalisation refine over a stored keyframe (k_reloc.hip, orbfe_reloc.hip) -------------------------------------
 // Everything the kernels of one call read and write: the frame where its slot keeps it, the keyframe where the store keeps it, the map
 // state of the call's upload, the state that stays on the device and the block that goes down.  hdr: [0] verdict (0: still running),
@@ -517,13 +539,13 @@ struct FusePtsParams {
 #define RELOC_H_ADDED 5
 #define RELOC_H_TLCZ 7
 struct RelocDev {
-  // the frame (slot arrays) and its grid
-  const orbfe_keypoint* f_kps;
+  PoseFrameDev F;  // R0, t0: the PnP pose
+  PoseEdgesDev E;
+  // the frame's packed records, descriptors and grid
   const uint4* f_kpl;
   const uint8_t* f_desc;
-  const int32_t* f_n_kp;
   const int32_t *cell_off, *cell_feat;
-  int32_t rows, cols, clip_w, clip_h, nf, n_levels;
+  int32_t rows, cols, clip_w, clip_h;
   // the stored keyframe and its map state
   const orbfe_keypoint* k_kps;
   const uint8_t* k_desc;
@@ -533,16 +555,11 @@ struct RelocDev {
   float kf_R[9], kf_t[3];
   // the call
   const int32_t* held;
-  const double* right_u;
-  const float *sigma2, *inv_sigma2;
-  float R0[9], t0[3];
-  float fx, fy, cx, cy, max_u, max_v, baseline, th[2], ratio;
+  float baseline, th[2], ratio;
   int32_t min_threshold, min_inliers, enough;
-  // device state: what the frame holds, the claims of a search, the edge list of an optimisation and its results
-  int32_t *cur, *claim /*[2][nf]*/, *edge_of, *cnt /*[2] edge counts, -1: no optimisation*/;
-  double *Xw, *meas, *info, *p_init /*[2][7]*/, *p_opt /*[2][7]*/;
-  float* sig;
-  const uint8_t* e_inl;  // the optimiser's inlier flag per edge
+  // device state: what the frame holds, the claims of a search, the optimisations' counts and estimates
+  int32_t *cur, *claim /*[2][nf]*/, *cnt /*[2] edge counts, -1: no optimisation*/;
+  double *p_init /*[2][7]*/, *p_opt /*[2][7]*/;
   // the downloaded block
   int32_t* hdr;
   double* pose_out /*[2][7]*/;
@@ -559,27 +576,19 @@ struct RelocDev {
 #define TRACKREF_H_EDGES 2
 #define TRACKREF_H_INLIERS 3
 struct TrackRefDev {
-  // the frame (slot arrays)
-  const orbfe_keypoint* f_kps;
-  const int32_t* f_n_kp;
-  int32_t nf, n_levels;
+  PoseFrameDev F;
+  PoseEdgesDev E;
   // the map state of the call's upload: the keyframe's, then what the frame came with
-  const float* pos;         // [n][3]
-  const uint8_t* f_good;    // [nf]
-  const float* f_pos;       // [nf][3]
-  const double* right_u;    // [nf]
-  const float *sigma2, *inv_sigma2;
-  float R0[9], t0[3];
-  float fx, fy, cx, cy, max_u, max_v;
+  const float* pos;       // [n][3]
+  const uint8_t* f_good;  // [nf]
+  const float* f_pos;     // [nf][3]
   int32_t n, min_matches, min_inliers;
   // searchByBow's list (k_bow_select, one candidate) and its length
   const BowMatch* list;
   const int32_t* n_list;
-  // device state: the edge list of the optimisation and its results
-  int32_t *edge_of, *cnt /*[1] edge count, -1: no optimisation*/;
-  double *Xw, *meas, *info, *p_init /*[7]*/, *p_opt /*[7]*/;
-  float* sig;
-  const uint8_t* e_inl;
+  // device state: the optimisation's count and estimates
+  int32_t* cnt /*[1] edge count, -1: no optimisation*/;
+  double *p_init /*[7]*/, *p_opt /*[7]*/;
   // the downloaded block
   int32_t* hdr;
   BowMatch* matches /*[n]*/;
@@ -601,32 +610,31 @@ struct TrackRefDev {
 #define MOTION_H_INLIERS 4
 #define MOTION_H_INMAP 5
 struct MotionDev {
-  // the two frames (slot arrays); l_depth nullptr: no depth
-  const orbfe_keypoint *f_kps, *l_kps;
-  const int32_t *f_n_kp, *l_n_kp;
+  PoseFrameDev F;  // the current frame; R0, t0: the predicted pose
+  PoseEdgesDev E;  // (written by k_track_edges: the glue kernels only read it)
+  // the last frame (slot arrays); l_depth nullptr: no depth
+  const orbfe_keypoint* l_kps;
+  const int32_t* l_n_kp;
   const double* l_depth;
-  int32_t nf, n_levels;
   // the map state of the call's upload; table nullptr: positions from l_pos, else from the store's rows of l_ids (MpTable's fields)
   const uint8_t* l_flags;
   const uint64_t* l_ids;
   const float* l_pos;
   const uint8_t* const* table;
   uint32_t rows_per_page, max_pages;
-  const float *sigma2, *inv_sigma2;
-  float R0[9], t0[3], lR[9], lt[3], lRwc[9], ltwc[3];
-  float fx, fy, cx, cy, max_u, max_v, baseline, th, th_second;
+  float lR[9], lt[3], lRwc[9], ltwc[3];
+  float baseline, th, th_second;
   int32_t min_matches, min_inliers;
-  // device state: the query arrays of both passes, the claims and the accepted-query counter, what the second pass excludes, the edge
-  // list's results
+  // device state: the query arrays of both passes, the claims and the accepted-query counter, what the second pass excludes, the
+  // optimisation's counts and estimates
   float *qxy, *rad1, *rad2, *q_pos;
   int8_t *lo, *hi;
   uint8_t *q_flags, *ex2;
   const int32_t *claim1, *n_accept;
   const uint8_t *qa1, *qa2;
-  const int32_t *edge_of, *cnt /*[0] n_matches, [1] edge count, -1: no optimisation*/;
-  double *p_init /*[7]*/;
+  const int32_t* cnt /*[0] n_matches, [1] edge count, -1: no optimisation*/;
+  double* p_init /*[7]*/;
   const double* p_opt /*[7]*/;
-  const uint8_t* e_inl;
   // the downloaded block
   int32_t* hdr;
   uint32_t* bad;  // set by a flagged id without a row

@@ -5,7 +5,7 @@
 // device (k_motion.hip), so nothing is synchronised between the upload and the download.
 #include "orbfe_ctx.h"
 #include "orbfe_mpstore.h"
-#include "search_area_layout.h"
+#include "pose_call.h"
 
 namespace orbfe {
 void launch_motion_prep(hipStream_t st, const MotionDev& P);
@@ -32,25 +32,14 @@ orbfe_status orbfe_track_motion_model_slots(orbfe_ctx* c, int32_t slot, int32_t 
     return fail(c, ORBFE_EBADARG, "%s: exactly one of a store with last_ids and last_pos without a store must be given", fn);
   const int nl = c->cfg.n_levels;
   const size_t NF = (size_t)std::max(c->cfg.n_features, 1);
-  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "%s: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", fn, NF);
+  TRY(pose_check_features(c, fn, NF));
   if (store) TRY(mpstore_check_ctx(c, store, fn));
   const orbfe_camera* cam = in->cam;
   const float scalars[] = {cam->fx,       cam->fy,       cam->cx,       cam->cy,       cam->bf,  in->baseline, in->th,
                            in->th_second, in->ratio,     in->bounds[0], in->bounds[1], in->bounds[2], in->bounds[3]};
-  for (float v : scalars)
-    if (!std::isfinite(v)) return fail(c, ORBFE_EBADARG, "%s: a camera entry, a bound, the baseline, a radius or the ratio is not finite", fn);
-  const float* mats[] = {in->Rcw, in->last_Rcw, in->last_Rwc};
-  const float* vecs[] = {in->tcw, in->last_tcw, in->last_twc};
-  for (int m = 0; m < 3; ++m) {
-    for (int k = 0; k < 9; ++k)
-      if (!std::isfinite(mats[m][k])) return fail(c, ORBFE_EBADARG, "%s: a rotation entry is not finite", fn);
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(vecs[m][k])) return fail(c, ORBFE_EBADARG, "%s: a translation entry is not finite", fn);
-  }
+  TRY(check_finite(c, fn, {{scalars, 13}, {in->Rcw, 9}, {in->last_Rcw, 9}, {in->last_Rwc, 9}, {in->tcw, 3}, {in->last_tcw, 3}, {in->last_twc, 3}}));
   AreaGrid ag;
-  if (!area_grid(c->cfg.width, c->cfg.height, in->bounds, &ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", fn);
-  const size_t ncells = (size_t)ag.rows * ag.cols;
-  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", fn, ncells);
+  TRY(check_area_grid(c, fn, in->bounds, NF, &ag));
   TRY(slots_idle(c, slot, 1, fn));
   TRY(slots_idle(c, last_slot, 1, fn));
   // held until the results are down: no upsert or erase touches a row or a page under the running kernels
@@ -61,18 +50,16 @@ orbfe_status orbfe_track_motion_model_slots(orbfe_ctx* c, int32_t slot, int32_t 
   // [ upload | claims (-1 fill) | header, results (0 fill; downloaded), accepted flags, counters (0 fill) | device-only ]
   ScratchLayout L;
   ScratchRegion up, claim, zero, down;
+  PoseWorkspace W(NF);
   const size_t o_fl = L.open(up).take(NF), o_ids = L.take<uint64_t>(store ? NF : 0), o_lp = L.take<float>(store ? 0 : NF * 3),
                o_s2 = L.take<float>((size_t)nl), o_is2 = L.take<float>((size_t)nl), o_c1 = L.close(up).open(claim).take<int32_t>(NF),
                o_c2 = L.take<int32_t>(NF), o_hdr = L.close(claim).open(zero).open(down).take<int32_t>(8), o_bad = L.take(8),
                o_eh = L.take<int32_t>(NF), o_qm = L.take<int32_t>(NF), o_asg = L.take<int32_t>(NF), o_cur = L.take<int32_t>(NF), o_in = L.take(NF),
                o_tmp = L.take(NF), o_tpos = L.take<float>(NF * 3), o_po = L.take<double>(7), o_tc = L.take<float>(12),
-               o_qa1 = L.close(down).take(NF), o_qa2 = L.take(NF), o_acc = L.take(16), o_cnt = L.take(16), o_ng = L.take(8),
-               o_qxy = L.close(zero).take<float>(NF * 2), o_r1 = L.take<float>(NF), o_r2 = L.take<float>(NF), o_lo = L.take(NF), o_hi = L.take(NF),
+               o_qa1 = L.close(down).take(NF), o_qa2 = L.take(NF), o_acc = L.take(16), o_cnt = L.take(16),
+               o_qxy = W.take_results(L).close(zero).take<float>(NF * 2), o_r1 = L.take<float>(NF), o_r2 = L.take<float>(NF), o_lo = L.take(NF), o_hi = L.take(NF),
                o_qp = L.take<float>(NF * 3), o_qf = L.take(NF), o_ex = L.take(NF), o_bi = L.take<int32_t>(NF), o_bd = L.take<int32_t>(NF),
-               o_sd = L.take<int32_t>(NF), o_nc = L.take<int32_t>(NF), o_p0 = L.take<double>(7), o_p1 = L.take<double>(7),
-               o_eo = L.take<int32_t>(NF), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF),
-               o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF), o_ei = L.take(NF),
-               o_ru = L.take<double>(pair < 0 ? NF : 0);
+               o_sd = L.take<int32_t>(NF), o_nc = L.take<int32_t>(NF), o_ru = W.take_list(W.take_seed(L)).take<double>(pair < 0 ? NF : 0);
   StagedIo io;
   TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
   uint8_t* b = io.d;
@@ -89,31 +76,27 @@ orbfe_status orbfe_track_motion_model_slots(orbfe_ctx* c, int32_t slot, int32_t 
   const double* d_ru = pair >= 0 ? c->d_right_u + (size_t)pair * NF : (const double*)(b + o_ru);
   if (pair < 0) HIP_TRY(c, hipMemsetAsync(b + o_ru, 0xBF, NF * 8, st));
   MotionDev P = {};
-  P.f_kps = c->d_kps + (size_t)slot * NF, P.l_kps = c->d_kps + (size_t)last_slot * NF;
-  P.f_n_kp = c->d_n_kp + slot, P.l_n_kp = c->d_n_kp + last_slot;
+  P.F = pose_frame(c, slot, d_ru, (const float*)(b + o_s2), (const float*)(b + o_is2));
+  pose_frame_camera(P.F, in->Rcw, in->tcw, cam, in->bounds);
+  P.E = pose_edges(W, b);
+  P.l_kps = c->d_kps + (size_t)last_slot * NF, P.l_n_kp = c->d_n_kp + last_slot;
   P.l_depth = last_pair >= 0 ? c->d_depth + (size_t)last_pair * NF : nullptr;
-  P.nf = (int32_t)NF, P.n_levels = nl;
   P.l_flags = b + o_fl, P.l_ids = (const uint64_t*)(b + o_ids), P.l_pos = (const float*)(b + o_lp);
   if (store) {
     const MpTable T = store->table();
     P.table = T.table, P.rows_per_page = T.rows_per_page, P.max_pages = T.max_pages;
   }
-  P.sigma2 = (const float*)(b + o_s2), P.inv_sigma2 = (const float*)(b + o_is2);
-  std::memcpy(P.R0, in->Rcw, sizeof P.R0), std::memcpy(P.t0, in->tcw, sizeof P.t0);
   std::memcpy(P.lR, in->last_Rcw, sizeof P.lR), std::memcpy(P.lt, in->last_tcw, sizeof P.lt);
   std::memcpy(P.lRwc, in->last_Rwc, sizeof P.lRwc), std::memcpy(P.ltwc, in->last_twc, sizeof P.ltwc);
-  P.fx = cam->fx, P.fy = cam->fy, P.cx = cam->cx, P.cy = cam->cy, P.max_u = in->bounds[1], P.max_v = in->bounds[3];
   P.baseline = in->baseline, P.th = in->th, P.th_second = in->th_second;
   P.min_matches = in->min_matches, P.min_inliers = in->min_inliers;
   P.qxy = (float*)(b + o_qxy), P.rad1 = (float*)(b + o_r1), P.rad2 = (float*)(b + o_r2), P.q_pos = (float*)(b + o_qp);
   P.lo = (int8_t*)(b + o_lo), P.hi = (int8_t*)(b + o_hi), P.q_flags = b + o_qf, P.ex2 = b + o_ex;
   P.claim1 = (const int32_t*)(b + o_c1), P.n_accept = (const int32_t*)(b + o_acc), P.qa1 = b + o_qa1, P.qa2 = b + o_qa2;
-  P.edge_of = (const int32_t*)(b + o_eo), P.cnt = (const int32_t*)(b + o_cnt);
-  P.p_init = (double*)(b + o_p0), P.p_opt = (const double*)(b + o_p1), P.e_inl = b + o_ei;
+  P.cnt = (const int32_t*)(b + o_cnt), P.p_init = (double*)(b + W.o_p0), P.p_opt = (const double*)(b + W.o_p1);
   P.hdr = (int32_t*)(b + o_hdr), P.bad = (uint32_t*)(b + o_bad), P.assigned = (const int32_t*)(b + o_asg);
   P.cur = (int32_t*)(b + o_cur), P.qm = (int32_t*)(b + o_qm), P.inlier = b + o_in, P.temp = b + o_tmp, P.temp_pos = (float*)(b + o_tpos);
   P.pose_out = (double*)(b + o_po), P.tcw_out = (float*)(b + o_tc);
-  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
   const uint4* f_kpl = c->d_kpl + (size_t)slot * NF;
   const uint8_t *f_desc = c->d_desc + (size_t)slot * NF * 32, *l_desc = c->d_desc + (size_t)last_slot * NF * 32;
   int32_t *bi = (int32_t*)(b + o_bi), *bd = (int32_t*)(b + o_bd), *sd = (int32_t*)(b + o_sd), *nc = (int32_t*)(b + o_nc);
@@ -131,16 +114,10 @@ orbfe_status orbfe_track_motion_model_slots(orbfe_ctx* c, int32_t slot, int32_t 
                          (int32_t*)(b + o_acc), b + (pass == 0 ? o_qa1 : o_qa2));
     }
     // what search 1 assigned is held, what search 2 claims is new: a feature of search 1 was no candidate of search 2
-    launch_track_edges(st, P.f_kps, P.f_n_kp, (int)NF, P.claim1, (const int32_t*)(b + o_c2), P.q_flags, P.q_pos, d_ru, P.sigma2, P.inv_sigma2,
-                       in->min_matches, (int32_t*)(b + o_asg), (int32_t*)(b + o_eo), (double*)(b + o_xw), (double*)(b + o_ms), (double*)(b + o_info),
-                       (float*)(b + o_sig), (int32_t*)(b + o_cnt), -1, (const int32_t*)(b + o_acc), 0);
+    launch_track_edges(st, P.F, P.E, P.claim1, (const int32_t*)(b + o_c2), P.q_flags, P.q_pos, in->min_matches, (int32_t*)(b + o_asg),
+                       (int32_t*)(b + o_cnt), -1, (const int32_t*)(b + o_acc), 0);
   }
-  {
-    StageTimer tm(c, ORBFE_STAGE_BA, st);
-    launch_pose_only(st, (int)NF, (const double*)(b + o_xw), (const double*)(b + o_ms), (const double*)(b + o_info), (const float*)(b + o_sig),
-                     P.p_init, prm, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815), (double*)(b + o_err), b + o_l, b + o_r, b + o_ei,
-                     (double*)(b + o_p1), (int32_t*)(b + o_ng), P.cnt + 1);
-  }
+  pose_optimise(c, st, W, b, cam, 0, P.cnt + 1);
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, st);
     launch_motion_check(st, P);

@@ -3,6 +3,7 @@
 // search, after -- whose kernels leave at once when the verdict has fallen (k_reloc.hip), one download.  The frame's features and grid
 // are the slot's, the keyframe's features the store's; nothing is synchronised between the upload and the download.
 #include "orbfe_kfstore.h"
+#include "pose_call.h"
 
 namespace orbfe {
 void launch_reloc_seed(hipStream_t st, const RelocDev& P);
@@ -24,23 +25,15 @@ orbfe_status orbfe_reloc_refine_stored(orbfe_ctx* c, int32_t slot, orbfe_kfstore
       !out->n_edges || !out->n_inliers || !out->n_added || !out->tlc_z || !out->pose_se3 || !out->Tcw || !out->inlier || !out->assigned ||
       !out->final_assigned || !out->excluded_hits || (n && !out->query_accepted))
     return fail(c, ORBFE_EBADARG, "%s: NULL array", fn);
-  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "%s: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", fn, NF);
+  TRY(pose_check_features(c, fn, NF));
   TRY(kfstore_check_ctx(c, store, fn));
   if (nl < store->n_levels) return fail(c, ORBFE_EBADARG, "%s: the context has %d levels, the store's octaves go up to %d", fn, nl, store->n_levels - 1);
   const orbfe_camera* cam = in->cam;
   const float scalars[] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, in->baseline, in->th_first, in->th_second, in->ratio};
-  for (float v : scalars)
-    if (!std::isfinite(v)) return fail(c, ORBFE_EBADARG, "%s: a camera entry, the baseline, a radius or the ratio is not finite", fn);
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(in->Rcw[k]) || !std::isfinite(in->kf_Rcw[k])) return fail(c, ORBFE_EBADARG, "%s: rotation entry %d is not finite", fn, k);
-  for (int k = 0; k < 3; ++k)
-    if (!std::isfinite(in->tcw[k]) || !std::isfinite(in->kf_tcw[k])) return fail(c, ORBFE_EBADARG, "%s: translation entry %d is not finite", fn, k);
-  for (size_t f = 0; f < NF; ++f)
-    if (in->held[f] < -1 || in->held[f] >= n) return fail(c, ORBFE_EBADARG, "%s: held[%zu] = %d out of range", fn, f, in->held[f]);
+  TRY(check_finite(c, fn, {{scalars, 9}, {in->Rcw, 9}, {in->kf_Rcw, 9}, {in->tcw, 3}, {in->kf_tcw, 3}}));
+  TRY(check_held(c, fn, in->held, NF, n));
   AreaGrid ag;
-  if (!area_grid(c->cfg.width, c->cfg.height, in->bounds, &ag)) return fail(c, ORBFE_EBADARG, "%s: bad frame bounds", fn);
-  const size_t ncells = (size_t)ag.rows * ag.cols;
-  if (area_grid_lds(ncells, NF).refused) return fail(c, ORBFE_EBADSIZE, "%s: %zu grid cells exceed the LDS counters", fn, ncells);
+  TRY(check_area_grid(c, fn, in->bounds, NF, &ag));
   std::shared_lock<std::shared_timed_mutex> store_lk(store->mu);  // held until the results are down: no erase frees memory under the kernels
   const KfEntry* e = store->map.find(in->kf_id);
   if (!e) return fail(c, ORBFE_EBADARG, "%s: keyframe %llu is not in the store", fn, (unsigned long long)in->kf_id);
@@ -53,60 +46,48 @@ orbfe_status orbfe_reloc_refine_stored(orbfe_ctx* c, int32_t slot, orbfe_kfstore
   // from the assignments to the accepted queries
   ScratchLayout L;
   ScratchRegion up, ones, zero, down;
-  const size_t o_good = L.open(up).take(N), o_pos = L.take<float>(N * 3), o_held = L.take<int32_t>(NF), o_ru = L.take<double>(NF),
-               o_s2 = L.take<float>((size_t)nl), o_is2 = L.take<float>((size_t)nl), o_claim = L.close(up).open(ones).take<int32_t>(2 * NF),
-               o_asg = L.open(down).take<int32_t>(2 * NF), o_cur = L.take<int32_t>(NF), o_hdr = L.close(ones).open(zero).take<int32_t>(16),
-               o_po = L.take<double>(14), o_tc = L.take<float>(24), o_in = L.take(2 * NF), o_eh = L.take<int32_t>(2 * NF), o_qa = L.take(2 * N),
-               o_cnt = L.close(down).take<int32_t>(2), o_p0 = L.take<double>(14), o_p1 = L.take<double>(14), o_ng = L.take(8),
-               o_eo = L.close(zero).take<int32_t>(NF), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF),
-               o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF), o_ei = L.take(NF);
+  PoseWorkspace W(NF, 2);
+  FrameUpload U;
+  const size_t o_good = L.open(up).take(N), o_pos = L.take<float>(N * 3), o_held = L.take<int32_t>(NF),
+               o_claim = U.take(L, NF, (size_t)nl).close(up).open(ones).take<int32_t>(2 * NF), o_asg = L.open(down).take<int32_t>(2 * NF),
+               o_cur = L.take<int32_t>(NF), o_hdr = L.close(ones).open(zero).take<int32_t>(16), o_po = L.take<double>(14),
+               o_tc = L.take<float>(24), o_in = L.take(2 * NF), o_eh = L.take<int32_t>(2 * NF), o_qa = L.take(2 * N),
+               o_cnt = L.close(down).take<int32_t>(2);
+  W.take_seed(L), W.take_results(L), L.close(zero), W.take_list(L);
   StagedIo io;
   TRY(io.reserve(c, L.end(), std::max(up.end, down.bytes())));
   io.put(o_good, in->good, N);
   io.put(o_pos, in->pos, N * 12);
   io.put(o_held, in->held, NF * 4);
-  if (in->right_u) io.put(o_ru, in->right_u, NF * 8);
-  else
-    for (size_t f = 0; f < NF; ++f) io.host<double>(o_ru)[f] = -1.0;
-  io.put(o_s2, in->level_sigma2, (size_t)nl * 4);
-  io.put(o_is2, in->level_inv_sigma2, (size_t)nl * 4);
+  put_frame(io, U, NF, (size_t)nl, in->right_u, in->level_sigma2, in->level_inv_sigma2);
   hipStream_t st = c->stream;
   uint8_t* b = io.d;
   HIP_TRY(c, io.upload(up));
   HIP_TRY(c, hipMemsetAsync(b + ones.begin, 0xFF, ones.bytes(), st));
   HIP_TRY(c, hipMemsetAsync(b + zero.begin, 0, zero.bytes(), st));
   RelocDev P = {};
-  P.f_kps = c->d_kps + (size_t)slot * NF, P.f_kpl = c->d_kpl + (size_t)slot * NF, P.f_desc = c->d_desc + (size_t)slot * NF * 32;
-  P.f_n_kp = c->d_n_kp + slot;
-  P.rows = ag.rows, P.cols = ag.cols, P.clip_w = ag.clip_w, P.clip_h = ag.clip_h, P.nf = (int32_t)NF, P.n_levels = nl;
+  P.F = pose_frame(c, slot, b, U);
+  pose_frame_camera(P.F, in->Rcw, in->tcw, cam, in->bounds);
+  P.E = pose_edges(W, b);
+  P.f_kpl = c->d_kpl + (size_t)slot * NF, P.f_desc = c->d_desc + (size_t)slot * NF * 32;
+  P.rows = ag.rows, P.cols = ag.cols, P.clip_w = ag.clip_w, P.clip_h = ag.clip_h;
   P.k_kps = e->at<orbfe_keypoint>(e->o_kps), P.k_desc = e->at<uint8_t>(e->o_desc);
   P.good = b + o_good, P.pos = (const float*)(b + o_pos), P.n = n;
   std::memcpy(P.kf_R, in->kf_Rcw, sizeof P.kf_R), std::memcpy(P.kf_t, in->kf_tcw, sizeof P.kf_t);
-  P.held = (const int32_t*)(b + o_held), P.right_u = (const double*)(b + o_ru);
-  P.sigma2 = (const float*)(b + o_s2), P.inv_sigma2 = (const float*)(b + o_is2);
-  std::memcpy(P.R0, in->Rcw, sizeof P.R0), std::memcpy(P.t0, in->tcw, sizeof P.t0);
-  P.fx = cam->fx, P.fy = cam->fy, P.cx = cam->cx, P.cy = cam->cy, P.max_u = in->bounds[1], P.max_v = in->bounds[3];
+  P.held = (const int32_t*)(b + o_held);
   P.baseline = in->baseline, P.th[0] = in->th_first, P.th[1] = in->th_second, P.ratio = in->ratio;
   P.min_threshold = in->min_threshold, P.min_inliers = in->min_inliers, P.enough = in->enough;
-  P.cur = (int32_t*)(b + o_cur), P.claim = (int32_t*)(b + o_claim), P.edge_of = (int32_t*)(b + o_eo), P.cnt = (int32_t*)(b + o_cnt);
-  P.Xw = (double*)(b + o_xw), P.meas = (double*)(b + o_ms), P.info = (double*)(b + o_info), P.p_init = (double*)(b + o_p0);
-  P.p_opt = (double*)(b + o_p1), P.sig = (float*)(b + o_sig), P.e_inl = b + o_ei;
+  P.cur = (int32_t*)(b + o_cur), P.claim = (int32_t*)(b + o_claim), P.cnt = (int32_t*)(b + o_cnt);
+  P.p_init = (double*)(b + W.o_p0), P.p_opt = (double*)(b + W.o_p1);
   P.hdr = (int32_t*)(b + o_hdr), P.pose_out = (double*)(b + o_po), P.tcw_out = (float*)(b + o_tc), P.inlier = b + o_in;
   P.assigned = (int32_t*)(b + o_asg), P.hits = (int32_t*)(b + o_eh), P.qa = b + o_qa;
-  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
-  const double d_mono = (double)(float)std::sqrt(5.991), d_stereo = (double)(float)std::sqrt(7.815);
-  auto optimise = [&](int s) {
-    StageTimer tm(c, ORBFE_STAGE_BA, st);
-    launch_pose_only(st, (int)NF, P.Xw, P.meas, P.info, P.sig, P.p_init + 7 * s, prm, d_mono, d_stereo, (double*)(b + o_err), b + o_l, b + o_r,
-                     b + o_ei, P.p_opt + 7 * s, (int32_t*)(b + o_ng), P.cnt + s);
-  };
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, st);
     TRY(slot_grid(c, st, slot, ag, &P.cell_off, &P.cell_feat));
     launch_reloc_seed(st, P);
   }
   for (int s = 0; s < 2; ++s) {
-    optimise(s);
+    pose_optimise(c, st, W, b, cam, s, P.cnt + s);
     StageTimer tm(c, ORBFE_STAGE_MATCH, st);
     launch_reloc_check(st, P, s);
     launch_reloc_search(st, P, s);

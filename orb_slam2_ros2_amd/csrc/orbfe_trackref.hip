@@ -4,6 +4,7 @@
 // once when the verdict has fallen (k_trackref.hip), one download.  The frame's features are the slot's, the keyframe's features and
 // FeatureVector the store's; nothing is synchronised between the upload and the download.
 #include "orbfe_kfstore.h"
+#include "pose_call.h"
 
 void launch_bow(hipStream_t s, const uint8_t* d_desc, size_t desc_img_stride, const int32_t* d_counts, int count_step, int n_fixed, int n_img, int cap,
                 const BowVocabDev& vd, int levelsup, uint64_t* d_wkey, uint64_t* d_nkey, double* d_wts, size_t key_stride, uint32_t* o_words,
@@ -33,7 +34,7 @@ orbfe_status orbfe_track_reference_stored(orbfe_ctx* c, int32_t slot, const orbf
       !out->verdict || !out->n_matches || (n && !out->matches) || !out->assigned || !out->n_edges || !out->n_inliers || !out->inlier ||
       !out->final_assigned || !out->pose_se3 || !out->Tcw)
     return fail(c, ORBFE_EBADARG, "%s: NULL array", fn);
-  if (NF > 2048) return fail(c, ORBFE_EBADSIZE, "%s: %zu features per frame (the fused pose kernel keeps up to 2048 edges in registers)", fn, NF);
+  TRY(pose_check_features(c, fn, NF));
   const bool host_fv = in->n_nodes != 0 || in->nodes || in->node_offsets || in->features;
   if ((vocab != nullptr) == host_fv)
     return fail(c, ORBFE_EBADARG, "%s: exactly one of a vocabulary and a host FeatureVector of the frame must be given", fn);
@@ -43,12 +44,7 @@ orbfe_status orbfe_track_reference_stored(orbfe_ctx* c, int32_t slot, const orbf
   if (nl < store->n_levels) return fail(c, ORBFE_EBADARG, "%s: the context has %d levels, the store's octaves go up to %d", fn, nl, store->n_levels - 1);
   const orbfe_camera* cam = in->cam;
   const float scalars[] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, in->ratio, in->bounds[0], in->bounds[1], in->bounds[2], in->bounds[3]};
-  for (float v : scalars)
-    if (!std::isfinite(v)) return fail(c, ORBFE_EBADARG, "%s: a camera entry, a bound or the ratio is not finite", fn);
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(in->Rcw[k])) return fail(c, ORBFE_EBADARG, "%s: rotation entry %d is not finite", fn, k);
-  for (int k = 0; k < 3; ++k)
-    if (!std::isfinite(in->tcw[k])) return fail(c, ORBFE_EBADARG, "%s: translation entry %d is not finite", fn, k);
+  TRY(check_finite(c, fn, {{scalars, 10}, {in->Rcw, 9}, {in->tcw, 3}}));
   std::shared_lock<std::shared_timed_mutex> store_lk(store->mu);  // held until the results are down: no erase frees memory under the kernels
   const KfEntry* e = store->map.find(in->kf_id);
   if (!e) return fail(c, ORBFE_EBADARG, "%s: keyframe %llu is not in the store", fn, (unsigned long long)in->kf_id);
@@ -68,18 +64,19 @@ orbfe_status orbfe_track_reference_stored(orbfe_ctx* c, int32_t slot, const orbf
   // when the caller takes the frame's BoW
   ScratchLayout L;
   ScratchRegion up, bow, zero, down;
+  PoseWorkspace W(NF);
+  FrameUpload U;
   const size_t o_kf = L.open(up).take<BowKf>(1), o_good = L.take(N), o_pos = L.take<float>(N * 3), o_fg = L.take(NF),
-               o_fp = L.take<float>(in->frame_good ? NF * 3 : 0), o_ru = L.take<double>(NF), o_s2 = L.take<float>((size_t)nl),
-               o_is2 = L.take<float>((size_t)nl), o_hn = L.take<int32_t>(1), o_hnodes = L.take<uint32_t>(nn), o_hoffs = L.take<int32_t>(nn + 1),
+               o_fp = L.take<float>(in->frame_good ? NF * 3 : 0), o_hn = U.take(L, NF, (size_t)nl).take<int32_t>(1),
+               o_hnodes = L.take<uint32_t>(nn), o_hoffs = L.take<int32_t>(nn + 1),
                o_hfeat = L.take<uint32_t>(nfv), o_wkey = L.close(up).take<uint64_t>(np2), o_nkey = L.take<uint64_t>(np2),
                o_wts = L.take<double>(np2), o_slots = L.take<BowSlot>(NE), o_list = L.take<BowMatch>(NE), o_ln = L.take<int32_t>(1),
                o_values = L.open(bow).take<double>(NF), o_words = L.take<uint32_t>(NF), o_nodes = L.take<uint32_t>(NF),
                o_feat = L.take<uint32_t>(NF), o_offs = L.take<int32_t>(NF + 1), o_bc = L.take<int32_t>(2),
                o_hdr = L.close(bow).open(zero).open(down).take<int32_t>(4), o_m = L.take<BowMatch>(N), o_asg = L.take<int32_t>(NF),
                o_cur = L.take<int32_t>(NF), o_po = L.take<double>(7), o_tc = L.take<float>(12), o_in = L.take(NF),
-               o_cnt = L.close(down).take<int32_t>(1), o_p0 = L.take<double>(7), o_p1 = L.take<double>(7), o_ng = L.take(8),
-               o_eo = L.close(zero).take<int32_t>(NF), o_xw = L.take<double>(NF * 3), o_ms = L.take<double>(NF * 3), o_info = L.take<double>(NF),
-               o_sig = L.take<float>(NF), o_err = L.take<double>(NF * 3), o_l = L.take(NF), o_r = L.take(NF), o_ei = L.take(NF);
+               o_cnt = L.close(down).take<int32_t>(1);
+  W.take_seed(L), W.take_results(L), L.close(zero), W.take_list(L);
   const ScratchRegion fetch = {want_bow ? bow.begin : down.begin, down.end};
   StagedIo io;
   TRY(io.reserve(c, L.end(), std::max(up.end, fetch.bytes())));
@@ -98,11 +95,7 @@ orbfe_status orbfe_track_reference_stored(orbfe_ctx* c, int32_t slot, const orbf
     io.put(o_fp, in->frame_pos, NF * 12);
   } else
     std::memset(io.host<uint8_t>(o_fg), 0, NF);
-  if (in->right_u) io.put(o_ru, in->right_u, NF * 8);
-  else
-    for (size_t f = 0; f < NF; ++f) io.host<double>(o_ru)[f] = -1.0;
-  io.put(o_s2, in->level_sigma2, (size_t)nl * 4);
-  io.put(o_is2, in->level_inv_sigma2, (size_t)nl * 4);
+  put_frame(io, U, NF, (size_t)nl, in->right_u, in->level_sigma2, in->level_inv_sigma2);
   if (host_fv) {
     io.put(o_hn, &in->n_nodes, 4);
     io.put(o_hnodes, in->nodes, nn * 4);
@@ -113,20 +106,17 @@ orbfe_status orbfe_track_reference_stored(orbfe_ctx* c, int32_t slot, const orbf
   HIP_TRY(c, io.upload(up));
   HIP_TRY(c, hipMemsetAsync(b + zero.begin, 0, zero.bytes(), st));
   TrackRefDev P = {};
-  P.f_kps = c->d_kps + (size_t)slot * NF, P.f_n_kp = c->d_n_kp + slot, P.nf = (int32_t)NF, P.n_levels = nl;
-  P.pos = (const float*)(b + o_pos), P.f_good = b + o_fg, P.f_pos = (const float*)(b + o_fp), P.right_u = (const double*)(b + o_ru);
-  P.sigma2 = (const float*)(b + o_s2), P.inv_sigma2 = (const float*)(b + o_is2);
-  std::memcpy(P.R0, in->Rcw, sizeof P.R0), std::memcpy(P.t0, in->tcw, sizeof P.t0);
-  P.fx = cam->fx, P.fy = cam->fy, P.cx = cam->cx, P.cy = cam->cy, P.max_u = in->bounds[1], P.max_v = in->bounds[3];
+  P.F = pose_frame(c, slot, b, U);
+  pose_frame_camera(P.F, in->Rcw, in->tcw, cam, in->bounds);
+  P.E = pose_edges(W, b);
+  P.pos = (const float*)(b + o_pos), P.f_good = b + o_fg, P.f_pos = (const float*)(b + o_fp);
   P.n = n, P.min_matches = in->min_matches, P.min_inliers = in->min_inliers;
   P.list = (const BowMatch*)(b + o_list), P.n_list = (const int32_t*)(b + o_ln);
-  P.edge_of = (int32_t*)(b + o_eo), P.cnt = (int32_t*)(b + o_cnt);
-  P.Xw = (double*)(b + o_xw), P.meas = (double*)(b + o_ms), P.info = (double*)(b + o_info), P.p_init = (double*)(b + o_p0);
-  P.p_opt = (double*)(b + o_p1), P.sig = (float*)(b + o_sig), P.e_inl = b + o_ei;
+  P.cnt = (int32_t*)(b + o_cnt), P.p_init = (double*)(b + W.o_p0), P.p_opt = (double*)(b + W.o_p1);
   P.hdr = (int32_t*)(b + o_hdr), P.matches = (BowMatch*)(b + o_m), P.assigned = (int32_t*)(b + o_asg), P.cur = (int32_t*)(b + o_cur);
   P.pose_out = (double*)(b + o_po), P.tcw_out = (float*)(b + o_tc), P.inlier = b + o_in;
   BowQuerySlot Q = {};
-  Q.kps = P.f_kps, Q.desc = c->d_desc + (size_t)slot * NF * 32, Q.o_flags = (uint32_t)o_fg;
+  Q.kps = P.F.kps, Q.desc = c->d_desc + (size_t)slot * NF * 32, Q.o_flags = (uint32_t)o_fg;
   if (host_fv)
     Q.nodes = (const uint32_t*)(b + o_hnodes), Q.offs = (const int32_t*)(b + o_hoffs), Q.feat = (const uint32_t*)(b + o_hfeat),
     Q.n_nodes = (const int32_t*)(b + o_hn);
@@ -136,23 +126,17 @@ orbfe_status orbfe_track_reference_stored(orbfe_ctx* c, int32_t slot, const orbf
   BowParams BP = {};
   BP.mode = ORBFE_BOW_TRACK, BP.dist_threshold = in->dist_threshold, BP.check_orientation = in->check_orientation ? 1 : 0, BP.n_kf = 1;
   BP.ratio = in->ratio, BP.cap = n;
-  const BaParamsDev prm = {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->bf};
-  const double d_mono = (double)(float)std::sqrt(5.991), d_stereo = (double)(float)std::sqrt(7.815);
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, st);
     if (vocab)
-      launch_bow(st, Q.desc, 0, P.f_n_kp, 1, 0, 1, (int)NF, vd, in->levelsup, (uint64_t*)(b + o_wkey), (uint64_t*)(b + o_nkey),
+      launch_bow(st, Q.desc, 0, P.F.n_kp, 1, 0, 1, (int)NF, vd, in->levelsup, (uint64_t*)(b + o_wkey), (uint64_t*)(b + o_nkey),
                  (double*)(b + o_wts), np2, (uint32_t*)(b + o_words), (double*)(b + o_values), (uint32_t*)(b + o_nodes), (int32_t*)(b + o_offs),
                  (uint32_t*)(b + o_feat), (int32_t*)(b + o_bc));
     launch_bow_search_one(st, b, (const BowKf*)(b + o_kf), Q, BP, e->n_feat, (BowSlot*)(b + o_slots), (BowMatch*)(b + o_list),
                           (int32_t*)(b + o_ln));
     launch_trackref_seed(st, P);
   }
-  {
-    StageTimer tm(c, ORBFE_STAGE_BA, st);
-    launch_pose_only(st, (int)NF, P.Xw, P.meas, P.info, P.sig, P.p_init, prm, d_mono, d_stereo, (double*)(b + o_err), b + o_l, b + o_r, b + o_ei,
-                     P.p_opt, (int32_t*)(b + o_ng), P.cnt);
-  }
+  pose_optimise(c, st, W, b, cam, 0, P.cnt);
   {
     StageTimer tm(c, ORBFE_STAGE_MATCH, st);
     launch_trackref_check(st, P);

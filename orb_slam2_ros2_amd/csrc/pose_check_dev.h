@@ -1,14 +1,16 @@
-// pose_check_dev.h -- what surrounds a pose-only optimisation inside a fused Tracking step, shared by k_reloc.hip,
-// k_trackref.hip and k_motion.hip: the two pose conversions of Optimizer::OptimizePoseOnly
-// (src/Optimizer.cc:119, :201) in fp64 and its projection post-check (:179-199), as the 1024 threads of one workgroup run it.  The kernels
-// differ only in where a held point's position comes from and in what a feature that is no inlier loses; both are parameters here, so
-// the post-check has one text.  Beside them the motion direction and the octave window of searchByProjection(frame, other frame), which
-// the relocalisation refine and the motion model share.
+// pose_check_dev.h -- what surrounds a pose-only optimisation inside a Tracking step, shared by k_guided.hip (k_track_edges), k_reloc.hip
+// (DESIGN 4.28), k_trackref.hip and k_motion.hip: the edge list of Optimizer::OptimizePoseOnly in feature
+// order (src/Optimizer.cc:58-117), its two pose conversions (:119, :201) in fp64, its projection post-check (:179-199) and the write-back
+// of the estimate, as the 1024 threads of one workgroup run them over orbfe_internal.h's PoseFrameDev / PoseEdgesDev.  The callers differ
+// only in where a feature's point comes from and in what a feature that is no inlier loses; both are parameters here, so the edge
+// builder and the post-check have one text each.  Beside them the motion direction and the octave window of
+// searchByProjection(frame, other frame), which the relocalisation refine and the motion model share.
 // Float arithmetic: map_point_dev.h's rows and `A x + t`; the includer switches contraction off.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "map_point_dev.h"
+#include "orbfe_internal.h"
 
 namespace orbfe {
 
@@ -85,34 +87,76 @@ __device__ __forceinline__ void motion_window(int o, float z, float baseline, in
     lo = max(0, o - 1), hi = min(o + 1, 7);
 }
 
-struct PostCheckCam {
-  float fx, fy, cx, cy, max_u, max_v;
-};
-
-// The post-check over the nf features of a frame by the 1024 threads of one workgroup (all of them call it): feature f is an inlier when
-// its edge is one of the optimiser's and its point projects into the image under (Rb, tb), the pose the frame still has.  pos_of(f, X)
-// gives the position of the point feature f holds (called for the optimiser's inliers only), drop(f) takes the point from a feature
-// that is no inlier (`if (!inLier[idx]) mvpMapPoints[idx] = nullptr`, :191-194).  Writes inlier[f]; returns edges - nBad to every thread.
-template <class PosOf, class Drop>
-__device__ __forceinline__ int post_check_1024(int nf, const int32_t* __restrict__ edge_of, const uint8_t* __restrict__ e_inl, const float (&Rb)[9],
-                                               const float (&tb)[3], const PostCheckCam& K, uint8_t* __restrict__ inlier, int* s_wave, PosOf pos_of,
-                                               Drop drop) {
+// The edge list of Optimizer::OptimizePoseOnly (src/Optimizer.cc:58-117) over the features of F, in feature order, by the 1024 threads of
+// one workgroup (all of them call it): a ballot per wave, the waves' counts summed in wave order, the base carried across the trips.
+// point_of(f), called once for every f < F.nf by the thread that owns f, returns the position of the point the feature's edge goes to, or
+// nullptr when the feature has no edge; what else the caller does per feature (its assignment, its counts) it does in there.  Writes
+// E.edge_of[f] for every feature and Xw, meas, info, sig per edge; the octave that indexes the level tables is clamped into them.
+// Returns the edge count to every thread.  s_wave[16], s_base: LDS of the caller.
+template <class PointOf>
+__device__ __forceinline__ int pose_edges_1024(const PoseFrameDev& F, const PoseEdgesDev& E, int* s_wave, int* s_base, PointOf point_of) {
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (t == 0) *s_base = 0;
+  __syncthreads();
+  for (int f0 = 0; f0 < F.nf; f0 += 1024) {
+    const int f = f0 + t;
+    const float* X = f < F.nf ? point_of(f) : nullptr;
+    const bool edge = X != nullptr;
+    const unsigned long long me = __ballot(edge);
+    if (lane == 0) s_wave[wv] = __popcll(me);
+    __syncthreads();
+    int before = *s_base, chunk = 0;
+    for (int w = 0; w < 16; ++w) {
+      if (w < wv) before += s_wave[w];
+      chunk += s_wave[w];
+    }
+    const int e = before + __popcll(me & ((1ull << lane) - 1ull));
+    if (f < F.nf) E.edge_of[f] = edge ? e : -1;
+    if (edge) {
+      const orbfe_keypoint k = F.kps[f];
+      E.Xw[3 * e] = (double)X[0], E.Xw[3 * e + 1] = (double)X[1], E.Xw[3 * e + 2] = (double)X[2];
+      const double ru = F.right_u[f];
+      E.meas[3 * e] = (double)k.x, E.meas[3 * e + 1] = (double)k.y, E.meas[3 * e + 2] = ru < 0 ? -1.0 : ru;
+      const int oc = min(max(k.octave, 0), F.n_levels - 1);
+      E.info[e] = (double)F.inv_sigma2[oc];
+      E.sig[e] = F.sigma2[oc];
+    }
+    __syncthreads();
+    if (t == 0) *s_base += chunk;
+    __syncthreads();
+  }
+  return *s_base;
+}
+
+// The post-check over the features of F by the 1024 threads of one workgroup (all of them call it): feature f is an inlier when its edge
+// is one of the optimiser's and its point projects into the image under (Rf, tf), the pose the frame still has -- setPose comes last
+// (Optimizer.cc:201).  pos_of(f, X) gives the position of the point feature f holds (called for the optimiser's inliers only), drop(f)
+// takes the point from a feature that is no inlier (`if (!inLier[idx]) mvpMapPoints[idx] = nullptr`, :191-194).  Writes inlier[f];
+// returns edges - nBad to every thread.
+template <class PosOf, class Drop>
+__device__ __forceinline__ int post_check_1024(const PoseFrameDev& F, const float* Rf, const float* tf, const PoseEdgesDev& E,
+                                               uint8_t* __restrict__ inlier, int* s_wave, PosOf pos_of, Drop drop) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  float Rb[9], tb[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Rb[k] = Rf[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) tb[k] = tf[k];
   int mine = 0;
-  for (int f0 = 0; f0 < nf; f0 += 1024) {
+  for (int f0 = 0; f0 < F.nf; f0 += 1024) {
     const int f = f0 + t;
     bool inl = false;
-    if (f < nf) {
-      const int e = edge_of[f];
-      inl = e >= 0 && e_inl[e] != 0;
+    if (f < F.nf) {
+      const int e = E.edge_of[f];
+      inl = e >= 0 && E.e_inl[e] != 0;
       if (inl) {  // VirtualFrame::project2UV (src/Frame.cc:320-333) and the test of Optimizer.cc:185: 0, not mfMinU / mfMinV
         float X[3];
         pos_of(f, X);
         float pc[3];
         affine(1.0f, Rb, X, tb, pc);
         const float z = pc[2];
-        const float u = pc[0] / z * K.fx + K.cx, v = pc[1] / z * K.fy + K.cy;
-        if (!(z > 0.f) || u > K.max_u || u < 0.f || v > K.max_v || v < 0.f) inl = false;
+        const float u = pc[0] / z * F.fx + F.cx, v = pc[1] / z * F.fy + F.cy;
+        if (!(z > 0.f) || u > F.max_u || u < 0.f || v > F.max_v || v < 0.f) inl = false;
       }
       inlier[f] = inl ? 1 : 0;
       if (!inl) drop(f);
@@ -124,6 +168,13 @@ __device__ __forceinline__ int post_check_1024(int nf, const int32_t* __restrict
   int n_in = 0;
   for (int w = 0; w < 16; ++w) n_in += s_wave[w];
   return n_in;
+}
+
+// The close of a check, by one thread: the estimate and its float pose (Converter::ConvertSE32Tcw's R, tc) into the downloaded block.
+__device__ __forceinline__ void pose_write_back(const double* est, const float* R, const float* tc, double* pose_out, float* tcw_out) {
+  for (int k = 0; k < 7; ++k) pose_out[k] = est[k];
+  for (int k = 0; k < 9; ++k) tcw_out[k] = R[k];
+  for (int k = 0; k < 3; ++k) tcw_out[9 + k] = tc[k];
 }
 
 }  // namespace orbfe

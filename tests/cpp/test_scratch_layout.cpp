@@ -1,9 +1,11 @@
-// test_scratch_layout.cpp -- csrc/scratch_layout.h and csrc/search_area_layout.h, host only (no HIP header, no device): the padding rule,
-// regions, that a reservation sized from the guided search's layout is exactly what the search takes, and the grid build's LDS rule.
+// test_scratch_layout.cpp -- csrc/scratch_layout.h, csrc/search_area_layout.h and the layout part of csrc/pose_call.h, host only (no HIP
+// header, no device): the padding rule, regions, that a reservation sized from the guided search's layout is exactly what the search
+// takes, the grid build's LDS rule, and the pose-only workspace of the tracking calls.
 #include <cstdint>
 #include <cstdio>
 #include <initializer_list>
 
+#include "../../orb_slam2_ros2_amd/csrc/pose_call.h"
 #include "../../orb_slam2_ros2_amd/csrc/search_area_layout.h"
 
 static int failures = 0;
@@ -123,6 +125,40 @@ int main() {
     CHECK(area_grid_lds(7167, 0).in_lds == 1 && area_grid_lds(7167, 0).bytes == KB56 - 4);
     CHECK(area_grid_lds(7168, 0).in_lds == 0 && area_grid_lds(7168, 0).bytes == KB56 + 4);
   }
+  // the pose-only workspace (pose_call.h) for one and two optimisations: its three takes, each inside a region of the caller's with a
+  // take of the caller's own between them -- every field inside its region, aligned by the one padding rule, disjoint from the others;
+  // p_init and p_opt hold k * 7 doubles
+  for (size_t k : {(size_t)1, (size_t)2})
+    for (size_t nf : {(size_t)1, (size_t)500, (size_t)2048}) {
+      ScratchLayout L(512);
+      ScratchRegion seed, list, results;
+      PoseWorkspace W(nf, k);
+      FrameUpload U;
+      const size_t own0 = L.take(24);
+      const size_t own1 = W.take_seed(L.open(seed)).close(seed).take(24);
+      const size_t own2 = W.take_list(L.open(list)).close(list).take(24);
+      const size_t own3 = U.take(W.take_results(L.open(results)).close(results), nf, 8).take(24);
+      CHECK(W.NF == nf && W.k == k);
+      struct Field {
+        size_t off, bytes;
+        const ScratchRegion* in;
+      };
+      const ScratchRegion whole = {own0, L.end()};
+      const Field fields[] = {{own0, 24, &whole},          {W.o_p0, k * 7 * 8, &seed},   {own1, 24, &whole},         {W.o_xw, nf * 24, &list},
+                              {W.o_ms, nf * 24, &list},    {W.o_info, nf * 8, &list},    {W.o_sig, nf * 4, &list},   {own2, 24, &whole},
+                              {W.o_p1, k * 7 * 8, &results}, {W.o_ng, 8, &results},      {W.o_eo, nf * 4, &results}, {W.o_ei, nf, &results},
+                              {U.o_ru, nf * 8, &whole},    {U.o_s2, 8 * 4, &whole},      {U.o_is2, 8 * 4, &whole},   {own3, 24, &whole}};
+      size_t prev_end = 512;
+      for (const Field& f : fields) {  // (in take order: each starts where the one before it ends, padding included)
+        CHECK(f.off % 256 == 0);
+        CHECK(f.off == prev_end);
+        CHECK(f.off >= f.in->begin && f.off + f.bytes <= f.in->end);
+        prev_end = f.off + padded(f.bytes);
+      }
+      CHECK(prev_end == L.end());
+      CHECK(seed.bytes() == padded(k * 56) && list.bytes() == 2 * padded(nf * 24) + padded(nf * 8) + padded(nf * 4));
+      CHECK(results.bytes() == padded(k * 56) + padded(8) + padded(nf * 4) + padded(nf));
+    }
   if (failures) return 1;
   std::printf("SCRATCH_LAYOUT_OK\n");
   return 0;
